@@ -9,6 +9,11 @@ construct_ctu_hydro_source, clean_state, dt estimate), i.e. the reference's own 
 ("zones advanced per microsecond", Source/driver/Castro_advance.cpp:461-471).  Inputs are
 synthetic (the Sedov initial data generated on the device) and resident in HBM before the
 timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times K steps and prints the line.  --full adds what earlier rounds measured beside the
+headline: the untimed per-kernel pass (roofline.kernel_utilisation), the 600-B contract leg, the other numerics build, other
+states, the halo timings, the rank proxies, the overlap leg of a multi-GPU run and the CPU baseline (--no-* switch single ones off).
+--dump-outputs DIR writes the state of the last timed step (and its dt, time) as .npy files (dump_selection).
 """
 import argparse
 import json
@@ -218,6 +223,55 @@ def self_launch(nproc):
     return p.returncode if p.returncode else (0 if lines else 1)
 
 
+DUMP_FULL_BYTES = 32 << 20         # --dump-outputs: the whole state up to this size, a fixed sample above it
+DUMP_CUBE = 64                      # side of the central cube of the sample (the blast starts there)
+DUMP_POINTS = 1 << 18               # zones drawn from the whole domain, fixed seed
+DUMP_SEED = 20241016
+
+
+def dump_selection(n_cell):
+    """The zones --dump-outputs writes: {name: (k, j, i, shape)} with global zone indices (numpy int64) in the (z, y, x) order of
+    the state and the shape each array gets after its component axis.  Every zone if the float64 state fits in DUMP_FULL_BYTES;
+    otherwise the central cube of up to DUMP_CUBE^3 zones and DUMP_POINTS zones drawn with a fixed seed (32 MB in all)."""
+    import numpy as np
+    nx, ny, nz = n_cell
+
+    def box(lo, n):
+        k, j, i = np.meshgrid(*(np.arange(lo[d], lo[d] + n[d], dtype=np.int64) for d in range(3)), indexing="ij")
+        return k.ravel(), j.ravel(), i.ravel(), tuple(n)
+    if 8 * 8 * nx * ny * nz <= DUMP_FULL_BYTES:
+        return {"state": box((0, 0, 0), (nz, ny, nx))}
+    side = tuple(min(m, DUMP_CUBE) for m in (nz, ny, nx))
+    flat = np.sort(np.random.default_rng(DUMP_SEED).choice(nx * ny * nz, size=min(DUMP_POINTS, nx * ny * nz), replace=False))
+    k, rest = np.divmod(flat, ny * nx)
+    j, i = np.divmod(rest, nx)
+    return {"state_center": box(tuple(m // 2 - s // 2 for m, s in zip((nz, ny, nx), side)), side),
+            "state_sample": (k, j, i, (len(flat),))}
+
+
+def gather_outputs(c, n_cell):
+    """What a caller of the timed path receives after its last step -- the new state, dt and time -- as {name: float64 array} on
+    every rank (collective: each rank contributes the selected zones of its own box)."""
+    import numpy as np
+    import torch
+    S = c.S_new()                             # (NUM_STATE, nz, ny, nx) of this rank's box
+    mine = {}
+    for name, (k, j, i, shape) in dump_selection(n_cell).items():
+        inside = ((k >= c.lo[2]) & (k <= c.hi[2]) & (j >= c.lo[1]) & (j <= c.hi[1]) & (i >= c.lo[0]) & (i <= c.hi[0]))
+        pos = np.nonzero(inside)[0]
+        idx = [torch.from_numpy(a[pos] - c.lo[d]).to(S.device) for a, d in ((k, 2), (j, 1), (i, 0))]
+        mine[name] = (pos, S[:, idx[0], idx[1], idx[2]].cpu().numpy())
+    out = {"dt": np.array([c.dt], dtype=np.float64), "time": np.array([c.time], dtype=np.float64)}
+    parts = c.comm.gather_objects(mine)
+    for name, (k, j, i, shape) in dump_selection(n_cell).items():
+        a = np.full((S.shape[0], len(k)), np.nan)
+        for p in parts:
+            pos, vals = p[name]
+            a[:, pos] = vals
+        out[name] = a.reshape((S.shape[0],) + shape)
+    return out
+
+
 def noise_state(torch, n, device):
     """A rough but physical conserved state (NUM_STATE, nz, ny, nx), generated on the device: a smooth background, an oblique
     density / pressure jump and zone-to-zone noise of +-20 % in rho and p -- every limiter, the flattening and all wave
@@ -285,7 +339,14 @@ def main():
                     "that nothing they do can take the bench line down with it)")
     ap.add_argument("--proxy-child", action="store_true", help=argparse.SUPPRESS)          # internal: this IS the child
     ap.add_argument("--proxy-value", type=float, default=0.0, help=argparse.SUPPRESS)       # internal: the parent's cell-updates/s
+    ap.add_argument("--full", action="store_true", help="everything beside the headline as well: the per-kernel pass, the 600-B "
+                    "contract leg, the other numerics build, other states, halo timings, rank proxies, the overlap leg of a multi-GPU "
+                    "run, the CPU baseline (the --no-* options and --proxy-rank-of select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the state after the last timed step (all of it up to "
+                    "32 MB, else a central cube and a seeded sample of zones), its dt and time as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.proxy_rank_of is not None and not args.full and not args.proxy_child:
+        ap.error("--proxy-rank-of is one of the extras of --full")
 
     # `python bench.py --gpus N` outside a launcher: start the N ranks as a CHILD torch.distributed.run (never an exec, and
     # before this process has imported torch or touched the GPU), relay rank 0's JSON line and exit with the child's code.
@@ -402,20 +463,24 @@ def main():
         os.write(real_stdout, (json.dumps({"rank_proxies": out}) + "\n").encode())
         return
 
-    def run(contract_mode, steps, warmup, kernel_pass, stepwise=None, state="sedov", per_step=False, numerics=None, overlap_=None):
+    def run(contract_mode, steps, warmup, kernel_pass, stepwise=None, state="sedov", per_step=False, numerics=None, overlap_=None,
+            outputs=False):
         """W untimed warm-up steps, K timed steps (no profiling events in the timed region), then -- untimed -- a second
-        pass of min(K, 5) steps with hipEvents around every kernel on its launch stream for the per-kernel table."""
+        pass of min(K, 5) steps with hipEvents around every kernel on its launch stream for the per-kernel table.
+        outputs: info["outputs"] = gather_outputs after the K timed steps (before the per-kernel pass)."""
         if stepwise is None and (args.stepwise or world > 1):
             stepwise = bool(args.stepwise)
         if stepwise is None:
             try:
-                return run(contract_mode, steps, warmup, kernel_pass, stepwise=False, state=state, per_step=per_step, numerics=numerics, overlap_=overlap_)
+                return run(contract_mode, steps, warmup, kernel_pass, stepwise=False, state=state, per_step=per_step, numerics=numerics, overlap_=overlap_,
+                           outputs=outputs)
             except castro_amd.AdvanceFailure:
                 raise
             except Exception as e:          # a box whose runtime refuses the graph capture: the stepwise form measures the same kernels
                 print("bench.py: host-free batch failed (%s: %s); falling back to --stepwise" % (type(e).__name__, e), file=sys.stderr)
                 torch.cuda.synchronize()
-                return run(contract_mode, steps, warmup, kernel_pass, stepwise=True, state=state, per_step=per_step, numerics=numerics, overlap_=overlap_)
+                return run(contract_mode, steps, warmup, kernel_pass, stepwise=True, state=state, per_step=per_step, numerics=numerics, overlap_=overlap_,
+                           outputs=outputs)
         c = castro_amd.Castro(n_cell, comm=comm, grid=grid, lo_bc=bc, hi_bc=bc, overlap=overlap if overlap_ is None else overlap_,
                               fuse_clean=not contract_mode, flux_assign=not contract_mode, numerics=numerics or args.numerics)
         if state == "noise":
@@ -456,6 +521,7 @@ def main():
             w = torch.tensor([wall], dtype=torch.float64, device="cpu" if comm.dist.get_backend() == "gloo" else "cuda")
             comm.dist.all_reduce(w, op=comm.dist.ReduceOp.MAX)
             wall = w.item()
+        dumped = gather_outputs(c, n_cell) if outputs else None
         prof, ksteps = {}, 0
         if kernel_pass:
             ksteps = min(steps, 5)
@@ -468,15 +534,20 @@ def main():
             c.hydro.profile(False)
         info = {"zones_per_gpu": c.n[0] * c.n[1] * c.n[2], "sim_time": c.time, "nstep": c.nstep, "n": c.n,
                 "overlap_halo": (c.overlap if c.overlap in ("tiles", "staged") else bool(c.overlap and c._comm_stream is not None and c.neighbors)),
-                "halo": c.halo_stats() if hasattr(c, "halo_stats") else None, "host_free": host_free,
+                "halo": c.halo_stats() if (args.full and hasattr(c, "halo_stats")) else None, "host_free": host_free,
                 "step_graph": bool(host_free and getattr(c, "_graphs", None)), "per_step": per,
-                "numerics": c.hydro.numerics, "library": c.hydro.lib.castro_amd_version().decode()}
+                "numerics": c.hydro.numerics, "library": c.hydro.lib.castro_amd_version().decode(), "outputs": dumped}
         c.close()                                # the C-ABI halo plans own device buffers outside torch's allocator
         del c
         torch.cuda.empty_cache()
         return wall, prof, ksteps, info
 
-    wall, prof, ksteps, info = run(contract, args.steps, args.warmup, True)
+    wall, prof, ksteps, info = run(contract, args.steps, args.warmup, args.full, outputs=args.dump_outputs is not None)
+    if args.dump_outputs is not None and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in info["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
     total_cells = n_cell[0] * n_cell[1] * n_cell[2]
     value = total_cells * args.steps / wall
     bytes_per_cell = path_bytes(contract, info["numerics"], fused_clean=not contract)
@@ -502,12 +573,13 @@ def main():
             "traffic": traffic_step, "traffic_source": traffic_src,
             "bytes_per_cell_update": bytes_per_cell,
             "definition": "SURVEY 8(d): cell-updates/s x declared contract bytes per cell-update / 8 TB/s; traffic = L2->fabric "
-                          "bytes of one step (PMC, committed profile of the same sources)",
-            "kernel_utilisation": kutil}
+                          "bytes of one step (PMC, committed profile of the same sources)"}
+    if args.full:
+        roof["kernel_utilisation"] = kutil
     if traffic_step:
         roof["traffic_GBs"] = traffic_step / (wall / args.steps) / 1e9
         roof["traffic_over_algorithmic"] = traffic_step / (bytes_per_cell * total_cells)
-    if not contract and world == 1 and not args.no_contract_leg:
+    if args.full and not contract and world == 1 and not args.no_contract_leg:
         # the reference's full output contract (zero-filled fluxes accumulated with +=, S_new read-modify-write,
         # clean_state / estdt as separate passes) timed in the same run
         w6, _, _, _ = run(True, max(5, args.steps // 2), 2, False)
@@ -517,7 +589,7 @@ def main():
 
     # the other build of the same sources, same workload, timed in the same process (both libraries are loaded side by side)
     other_leg = None
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         other = "exact" if args.numerics == "contract" else "contract"
         try:
             w_o, _, _, i_o = run(contract, args.steps, args.warmup, False, numerics=other)
@@ -530,7 +602,7 @@ def main():
     # a multi-GPU run: the same workload with the halo overlap switched the other way (castro.py OVERLAP_MIN_ZONES was set from
     # one GPU; this leg is the measurement on real links), untimed extra
     overlap_leg = None
-    if world > 1 and not args.no_extras and overlap is None:
+    if args.full and world > 1 and not args.no_extras and overlap is None:
         try:
             # the other setting of the halo overlap (default since round 6: the light split, on) on the same links
             w_v, _, _, i_v = run(contract, args.steps, args.warmup, False, overlap_=not info["overlap_halo"])
@@ -540,7 +612,7 @@ def main():
             overlap_leg = {"error": "%s: %s" % (type(e).__name__, e)}
             torch.cuda.synchronize()
     extras = None
-    if world == 1 and not contract and not args.no_extras:
+    if args.full and world == 1 and not contract and not args.no_extras:
         # untimed extras (the headline above is unchanged): the same step on states that are not
         # 99.9 % ambient gas, and per-step medians as BASELINE.md section 3 words the protocol
         ks = max(10, min(args.steps, 50))
@@ -565,7 +637,7 @@ def main():
     # self-send inside captured two-stream graphs, and whatever could go wrong there (round 6 met a segmentation fault inside
     # hipStreamEndCapture with another stream arrangement) must not cost the measured line of this process
     proxies = None
-    want = args.proxy_rank_of if args.proxy_rank_of is not None else ([2, 4, 8] if (world == 1 and not args.no_extras and not contract) else [])
+    want = args.proxy_rank_of if args.proxy_rank_of is not None else ([2, 4, 8] if (args.full and world == 1 and not args.no_extras and not contract) else [])
     if world == 1 and want and args.proxy_in_process:
         proxies = run_proxies(want, value)
     elif world == 1 and want:
@@ -606,10 +678,11 @@ def main():
                    "numerics": info["numerics"], "library": info["library"],
                    "numerics_parity": {"contract": "rtol 1e-10 on all 33 plotfile fields vs the CPU oracle (tests/test_gpu_contract.py)",
                                        "exact": "bit-identical to the CPU oracle (tests/test_gpu_parity.py)"}[info["numerics"]],
-                   "other_numerics_leg": other_leg, "other_states": extras, "rank_proxies": proxies, "overlap_leg": overlap_leg},
+                   "other_numerics_leg": other_leg, "other_states": extras, "rank_proxies": proxies, "overlap_leg": overlap_leg,
+                   "full": args.full},
         "roofline": roof,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_ncell, args.cpu_steps)
     elif rank == 0:
         out["cpu_baseline"] = None

@@ -618,15 +618,10 @@ def test_amr_orchestration_oracle_on_data_where_clean_state_is_not_idempotent(or
 # ---- the boxes of the refined levels spread over ranks (gloo, oracle backend) -----------------------------------------
 import itertools
 import os
-import socket
 
 import torch.multiprocessing as mp
 
-
-def _free_port():
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        return sk.getsockname()[1]
+from tests.test_driver_cpu import _free_port
 
 
 # level 1: four boxes (two ranks -> boxes 0, 2 here, 1, 3 there), level 2: three boxes over two of them, one at the edge

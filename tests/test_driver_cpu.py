@@ -88,11 +88,25 @@ def test_default_grid():
 
 # ---------------------------------------------------------------------------------------------
 def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+    """A free port for the rendezvous of spawned ranks, drawn BELOW the kernel's ephemeral range: a port bound to 0 comes from
+    that range, and once released the kernel may hand it to another socket (an outgoing connection, another bind to 0) in the
+    seconds before rank 0 listens on it (EADDRINUSE)."""
+    import random
+    lo = 32768
+    try:
+        lo = int(open("/proc/sys/net/ipv4/ip_local_port_range").read().split()[0])
+    except (OSError, ValueError, IndexError):
+        pass
+    rng = random.Random()                   # seeded from the system, not from the tests' seeds
+    for _ in range(200):
+        p = rng.randrange(max(1024, lo // 2), lo)
+        with socket.socket() as s:
+            try:
+                s.bind(("127.0.0.1", p))
+            except OSError:
+                continue
+        return p
+    raise RuntimeError("no free port below %d" % lo)
 
 
 def _worker(rank, world, port, n, bcs, nsteps, out_path):

@@ -5,7 +5,7 @@
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out
 export TMPDIR=/tmp
-ARGS="--numerics contract --steps 10 --warmup 3 --no-cpu-baseline --no-contract-leg --no-extras"
+ARGS="--numerics contract --steps 10 --warmup 3 --full --no-cpu-baseline --no-contract-leg --no-extras"
 run() {   # name, env assignments...
   name=$1; shift
   for rep in 1 2; do

@@ -6,12 +6,14 @@
 # overlap: --force-overlap = the light split of round 6 (ctoprim on the valid zones beside the exchange; host-free and graph-replayed
 # like the plain form: `graph True` on both legs), --overlap-staged = the round-2 form.  Sets castro_amd/castro.py: OVERLAP_MIN_ZONES.
 N=${NUMERICS:-contract}
+OUT=${OUT:-bench_out}     # where the error logs go (environment)
+mkdir -p $OUT
 for mode in "--no-overlap" "--force-overlap" "--overlap-staged"; do
-  python bench.py --numerics $N --steps 20 --warmup 3 --no-cpu-baseline --no-contract-leg --no-extras --proxy-rank-of 1 2 4 8 $mode 2> gpurun_out/ov$mode.err | python -c "
+  python bench.py --numerics $N --steps 20 --warmup 3 --full --no-cpu-baseline --no-contract-leg --no-extras --proxy-rank-of 1 2 4 8 $mode 2> $OUT/ov$mode.err | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{') and 'metric' in l][-1]); p=d['config']['rank_proxies']
 for k in ('1','2','4','8'):
     e=p[k]
     print('[$N] $mode N=%s box %s: %.3f ms/step (graph %s, overlap %s, fillboundary alone %.3f ms, %.1f MB exchanged)' % (k, e['box'], e['ms_per_step'], e.get('step_graph'), e.get('overlap_halo'), e.get('fillboundary_ms', 0), e.get('bytes_exchanged_per_step', 0)/1e6) if 'error' not in e else (k, e))
-" || tail -30 gpurun_out/ov$mode.err
+" || tail -30 $OUT/ov$mode.err
 done

@@ -9,8 +9,8 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out
 export TMPDIR=/tmp
 cd $REPO
-python3 bench.py --numerics $NUMERICS > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
-python3 bench.py --numerics $NUMERICS --reference-contract --no-cpu-baseline > $OUT/${TAG}_bench_reference_contract.json 2>/dev/null
+python3 bench.py --numerics $NUMERICS --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python3 bench.py --numerics $NUMERICS --full --reference-contract --no-cpu-baseline > $OUT/${TAG}_bench_reference_contract.json 2>/dev/null
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_samebox_stats -- python3 $REPO/bench.py --numerics $NUMERICS --no-cpu-baseline --no-extras --no-contract-leg > $OUT/${TAG}_samebox_stats.log 2>&1
 cd $REPO
