@@ -66,6 +66,8 @@ EXPORTED_SYMBOLS = (
     "castro_amd_ctx_profile_reset",
     "castro_amd_berger_rigoutsos",
     "castro_amd_cmpflx_points", "castro_amd_ppm_points", "castro_amd_flatten_points", "castro_amd_trans_points",
+    "castro_amd_temp_diffusion_fab", "castro_amd_temp_diffusion_mf", "castro_amd_estdt_temp_diffusion_fab",
+    "castro_amd_estdt_temp_diffusion_mf", "castro_amd_sources_mf_ex",
 )
 
 
@@ -130,6 +132,35 @@ def make_rotation(rotational_period, rot_axis=3, center=(0.5, 0.5, 0.5), include
     R.include_centrifugal, R.include_coriolis = include_centrifugal, include_coriolis
     R.rot_source_type, R.implicit_rotation_update = rot_source_type, implicit_rotation_update
     return R
+
+
+class Diffusion(C.Structure):
+    """castro_amd_diffusion"""
+    _fields_ = [("const_conductivity", C.c_double), ("diffuse_cutoff_density", C.c_double),
+                ("diffuse_cutoff_density_hi", C.c_double), ("diffuse_cond_scale_fac", C.c_double)]
+
+
+def make_diffusion(const_conductivity, diffuse_cutoff_density=-1.e200, diffuse_cutoff_density_hi=-1.e200,
+                   diffuse_cond_scale_fac=1.0):
+    """castro.diffuse_temp = 1 with conductivity.const_conductivity and the castro.diffuse_* parameters
+    (Source/driver/_cpp_parameters:401-416)"""
+    return Diffusion(float(const_conductivity), float(diffuse_cutoff_density), float(diffuse_cutoff_density_hi),
+                     float(diffuse_cond_scale_fac))
+
+
+class DiffusionBox(C.Structure):
+    """castro_amd_diffusion_box: one box of a castro_amd_temp_diffusion_mf call"""
+    _fields_ = [("lo", C.c_int * 3), ("hi", C.c_int * 3), ("state", Fab), ("source", Fab)]
+
+
+# CODATA-2010 cgs constants of the gamma-law restatement (castro_amd/csrc/hydro_device.h)
+K_B, M_U = 1.3806488e-16, 1.660538921e-24
+
+
+def gamma_law_cv(params, xn=1.0):
+    """c_v = e / T of the gamma-law gas, with the expressions of the kernels (eos_mu, eos_e_of_T)"""
+    mu = 1.0 / (xn * (1.0 / params.abar))
+    return K_B / ((params.eos_gamma - 1.0) * (mu * M_U))
 
 
 class Geom(C.Structure):
@@ -218,6 +249,18 @@ def load(numerics=None):
     L.castro_amd_fab_ops_p.argtypes = [C.c_void_p, C.c_int, C.POINTER(FabOp), C.POINTER(Params), C.c_void_p]
     L.castro_amd_sources_mf.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(SourceBox), C.POINTER(C.c_double), C.c_int,
                                         C.POINTER(Rotation), C.POINTER(Geom), C.POINTER(Params), C.c_double, C.c_int, C.c_void_p]
+    if hasattr(L, "castro_amd_temp_diffusion_fab"):         # absent from A/B builds of revisions before thermal diffusion
+        PD = C.POINTER(Diffusion)
+        L.castro_amd_temp_diffusion_fab.argtypes = [C.c_void_p, PF, PF, PF, I3, I3, PD, C.POINTER(Geom), C.c_double, C.c_void_p]
+        L.castro_amd_temp_diffusion_mf.argtypes = [C.c_void_p, C.c_int, C.POINTER(DiffusionBox), PD, C.POINTER(Geom), C.c_double,
+                                                   C.c_void_p]
+        L.castro_amd_estdt_temp_diffusion_fab.argtypes = [C.c_void_p, PF, I3, I3, C.POINTER(Geom), C.POINTER(Params), PD,
+                                                          C.c_double, C.c_void_p, C.c_void_p]
+        L.castro_amd_estdt_temp_diffusion_mf.argtypes = [C.c_void_p, C.c_int, C.POINTER(StateBox), C.POINTER(Geom),
+                                                         C.POINTER(Params), PD, C.c_double, C.c_void_p, C.c_void_p]
+        L.castro_amd_sources_mf_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(SourceBox), C.POINTER(C.c_double), C.c_int,
+                                               C.POINTER(Rotation), PD, C.POINTER(Geom), C.POINTER(Params), C.c_double, C.c_int,
+                                               C.c_void_p]
     L.castro_amd_clean_state_reduce_mf.argtypes = [C.c_void_p, C.c_int, C.POINTER(StateBox), C.POINTER(Geom), C.POINTER(Params),
                                                    C.c_int, C.c_void_p, C.c_void_p]
     L.castro_amd_estdt_mf.argtypes = [C.c_void_p, C.c_int, C.POINTER(StateBox), C.POINTER(Geom), C.POINTER(Params), C.c_void_p, C.c_void_p]

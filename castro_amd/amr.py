@@ -670,7 +670,8 @@ class CastroAmr:
     def __init__(self, n_cell, patch_crse=None, prob_lo=(0., 0., 0.), prob_hi=(1., 1., 1.), lo_bc=(2, 2, 2), hi_bc=(2, 2, 2),
                  params=None, make_hydro=None, make_params=None, refine=None, regrid_int=2, n_error_buf=1,
                  blocking_factor=8, patches=None, max_level=1, cluster=False, grid_eff=0.7, max_grid_size=128,
-                 do_grav=False, const_grav=0.0, grav_source_type=4, rotation=None, comm=None, base_grid=None, box_streams=4):
+                 do_grav=False, const_grav=0.0, grav_source_type=4, rotation=None, comm=None, base_grid=None, box_streams=4,
+                 diffusion=None):
         """base_grid = (gx, gy, gz): level 0 as gx x gy x gz equal boxes instead of one (amr.max_grid_size on the base level);
         with `comm` they are dealt over the ranks like the boxes of the refined levels.
         comm: a castro_amd.DistComm to spread the boxes of every refined level over its ranks (box i of level l on rank
@@ -686,6 +687,10 @@ class CastroAmr:
         value_greater | value_less | gradient | relative_gradient) for boxes that follow the tags up to
         amr.max_level = max_level: one bounding box per level, or with cluster=True the Berger-Rigoutsos boxes
         (amr.grid_eff, amr.blocking_factor and amr.max_grid_size in zones of the new level)."""
+        if diffusion is not None:
+            # the operator of a refined level needs AMReX's coarse-fine boundary stencil [3P], which is not restated
+            raise NotImplementedError("CastroAmr: thermal diffusion (diffusion=...) is built for a single level only; "
+                                      "use castro_amd.Castro")
         if patch_crse is not None:
             assert patches is None
             patches = [patch_crse]

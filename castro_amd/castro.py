@@ -224,8 +224,9 @@ class Castro:
                  params=None, hydro=None, comm=None, grid=None, overlap=None, make_params=None, fuse_clean=True, flux_assign=True,
                  use_retry=True, retry_subcycle_factor=0.5, max_subcycles=10, dt_cutoff=1.e-12,
                  do_grav=False, const_grav=0.0, grav_source_type=4, box=None, rotation=None, fixed_dt=-1.0, initial_dt=-1.0, max_dt=1.e200,
-                 alloc=True, numerics=None, proxy_ranks=1):
-        """numerics: "exact" | "contract" for the HipHydro this object creates (castro_amd/_lib.py).  alloc=False: the geometry and bookkeeping of a box another rank owns (castro_amd/amr.py), no device memory."""
+                 alloc=True, numerics=None, proxy_ranks=1, diffusion=None, do_hydro=True):
+        """diffusion: _lib.make_diffusion(const_conductivity=..., ...) turns on castro.diffuse_temp = 1 (explicit thermal diffusion,
+        Source/diffusion/); do_hydro=False: castro.do_hydro = 0, the source stages without the hydro update.  numerics: "exact" | "contract" for the HipHydro this object creates (castro_amd/_lib.py).  alloc=False: the geometry and bookkeeping of a box another rank owns (castro_amd/amr.py), no device memory."""
         self.n_cell = tuple(int(x) for x in n_cell)
         self.owned = bool(alloc)
         self.comm = comm if comm is not None else SingleComm()
@@ -333,7 +334,12 @@ class Castro:
         self.do_grav, self.grav, self.grav_source_type = bool(do_grav), (0.0, 0.0, float(const_grav)), int(grav_source_type)
         # castro.do_rotation: `rotation` = _lib.make_rotation(rotational_period, rot_axis, ...)
         self.rotation = rotation
-        self.have_sources = self.do_grav or rotation is not None
+        # castro.diffuse_temp = 1: `diffusion` = _lib.make_diffusion(const_conductivity, ...); castro.do_hydro
+        self.diffusion, self.do_hydro = diffusion, bool(do_hydro)
+        if diffusion is not None and box is not None:
+            raise NotImplementedError("thermal diffusion on a refined patch needs the coarse-fine boundary of the operator")
+        self.dt_limiter = ""                    # "hydro" | "diffusion" | "castro.max_dt": what the last estTimeStep was limited by
+        self.have_sources = self.do_grav or rotation is not None or diffusion is not None or not self.do_hydro
         if self.have_sources:
             NSRC, NGS = 7, 3            # NSRC, NUM_GROW_SRC (Castro_setup.cpp:317-327)
             self.sbox = (tuple(x - NGS for x in self.lo), tuple(x + NGS for x in self.hi))
@@ -563,10 +569,40 @@ class Castro:
             h.sedov_init(self.S_new_b, self.gbox, self.lo, self.hi, self.geom, self.params, **kw)
         elif problem == "sod":
             h.sod_init(self.S_new_b, self.gbox, self.lo, self.hi, self.geom, self.params, **kw)
+        elif problem == "diffusion_test":
+            return self.set_state(self.diffusion_test_state(**kw))
         else:
             raise ValueError(problem)
         self.clean_state(self.S_new_b, 1)      # Castro.cpp:1100-1160
         self.time, self.nstep, self.dt = 0.0, 0, 0.0
+
+    def diffusion_test_analytic(self, time, diff_coeff=1.0, T1=1.0, T2=2.0, t_0=1.e-3):
+        """The temperature of Exec/unit_tests/diffusion_test at `time` on the whole domain, (nz, ny, nx): a Gaussian pulse about
+        the domain centre stays Gaussian under a constant diffusivity (prob_util.H, 3-D Cartesian: exponent 3/2)."""
+        import numpy as np
+        g = self.geom
+        x = [g.problo[d] + g.dx[d] * (np.arange(self.n_cell[d], dtype=np.float64) + 0.5) for d in range(3)]
+        c = [0.5 * (g.problo[d] + g.probhi[d]) for d in range(3)]
+        Z, Y, X = np.meshgrid(x[2] - c[2], x[1] - c[1], x[0] - c[0], indexing="ij")
+        r2 = X * X + Y * Y + Z * Z
+        return T1 + (T2 - T1) * (t_0 / (time + t_0)) ** 1.5 * np.exp(-0.25 * r2 / (diff_coeff * (time + t_0)))
+
+    def diffusion_test_state(self, diff_coeff=1.0, T1=1.0, T2=2.0, t_0=1.e-3):
+        """problem_initialize_state_data of Exec/unit_tests/diffusion_test for a constant conductivity k: the density that makes
+        the diffusivity k / (rho c_v) equal to diff_coeff, the Gaussian temperature at t = 0, no motion, one species."""
+        import numpy as np
+        assert self.diffusion is not None, "diffusion_test needs Castro(..., diffusion=make_diffusion(const_conductivity=...))"
+        cv = L.gamma_law_cv(self.params)
+        rho0 = self.diffusion.const_conductivity / (diff_coeff * cv)
+        assert rho0 > self.params.small_dens, "diffusion_test: rho = %g is not above small_dens = %g" % (rho0, self.params.small_dens)
+        T = self.diffusion_test_analytic(0.0, diff_coeff, T1, T2, t_0)
+        U = np.zeros((NUM_STATE,) + T.shape)
+        U[L.URHO] = rho0
+        U[L.UTEMP] = T
+        U[L.UEINT] = rho0 * (cv * T)
+        U[L.UEDEN] = U[L.UEINT]
+        U[L.UFS] = rho0
+        return U
 
     def set_state(self, full_state):
         """Initial data from a host array (NUM_STATE, nz, ny, nx) covering the whole domain (a custom
@@ -589,8 +625,30 @@ class Castro:
     def estTimeStep(self):
         if self.fixed_dt > 0.0:                                 # Castro.cpp:1511-1513
             return self.fixed_dt
-        est, _ = self._reduce()
-        return min(self.max_dt, checked_estimate(est) * self.params.cfl)
+        # Castro.cpp:1515-1590: max_dt, then the hydro limit (castro.do_hydro), then the diffusion limit (castro.diffuse_temp)
+        estdt, self.dt_limiter = self.max_dt, "castro.max_dt"
+        if self.do_hydro:
+            est, _ = self._reduce()
+            estdt_hydro = checked_estimate(est) * self.params.cfl
+            if estdt_hydro < estdt:
+                estdt, self.dt_limiter = estdt_hydro, "hydro"
+        if self.diffusion is not None:
+            est_d = self._reduce_diffusion()            # max_dt / cfl where no zone is above the cutoff density
+            if not est_d > 0.0:
+                raise AdvanceFailure("estTimeStep: the diffusion estimate is not a positive number (%r)" % (est_d,))
+            estdt_diffusion = est_d * self.params.cfl
+            if estdt_diffusion < estdt:
+                estdt, self.dt_limiter = estdt_diffusion, "diffusion"
+        return estdt
+
+    def _reduce_diffusion(self):
+        """min 0.5 dx^2 / D over the whole level (Castro::estdt_temp_diffusion + ReduceRealMin)"""
+        red = self.red[:1]
+        red.fill_(float("inf"))
+        self.hydro.estdt_temp_diffusion(self.S_new_b, self.gbox, self.lo, self.hi, self.geom, self.params, self.diffusion,
+                                        self.max_dt, red)
+        self.comm.allreduce_min(red)
+        return red.tolist()[0]
 
     def computeInitialDt(self, stop_time=-1.0):
         # Castro::initialTimeStep (Castro.cpp:1490-1504)
@@ -768,15 +826,18 @@ class Castro:
         # one pass (castro_amd_sources_mf, round 6): zero + gravity + rotation + apply + clean_state of a stage in one kernel
         # -- the separate calls below read and write the source and the state three to four times
         one_pass = hasattr(h, "sources_mf") and os.environ.get("CASTRO_AMD_SOURCES_ONE_PASS", "1") != "0"
+        dkw = {} if self.diffusion is None else {"diffusion": self.diffusion}      # diff_src goes first (Castro_sources.cpp)
         if one_pass:
             h.sources_mf(0, h.make_source_boxes([(lo, hi, (S, self.gbox), (self.S_new_b, self.gbox), (self.old_source, self.sbox),
                                                   self.mass_fluxes, self.flux_boxes)]),
                          self.grav if self.do_grav else None, self.grav_source_type if self.do_grav else 4, self.rotation, self.geom,
-                         self.params, dt, ntimes=1)
+                         self.params, dt, ntimes=1, **dkw)
         elif not fused:
             h.copy(self.S_new_b, self.gbox, S, self.gbox, lo, hi)
         if not one_pass:
             self.old_source.zero_()
+            if self.diffusion is not None:              # construct_old_diff_source: + 1.0 x DiffTerm(Sborder)
+                h.temp_diffusion(S, self.gbox, self.old_source, self.sbox, lo, hi, self.diffusion, self.geom, 1.0)
             if self.do_grav:
                 h.old_gravity_source(S, self.gbox, self.old_source, self.sbox, lo, hi, self.grav, self.grav_source_type, dt)
             if self.rotation is not None:
@@ -786,29 +847,44 @@ class Castro:
             else:
                 h.saxpy(self.S_new_b, self.gbox, dt, self.old_source, self.sbox, 7, lo, hi)
                 h.clean_state(self.S_new_b, self.gbox, lo, hi, self.params, ntimes=1)
-        # FillPatch of the source for the tracing
-        self.expand_state(self.old_source, self.sbox, self.src_neighbors)
-        # hydro with the old source traced in the predictor; S_new += (it already holds the old source)
-        try:
-            self.construct_ctu_hydro_source(time, dt, src=self.old_source)
-        finally:
+        if self.do_hydro:
+            # FillPatch of the source for the tracing
+            self.expand_state(self.old_source, self.sbox, self.src_neighbors)
+            # hydro with the old source traced in the predictor; S_new += (it already holds the old source)
+            try:
+                self.construct_ctu_hydro_source(time, dt, src=self.old_source)
+            finally:
+                if self.params.source_term_predictor == 1:
+                    h.set_source_corrector(None, None)        # the context must not keep a pointer into this object's tensor
+            self._flux_clear = False
+            # S_new.min(URHO) (:168-216), clean_state(S_new) (:221-225)
+            h.clean_state_reduce(self.S_new_b, self.gbox, lo, hi, self.geom, self.params, self.red, ntimes=1)
+            self.comm.allreduce_min(self.red)
+            _, rho_min, _ = self.red.tolist()
+            if rho_min < self.params.small_dens:
+                return False, ("negative density" if rho_min < 0.0 else "small density") + " (density = %e)" % rho_min, None
+        else:
+            # castro.do_hydro = 0 (:137-217): no FillPatch of the old source, no hydro update, no density check;
+            # the clean_state(S_new) of :221-225 stays
             if self.params.source_term_predictor == 1:
-                h.set_source_corrector(None, None)        # the context must not keep a pointer into this object's tensor
-        self._flux_clear = False
-        # S_new.min(URHO) (:168-216), clean_state(S_new) (:221-225)
-        h.clean_state_reduce(self.S_new_b, self.gbox, lo, hi, self.geom, self.params, self.red, ntimes=1)
-        self.comm.allreduce_min(self.red)
-        _, rho_min, _ = self.red.tolist()
-        if rho_min < self.params.small_dens:
-            return False, ("negative density" if rho_min < 0.0 else "small density") + " (density = %e)" % rho_min, None
+                h.set_source_corrector(None, None)
+            h.clean_state(self.S_new_b, self.gbox, lo, hi, self.params, ntimes=1)
+        if self.diffusion is not None:
+            # the new-time term reads T of S_new one zone outside the box: same-level ghost fill of S_new (the reference
+            # FillPatches the new state with one ghost zone, Castro_diffusion.cpp:113).  The physical-boundary faces carry no
+            # flux whatever their ghost zones hold, so no boundary fill.
+            self.expand_state(self.S_new_b, bc=False)
         # do_new_sources (:262-268): corrector from the new state, apply, clean_state
         if one_pass:
             h.sources_mf(1, h.make_source_boxes([(lo, hi, (S, self.gbox), (self.S_new_b, self.gbox), (self.new_source, (lo, hi)),
                                                   self.mass_fluxes, self.flux_boxes)]),
                          self.grav if self.do_grav else None, self.grav_source_type if self.do_grav else 4, self.rotation, self.geom,
-                         self.params, dt, ntimes=1)
+                         self.params, dt, ntimes=1, **dkw)
         else:
             self.new_source.zero_()
+            if self.diffusion is not None:              # construct_new_diff_source: + 0.5 x DiffTerm(S_new) - 0.5 x DiffTerm(Sborder)
+                h.temp_diffusion(self.S_new_b, self.gbox, self.new_source, (lo, hi), lo, hi, self.diffusion, self.geom, 0.5)
+                h.temp_diffusion(S, self.gbox, self.new_source, (lo, hi), lo, hi, self.diffusion, self.geom, -0.5)
             if self.do_grav:
                 h.new_gravity_source(S, self.gbox, self.S_new_b, self.gbox, self.new_source, (lo, hi), self.mass_fluxes,
                                      self.flux_boxes, lo, hi, self.grav, self.grav_source_type, dt, self.geom)

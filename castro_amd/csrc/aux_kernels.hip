@@ -684,7 +684,7 @@ struct GravDev { double g[3]; int type, on; };
 template <int STAGE>
 __global__ void __launch_bounds__(256) k_sources_apply(const SrcBoxDev* __restrict__ tab, const long* __restrict__ start, int nbox,
                                                        GravDev G, RotDev R, int rot_on, double dt, double dx0, double dx1, double dx2,
-                                                       DevParams P, int ntimes)
+                                                       DevParams P, int ntimes, int diff_on)
 {
     long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= start[nbox]) return;
@@ -705,6 +705,12 @@ __global__ void __launch_bounds__(256) k_sources_apply(const SrcBoxDev* __restri
     }
     double acc[NSRC], src[NSRC];
     for (int n = 0; n < NSRC; ++n) acc[n] = 0.0;
+    if (diff_on) {
+        // diff_src comes first in the dispatch order of the sources (Castro_sources.cpp): k_temp_diffusion has left
+        // 0 + the diffusion term in the two energy components of the valid zones, the other sources are added to it
+        acc[UEDEN] = B.Src.p[cs + B.Src.sn * UEDEN];
+        acc[UEINT] = B.Src.p[cs + B.Src.sn * UEINT];
+    }
     if (G.on) {
         if (STAGE == 0) old_grav_zone(B.So, i, j, k, G.g, G.type, dt, src);
         else new_grav_zone(B.So, B.Sn, B.M0, B.M1, B.M2, i, j, k, G.g, G.type, dt, dx0, dx1, dx2, src);
@@ -734,7 +740,7 @@ static RotDev make_rotdev(const castro_amd_rotation* r, const castro_amd_geom* g
 
 int launch_sources_apply(int stage, int nbox, const SrcBoxDev* boxes, const double* grav, int grav_type, const castro_amd_rotation* rot,
                          const castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
-                         hipStream_t stream, Profiler* prof)
+                         hipStream_t stream, Profiler* prof, int diff_on)
 {
     if (nbox < 1 || !boxes || !arena) return 0;
     std::vector<long> start((size_t)nbox + 1, 0);
@@ -764,9 +770,9 @@ int launch_sources_apply(int stage, int nbox, const SrcBoxDev* boxes, const doub
     const unsigned nb = (unsigned)((start.back() + 255) / 256);
     prof_begin(prof, stage == 0 ? "k_sources_old" : "k_sources_new", stream);
     if (stage == 0) hipLaunchKernelGGL(k_sources_apply<0>, dim3(nb), dim3(256), 0, stream, (const SrcBoxDev*)base, (const long*)dstart, nbox, G, R,
-                                       rot ? 1 : 0, dt, geom->dx[0], geom->dx[1], geom->dx[2], P, ntimes);
+                                       rot ? 1 : 0, dt, geom->dx[0], geom->dx[1], geom->dx[2], P, ntimes, diff_on);
     else hipLaunchKernelGGL(k_sources_apply<1>, dim3(nb), dim3(256), 0, stream, (const SrcBoxDev*)base, (const long*)dstart, nbox, G, R,
-                            rot ? 1 : 0, dt, geom->dx[0], geom->dx[1], geom->dx[2], P, ntimes);
+                            rot ? 1 : 0, dt, geom->dx[0], geom->dx[1], geom->dx[2], P, ntimes, diff_on);
     prof_end(prof, stream);
     return launch_status();
 }

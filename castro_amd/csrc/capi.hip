@@ -27,6 +27,7 @@ struct castro_amd_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     FabOpsArena ops_arena;                          // device table of castro_amd_fab_ops_p calls with more than 16 operations
     FabOpsArena level_arena;                        // device table of a level-wide hydro launch (castro_amd_ctu_hydro_mf)
+    FabOpsArena diff_arena;                         // device table of a thermal-diffusion launch (castro_amd_temp_diffusion_*)
     hipEvent_t mf_fork = nullptr, mf_join = nullptr;   // castro_amd_ctu_hydro_mf: fork from / join to the caller's stream
 };
 
@@ -263,6 +264,7 @@ void castro_amd_ctx_destroy(castro_amd_ctx* c)
     if (c->mf_join) hipEventDestroy(c->mf_join);
     if (c->ops_arena.p) hipFree(c->ops_arena.p);
     if (c->level_arena.p) hipFree(c->level_arena.p);
+    if (c->diff_arena.p) hipFree(c->diff_arena.p);
     prof_collect(&c->prof);
     for (auto e : c->prof.pool) hipEventDestroy(e);
     if (c->arena) hipFree(c->arena);
@@ -585,9 +587,116 @@ int castro_amd_new_rotation_source_fab(castro_amd_ctx* c, const castro_amd_fab* 
 }
 
 // ---- the source stages and the level reductions for every box of a level in one call (include/castro_hydro_amd.h) ----
+// ---- thermal diffusion (diffusion_kernels.hip) ----
+// the operator's boundary conditions (Diffusion.cpp:99-126): Neumann, except Dirichlet for Inflow on a low face and for Symmetry
+// on a high face -- those two need AMReX's high-order extrapolation [3P] and are refused, like every non-Cartesian geometry
+static int diff_check(const castro_amd_diffusion* diff, const castro_amd_geom* geom)
+{
+    if (!diff || !geom) return CASTRO_AMD_ERR_ARG;
+    if (geom->coord != 0) return CASTRO_AMD_ERR_UNSUPPORTED;
+    for (int d = 0; d < 3; ++d)
+        if (geom->lo_bc[d] == 1 || geom->hi_bc[d] == 3) return CASTRO_AMD_ERR_UNSUPPORTED;
+    return CASTRO_AMD_OK;
+}
+
+static DiffDev to_diffdev(const castro_amd_diffusion* diff, const castro_amd_geom* g)
+{
+    DiffDev D;
+    D.cond = diff->const_conductivity; D.cutoff = diff->diffuse_cutoff_density; D.cutoff_hi = diff->diffuse_cutoff_density_hi;
+    D.scale = diff->diffuse_cond_scale_fac;
+    for (int d = 0; d < 3; ++d) {
+        D.dh[d] = 1.0 / (g->dx[d] * g->dx[d]);
+        D.domlo[d] = g->domlo[d]; D.domhi[d] = g->domhi[d];
+        D.phys_lo[d] = g->lo_bc[d] != 0 ? 1 : 0;
+        D.phys_hi[d] = g->hi_bc[d] != 0 ? 1 : 0;
+    }
+    return D;
+}
+
+// [lo, hi] grown by one inside the FAB: the stencil reads one ghost zone in every direction
+static bool fab_contains_grown1(const castro_amd_fab* f, const int lo[3], const int hi[3])
+{
+    for (int d = 0; d < 3; ++d) if (f->lo[d] > lo[d] - 1 || f->hi[d] < hi[d] + 1) return false;
+    return true;
+}
+
+static int diff_box(DiffBoxDev& T, const castro_amd_fab* state, const castro_amd_fab* state2, const castro_amd_fab* source,
+                    const castro_amd_fab* out, const int lo[3], const int hi[3])
+{
+    if (!state || !state->p || state->ncomp != NUM_STATE || !fab_contains_grown1(state, lo, hi)) return CASTRO_AMD_ERR_ARG;
+    if (state2 && (!state2->p || state2->ncomp != NUM_STATE || !fab_contains_grown1(state2, lo, hi))) return CASTRO_AMD_ERR_ARG;
+    if (source && source->p && (source->ncomp <= UEINT || !fab_contains(source, lo, hi))) return CASTRO_AMD_ERR_ARG;
+    if (out && out->p && (out->ncomp != 1 || !fab_contains(out, lo, hi))) return CASTRO_AMD_ERR_ARG;
+    T.U = to_dfab(state); T.U2 = to_dfab(state2); T.Src = to_dfab(source); T.Out = to_dfab(out);
+    for (int d = 0; d < 3; ++d) { T.lo[d] = lo[d]; T.hi[d] = hi[d]; T.nt[d] = 0; }
+    return CASTRO_AMD_OK;
+}
+
+int castro_amd_temp_diffusion_fab(castro_amd_ctx* c, const castro_amd_fab* state, const castro_amd_fab* source,
+                                  const castro_amd_fab* diff_term, const int lo[3], const int hi[3],
+                                  const castro_amd_diffusion* diff, const castro_amd_geom* geom, double mult, void* stream)
+{
+    if (!c || !lo || !hi || ((!source || !source->p) && (!diff_term || !diff_term->p))) return CASTRO_AMD_ERR_ARG;
+    int rc = diff_check(diff, geom);
+    if (rc != CASTRO_AMD_OK) return rc;
+    DiffBoxDev T;
+    rc = diff_box(T, state, nullptr, source, diff_term, lo, hi);
+    if (rc != CASTRO_AMD_OK) return rc;
+    hipSetDevice(c->device);
+    return launch_temp_diffusion(1, &T, false, to_diffdev(diff, geom), mult, 0.0, 0, &c->diff_arena, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_temp_diffusion_mf(castro_amd_ctx* c, int nboxes, const castro_amd_diffusion_box* boxes,
+                                 const castro_amd_diffusion* diff, const castro_amd_geom* geom, double mult, void* stream)
+{
+    if (!c || nboxes < 0 || (nboxes > 0 && !boxes)) return CASTRO_AMD_ERR_ARG;
+    int rc = diff_check(diff, geom);
+    if (rc != CASTRO_AMD_OK) return rc;
+    if (nboxes == 0) return CASTRO_AMD_OK;
+    std::vector<DiffBoxDev> tab((size_t)nboxes);
+    for (int i = 0; i < nboxes; ++i) {
+        if (!boxes[i].source.p) return CASTRO_AMD_ERR_ARG;
+        rc = diff_box(tab[(size_t)i], &boxes[i].state, nullptr, &boxes[i].source, nullptr, boxes[i].lo, boxes[i].hi);
+        if (rc != CASTRO_AMD_OK) return rc;
+    }
+    hipSetDevice(c->device);
+    return launch_temp_diffusion(nboxes, tab.data(), false, to_diffdev(diff, geom), mult, 0.0, 0, &c->diff_arena, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_estdt_temp_diffusion_fab(castro_amd_ctx* c, const castro_amd_fab* state, const int lo[3], const int hi[3],
+                                        const castro_amd_geom* geom, const castro_amd_params* params,
+                                        const castro_amd_diffusion* diff, double max_dt, double* d_out, void* stream)
+{
+    if (!c || !state || !state->p || !lo || !hi || !geom || !params || !diff || !d_out || state->ncomp != NUM_STATE) return CASTRO_AMD_ERR_ARG;
+    if (!fab_contains(state, lo, hi)) return CASTRO_AMD_ERR_ARG;
+    hipSetDevice(c->device);
+    return launch_estdt_temp_diffusion(to_dfab(state), lo, hi, geom->dx, to_devparams(params), diff->const_conductivity,
+                                       diff->diffuse_cutoff_density, max_dt / params->cfl, d_out, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_estdt_temp_diffusion_mf(castro_amd_ctx* c, int nboxes, const castro_amd_state_box* boxes, const castro_amd_geom* geom,
+                                       const castro_amd_params* params, const castro_amd_diffusion* diff, double max_dt,
+                                       double* d_out, void* stream)
+{
+    if (!c || nboxes < 0 || (nboxes > 0 && !boxes)) return CASTRO_AMD_ERR_ARG;
+    for (int i = 0; i < nboxes; ++i) {
+        const int rc = castro_amd_estdt_temp_diffusion_fab(c, &boxes[i].state, boxes[i].lo, boxes[i].hi, geom, params, diff, max_dt, d_out, stream);
+        if (rc != CASTRO_AMD_OK) return rc;
+    }
+    return CASTRO_AMD_OK;
+}
+
 int castro_amd_sources_mf(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
                           const double* grav, int grav_source_type, const castro_amd_rotation* rot,
                           const castro_amd_geom* geom, const castro_amd_params* params, double dt, int clean_ntimes, void* stream)
+{
+    return castro_amd_sources_mf_ex(c, stage, nboxes, boxes, grav, grav_source_type, rot, nullptr, geom, params, dt, clean_ntimes, stream);
+}
+
+int castro_amd_sources_mf_ex(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
+                             const double* grav, int grav_source_type, const castro_amd_rotation* rot,
+                             const castro_amd_diffusion* diff, const castro_amd_geom* geom, const castro_amd_params* params,
+                             double dt, int clean_ntimes, void* stream)
 {
     if (!c || (stage != 0 && stage != 1) || nboxes < 0 || (nboxes > 0 && !boxes) || !geom || !params || clean_ntimes < 0) return CASTRO_AMD_ERR_ARG;
     // the checks of the single-box entry points (castro_amd_old/new_gravity_source_fab, _rotation_source_fab, _apply_source_fab)
@@ -595,8 +704,13 @@ int castro_amd_sources_mf(castro_amd_ctx* c, int stage, int nboxes, const castro
     if (rot && (rot->rot_source_type < 1 || rot->rot_source_type > 4)) return CASTRO_AMD_ERR_ARG;
     if ((rot || (grav && stage == 1)) && geom->coord != 0) return CASTRO_AMD_ERR_ARG;
     if (rot && stage == 1 && !(dt > 0.0)) return CASTRO_AMD_ERR_ARG;
+    if (diff) {
+        const int rc = diff_check(diff, geom);
+        if (rc != CASTRO_AMD_OK) return rc;
+    }
     if (nboxes == 0) return CASTRO_AMD_OK;
     std::vector<SrcBoxDev> tab((size_t)nboxes);
+    std::vector<DiffBoxDev> dtab(diff ? (size_t)nboxes : 0);
     for (int i = 0; i < nboxes; ++i) {
         const castro_amd_source_box& b = boxes[i];
         if (!b.S_old.p || !b.S_new.p || !b.source.p || b.S_old.ncomp != NUM_STATE || b.S_new.ncomp != NUM_STATE || b.source.ncomp < 7)
@@ -621,10 +735,24 @@ int castro_amd_sources_mf(castro_amd_ctx* c, int stage, int nboxes, const castro
             T.vlo[d] = b.lo[d]; T.vhi[d] = b.hi[d];
         }
         T.nsc = b.source.ncomp;
+        // diff_src: stage 0 the term of S_old, stage 1 the corrector 0.5 DiffTerm(S_new) - 0.5 DiffTerm(S_old)
+        if (diff) {
+            const int rd = stage == 0 ? diff_box(dtab[(size_t)i], &b.S_old, nullptr, &b.source, nullptr, b.lo, b.hi)
+                                      : diff_box(dtab[(size_t)i], &b.S_new, &b.S_old, &b.source, nullptr, b.lo, b.hi);
+            if (rd != CASTRO_AMD_OK) return rd;
+        }
     }
     hipSetDevice(c->device);
+    if (diff) {
+        // a launch of its own in front of the one-pass kernel: that kernel writes S_new in place, and the stencil of the
+        // new-time term reads the neighbours' S_new.  It leaves 0 + term in UEDEN / UEINT of the valid zones; the one-pass
+        // kernel starts its sums of those two components from there instead of from zero.
+        const int rd = launch_temp_diffusion(nboxes, dtab.data(), stage == 1, to_diffdev(diff, geom), stage == 0 ? 1.0 : 0.5, -0.5, 1,
+                                             &c->diff_arena, (hipStream_t)stream, &c->prof);
+        if (rd != 0) return rd < 0 ? rd : CASTRO_AMD_ERR_HIP;
+    }
     const int rc = launch_sources_apply(stage, nboxes, tab.data(), grav, grav_source_type, rot, geom, to_devparams(params), dt, clean_ntimes,
-                                        &c->ops_arena, (hipStream_t)stream, &c->prof);
+                                        &c->ops_arena, (hipStream_t)stream, &c->prof, diff ? 1 : 0);
     return rc == 0 ? CASTRO_AMD_OK : (rc < 0 ? CASTRO_AMD_ERR_HIP : rc);
 }
 

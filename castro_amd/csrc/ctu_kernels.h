@@ -114,7 +114,17 @@ int launch_new_rot_source(const DFab& UO, const DFab& UN, const DFab& SRC, const
 struct SrcBoxDev { DFab So, Sn, Src, M0, M1, M2; int lo[3], n[3]; int vlo[3], vhi[3]; int nsc; };
 int launch_sources_apply(int stage, int nbox, const SrcBoxDev* boxes, const double* grav, int grav_type, const ::castro_amd_rotation* rot,
                          const ::castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
-                         hipStream_t stream, Profiler* prof);
+                         hipStream_t stream, Profiler* prof, int diff_on = 0);
+// thermal diffusion (diffusion_kernels.hip).  One box of a castro_amd_temp_diffusion_* launch: U (and U2, the old state of the
+// time-centred corrector) with at least one ghost zone around [lo, hi]; Src: the Source_Type FAB (p == nullptr: none);
+// Out: a one-component FAB for the bare term (p == nullptr: none); nt: tiles per direction, set by the launcher
+struct DiffBoxDev { DFab U, U2, Src, Out; int lo[3], hi[3], nt[3]; };
+// phys_lo / phys_hi: the domain face of that direction is a physical boundary (zero flux) rather than periodic
+struct DiffDev { double cond, cutoff, cutoff_hi, scale; double dh[3]; int domlo[3], domhi[3]; int phys_lo[3], phys_hi[3]; };
+int launch_temp_diffusion(int nbox, DiffBoxDev* boxes, bool two, const DiffDev& D, double m1, double m2, int init,
+                          FabOpsArena* arena, hipStream_t stream, Profiler* prof);
+int launch_estdt_temp_diffusion(const DFab& U, const int lo[3], const int hi[3], const double dx[3], const DevParams& P,
+                                double cond, double cutoff, double below, double* d_out, hipStream_t stream, Profiler* prof);
 int launch_saxpy(const DFab& D, const DFab& S, const int lo[3], const int hi[3], double a, int ncomp,
                  hipStream_t stream, Profiler* prof);
 int launch_fab_ops(int nops, const DFab* D, const DFab* X, const DFab* Y, const int* lo, const int* hi, const int* kind,

@@ -313,15 +313,65 @@ class HipHydro:
             sb.S_old, sb.S_new, sb.source = L.fab_of(so[0], *so[1]), L.fab_of(sn[0], *sn[1]), L.fab_of(src[0], *src[1])
         return arr, len(specs)
 
-    def sources_mf(self, stage, boxes, grav, grav_source_type, rot, geom, params, dt, ntimes=1, stream=None):
+    def sources_mf(self, stage, boxes, grav, grav_source_type, rot, geom, params, dt, ntimes=1, stream=None, diffusion=None):
         """castro_amd_sources_mf: stage 0 = old-time sources + S_new = S_old + dt * source + clean_state, stage 1 = new-time
-        sources + S_new += dt * source + clean_state, for every box of `boxes` (make_source_boxes)."""
+        sources + S_new += dt * source + clean_state, for every box of `boxes` (make_source_boxes).  diffusion
+        (_lib.make_diffusion): castro_amd_sources_mf_ex, the thermal-diffusion term in front of gravity and rotation."""
         arr, n = boxes
         if n:
             g = (C.c_double * 3)(*[float(x) for x in grav]) if grav is not None else None
+            if diffusion is not None:
+                L.check(self.lib.castro_amd_sources_mf_ex(self.h, int(stage), n, arr, g, int(grav_source_type),
+                                                          C.byref(rot) if rot is not None else None, C.byref(diffusion),
+                                                          C.byref(geom), C.byref(params), float(dt), int(ntimes),
+                                                          _stream_ptr(stream)), "sources_mf_ex")
+                return
             L.check(self.lib.castro_amd_sources_mf(self.h, int(stage), n, arr, g, int(grav_source_type),
                                                    C.byref(rot) if rot is not None else None, C.byref(geom), C.byref(params),
                                                    float(dt), int(ntimes), _stream_ptr(stream)), "sources_mf")
+
+    # ---- thermal diffusion (Source/diffusion/) -----------------------------------------------------------------
+    def temp_diffusion(self, state, box, source, src_box, lo, hi, diffusion, geom, mult=1.0, diff_term=None, diff_term_box=None,
+                       stream=None):
+        """source(UEDEN, UEINT) += mult * div(k grad T)(state) on [lo, hi] (Castro::add_temp_diffusion_to_source); state holds
+        one filled ghost zone around [lo, hi].  diff_term: a one-component FAB for the bare term (source may be None then)."""
+        sf = L.fab_of(source, *src_box) if source is not None else L.fab_desc(None, lo, hi, 0)
+        df = L.fab_of(diff_term, *diff_term_box) if diff_term is not None else L.fab_desc(None, lo, hi, 0)
+        L.check(self.lib.castro_amd_temp_diffusion_fab(self.h, C.byref(L.fab_of(state, *box)), C.byref(sf), C.byref(df), L.i3(lo),
+                                                       L.i3(hi), C.byref(diffusion), C.byref(geom), float(mult),
+                                                       _stream_ptr(stream)), "temp_diffusion_fab")
+
+    @staticmethod
+    def make_diffusion_boxes(specs):
+        """ctypes array of castro_amd_diffusion_box from (lo, hi, (state, box), (source, box))."""
+        arr = (L.DiffusionBox * max(len(specs), 1))()
+        for db, (lo, hi, st, src) in zip(arr, specs):
+            for d in range(3):
+                db.lo[d], db.hi[d] = lo[d], hi[d]
+            db.state, db.source = L.fab_of(st[0], *st[1]), L.fab_of(src[0], *src[1])
+        return arr, len(specs)
+
+    def temp_diffusion_mf(self, boxes, diffusion, geom, mult=1.0, stream=None):
+        """temp_diffusion for every box of `boxes` (make_diffusion_boxes) in one launch"""
+        arr, n = boxes
+        if n:
+            L.check(self.lib.castro_amd_temp_diffusion_mf(self.h, n, arr, C.byref(diffusion), C.byref(geom), float(mult),
+                                                          _stream_ptr(stream)), "temp_diffusion_mf")
+
+    def estdt_temp_diffusion(self, state, box, lo, hi, geom, params, diffusion, max_dt, out, stream=None):
+        """Castro::estdt_temp_diffusion: min-reduces 0.5 dx^2 / D over [lo, hi] into `out` (ONE device double the caller
+        initialised, e.g. out.fill_(1e200)); the caller multiplies the level minimum by cfl."""
+        L.check(self.lib.castro_amd_estdt_temp_diffusion_fab(self.h, C.byref(L.fab_of(state, *box)), L.i3(lo), L.i3(hi),
+                                                             C.byref(geom), C.byref(params), C.byref(diffusion), float(max_dt),
+                                                             C.c_void_p(out.data_ptr()), _stream_ptr(stream)),
+                "estdt_temp_diffusion_fab")
+
+    def estdt_temp_diffusion_mf(self, boxes, geom, params, diffusion, max_dt, out, stream=None):
+        arr, n = boxes
+        if n:
+            L.check(self.lib.castro_amd_estdt_temp_diffusion_mf(self.h, n, arr, C.byref(geom), C.byref(params), C.byref(diffusion),
+                                                                float(max_dt), C.c_void_p(out.data_ptr()), _stream_ptr(stream)),
+                    "estdt_temp_diffusion_mf")
 
     @staticmethod
     def make_state_boxes(specs):

@@ -54,6 +54,9 @@ extern "C" {
  *      castro_amd_halo_group_* / castro_amd_fill_boundary_group (several boxes per rank), castro_amd_berger_rigoutsos;
  *      castro_amd_hydro_opts.sborder_clean_ntimes is accepted by the staged calls; CASTRO_AMD_OP_INTERP, castro_amd_sources_mf,
  *      castro_amd_clean_state_reduce_mf, castro_amd_estdt_mf.
+ *   5 (not bumped: new entry points and a new struct only, nothing an existing caller allocates changes size or meaning):
+ *      castro_amd_diffusion, castro_amd_temp_diffusion_fab / _mf, castro_amd_estdt_temp_diffusion_fab / _mf,
+ *      castro_amd_sources_mf_ex.
  * A caller checks `castro_amd_abi_version() == CASTRO_AMD_ABI_VERSION` once after loading the library; a mismatch means
  * the library was built from another revision of this header (a 0.2 caller with 2-double vectors would be written 8 bytes
  * out of bounds by a 0.3 library). */
@@ -389,6 +392,45 @@ typedef struct castro_amd_source_box {
 int castro_amd_sources_mf(castro_amd_ctx *ctx, int stage, int nboxes, const castro_amd_source_box *boxes,
                           const double *grav /* [3] or NULL */, int grav_source_type, const castro_amd_rotation *rot /* or NULL */,
                           const castro_amd_geom *geom, const castro_amd_params *params, double dt, int clean_ntimes, void *stream);
+
+/* Explicit thermal diffusion (castro.diffuse_temp = 1, Source/diffusion/): the term div(k grad T) added to (rho E) and (rho e)
+ * at old and new time (Castro_diffusion.cpp:11-176) and the diffusion limit on the time step (timestep.cpp:259-345).
+ * Constant conductivity only (conductivity.const_conductivity; the other conductivities of Microphysics are not restated).
+ * The reference applies AMReX's MLABecLaplacian [3P, not in the reference tree]; what is evaluated here is this restatement,
+ * NOT pinned against an AMReX build.  With T = state(UTEMP) as stored (it is not recomputed), per zone
+ *   k_cc = diffuse_cond_scale_fac * (rho > cutoff ? const_conductivity * (rho < cutoff_hi ? (rho - cutoff) / (cutoff_hi - cutoff) : 1) : 0)
+ *   bx(i) = 0.5 * (k_cc(i) + k_cc(i-1)),   fx = bx(i+1) * (T(i+1) - T(i)) - bx(i) * (T(i) - T(i-1)),   likewise fy, fz
+ *   DiffTerm = fx / dx^2 + fy / dy^2 + fz / dz^2        (as dhx * fx + dhy * fy + dhz * fz, dhx = 1.0 / (dx * dx), left to right)
+ * A face on a physical domain boundary (lo_bc / hi_bc != Interior) contributes a zero flux whatever its ghost zone holds (the
+ * operator's Neumann condition, Diffusion.cpp:99-126); periodic and interior faces read the ghost zone, so `state` must hold
+ * at least ONE filled ghost zone around [lo, hi].  Inflow on a low face, Symmetry on a high face (Dirichlet in the reference,
+ * with an extrapolation of AMReX's that is not restated) and coord != 0 return CASTRO_AMD_ERR_UNSUPPORTED. */
+typedef struct castro_amd_diffusion {
+    double const_conductivity;          /* conductivity.const_conductivity */
+    double diffuse_cutoff_density;      /* castro.diffuse_cutoff_density (default -1e200) */
+    double diffuse_cutoff_density_hi;   /* castro.diffuse_cutoff_density_hi (default -1e200) */
+    double diffuse_cond_scale_fac;      /* castro.diffuse_cond_scale_fac (default 1.0) */
+} castro_amd_diffusion;
+/* source(UEDEN) += mult * DiffTerm(state), source(UEINT) += mult * DiffTerm(state) on [lo, hi] (add_temp_diffusion_to_source);
+ * diff_term (one component, or NULL): the bare DiffTerm as well (the reference's `diff_term` derive); source may be NULL then. */
+int castro_amd_temp_diffusion_fab(castro_amd_ctx *ctx, const castro_amd_fab *state, const castro_amd_fab *source /* or NULL */,
+                                  const castro_amd_fab *diff_term /* or NULL */, const int lo[3], const int hi[3],
+                                  const castro_amd_diffusion *diff, const castro_amd_geom *geom, double mult, void *stream);
+/* the same for every box of a level in ONE launch (a device table of the boxes is uploaded from host memory by the call) */
+typedef struct castro_amd_diffusion_box {
+    int lo[3], hi[3];
+    castro_amd_fab state, source;
+} castro_amd_diffusion_box;
+int castro_amd_temp_diffusion_mf(castro_amd_ctx *ctx, int nboxes, const castro_amd_diffusion_box *boxes,
+                                 const castro_amd_diffusion *diff, const castro_amd_geom *geom, double mult, void *stream);
+/* Castro::estdt_temp_diffusion: d_out[0] = min(d_out[0], min over [lo, hi] of 0.5 * dx_d^2 / D), D = const_conductivity /
+ * (rho c_v) with the RAW conductivity (no scale factor, no ramp) and c_v = k_B / ((gamma - 1) mu m_u); a zone with
+ * rho <= diffuse_cutoff_density contributes max_dt / cfl.  d_out: ONE device double the caller initialised; the caller
+ * multiplies the level minimum by cfl (Castro.cpp:1566-1590). */
+int castro_amd_estdt_temp_diffusion_fab(castro_amd_ctx *ctx, const castro_amd_fab *state, const int lo[3], const int hi[3],
+                                        const castro_amd_geom *geom, const castro_amd_params *params,
+                                        const castro_amd_diffusion *diff, double max_dt, double *d_out, void *stream);
+
 /* castro_amd_clean_state_reduce_fab / castro_amd_estdt_fab on the valid zones [lo, hi] of every box of a level, reduced
  * into ONE d_out (3 device doubles initialised by the caller): Castro_advance_ctu.cpp:168-225 and Castro::estTimeStep
  * (Castro.cpp:1507-1626) as one call per level. */
@@ -401,6 +443,19 @@ int castro_amd_clean_state_reduce_mf(castro_amd_ctx *ctx, int nboxes, const cast
                                      double *d_out, void *stream);
 int castro_amd_estdt_mf(castro_amd_ctx *ctx, int nboxes, const castro_amd_state_box *boxes,
                         const castro_amd_geom *geom, const castro_amd_params *params, double *d_out, void *stream);
+int castro_amd_estdt_temp_diffusion_mf(castro_amd_ctx *ctx, int nboxes, const castro_amd_state_box *boxes,
+                                       const castro_amd_geom *geom, const castro_amd_params *params,
+                                       const castro_amd_diffusion *diff, double max_dt, double *d_out, void *stream);
+/* castro_amd_sources_mf with the thermal-diffusion source in front of gravity and rotation, the reference's dispatch order
+ * (diff_src, grav_src, rot_src: Castro_sources.cpp): stage 0 adds DiffTerm(S_old), stage 1 adds 0.5 * DiffTerm(S_new) and then
+ * -0.5 * DiffTerm(S_old) to UEDEN and UEINT of the zeroed source before the other terms.  Two launches per stage: the stencil
+ * goes first (the one-pass kernel writes S_new in place, and the new-time term reads the neighbours' S_new), the one-pass kernel
+ * continues from the two components it left.  S_old (stage 1: S_new too) needs one filled ghost zone around [lo, hi].
+ * diff == NULL: castro_amd_sources_mf, the same bits. */
+int castro_amd_sources_mf_ex(castro_amd_ctx *ctx, int stage, int nboxes, const castro_amd_source_box *boxes,
+                             const double *grav /* [3] or NULL */, int grav_source_type, const castro_amd_rotation *rot /* or NULL */,
+                             const castro_amd_diffusion *diff /* or NULL */, const castro_amd_geom *geom,
+                             const castro_amd_params *params, double dt, int clean_ntimes, void *stream);
 
 /* Two-level AMR building blocks, refinement ratio 2 (first slice).  The reference calls AMReX for
  * all of these [3P, not in the reference tree]; the arithmetic is restated from the published descriptions and is
