@@ -9,12 +9,12 @@
 #include "../../include/castro_hydro_amd.h"
 #include <cstdlib>
 #include "ctu_kernels.h"
-namespace cad { extern int g_tile_rows; extern int g_xpad; extern int g_fuse_consup; extern int g_fused_tile_rows; extern int g_trace_tile_rows; extern int g_side_stream; extern int g_fold_r1; extern int g_fold_tile; extern int g_final_tile; extern int g_gl_sources; extern int g_gl_plm; extern int g_fold_tile_rows; extern int g_wg; extern int g_final_wg; extern int g_fused_wg; extern int g_trace_one_zone; extern int g_divu_in_trace; }
 
 using namespace cad;
 
 struct castro_amd_ctx {
     int device = 0;
+    LaunchKnobs knobs;         // read from the environment at creation, never written again
     double* arena = nullptr;
     size_t arena_doubles = 0;
     int* d_status = nullptr;
@@ -139,13 +139,13 @@ static DevGeom to_devgeom(const castro_amd_geom* g)
     return G;
 }
 
-// x extent of a scratch plane: the tile grown by 4, preceded by g_xpad unused columns and rounded up to a multiple of
-// 16 doubles when g_xpad > 0, so that zone lo[0] - 4 + (4 + g_xpad) starts a 128-byte line in every row
-static int scratch_nx(int nx) { return cad::g_xpad > 0 ? ((nx + 8 + cad::g_xpad + 15) & ~15) : nx + 8; }
+// x extent of a scratch plane: the tile grown by 4, preceded by xpad unused columns (the context's LaunchKnobs::xpad) and rounded
+// up to a multiple of 16 doubles when xpad > 0, so that zone lo[0] - 4 + (4 + xpad) starts a 128-byte line in every row
+static int scratch_nx(int xpad, int nx) { return xpad > 0 ? ((nx + 8 + xpad + 15) & ~15) : nx + 8; }
 
-static size_t plane_doubles(int nx, int ny, int nz)
+static size_t plane_doubles(int xpad, int nx, int ny, int nz)
 {
-    size_t n = (size_t)scratch_nx(nx) * (ny + 8) * (nz + 8);
+    size_t n = (size_t)scratch_nx(xpad, nx) * (ny + 8) * (nz + 8);
     return (n + 31) & ~(size_t)31;     // keep every component plane 256-byte aligned
 }
 
@@ -216,32 +216,9 @@ int castro_amd_ctx_create(castro_amd_ctx** out, int device)
     if (hipMalloc(&c->d_status, sizeof(int)) != hipSuccess) { delete c; return CASTRO_AMD_ERR_NOMEM; }
     hipMemset(c->d_status, 0, sizeof(int));
     if (hipHostMalloc(&c->h_status, sizeof(int)) != hipSuccess) { hipFree(c->d_status); delete c; return CASTRO_AMD_ERR_NOMEM; }
-    // tuning knobs (ctu_kernels.hip), process-wide, read afresh by every context creation: a variable that is not set puts its
-    // knob back to the default (until round 6 a knob kept the last value it had been given, so "unset" did not undo "set")
-    auto knob = [](const char* name, int dflt) { const char* e = std::getenv(name); return e ? std::atoi(e) : dflt; };
-    auto wg_knob = [&](const char* name, int dflt) { const int v = knob(name, dflt); return (v == 64 || v == 128 || v == 256) ? v : dflt; };
-    g_tile_rows = knob("CASTRO_AMD_TILE_ROWS", 32);
-    g_fused_tile_rows = knob("CASTRO_AMD_FUSED_TILE_ROWS", 16);
-    g_fuse_consup = knob("CASTRO_AMD_FUSE_CONSUP", 1);                 // 0: k_final<x> + k_consup
-    g_trace_tile_rows = knob("CASTRO_AMD_TRACE_TILE_ROWS", 64);
-    g_xpad = knob("CASTRO_AMD_XPAD", 0);                               // unused columns in front of every scratch row
-    g_side_stream = knob("CASTRO_AMD_SIDE_STREAM", 0);
-    g_trace_one_zone = knob("CASTRO_AMD_TRACE_ONE_ZONE", 0);
-#ifdef CAD_NUMERICS_CONTRACT
-    g_divu_in_trace = knob("CASTRO_AMD_DIVU_IN_TRACE", 1);
-#else
-    g_divu_in_trace = knob("CASTRO_AMD_DIVU_IN_TRACE", 0);
-#endif
-    g_fold_r1 = knob("CASTRO_AMD_FOLD_R1", 2);
-    g_fold_tile_rows = knob("CASTRO_AMD_FOLD_TILE_ROWS", -1);
-    g_fold_tile = knob("CASTRO_AMD_FOLD_TILE", -1);
-    g_final_tile = knob("CASTRO_AMD_FINAL_TILE", 0);
-    g_gl_sources = knob("CASTRO_AMD_GL_SOURCES", 1);
-    g_gl_plm = knob("CASTRO_AMD_GL_PLM", 1);
-    g_wg = wg_knob("CASTRO_AMD_WG", 256);
-    g_fused_wg = wg_knob("CASTRO_AMD_FUSED_WG", 128);
-    g_final_wg = wg_knob("CASTRO_AMD_FINAL_WG", 0);
-    if (g_side_stream) {
+    // a variable that is not set gives its default; what is read here holds for this context, whatever is created after it
+    c->knobs = launch_knobs_from_env();
+    if (c->knobs.side_stream) {
         if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
@@ -276,7 +253,7 @@ void castro_amd_ctx_destroy(castro_amd_ctx* c)
 static int reserve_planes(castro_amd_ctx* c, int nx, int ny, int nz, int planes)
 {
     if (!c || nx <= 0 || ny <= 0 || nz <= 0) return CASTRO_AMD_ERR_ARG;
-    size_t need = plane_doubles(nx, ny, nz) * (size_t)planes;
+    size_t need = plane_doubles(c->knobs.xpad, nx, ny, nz) * (size_t)planes;
     if (need <= c->arena_doubles) return CASTRO_AMD_OK;
     hipSetDevice(c->device);
     if (c->arena) { hipDeviceSynchronize(); hipFree(c->arena); c->arena = nullptr; c->arena_doubles = 0; }
@@ -380,9 +357,9 @@ static int prepare_box(castro_amd_ctx* c, const int bxlo[3], const int bxhi[3], 
     }
     const int nx = bxhi[0] - bxlo[0] + 1, ny = bxhi[1] - bxlo[1] + 1, nz = bxhi[2] - bxlo[2] + 1;
     B.nx = nx; B.ny = ny; B.nz = nz;
-    t.glo[0] -= g_xpad;
-    t.NX = scratch_nx(nx); t.NY = ny + 8; t.NZ = nz + 8;
-    t.NC = (long)plane_doubles(nx, ny, nz);
+    t.glo[0] -= c->knobs.xpad;
+    t.NX = scratch_nx(c->knobs.xpad, nx); t.NY = ny + 8; t.NZ = nz + 8;
+    t.NC = (long)plane_doubles(c->knobs.xpad, nx, ny, nz);
 
     if (!fab_contains(Sborder, glo, ghi)) return CASTRO_AMD_ERR_ARG;
     if (!fab_contains(S_new, bxlo, bxhi)) return CASTRO_AMD_ERR_ARG;
@@ -471,6 +448,7 @@ int castro_amd_ctu_hydro_fab_ex(castro_amd_ctx* c, const int bxlo[3], const int 
     DevScratch S;
     carve_scratch(c->arena, B.t, B.reset_rhoe, S);
     LaunchAux aux;
+    aux.knobs = c->knobs;
     aux.sb_clean = opts->sborder_clean_ntimes;
     aux.side = c->side; aux.ev_fork = c->ev_fork; aux.ev_join = c->ev_join;
     for (int d = 0; d < 3; ++d) { aux.bc_lo[d] = geom->lo_bc[d]; aux.bc_hi[d] = geom->hi_bc[d]; }
@@ -917,7 +895,7 @@ int castro_amd_ctu_hydro_mf(castro_amd_ctx* const* ctxs, void* const* streams, i
         if (with_src && (params->source_term_predictor == 1 || ctxs[0]->src_corr.p || opts->sborder_clean_ntimes > 0 || opts->clean_ntimes > 0)) ok = false;
         DevParams devP = to_devparams(params);
         devP.dtp = opts->d_dt;
-        if (ok && level_launch_supported(devP, opts->flags, with_src)) {
+        if (ok && level_launch_supported(ctxs[0]->knobs, devP, opts->flags, with_src)) {
             castro_amd_ctx* c0 = ctxs[0];
             hipSetDevice(c0->device);
             std::vector<PreparedBox> pb((size_t)nboxes);
@@ -975,7 +953,7 @@ int castro_amd_ctu_hydro_mf(castro_amd_ctx* const* ctxs, void* const* streams, i
                         L.U = B.dS; L.Unew = B.dN; L.Src = B.dSrc;
                         for (int d = 0; d < 3; ++d) { L.fl[d] = B.dF[d]; L.mass[d] = B.dM[d]; L.qe[d] = B.dQ[d]; L.acc_hi[d] = B.acc_hi[d]; }
                     }
-                    const int rc = launch_ctu_hydro_level(i1 - i0, lb.data(), &c0->level_arena, dg, devP, dt, opts->flags, c0->d_status,
+                    const int rc = launch_ctu_hydro_level(c0->knobs, i1 - i0, lb.data(), &c0->level_arena, dg, devP, dt, opts->flags, c0->d_status,
                                                           main_s, &c0->prof, opts->clean_ntimes, opts->d_out, opts->sborder_clean_ntimes);
                     if (rc != 0) return rc;
                 }

@@ -62,8 +62,48 @@ void prof_begin(Profiler* p, const char* name, hipStream_t s);
 void prof_end(Profiler* p, hipStream_t s);
 void prof_collect(Profiler* p);
 
-// what a call carries besides its arrays: in-place cleaning of Sborder inside k_ctoprim, the context's side stream
+// Launch forms and launch geometry of the hydro path.  A context reads them from the environment when it is created
+// (launch_knobs_from_env) and never writes them again: they hold for that context only, whatever is created beside it.
+struct LaunchKnobs {
+    int tile_rows = 32;         // CASTRO_AMD_TILE_ROWS: 0 = plain row-major workgroup order; > 0 = XCD-tiled order with this many rows per y-tile
+    int trace_tile_rows = 64;   // CASTRO_AMD_TRACE_TILE_ROWS: rows per y-tile of the trace launch and its block-start fix-up (its L2 holds
+                                // only Q now that the stores are non-temporal: 2.72 -> 2.60 ms; -1: tile_rows)
+    int fold_tile_rows = -1;    // CASTRO_AMD_FOLD_TILE_ROWS: rows per y-tile of the k_trans1_fold launch (-1: tile_rows)
+    int fused_tile_rows = 16;   // CASTRO_AMD_FUSED_TILE_ROWS: rows per y-tile of the k_finalx_consup row order (0: plain)
+    int wg = 256;               // CASTRO_AMD_WG: threads per workgroup of every launch built from a LinBox (64, 128 or 256)
+    int final_wg = 0;           // CASTRO_AMD_FINAL_WG: k_final<y>, k_final<z> only (0: wg)
+    int fused_wg = 128;         // CASTRO_AMD_FUSED_WG: k_finalx_consup (its waves share nothing: 2.16-2.20 ms at 256, 2.04-2.05 at 128 / 64
+                                // threads, profiles/r03x_*)
+    int xpad = 0;               // CASTRO_AMD_XPAD: unused columns in front of every scratch row (capi.hip: scratch_nx)
+    int fuse_consup = 1;        // CASTRO_AMD_FUSE_CONSUP: 1 = k_finalx_consup (the x faces of the final stage and consup_hydro in one
+                                // kernel), 0 = k_final<x> + k_consup
+    int fold_r1 = 2;            // CASTRO_AMD_FOLD_R1: the first y / z Riemann solves inside the transverse stage: != 0 = k_trans1_fold_lds
+                                // (records parked in LDS; -0.35 ms per 256^3 step), 0 = two k_riemann1 launches + k_trans1 (profiles/r03c_*, r03d_*)
+    int fold_tile = -1;         // CASTRO_AMD_FOLD_TILE: 1 = k_trans1_tile<4, 2> (a 4 x 2 tile of rows per workgroup), 2 = <2, 4>,
+                                // 0 = k_trans1_fold_lds; -1: <4, 2> for boxes of at least 96 rows in y and z (128^3: equal, 64^3: the fold
+                                // kernel is faster; profiles/r05c_ab_fold_tile_kernel.txt); `contract` build only
+    int final_tile = 0;         // CASTRO_AMD_FINAL_TILE: 1 = the final stage as ONE zone-centred launch (k_final_tile<4, 2>); `contract` build only
+    int gl_sources = 1;         // CASTRO_AMD_GL_SOURCES: 0 = traced source terms run the 7-variable kernels as in round 4 (A/B)
+    int gl_plm = 1;             // CASTRO_AMD_GL_PLM: 0 = the PLM trace (ppm_type = 0) runs the 7-variable kernels as before round 6 (A/B)
+    // CASTRO_AMD_DIVU_IN_TRACE: div(u) inside k_trace_pair instead of a k_divu_pair launch of its own.  `contract`: on (-0.08 ms per
+    // 256^3 step, -0.02 ms at 128^3: the launch of 0.18 ms becomes 0.09 ms more trace); `exact`: off (its trace kernel sits at
+    // 252 VGPRs: +0.1 ms).  profiles/r06j_*
+#ifdef CAD_NUMERICS_CONTRACT
+    int divu_in_trace = 1;
+#else
+    int divu_in_trace = 0;
+#endif
+    int trace_one_zone = 0;     // CASTRO_AMD_TRACE_ONE_ZONE: 1 = k_trace (one zone per thread) + k_riemann1<x> instead of k_trace_pair: an
+                                // occupancy A/B, slower
+    int side_stream = 0;        // CASTRO_AMD_SIDE_STREAM: 1 = k_divu runs on the context's side stream beside the trace kernel; measured: no
+                                // gain, two independent pipelines on two streams take as long as one after the other (tools/concurrency_probe.py)
+};
+// the variables above as the environment has them now; one that is not set gives the default
+LaunchKnobs launch_knobs_from_env();
+
+// what a call carries besides its arrays: the context's knobs, in-place cleaning of Sborder inside k_ctoprim, the context's side stream
 struct LaunchAux {
+    LaunchKnobs knobs;
     int sb_clean = 0;
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -88,9 +128,10 @@ struct LevelBoxDesc {
     DFab Src;              // old-time source FAB to be traced (p == nullptr: none); all boxes of a launch alike
 };
 // default options only (PPM, CGF solver, no staging, the default kernel forms; traced source terms without a predictor): else box by box
-bool level_launch_supported(const DevParams& P, int flags, bool with_src = false);
-int launch_ctu_hydro_level(int nbox, const LevelBoxDesc* boxes, FabOpsArena* table, const DevGeom& g, const DevParams& P, double dt,
-                           int flags, int* d_status, hipStream_t stream, Profiler* prof, int clean_ntimes, double* red, int sb_clean);
+// K: the knobs of the context whose prepare_box laid out the boxes' scratch
+bool level_launch_supported(const LaunchKnobs& K, const DevParams& P, int flags, bool with_src = false);
+int launch_ctu_hydro_level(const LaunchKnobs& K, int nbox, const LevelBoxDesc* boxes, FabOpsArena* table, const DevGeom& g, const DevParams& P,
+                           double dt, int flags, int* d_status, hipStream_t stream, Profiler* prof, int clean_ntimes, double* red, int sb_clean);
 
 // auxiliary per-FAB kernels (aux_kernels.hip)
 int launch_clean_state(const DFab& U, const int lo[3], const int hi[3], const DevParams& P, int ntimes,

@@ -3326,57 +3326,59 @@ k_final_tile(Tile t, TileRows b, const double* __restrict__ Q, DevScratch S, Dev
 // ---------------------------------------------------------------------------------------
 // host-side launcher
 // ---------------------------------------------------------------------------------------
-int g_fold_tile_rows = -1; // rows per y-tile of the k_trans1_fold launch (-1: g_tile_rows)
-int g_gl_sources = 1;     // CASTRO_AMD_GL_SOURCES=0: traced source terms run the 7-variable kernels as in round 4 (A/B)
-int g_gl_plm = 1;         // CASTRO_AMD_GL_PLM=0: the PLM trace (ppm_type = 0) runs the 7-variable kernels as before round 6 (A/B)
-int g_final_tile = 0;     // CASTRO_AMD_FINAL_TILE: 1 = the final stage as ONE zone-centred launch (k_final_tile<4, 2>); `contract` build only
-int g_fold_tile = -1;     // CASTRO_AMD_FOLD_TILE: 1 = k_trans1_tile<4, 2> (a 4 x 2 tile of rows per workgroup), 2 = <2, 4>, 0 = k_trans1_fold_lds;
-                          // -1 (default): <4, 2> for boxes of at least 96 rows in y and z (128^3: equal, 64^3: the fold kernel is faster;
-                          // profiles/r05c_ab_fold_tile_kernel.txt); `contract` build only
-int g_fold_r1 = 2;        // the first y / z Riemann solves inside the transverse stage: != 0 = k_trans1_fold_lds (records parked in LDS;
-                          // -0.35 ms per 256^3 step), 0 = two k_riemann1 launches + k_trans1 (CASTRO_AMD_FOLD_R1; profiles/r03c_*, r03d_*)
-// CASTRO_AMD_DIVU_IN_TRACE: div(u) inside k_trace_pair instead of a k_divu_pair launch of its own.  `contract`: on (-0.08 ms per 256^3 step,
-// -0.02 ms at 128^3: the launch of 0.18 ms becomes 0.09 ms more trace); `exact`: off (its trace kernel sits at 252 VGPRs: +0.1 ms).
-// profiles/r06j_*
-#ifdef CAD_NUMERICS_CONTRACT
-int g_divu_in_trace = 1;
-#else
-int g_divu_in_trace = 0;
-#endif
-int g_trace_one_zone = 0; // CASTRO_AMD_TRACE_ONE_ZONE=1: k_trace (one zone per thread) + k_riemann1<x> instead of k_trace_pair: an occupancy A/B, slower
-int g_side_stream = 0;    // 1: k_divu runs on the context's side stream beside the trace kernel (CASTRO_AMD_SIDE_STREAM); measured: no gain,
-                          // two independent pipelines on two streams take as long as one after the other (tools/concurrency_probe.py)
-int g_tile_rows = 32;     // 0: plain row-major workgroup order; > 0: XCD-tiled order with this many rows per y-tile
-int g_trace_tile_rows = 64;   // rows per y-tile of the trace launch (its L2 holds only Q now that the stores are non-temporal: 2.72 -> 2.60 ms; -1: g_tile_rows)
+// the one table of the launcher's environment variables (defaults: LaunchKnobs, ctu_kernels.h)
+LaunchKnobs launch_knobs_from_env()
+{
+    auto knob = [](const char* name, int dflt) { const char* e = std::getenv(name); return e ? std::atoi(e) : dflt; };
+    auto wg_knob = [&](const char* name, int dflt) { const int v = knob(name, dflt); return (v == 64 || v == 128 || v == 256) ? v : dflt; };
+    const LaunchKnobs d;
+    LaunchKnobs K;
+    K.tile_rows = knob("CASTRO_AMD_TILE_ROWS", d.tile_rows);
+    K.trace_tile_rows = knob("CASTRO_AMD_TRACE_TILE_ROWS", d.trace_tile_rows);
+    K.fold_tile_rows = knob("CASTRO_AMD_FOLD_TILE_ROWS", d.fold_tile_rows);
+    K.fused_tile_rows = knob("CASTRO_AMD_FUSED_TILE_ROWS", d.fused_tile_rows);
+    K.wg = wg_knob("CASTRO_AMD_WG", d.wg);
+    K.final_wg = wg_knob("CASTRO_AMD_FINAL_WG", d.final_wg);
+    K.fused_wg = wg_knob("CASTRO_AMD_FUSED_WG", d.fused_wg);
+    K.xpad = knob("CASTRO_AMD_XPAD", d.xpad);
+    K.fuse_consup = knob("CASTRO_AMD_FUSE_CONSUP", d.fuse_consup);
+    K.fold_r1 = knob("CASTRO_AMD_FOLD_R1", d.fold_r1);
+    K.fold_tile = knob("CASTRO_AMD_FOLD_TILE", d.fold_tile);
+    K.final_tile = knob("CASTRO_AMD_FINAL_TILE", d.final_tile);
+    K.gl_sources = knob("CASTRO_AMD_GL_SOURCES", d.gl_sources);
+    K.gl_plm = knob("CASTRO_AMD_GL_PLM", d.gl_plm);
+    K.divu_in_trace = knob("CASTRO_AMD_DIVU_IN_TRACE", d.divu_in_trace);
+    K.trace_one_zone = knob("CASTRO_AMD_TRACE_ONE_ZONE", d.trace_one_zone);
+    K.side_stream = knob("CASTRO_AMD_SIDE_STREAM", d.side_stream);
+    return K;
+}
 
-// rows per y-tile of the launches the calling thread is building right now, if it differs from g_tile_rows (the trace launch
-// and its block-start fix-up must agree on one workgroup order); thread-local, so that host threads driving their own
-// contexts never see each other's choice.  The g_* knobs themselves are written by castro_amd_ctx_create only.
-static thread_local int tl_tile_rows = -1;
-// threads per workgroup of the launches the calling thread is building (A/B: CASTRO_AMD_FINAL_WG for k_final<y,z>)
-static thread_local unsigned tl_wg = 0;     // 0: g_wg
-int g_wg = 256;           // CASTRO_AMD_WG: every launch built by linbox / linbox2 (64, 128 or 256)
-int g_final_wg = 0;       // CASTRO_AMD_FINAL_WG: k_final<y>, k_final<z> only (0: g_wg)
-int g_fused_wg = 128;     // CASTRO_AMD_FUSED_WG: k_finalx_consup (its waves share nothing: 2.16-2.20 ms at 256, 2.04-2.05 at 128 / 64 threads, profiles/r03x_*)
+// Workgroup order and size of a launch: rows per y-tile (0: plain row-major order) and threads per workgroup.  The knobs whose
+// -1 / 0 stands for "the general value" are resolved here and nowhere else.
+struct Shape { int ty; unsigned wg; };
+static Shape plain_shape(const LaunchKnobs& K) { return { K.tile_rows, (unsigned)K.wg }; }
+static Shape trace_shape(const LaunchKnobs& K) { return { K.trace_tile_rows >= 0 ? K.trace_tile_rows : K.tile_rows, (unsigned)K.wg }; }
+static Shape fold_shape(const LaunchKnobs& K) { return { K.fold_tile_rows >= 0 ? K.fold_tile_rows : K.tile_rows, (unsigned)K.wg }; }
+static Shape final_shape(const LaunchKnobs& K) { return { K.tile_rows, (unsigned)(K.final_wg > 0 ? K.final_wg : K.wg) }; }   // k_final<y>, k_final<z>
 
-static LinBox linbox(const int lo[3], const int hi[3], long& n)
+static LinBox linbox(const int lo[3], const int hi[3], Shape sh, long& n)
 {
     LinBox b;
     n = 1;
     for (int d = 0; d < 3; ++d) { b.lo[d] = lo[d]; b.n[d] = hi[d] - lo[d] + 1; n *= b.n[d]; }
-    b.ty = tl_tile_rows >= 0 ? tl_tile_rows : g_tile_rows;
+    b.ty = sh.ty;
     b.w = 1;
     b.hi0 = hi[0];
-    b.wg = tl_wg ? tl_wg : (unsigned)g_wg;
+    b.wg = sh.wg;
     b.nb = (unsigned)((n + b.wg - 1) / b.wg);
     if (b.ty > 0) b.nb = (b.nb + 7u) & ~7u;
     return b;
 }
 
 // pairs of x-adjacent zones: thread ii of a row handles lo[0] + 2 ii and, if <= hi0, the next one
-static LinBox linbox2(const int lo[3], const int hi[3], long& n)
+static LinBox linbox2(const int lo[3], const int hi[3], Shape sh, long& n)
 {
-    LinBox b = linbox(lo, hi, n);
+    LinBox b = linbox(lo, hi, sh, n);
     b.w = 2;
     b.n[0] = (b.n[0] + 1) / 2;
     n = (long)b.n[0] * b.n[1] * b.n[2];
@@ -3385,16 +3387,77 @@ static LinBox linbox2(const int lo[3], const int hi[3], long& n)
     return b;
 }
 
-#define KL2(name, kern, lo, hi, ...)                                                         \
+// ---- launch geometry shared by launch_ctu_hydro and launch_ctu_hydro_level (which must give every box what the former gives it)
+static SkipBox grow(const Tile& t, int n)
+{
+    SkipBox b;
+    for (int d = 0; d < 3; ++d) { b.lo[d] = t.lo[d] - n; b.hi[d] = t.hi[d] + n; }
+    return b;
+}
+// the faces of direction d of bx, grown by n in the transverse directions
+static SkipBox face_box(const Tile& t, int d, int n)
+{
+    SkipBox b = grow(t, n);
+    b.lo[d] = t.lo[d]; b.hi[d] = t.hi[d] + 1;
+    return b;
+}
+// the kernels whose waves overlap by one slot (fold_thread) take 63 new slots per wave
+static long slot_waves(long slots) { return (slots + 62) / 63; }
+// x slots of a row of the final stage: pairs of x faces of bx
+static int face_slots(const Tile& t) { const int nx = t.hi[0] - t.lo[0] + 1; return (nx + 1) / 2 + 1; }
+// workgroups of k_trans1_fold_lds over the pairs of b
+static unsigned fold_blocks(const LinBox& b)
+{
+    const long n = (long)b.n[0] * b.n[1] * b.n[2];
+    unsigned nb = (unsigned)((slot_waves(n) + FOLD_WG / 64 - 1) / (FOLD_WG / 64));
+    if (b.ty > 0) nb = (nb + 7u) & ~7u;
+    return nb;
+}
+// k_finalx_consup over bx
+static XRows x_rows(const Tile& t, const LaunchKnobs& K)
+{
+    XRows xr;
+    for (int d = 0; d < 3; ++d) xr.lo[d] = t.lo[d];
+    xr.hi0 = t.hi[0];
+    xr.nslot = face_slots(t); xr.ny = t.hi[1] - t.lo[1] + 1; xr.nz = t.hi[2] - t.lo[2] + 1;
+    xr.ty = K.fused_tile_rows;
+    xr.wv = (unsigned)K.fused_wg / 64u;
+    xr.nb = ((unsigned)((slot_waves((long)xr.nslot * xr.ny * xr.nz) + xr.wv - 1) / xr.wv) + 7u) & ~7u;
+    return xr;
+}
+// an ry x rz tile of rows per workgroup (k_trans1_tile, k_final_tile): nslot x ny x nz slots from lo on, bands of band_rows rows (0: one band)
+static TileRows tile_rows(const int lo[3], int hi0, int nslot, int ny, int nz, int ry, int rz, int band_rows)
+{
+    TileRows tr;
+    for (int d = 0; d < 3; ++d) tr.lo[d] = lo[d];
+    tr.hi0 = hi0;
+    tr.nslot = nslot; tr.ny = ny; tr.nz = nz;
+    tr.ntj = (ny + ry - 1) / ry; tr.ntk = (nz + rz - 1) / rz;
+    tr.band = band_rows > 0 ? (band_rows + ry - 1) / ry : tr.ntj;
+    tr.nb = ((unsigned)slot_waves((long)tr.nslot * tr.ntj * tr.ntk) + 7u) & ~7u;
+    return tr;
+}
+// cdtdx = dt/dx/3 (Castro_ctu_hydro.cpp:688-690); hdtdx = 0.5*dt/dx (:684-686)
+struct StepConsts { double cdtdx, cdtdy, cdtdz, hdtdx, hdtdy, hdtdz, area0, area1, area2, vol; };
+static StepConsts step_consts(const DevGeom& g, double dt)
+{
+    return { dt / g.dx[0] / 3.0, dt / g.dx[1] / 3.0, dt / g.dx[2] / 3.0, 0.5 * dt / g.dx[0], 0.5 * dt / g.dx[1], 0.5 * dt / g.dx[2],
+             g.dx[1] * g.dx[2], g.dx[0] * g.dx[2], g.dx[0] * g.dx[1], g.dx[0] * g.dx[1] * g.dx[2] };
+}
+
+// one launch of `kern` over [lo, hi] on `strm` in the shape `sh`: BOX = linbox (a zone per thread) or linbox2 (an x pair per thread)
+#define KL_ON(strm, BOX, name, kern, sh, lo, hi, ...)                                        \
     do {                                                                                     \
         long n_;                                                                             \
-        LinBox b_ = linbox2(lo, hi, n_);                                                     \
+        LinBox b_ = BOX(lo, hi, sh, n_);                                                     \
         if (n_ > 0) {                                                                        \
-            prof_begin(prof, name, stream);                                                  \
-            hipLaunchKernelGGL(kern, dim3(b_.nb), dim3(b_.wg), 0, stream, t, b_, __VA_ARGS__); \
-            prof_end(prof, stream);                                                          \
+            prof_begin(prof, name, strm);                                                    \
+            hipLaunchKernelGGL(kern, dim3(b_.nb), dim3(b_.wg), 0, strm, t, b_, __VA_ARGS__); \
+            prof_end(prof, strm);                                                            \
         }                                                                                    \
     } while (0)
+#define KL(name, kern, sh, lo, hi, ...) KL_ON(stream, linbox, name, kern, sh, lo, hi, __VA_ARGS__)
+#define KL2(name, kern, sh, lo, hi, ...) KL_ON(stream, linbox2, name, kern, sh, lo, hi, __VA_ARGS__)
 
 #define K_R1_0(V) (k_riemann1<0, false, V>)
 #define K_R1_1(V) (k_riemann1<1, false, V>)
@@ -3403,27 +3466,13 @@ static LinBox linbox2(const int lo[3], const int hi[3], long& n)
 #define K_FY(V) (k_final<1, false, false, V>)
 #define K_FZ(V) (k_final<2, false, false, V>)
 // the instantiation of a kernel template for `solv` (see interface_flux): KERN(2), KERN(1) or KERN(0)
-#define KL2_SOLV(name, KERN, lo, hi, ...)                                                    \
+#define KL2_SOLV(name, KERN, sh, lo, hi, ...)                                                \
     do {                                                                                     \
-        if (solv == 2) KL2(name, KERN(2), lo, hi, __VA_ARGS__);                              \
-        else if (solv == 1) KL2(name, KERN(1), lo, hi, __VA_ARGS__);                         \
-        else KL2(name, KERN(0), lo, hi, __VA_ARGS__);                                        \
+        if (solv == 2) KL2(name, KERN(2), sh, lo, hi, __VA_ARGS__);                          \
+        else if (solv == 1) KL2(name, KERN(1), sh, lo, hi, __VA_ARGS__);                     \
+        else KL2(name, KERN(0), sh, lo, hi, __VA_ARGS__);                                    \
     } while (0)
 
-#define KL(name, kern, lo, hi, ...)                                                          \
-    do {                                                                                     \
-        long n_;                                                                             \
-        LinBox b_ = linbox(lo, hi, n_);                                                      \
-        if (n_ > 0) {                                                                        \
-            prof_begin(prof, name, stream);                                                  \
-            hipLaunchKernelGGL(kern, dim3(b_.nb), dim3(b_.wg), 0, stream, t, b_, __VA_ARGS__); \
-            prof_end(prof, stream);                                                          \
-        }                                                                                    \
-    } while (0)
-
-int g_xpad = 0;            // see capi.hip scratch_nx
-int g_fused_tile_rows = 16; // rows per y-tile of the k_finalx_consup row order (0: plain)
-int g_fuse_consup = 1;    // 1: k_finalx_consup (the x faces of the final stage and consup_hydro in one kernel)
 // outer box minus inner box as up to six slabs: z slabs over the full x,y extent, y slabs over the inner z range,
 // x slabs over the inner y,z range (thin in x: a wavefront then covers many rows, no idle lanes)
 static int shell_boxes(const int olo[3], const int ohi[3], const int ilo[3], const int ihi[3], int lo[6][3], int hi[6][3])
@@ -3449,6 +3498,8 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
                      const LaunchAux& aux)
 {
     const LevelTab nolv = { nullptr, nullptr, 0 };       // one box: the kernels take their arguments as passed
+    const LaunchKnobs& K = aux.knobs;
+    const Shape plain = plain_shape(K);
     // Staged execution (CASTRO_AMD_STAGE_A / _B): A = what needs no ghost zone of Sborder -- ctoprim on the valid
     // zones, PPM tracing on grow(bx, -3) -- so that a caller can run it while the halo exchange is in flight;
     // B = the rest (ctoprim on the ghost shell, tracing on the remaining zones, everything downstream).
@@ -3461,7 +3512,7 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
     // GEN == 0 instantiations keep their transverse-stage records in the 7-plane state form (store_f1: QI), so they are
     // used only where EVERY kernel of the call is one: the all-default path.  A non-default final stage, the flux
     // limiters, transverse_reset_rhoe and ppm_temp_fix run kernels of the full solver set (flux-form records).
-    const bool plain_path = !(P.ppm_temp_fix == 2 && P.riemann_solver != 2) && P.reset_rhoe != 1 && g_fuse_consup == 1
+    const bool plain_path = !(P.ppm_temp_fix == 2 && P.riemann_solver != 2) && P.reset_rhoe != 1 && K.fuse_consup == 1
                             && P.limit_small_dens != 1 && P.limit_large_vel != 1;
     // gamma_law_edges (contract build): the GEN == 0 readers take (rho e) of an edge state from its p, which only the trace
     // kernel of the no-source PPM path promises (k_trace_pair<true, 7, 0>); traces with source terms or PLM run the GEN >= 1 set
@@ -3471,7 +3522,7 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
     // arithmetic (for the default fourth-order limiter, plm_limiter = 2) --, with one it carries the hydrostatic part and at such a face it
     // drops the differences across it, and the slope of (rho e) would no longer be that of p over (gamma - 1): those runs keep the
     // 7-variable kernels.  CASTRO_AMD_GL_PLM=0 is the A/B knob)
-    bool plm_gl = P.ppm_type == 0 && g_gl_plm;
+    bool plm_gl = P.ppm_type == 0 && K.gl_plm;
     if (plm_gl && P.use_pslope == 1) {
         if (Src.p) plm_gl = false;
         // pslope is the fourth-order form whatever castro.plm_limiter says: with plm_limiter = 1 the other variables -- (rho e) among
@@ -3479,41 +3530,32 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
         if (P.plm_iorder != 1 && P.plm_limiter != 2) plm_gl = false;
         for (int d = 0; d < 3; ++d) if (g.sym_lo[d] || g.sym_hi[d]) plm_gl = false;
     }
-    const bool gl_ok = !gamma_law_edges(0) || ((P.ppm_type == 1 || plm_gl) && (!Src.p || g_gl_sources));
+    const bool gl_ok = !gamma_law_edges(0) || ((P.ppm_type == 1 || plm_gl) && (!Src.p || K.gl_sources));
     const int solv = (P.riemann_solver == 1) ? 2 : ((P.riemann_solver == 2 || P.hybrid_riemann == 1 || !plain_path || !gl_ok) ? 1 : 0);
     const int lean_q = (gamma_law_edges(0) && solv == 0) ? (clean_ntimes > 0 ? 3 : 1) : 0;      // see k_ctoprim
     const bool stage_a = (flags & 4) != 0, stage_b = (flags & 8) != 0, staged = stage_a || stage_b;
     const SkipBox none = { { 0, 0, 0 }, { -1, -1, -1 } };
-    SkipBox valid_box, inner_box;
-    for (int d = 0; d < 3; ++d) {
-        valid_box.lo[d] = t.lo[d]; valid_box.hi[d] = t.hi[d];
-        inner_box.lo[d] = t.lo[d] + 3; inner_box.hi[d] = t.hi[d] - 3;
-    }
+    const SkipBox inner_box = grow(t, -3);
     const bool inner_ok = inner_box.lo[0] <= inner_box.hi[0] && inner_box.lo[1] <= inner_box.hi[1] && inner_box.lo[2] <= inner_box.hi[2];
 
     // boxes
-    const int olo[3] = { t.lo[0] - 1, t.lo[1] - 1, t.lo[2] - 1 };
-    const int ohi[3] = { t.hi[0] + 1, t.hi[1] + 1, t.hi[2] + 1 };
-    const int qlo[3] = { t.lo[0] - 4, t.lo[1] - 4, t.lo[2] - 4 };     // grow(bx, 4): the zones of Sborder the path reads
-    const int qhi[3] = { t.hi[0] + 4, t.hi[1] + 4, t.hi[2] + 4 };
+    const SkipBox ob = grow(t, 1);
+    const SkipBox qb = grow(t, 4);      // the zones of Sborder the path reads
 
     // PPM tracing of the zones of [lo,hi] with the first x Riemann solve fused in, for the faces whose two zones the
     // launch covers; the faces at the workgroup starts follow in a one-thread-per-workgroup launch, those on the
     // x faces of the launch box (lo[0] and hi[0] + 1) are left to the caller.
     // div(u) of the nodes of grow(bx, 1) inside the trace launches (every zone of that box goes through trace_with_xriemann on this
     // path, staged or not) instead of a k_divu_pair launch of its own; the hybrid solver needs k_divu's shock flags before the trace
-    const bool divu_in_trace = g_divu_in_trace && !Src.p && P.ppm_type == 1 && !tfix && P.hybrid_riemann != 1 && !g_trace_one_zone;
+    const bool divu_in_trace = K.divu_in_trace && !Src.p && P.ppm_type == 1 && !tfix && P.hybrid_riemann != 1 && !K.trace_one_zone;
     auto trace_with_xriemann = [&](const int lo[3], const int hi[3]) {
-        // the trace launch and the block-start fix-up share one workgroup order: both see the trace's rows per y-tile
-        struct RowsGuard { int keep; RowsGuard() : keep(tl_tile_rows) { if (g_trace_tile_rows >= 0) tl_tile_rows = g_trace_tile_rows; }
-                           ~RowsGuard() { tl_tile_rows = keep; } } rows_guard;
-        {
+        // the trace launch and the block-start fix-up share one workgroup order: both get the trace's rows per y-tile
+        const Shape trace = trace_shape(K);
 #define K_(V) (k_trace_pair<true, 7, V>)
-            KL2_SOLV("k_trace", K_, lo, hi, S.Q, S, g, dt, P, none, nolv, divu_in_trace ? 1 : 0);
+        KL2_SOLV("k_trace", K_, trace, lo, hi, S.Q, S, g, dt, P, none, nolv, divu_in_trace ? 1 : 0);
 #undef K_
-        }
         long n_;
-        LinBox b_ = linbox2(lo, hi, n_);
+        LinBox b_ = linbox2(lo, hi, trace, n_);
         if (n_ > 0) {
             prof_begin(prof, "k_riemann1_blockstart", stream);
             auto kbs = solv == 2 ? k_riemann1_blockstart<2> : solv == 1 ? k_riemann1_blockstart<1> : k_riemann1_blockstart<0>;
@@ -3524,7 +3566,7 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
 
     if (stage_a) {
         if (splittable) {
-            KL("k_ctoprim", k_ctoprim<false>, t.lo, t.hi, Sborder, S.Q, P, d_status, none, 0, nolv, lean_q, 0, ShellBoxes{}, BcKinds{});
+            KL("k_ctoprim", k_ctoprim<false>, plain, t.lo, t.hi, Sborder, S.Q, P, d_status, none, 0, nolv, lean_q, 0, ShellBoxes{}, BcKinds{});
             if (inner_ok) trace_with_xriemann(inner_box.lo, inner_box.hi);
         }
         return hipGetLastError() == hipSuccess ? 0 : -4;
@@ -3541,17 +3583,17 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
     const ShellBoxes no_shell = {};
     bool have_bc = false;
     for (int d = 0; d < 3; ++d) {
-        ilo[d] = qlo[d]; ihi[d] = qhi[d];
+        ilo[d] = qb.lo[d]; ihi[d] = qb.hi[d];
         M.lo[d] = g.domlo[d]; M.hi[d] = g.domhi[d];
         M.kind_lo[d] = aux.bc_lo[d] == 0 ? 0 : (aux.bc_lo[d] >= 3 ? 2 : 1);      // Symmetry, SlipWall, NoSlipWall mirror
         M.kind_hi[d] = aux.bc_hi[d] == 0 ? 0 : (aux.bc_hi[d] >= 3 ? 2 : 1);
         if (!fill_bc) continue;
-        if (M.kind_lo[d] != 0 && qlo[d] < g.domlo[d]) { ilo[d] = g.domlo[d]; have_bc = true; }
-        if (M.kind_hi[d] != 0 && qhi[d] > g.domhi[d]) { ihi[d] = g.domhi[d]; have_bc = true; }
+        if (M.kind_lo[d] != 0 && qb.lo[d] < g.domlo[d]) { ilo[d] = g.domlo[d]; have_bc = true; }
+        if (M.kind_hi[d] != 0 && qb.hi[d] > g.domhi[d]) { ihi[d] = g.domhi[d]; have_bc = true; }
         // the tile lies inside the domain, and a mirrored ghost layer finds its image among the in-domain zones of this FAB
         if (t.lo[d] < ilo[d] || t.hi[d] > ihi[d]) return -1;
-        if (M.kind_lo[d] == 2 && 2 * g.domlo[d] - qlo[d] - 1 > ihi[d]) return -2;
-        if (M.kind_hi[d] == 2 && 2 * g.domhi[d] - qhi[d] + 1 < ilo[d]) return -2;
+        if (M.kind_lo[d] == 2 && 2 * g.domlo[d] - qb.lo[d] - 1 > ihi[d]) return -2;
+        if (M.kind_hi[d] == 2 && 2 * g.domhi[d] - qb.hi[d] + 1 < ilo[d]) return -2;
     }
     auto shell_launch_boxes = [&](const int olo_[3], const int ohi_[3], const int nlo_[3], const int nhi_[3], ShellBoxes& sb) {
         int lo6[6][3], hi6[6][3];
@@ -3570,8 +3612,8 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
         return sb.start[6];
     };
     if (light_a) {
-        if (aux.sb_clean > 0) KL("k_ctoprim_clean", k_ctoprim<true>, t.lo, t.hi, Sborder, S.Q, P, d_status, none, aux.sb_clean, nolv, lean_q, 0, no_shell, M);
-        else KL("k_ctoprim", k_ctoprim<false>, t.lo, t.hi, Sborder, S.Q, P, d_status, none, 0, nolv, lean_q, 0, no_shell, M);
+        if (aux.sb_clean > 0) KL("k_ctoprim_clean", k_ctoprim<true>, plain, t.lo, t.hi, Sborder, S.Q, P, d_status, none, aux.sb_clean, nolv, lean_q, 0, no_shell, M);
+        else KL("k_ctoprim", k_ctoprim<false>, plain, t.lo, t.hi, Sborder, S.Q, P, d_status, none, 0, nolv, lean_q, 0, no_shell, M);
         return hipGetLastError() == hipSuccess ? 0 : -4;
     }
     const bool second_half = stage_b && splittable;     // stage A has run on this tile
@@ -3587,16 +3629,16 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
             prof_end(prof, stream);
         }
     } else if (second_half) {
-        const int ns = shell_boxes(qlo, qhi, t.lo, t.hi, slo, shi);
-        for (int m = 0; m < ns; ++m) KL("k_ctoprim", k_ctoprim<false>, slo[m], shi[m], Sborder, S.Q, P, d_status, none, 0, nolv, lean_q, 0, no_shell, M);
+        const int ns = shell_boxes(qb.lo, qb.hi, t.lo, t.hi, slo, shi);
+        for (int m = 0; m < ns; ++m) KL("k_ctoprim", k_ctoprim<false>, plain, slo[m], shi[m], Sborder, S.Q, P, d_status, none, 0, nolv, lean_q, 0, no_shell, M);
     } else if (aux.sb_clean > 0) {
-        KL("k_ctoprim_clean", k_ctoprim<true>, ilo, ihi, Sborder, S.Q, P, d_status, none, aux.sb_clean, nolv, lean_q, 0, no_shell, M);
+        KL("k_ctoprim_clean", k_ctoprim<true>, plain, ilo, ihi, Sborder, S.Q, P, d_status, none, aux.sb_clean, nolv, lean_q, 0, no_shell, M);
     } else {
-        KL("k_ctoprim", k_ctoprim<false>, ilo, ihi, Sborder, S.Q, P, d_status, none, 0, nolv, lean_q, 0, no_shell, M);
+        KL("k_ctoprim", k_ctoprim<false>, plain, ilo, ihi, Sborder, S.Q, P, d_status, none, 0, nolv, lean_q, 0, no_shell, M);
     }
     if (have_bc) {
         ShellBoxes sb;
-        const unsigned nz_ = shell_launch_boxes(qlo, qhi, ilo, ihi, sb);
+        const unsigned nz_ = shell_launch_boxes(qb.lo, qb.hi, ilo, ihi, sb);
         if (nz_ > 0) {
             // the instantiation that did the in-domain zones of this call: one compiled copy of the arithmetic for both
             LinBox nobox = {};
@@ -3607,131 +3649,107 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
         }
     }
 
-    int flo[3][3], fhi[3][3], nlo[3][3], nhi[3][3];
-    for (int d = 0; d < 3; ++d)
-        for (int e = 0; e < 3; ++e) {
-            flo[d][e] = (e == d) ? t.lo[e] : t.lo[e] - 1;      // faces of d, grown by 1 in the transverse dirs
-            fhi[d][e] = t.hi[e] + 1;
-            nlo[d][e] = t.lo[e];                               // faces of d of bx
-            nhi[d][e] = (e == d) ? t.hi[e] + 1 : t.hi[e];
-        }
+    const SkipBox fg[3] = { face_box(t, 0, 1), face_box(t, 1, 1), face_box(t, 2, 1) };     // faces of d, grown by 1 in the transverse dirs
+    const SkipBox fb[3] = { face_box(t, 0, 0), face_box(t, 1, 0), face_box(t, 2, 0) };     // faces of d of bx
 
     // div(u) depends on Q only and is first read by the final stage: on the context's side stream it runs beside the
     // trace kernel (forked from and joined to `stream` by events; the hybrid solver's shock flags are read by the first
     // Riemann solves already, so that form stays in line)
     bool divu_forked = false;
-    if (P.hybrid_riemann == 1) { KL("k_divu", k_divu, olo, ohi, S.Q, S.DIV, S.SHK, 1.0 / g.dx[0], 1.0 / g.dx[1], 1.0 / g.dx[2]); }
+    if (P.hybrid_riemann == 1) { KL("k_divu", k_divu, plain, ob.lo, ob.hi, S.Q, S.DIV, S.SHK, 1.0 / g.dx[0], 1.0 / g.dx[1], 1.0 / g.dx[2]); }
     else if (divu_in_trace) { /* k_trace_pair computes it */ }
-    else if (aux.side && g_side_stream) {
+    else if (aux.side && K.side_stream) {
         hipEventRecord(aux.ev_fork, stream);
         hipStreamWaitEvent(aux.side, aux.ev_fork, 0);
-        {
-            hipStream_t main_stream = stream;
-            hipStream_t stream = aux.side;      // KL2 launches on `stream`
-            (void)main_stream;
-            KL2("k_divu", k_divu_pair<false>, olo, ohi, S.Q, S.DIV, 1.0 / g.dx[0], 1.0 / g.dx[1], 1.0 / g.dx[2], nolv);
-        }
+        KL_ON(aux.side, linbox2, "k_divu", k_divu_pair<false>, plain, ob.lo, ob.hi, S.Q, S.DIV, 1.0 / g.dx[0], 1.0 / g.dx[1], 1.0 / g.dx[2], nolv);
         hipEventRecord(aux.ev_join, aux.side);
         divu_forked = true;
     }
-    else { KL2("k_divu", k_divu_pair<false>, olo, ohi, S.Q, S.DIV, 1.0 / g.dx[0], 1.0 / g.dx[1], 1.0 / g.dx[2], nolv); }
+    else { KL2("k_divu", k_divu_pair<false>, plain, ob.lo, ob.hi, S.Q, S.DIV, 1.0 / g.dx[0], 1.0 / g.dx[1], 1.0 / g.dx[2], nolv); }
     // the join must precede the first reader of DIV (and every return path after this point)
     auto join_divu = [&]() { if (divu_forked) { hipStreamWaitEvent(stream, aux.ev_join, 0); divu_forked = false; } };
     bool x_done = false;      // first x Riemann solve already done inside the trace kernel
     bool one_zone_trace = false;
     if (Src.p) {
-        const int q3lo[3] = { t.lo[0] - 3, t.lo[1] - 3, t.lo[2] - 3 };
-        const int q3hi[3] = { t.hi[0] + 3, t.hi[1] + 3, t.hi[2] + 3 };
-        KL("k_src_to_prim", k_src_to_prim<false>, q3lo, q3hi, S.Q, Src, S.SRCQ, P, SrcCorr, dt, lean_q & 1, nolv);
-        if (P.ppm_type == 0 && (lean_q & 1)) { KL("k_trace_plm", (k_trace<true, true, gamma_law_edges(0)>), olo, ohi, S.Q, S, g, dt, P, nolv); }
-        else if (P.ppm_type == 0) { KL("k_trace_plm", (k_trace<true, true>), olo, ohi, S.Q, S, g, dt, P, nolv); }
-        else if (lean_q & 1) { KL("k_trace", (k_trace<true, false, gamma_law_edges(0)>), olo, ohi, S.Q, S, g, dt, P, nolv); }
-        else { KL("k_trace", (k_trace<true, false>), olo, ohi, S.Q, S, g, dt, P, nolv); }
+        const SkipBox q3 = grow(t, 3);
+        KL("k_src_to_prim", k_src_to_prim<false>, plain, q3.lo, q3.hi, S.Q, Src, S.SRCQ, P, SrcCorr, dt, lean_q & 1, nolv);
+        if (P.ppm_type == 0 && (lean_q & 1)) { KL("k_trace_plm", (k_trace<true, true, gamma_law_edges(0)>), plain, ob.lo, ob.hi, S.Q, S, g, dt, P, nolv); }
+        else if (P.ppm_type == 0) { KL("k_trace_plm", (k_trace<true, true>), plain, ob.lo, ob.hi, S.Q, S, g, dt, P, nolv); }
+        else if (lean_q & 1) { KL("k_trace", (k_trace<true, false, gamma_law_edges(0)>), plain, ob.lo, ob.hi, S.Q, S, g, dt, P, nolv); }
+        else { KL("k_trace", (k_trace<true, false>), plain, ob.lo, ob.hi, S.Q, S, g, dt, P, nolv); }
     } else {
-        if (P.ppm_type == 0 && (lean_q & 1)) { KL("k_trace_plm", (k_trace<false, true, gamma_law_edges(0)>), olo, ohi, S.Q, S, g, dt, P, nolv); }
-        else if (P.ppm_type == 0) { KL("k_trace_plm", (k_trace<false, true>), olo, ohi, S.Q, S, g, dt, P, nolv); }
-        else if (tfix) { KL2("k_trace", k_trace_pair<false>, olo, ohi, S.Q, S, g, dt, P, none, nolv, 0); }
-        else if (g_trace_one_zone && !second_half) {
+        if (P.ppm_type == 0 && (lean_q & 1)) { KL("k_trace_plm", (k_trace<false, true, gamma_law_edges(0)>), plain, ob.lo, ob.hi, S.Q, S, g, dt, P, nolv); }
+        else if (P.ppm_type == 0) { KL("k_trace_plm", (k_trace<false, true>), plain, ob.lo, ob.hi, S.Q, S, g, dt, P, nolv); }
+        else if (tfix) { KL2("k_trace", k_trace_pair<false>, plain, ob.lo, ob.hi, S.Q, S, g, dt, P, none, nolv, 0); }
+        else if (K.trace_one_zone && !second_half) {
             // A/B (CASTRO_AMD_TRACE_ONE_ZONE=1, round 6): ONE zone per thread at the occupancy that leaves (the kernel of the runs with
             // traced source terms, without the sources), the first x Riemann solve as a launch of its own
-            if (lean_q & 1) { KL("k_trace", (k_trace<false, false, gamma_law_edges(0)>), olo, ohi, S.Q, S, g, dt, P, nolv); }
-            else { KL("k_trace", (k_trace<false, false>), olo, ohi, S.Q, S, g, dt, P, nolv); }
+            if (lean_q & 1) { KL("k_trace", (k_trace<false, false, gamma_law_edges(0)>), plain, ob.lo, ob.hi, S.Q, S, g, dt, P, nolv); }
+            else { KL("k_trace", (k_trace<false, false>), plain, ob.lo, ob.hi, S.Q, S, g, dt, P, nolv); }
             one_zone_trace = true;
         }
         else if (second_half) {
             if (inner_ok) {
-                const int ns = shell_boxes(olo, ohi, inner_box.lo, inner_box.hi, slo, shi);
+                const int ns = shell_boxes(ob.lo, ob.hi, inner_box.lo, inner_box.hi, slo, shi);
                 for (int m = 0; m < ns; ++m) trace_with_xriemann(slo[m], shi[m]);
                 // the x faces between the inner launch of stage A and the two x slabs
                 for (int side = 0; side < 2; ++side) {
                     const int xf = side ? inner_box.hi[0] + 1 : inner_box.lo[0];
                     const int plo[3] = { xf, inner_box.lo[1], inner_box.lo[2] }, phi[3] = { xf, inner_box.hi[1], inner_box.hi[2] };
-                    KL2_SOLV("k_riemann1", K_R1_0, plo, phi, S.Q, S, g, P, nolv);
+                    KL2_SOLV("k_riemann1", K_R1_0, plain, plo, phi, S.Q, S, g, P, nolv);
                 }
             } else {
-                trace_with_xriemann(olo, ohi);
+                trace_with_xriemann(ob.lo, ob.hi);
             }
         } else {
-            trace_with_xriemann(olo, ohi);
+            trace_with_xriemann(ob.lo, ob.hi);
         }
         x_done = P.ppm_type != 0 && !tfix && !one_zone_trace;
     }
     (void)staged;
 
     // the first y / z solves folded into the transverse stage (k_trans1_fold): default solver set, default final-stage form
-    const bool fold_r1 = g_fold_r1 && solv == 0 && !tfix && P.reset_rhoe != 1 && g_fuse_consup;
+    const bool fold_r1 = K.fold_r1 && solv == 0 && !tfix && P.reset_rhoe != 1 && K.fuse_consup;
     if (tfix) {
-        KL2("k_riemann1", (k_riemann1<0, true>), flo[0], fhi[0], S.Q, S, g, P, nolv);
-        KL2("k_riemann1", (k_riemann1<1, true>), flo[1], fhi[1], S.Q, S, g, P, nolv);
-        KL2("k_riemann1", (k_riemann1<2, true>), flo[2], fhi[2], S.Q, S, g, P, nolv);
+        KL2("k_riemann1", (k_riemann1<0, true>), plain, fg[0].lo, fg[0].hi, S.Q, S, g, P, nolv);
+        KL2("k_riemann1", (k_riemann1<1, true>), plain, fg[1].lo, fg[1].hi, S.Q, S, g, P, nolv);
+        KL2("k_riemann1", (k_riemann1<2, true>), plain, fg[2].lo, fg[2].hi, S.Q, S, g, P, nolv);
     } else {
-        if (!x_done) KL2_SOLV("k_riemann1", K_R1_0, flo[0], fhi[0], S.Q, S, g, P, nolv);
+        if (!x_done) KL2_SOLV("k_riemann1", K_R1_0, plain, fg[0].lo, fg[0].hi, S.Q, S, g, P, nolv);
         if (!fold_r1) {
-            KL2_SOLV("k_riemann1", K_R1_1, flo[1], fhi[1], S.Q, S, g, P, nolv);
-            KL2_SOLV("k_riemann1", K_R1_2, flo[2], fhi[2], S.Q, S, g, P, nolv);
+            KL2_SOLV("k_riemann1", K_R1_1, plain, fg[1].lo, fg[1].hi, S.Q, S, g, P, nolv);
+            KL2_SOLV("k_riemann1", K_R1_2, plain, fg[2].lo, fg[2].hi, S.Q, S, g, P, nolv);
         }
     }
 
     join_divu();
-    // cdtdx = dt/dx/3 (Castro_ctu_hydro.cpp:688-690); hdtdx = 0.5*dt/dx (:684-686)
-    const double cdtdx = dt / g.dx[0] / 3.0, cdtdy = dt / g.dx[1] / 3.0, cdtdz = dt / g.dx[2] / 3.0;
-    const double hdtdx = 0.5 * dt / g.dx[0], hdtdy = 0.5 * dt / g.dx[1], hdtdz = 0.5 * dt / g.dx[2];
-    const double area0 = g.dx[1] * g.dx[2], area1 = g.dx[0] * g.dx[2], area2 = g.dx[0] * g.dx[1];
+    const auto [cdtdx, cdtdy, cdtdz, hdtdx, hdtdy, hdtdz, area0, area1, area2, vol] = step_consts(g, dt);
 
     // transverse_reset_rhoe = 1 (non-default) runs its own instantiations: the extra (rho e) flux loads cost the
     // default path 2 % when they sit behind a run-time branch
 #define TRANSVERSE_STAGES(RE, LIM)                                                                                \
     do {                                                                                                          \
-        KL2("k_trans1", k_trans1<RE>, olo, ohi, S.Q, S, g, cdtdx, cdtdy, cdtdz, P);                              \
-        KL2("k_final_x", (k_final<0, RE, LIM>), nlo[0], nhi[0], S.Q, S, g, Sborder, fluxes[0], mass[0], qe[0],      \
+        KL2("k_trans1", k_trans1<RE>, plain, ob.lo, ob.hi, S.Q, S, g, cdtdx, cdtdy, cdtdz, P);                              \
+        KL2("k_final_x", (k_final<0, RE, LIM>), plain, fb[0].lo, fb[0].hi, S.Q, S, g, Sborder, fluxes[0], mass[0], qe[0],      \
             hdtdy, hdtdz, dt, area0, g.dx[0], acc_hi[0], (flags & 2) ? 1 : 0, P, nolv);                                 \
-        KL2("k_final_y", (k_final<1, RE, LIM>), nlo[1], nhi[1], S.Q, S, g, Sborder, fluxes[1], mass[1], qe[1],      \
+        KL2("k_final_y", (k_final<1, RE, LIM>), plain, fb[1].lo, fb[1].hi, S.Q, S, g, Sborder, fluxes[1], mass[1], qe[1],      \
             hdtdx, hdtdz, dt, area1, g.dx[1], acc_hi[1], (flags & 2) ? 1 : 0, P, nolv);                                 \
-        KL2("k_final_z", (k_final<2, RE, LIM>), nlo[2], nhi[2], S.Q, S, g, Sborder, fluxes[2], mass[2], qe[2],      \
+        KL2("k_final_z", (k_final<2, RE, LIM>), plain, fb[2].lo, fb[2].hi, S.Q, S, g, Sborder, fluxes[2], mass[2], qe[2],      \
             hdtdx, hdtdy, dt, area2, g.dx[2], acc_hi[2], (flags & 2) ? 1 : 0, P, nolv);                                 \
     } while (0)
     // the flux limiters (non-default too) share one extra pair of instantiations: both flags are tested inside
     const bool lim = P.limit_small_dens == 1 || P.limit_large_vel == 1;
     if (P.reset_rhoe == 1 || tfix) { if (lim) TRANSVERSE_STAGES(true, true); else TRANSVERSE_STAGES(true, false); }
-    else if (g_fuse_consup) {
+    else if (K.fuse_consup) {
         // y and z first (they write FL[1], FL[2]), then the x faces with the conservative update fused in
         if (fold_r1) {
             long n_;
-            struct RowsGuard2 { int keep; RowsGuard2() : keep(tl_tile_rows) { if (g_fold_tile_rows >= 0) tl_tile_rows = g_fold_tile_rows; }
-                                ~RowsGuard2() { tl_tile_rows = keep; } } rows_guard2;
-            LinBox b_ = linbox2(olo, ohi, n_);
+            LinBox b_ = linbox2(ob.lo, ob.hi, fold_shape(K), n_);
 #ifdef CAD_NUMERICS_CONTRACT
-            const int fold_tile = g_fold_tile >= 0 ? g_fold_tile : ((b_.n[1] >= 96 && b_.n[2] >= 96 && b_.n[0] >= 48) ? 1 : 0);
+            const int fold_tile = K.fold_tile >= 0 ? K.fold_tile : ((b_.n[1] >= 96 && b_.n[2] >= 96 && b_.n[0] >= 48) ? 1 : 0);
             if (n_ > 0 && fold_tile) {
                 const int ry = fold_tile == 2 ? 2 : 4, rz = fold_tile == 2 ? 4 : 2;
-                TileRows tr;
-                for (int d = 0; d < 3; ++d) tr.lo[d] = olo[d];
-                tr.hi0 = ohi[0];
-                tr.nslot = b_.n[0]; tr.ny = b_.n[1]; tr.nz = b_.n[2];
-                tr.ntj = (tr.ny + ry - 1) / ry; tr.ntk = (tr.nz + rz - 1) / rz;
-                tr.band = b_.ty > 0 ? (b_.ty + ry - 1) / ry : tr.ntj;
-                const long total = (long)tr.nslot * tr.ntj * tr.ntk;
-                tr.nb = ((unsigned)((total + 62) / 63) + 7u) & ~7u;
+                const TileRows tr = tile_rows(ob.lo, ob.hi[0], b_.n[0], b_.n[1], b_.n[2], ry, rz, b_.ty);
                 prof_begin(prof, "k_trans1_fold", stream);
                 if (fold_tile == 2) hipLaunchKernelGGL((k_trans1_tile<0, 2, 4>), dim3(tr.nb), dim3(512), 0, stream, t, tr, S.Q, S, g, cdtdx, cdtdy, cdtdz, P);
                 else hipLaunchKernelGGL((k_trans1_tile<0, 4, 2>), dim3(tr.nb), dim3(512), 0, stream, t, tr, S.Q, S, g, cdtdx, cdtdy, cdtdz, P);
@@ -3740,63 +3758,42 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
 #endif
             if (n_ > 0) {
                 prof_begin(prof, "k_trans1_fold", stream);
-                b_.nb = (unsigned)(((n_ + 62) / 63 + FOLD_WG / 64 - 1) / (FOLD_WG / 64));   // 63 new slots per wave, see fold_thread
-                if (b_.ty > 0) b_.nb = (b_.nb + 7u) & ~7u;
+                b_.nb = fold_blocks(b_);
                 hipLaunchKernelGGL(k_trans1_fold_lds<0>, dim3(b_.nb), dim3(FOLD_WG), 0, stream, t, b_, S.Q, S, g, cdtdx, cdtdy, cdtdz, P, nolv);
                 prof_end(prof, stream);
             }
         } else
-        KL2_SOLV("k_trans1", K_T1, olo, ohi, S.Q, S, g, cdtdx, cdtdy, cdtdz, P);
+        KL2_SOLV("k_trans1", K_T1, plain, ob.lo, ob.hi, S.Q, S, g, cdtdx, cdtdy, cdtdz, P);
         const int assign_yz = (flags & 2) ? 1 : 0;
 #ifdef CAD_NUMERICS_CONTRACT
-        if (g_final_tile && solv == 0 && !lim) {
+        if (K.final_tile && solv == 0 && !lim) {
             constexpr int ry = 4, rz = 2;
-            TileRows tr;
-            for (int d = 0; d < 3; ++d) tr.lo[d] = t.lo[d];
-            tr.hi0 = t.hi[0];
-            const int nx = t.hi[0] - t.lo[0] + 1;
-            tr.nslot = (nx + 1) / 2 + 1; tr.ny = t.hi[1] - t.lo[1] + 1; tr.nz = t.hi[2] - t.lo[2] + 1;
-            tr.ntj = (tr.ny + ry - 1) / ry; tr.ntk = (tr.nz + rz - 1) / rz;
-            tr.band = g_fused_tile_rows > 0 ? (g_fused_tile_rows + ry - 1) / ry : tr.ntj;
-            const long total = (long)tr.nslot * tr.ntj * tr.ntk;
-            tr.nb = ((unsigned)((total + 62) / 63) + 7u) & ~7u;
+            const TileRows tr = tile_rows(t.lo, t.hi[0], face_slots(t), t.hi[1] - t.lo[1] + 1, t.hi[2] - t.lo[2] + 1, ry, rz, K.fused_tile_rows);
             FinalOut fo;
             for (int d = 0; d < 3; ++d) { fo.fl[d] = fluxes[d]; fo.mass[d] = mass[d]; fo.qe[d] = qe[d]; fo.acc_hi[d] = acc_hi[d]; }
-            const double vol_ = g.dx[0] * g.dx[1] * g.dx[2];
             prof_begin(prof, "k_final_tile", stream);
             if (clean_ntimes > 0)
                 hipLaunchKernelGGL((k_final_tile<true, 0, ry, rz>), dim3(tr.nb), dim3(64 * ry * rz), 0, stream, t, tr, S.Q, S, g, Sborder, fo, Snew, dt,
-                                   area0, area1, area2, vol_, assign_yz, (flags & 1) ? 1 : 0, P, clean_ntimes, red);
+                                   area0, area1, area2, vol, assign_yz, (flags & 1) ? 1 : 0, P, clean_ntimes, red);
             else
                 hipLaunchKernelGGL((k_final_tile<false, 0, ry, rz>), dim3(tr.nb), dim3(64 * ry * rz), 0, stream, t, tr, S.Q, S, g, Sborder, fo, Snew, dt,
-                                   area0, area1, area2, vol_, assign_yz, (flags & 1) ? 1 : 0, P, 0, (double*)nullptr);
+                                   area0, area1, area2, vol, assign_yz, (flags & 1) ? 1 : 0, P, 0, (double*)nullptr);
             prof_end(prof, stream);
             return hipGetLastError() == hipSuccess ? 0 : -4;
         }
 #endif
         if (lim) {
-            KL2("k_final_y", (k_final<1, false, true>), nlo[1], nhi[1], S.Q, S, g, Sborder, fluxes[1], mass[1], qe[1], hdtdx, hdtdz, dt, area1, g.dx[1], acc_hi[1], (flags & 2) ? 1 : 0, P, nolv);
-            KL2("k_final_z", (k_final<2, false, true>), nlo[2], nhi[2], S.Q, S, g, Sborder, fluxes[2], mass[2], qe[2], hdtdx, hdtdy, dt, area2, g.dx[2], acc_hi[2], (flags & 2) ? 1 : 0, P, nolv);
+            KL2("k_final_y", (k_final<1, false, true>), plain, fb[1].lo, fb[1].hi, S.Q, S, g, Sborder, fluxes[1], mass[1], qe[1], hdtdx, hdtdz, dt, area1, g.dx[1], acc_hi[1], (flags & 2) ? 1 : 0, P, nolv);
+            KL2("k_final_z", (k_final<2, false, true>), plain, fb[2].lo, fb[2].hi, S.Q, S, g, Sborder, fluxes[2], mass[2], qe[2], hdtdx, hdtdy, dt, area2, g.dx[2], acc_hi[2], (flags & 2) ? 1 : 0, P, nolv);
         } else {
-            struct WgGuard { unsigned keep; WgGuard() : keep(tl_wg) { if (g_final_wg > 0) tl_wg = (unsigned)g_final_wg; } ~WgGuard() { tl_wg = keep; } } wg_guard;
-            KL2_SOLV("k_final_y", K_FY, nlo[1], nhi[1], S.Q, S, g, Sborder, fluxes[1], mass[1], qe[1], hdtdx, hdtdz, dt, area1, g.dx[1], acc_hi[1], assign_yz, P, nolv);
-            KL2_SOLV("k_final_z", K_FZ, nlo[2], nhi[2], S.Q, S, g, Sborder, fluxes[2], mass[2], qe[2], hdtdx, hdtdy, dt, area2, g.dx[2], acc_hi[2], assign_yz, P, nolv);
+            KL2_SOLV("k_final_y", K_FY, final_shape(K), fb[1].lo, fb[1].hi, S.Q, S, g, Sborder, fluxes[1], mass[1], qe[1], hdtdx, hdtdz, dt, area1, g.dx[1], acc_hi[1], assign_yz, P, nolv);
+            KL2_SOLV("k_final_z", K_FZ, final_shape(K), fb[2].lo, fb[2].hi, S.Q, S, g, Sborder, fluxes[2], mass[2], qe[2], hdtdx, hdtdy, dt, area2, g.dx[2], acc_hi[2], assign_yz, P, nolv);
         }
-        XRows xr;
-        for (int d = 0; d < 3; ++d) xr.lo[d] = t.lo[d];
-        xr.hi0 = t.hi[0];
-        const int nx = t.hi[0] - t.lo[0] + 1;
-        xr.nslot = (nx + 1) / 2 + 1; xr.ny = t.hi[1] - t.lo[1] + 1; xr.nz = t.hi[2] - t.lo[2] + 1;
-        xr.ty = g_fused_tile_rows;
-        const long slots = (long)xr.nslot * xr.ny * xr.nz;
-        const long waves = (slots + 62) / 63;
-        xr.wv = (unsigned)g_fused_wg / 64u;
-        xr.nb = ((unsigned)((waves + xr.wv - 1) / xr.wv) + 7u) & ~7u;
-        const double vol_ = g.dx[0] * g.dx[1] * g.dx[2];
+        const XRows xr = x_rows(t, K);
         prof_begin(prof, "k_finalx_consup", stream);
 #define FXC(LIM, CLEAN, GENF, nt, rd)                                                                                        \
         hipLaunchKernelGGL((k_finalx_consup<LIM, CLEAN, GENF>), dim3(xr.nb), dim3(64u * xr.wv), 0, stream, t, xr, S.Q, S, g, Sborder,      \
-                           fluxes[0], mass[0], qe[0], Snew, hdtdy, hdtdz, dt, area0, area1, area2, vol_, acc_hi[0],      \
+                           fluxes[0], mass[0], qe[0], Snew, hdtdy, hdtdz, dt, area0, area1, area2, vol, acc_hi[0],      \
                            assign_yz, (flags & 1) ? 1 : 0, P, nt, rd, nolv)
         if (clean_ntimes > 0) {
             if (lim) FXC(true, true, 2, clean_ntimes, red);
@@ -3816,12 +3813,11 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
     else { if (lim) TRANSVERSE_STAGES(false, true); else TRANSVERSE_STAGES(false, false); }
 #undef TRANSVERSE_STAGES
 
-    const double vol = g.dx[0] * g.dx[1] * g.dx[2];
     if (clean_ntimes > 0) {
-        KL("k_consup_clean", k_consup<true>, t.lo, t.hi, S, Sborder, Snew, dt, area0, area1, area2, vol, (flags & 1) ? 1 : 0,
+        KL("k_consup_clean", k_consup<true>, plain, t.lo, t.hi, S, Sborder, Snew, dt, area0, area1, area2, vol, (flags & 1) ? 1 : 0,
            P, clean_ntimes, g.dx[0], g.dx[1], g.dx[2], red);
     } else {
-        KL("k_consup", k_consup<false>, t.lo, t.hi, S, Sborder, Snew, dt, area0, area1, area2, vol, (flags & 1) ? 1 : 0,
+        KL("k_consup", k_consup<false>, plain, t.lo, t.hi, S, Sborder, Snew, dt, area0, area1, area2, vol, (flags & 1) ? 1 : 0,
            P, 0, 0.0, 0.0, 0.0, (double*)nullptr);
     }
 
@@ -3831,19 +3827,19 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
 // ---------------------------------------------------------------------------------------
 // The default path for every box of a level at once (see LevelTab): 8 launches whatever the number of boxes.
 // ---------------------------------------------------------------------------------------
-bool level_launch_supported(const DevParams& P, int flags, bool with_src)
+bool level_launch_supported(const LaunchKnobs& K, const DevParams& P, int flags, bool with_src)
 {
     const bool tfix = P.ppm_temp_fix == 2 && P.riemann_solver != 2;
     const bool lim = P.limit_small_dens == 1 || P.limit_large_vel == 1;
     // traced source terms (round 6): the GEN == 0 kernels read (rho e) of an edge state from its p in the `contract` build, which
     // the trace with sources promises only with CASTRO_AMD_GL_SOURCES (launch_ctu_hydro: gl_ok)
-    if (with_src && gamma_law_edges(0) && !g_gl_sources) return false;
+    if (with_src && gamma_law_edges(0) && !K.gl_sources) return false;
     return P.ppm_type == 1 && P.riemann_solver == 0 && P.hybrid_riemann != 1 && !tfix && P.reset_rhoe != 1 && !lim &&
-           g_fuse_consup == 1 && g_fold_r1 != 0 && (flags & (4 | 8 | 16 | 32 | 64)) == 0;
+           K.fuse_consup == 1 && K.fold_r1 != 0 && (flags & (4 | 8 | 16 | 32 | 64)) == 0;
 }
 
-int launch_ctu_hydro_level(int nbox, const LevelBoxDesc* boxes, FabOpsArena* table, const DevGeom& g, const DevParams& P, double dt,
-                           int flags, int* d_status, hipStream_t stream, Profiler* prof, int clean_ntimes, double* red, int sb_clean)
+int launch_ctu_hydro_level(const LaunchKnobs& K, int nbox, const LevelBoxDesc* boxes, FabOpsArena* table, const DevGeom& g, const DevParams& P,
+                           double dt, int flags, int* d_status, hipStream_t stream, Profiler* prof, int clean_ntimes, double* red, int sb_clean)
 {
     if (nbox < 1 || !boxes || !table) return -1;
     // Traced source terms: every box of the launch has its old-time source FAB or none has.  The sequence is launch_ctu_hydro's
@@ -3852,6 +3848,7 @@ int launch_ctu_hydro_level(int nbox, const LevelBoxDesc* boxes, FabOpsArena* tab
     const bool with_src = boxes[0].Src.p != nullptr;
     for (int i = 1; i < nbox; ++i) if ((boxes[i].Src.p != nullptr) != with_src) return -1;
     if (with_src && sb_clean > 0) return -1;
+    const Shape plain = plain_shape(K);
     std::vector<LevelBox> hb((size_t)nbox);
     std::vector<unsigned> start((size_t)NLB * (size_t)(nbox + 1), 0u);
     auto st = [&](int kind, int i) -> unsigned& { return start[(size_t)kind * (size_t)(nbox + 1) + (size_t)i]; };
@@ -3861,43 +3858,27 @@ int launch_ctu_hydro_level(int nbox, const LevelBoxDesc* boxes, FabOpsArena* tab
         const Tile& t = D.t;
         B.t = t; B.S = D.S; B.U = D.U; B.Unew = D.Unew; B.Src = D.Src;
         for (int d = 0; d < 3; ++d) { B.fl[d] = D.fl[d]; B.mass[d] = D.mass[d]; B.qe[d] = D.qe[d]; B.acc_hi[d] = D.acc_hi[d]; }
-        const int olo[3] = { t.lo[0] - 1, t.lo[1] - 1, t.lo[2] - 1 }, ohi[3] = { t.hi[0] + 1, t.hi[1] + 1, t.hi[2] + 1 };
-        const int qlo[3] = { t.lo[0] - 4, t.lo[1] - 4, t.lo[2] - 4 }, qhi[3] = { t.hi[0] + 4, t.hi[1] + 4, t.hi[2] + 4 };
+        // every box in the shape launch_ctu_hydro gives the same launch
+        const SkipBox ob = grow(t, 1), qb = grow(t, 4);
         long n_;
-        tl_tile_rows = -1; tl_wg = 0;
-        B.b[LB_CTOPRIM] = linbox(qlo, qhi, n_);
-        B.b[LB_DIVU] = linbox2(olo, ohi, n_);
-        tl_tile_rows = g_trace_tile_rows >= 0 ? g_trace_tile_rows : -1;
-        B.b[LB_TRACE] = linbox2(olo, ohi, n_);
-        tl_tile_rows = g_fold_tile_rows >= 0 ? g_fold_tile_rows : -1;
-        B.b[LB_FOLD] = linbox2(olo, ohi, n_);
-        B.b[LB_FOLD].nb = (unsigned)(((n_ + 62) / 63 + FOLD_WG / 64 - 1) / (FOLD_WG / 64));      // 63 new slots per wave, see fold_thread
-        if (B.b[LB_FOLD].ty > 0) B.b[LB_FOLD].nb = (B.b[LB_FOLD].nb + 7u) & ~7u;
-        tl_tile_rows = -1;
+        B.b[LB_CTOPRIM] = linbox(qb.lo, qb.hi, plain, n_);
+        B.b[LB_DIVU] = linbox2(ob.lo, ob.hi, plain, n_);
+        B.b[LB_TRACE] = linbox2(ob.lo, ob.hi, trace_shape(K), n_);
+        B.b[LB_FOLD] = linbox2(ob.lo, ob.hi, fold_shape(K), n_);
+        B.b[LB_FOLD].nb = fold_blocks(B.b[LB_FOLD]);
         for (int m = 0; m < 3; ++m) { B.bs[m] = LinBox{}; B.bs[m].nb = 0; }
         if (with_src) {
-            const int q3lo[3] = { t.lo[0] - 3, t.lo[1] - 3, t.lo[2] - 3 }, q3hi[3] = { t.hi[0] + 3, t.hi[1] + 3, t.hi[2] + 3 };
-            const int f0lo[3] = { t.lo[0], t.lo[1] - 1, t.lo[2] - 1 }, f0hi[3] = { t.hi[0] + 1, t.hi[1] + 1, t.hi[2] + 1 };
-            B.bs[0] = linbox(q3lo, q3hi, n_);
-            B.bs[1] = linbox(olo, ohi, n_);
-            B.bs[2] = linbox2(f0lo, f0hi, n_);
+            const SkipBox q3 = grow(t, 3), f0 = face_box(t, 0, 1);
+            B.bs[0] = linbox(q3.lo, q3.hi, plain, n_);
+            B.bs[1] = linbox(ob.lo, ob.hi, plain, n_);
+            B.bs[2] = linbox2(f0.lo, f0.hi, plain, n_);
         }
-        tl_wg = g_final_wg > 0 ? (unsigned)g_final_wg : 0u;
         for (int d = 1; d <= 2; ++d) {
-            int nlo[3] = { t.lo[0], t.lo[1], t.lo[2] }, nhi[3] = { t.hi[0], t.hi[1], t.hi[2] };
-            nhi[d] += 1;
-            B.b[d == 1 ? LB_FY : LB_FZ] = linbox2(nlo, nhi, n_);
+            const SkipBox fb = face_box(t, d, 0);
+            B.b[d == 1 ? LB_FY : LB_FZ] = linbox2(fb.lo, fb.hi, final_shape(K), n_);
         }
-        tl_wg = 0;
-        XRows& xr = B.xr;
-        for (int d = 0; d < 3; ++d) xr.lo[d] = t.lo[d];
-        xr.hi0 = t.hi[0];
-        const int nx = t.hi[0] - t.lo[0] + 1;
-        xr.nslot = (nx + 1) / 2 + 1; xr.ny = t.hi[1] - t.lo[1] + 1; xr.nz = t.hi[2] - t.lo[2] + 1;
-        xr.ty = g_fused_tile_rows;
-        const long slots = (long)xr.nslot * xr.ny * xr.nz;
-        xr.wv = (unsigned)g_fused_wg / 64u;
-        xr.nb = ((unsigned)(((slots + 62) / 63 + xr.wv - 1) / xr.wv) + 7u) & ~7u;
+        B.xr = x_rows(t, K);
+        const XRows& xr = B.xr;
         // workgroup ranges: multiples of 8 wherever the kernel maps ids to XCDs (every LinBox with ty > 0 is one already)
         const unsigned nbs[NLB] = { B.b[LB_CTOPRIM].nb, B.b[LB_DIVU].nb, B.b[LB_TRACE].nb, B.b[LB_FOLD].nb, B.b[LB_FY].nb, B.b[LB_FZ].nb,
                                     xr.nb, (B.b[LB_TRACE].nb + 255u) / 256u, B.bs[0].nb, B.bs[1].nb, B.bs[2].nb };
@@ -3925,10 +3906,7 @@ int launch_ctu_hydro_level(int nbox, const LevelBoxDesc* boxes, FabOpsArena* tab
     const DevScratch S0 = hb[0].S;
     const SkipBox none = { { 0, 0, 0 }, { -1, -1, -1 } };
     const int assign = (flags & 2) ? 1 : 0;
-    const double cdtdx = dt / g.dx[0] / 3.0, cdtdy = dt / g.dx[1] / 3.0, cdtdz = dt / g.dx[2] / 3.0;
-    const double hdtdx = 0.5 * dt / g.dx[0], hdtdy = 0.5 * dt / g.dx[1], hdtdz = 0.5 * dt / g.dx[2];
-    const double area0 = g.dx[1] * g.dx[2], area1 = g.dx[0] * g.dx[2], area2 = g.dx[0] * g.dx[1];
-    const double vol = g.dx[0] * g.dx[1] * g.dx[2];
+    const auto [cdtdx, cdtdy, cdtdz, hdtdx, hdtdy, hdtdz, area0, area1, area2, vol] = step_consts(g, dt);
 
     prof_begin(prof, sb_clean > 0 ? "k_ctoprim_clean" : "k_ctoprim", stream);
     if (sb_clean > 0) hipLaunchKernelGGL((k_ctoprim<true, true>), dim3(total(LB_CTOPRIM)), dim3(hb[0].b[LB_CTOPRIM].wg), 0, stream, t0, hb[0].b[LB_CTOPRIM],
@@ -3936,7 +3914,7 @@ int launch_ctu_hydro_level(int nbox, const LevelBoxDesc* boxes, FabOpsArena* tab
     else hipLaunchKernelGGL((k_ctoprim<false, true>), dim3(total(LB_CTOPRIM)), dim3(hb[0].b[LB_CTOPRIM].wg), 0, stream, t0, hb[0].b[LB_CTOPRIM],
                             hb[0].U, S0.Q, P, d_status, none, 0, lv(LB_CTOPRIM), gamma_law_edges(0) ? (clean_ntimes > 0 ? 3 : 1) : 0, 0, ShellBoxes{}, BcKinds{});
     prof_end(prof, stream);
-    if (!g_divu_in_trace || with_src) {
+    if (!K.divu_in_trace || with_src) {
         prof_begin(prof, "k_divu", stream);
         hipLaunchKernelGGL(k_divu_pair<true>, dim3(total(LB_DIVU)), dim3(hb[0].b[LB_DIVU].wg), 0, stream, t0, hb[0].b[LB_DIVU], S0.Q, S0.DIV,
                            1.0 / g.dx[0], 1.0 / g.dx[1], 1.0 / g.dx[2], lv(LB_DIVU));
@@ -3958,7 +3936,7 @@ int launch_ctu_hydro_level(int nbox, const LevelBoxDesc* boxes, FabOpsArena* tab
     } else {
     prof_begin(prof, "k_trace", stream);
     hipLaunchKernelGGL((k_trace_pair<true, 7, 0, true>), dim3(total(LB_TRACE)), dim3(hb[0].b[LB_TRACE].wg), 0, stream, t0, hb[0].b[LB_TRACE], S0.Q, S0, g,
-                       dt, P, none, lv(LB_TRACE), g_divu_in_trace ? 1 : 0);
+                       dt, P, none, lv(LB_TRACE), K.divu_in_trace ? 1 : 0);
     prof_end(prof, stream);
     prof_begin(prof, "k_riemann1_blockstart", stream);
     hipLaunchKernelGGL((k_riemann1_blockstart<0, true>), dim3(total(LB_BSTART)), dim3(256), 0, stream, t0, hb[0].b[LB_TRACE], S0.Q, S0, g, P, lv(LB_BSTART));

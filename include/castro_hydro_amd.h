@@ -35,9 +35,9 @@
  *    concurrently (the reference calls the path from inside `#pragma omp
  *    parallel`, Castro_ctu_hydro.cpp:66-72); ONE context must not be entered
  *    by two threads at once.  The CASTRO_AMD_* environment knobs are read by
- *    castro_amd_ctx_create() into process-wide settings: create the contexts
- *    before the threads start using them, not while another thread is
- *    inside a call.
+ *    castro_amd_ctx_create() into the context it returns and apply to that
+ *    context only: creating a context changes nothing for the others, so
+ *    contexts may be created while other threads are inside calls.
  */
 #ifndef CASTRO_HYDRO_AMD_H
 #define CASTRO_HYDRO_AMD_H

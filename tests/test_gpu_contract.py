@@ -510,16 +510,19 @@ def test_contract_tile_kernels_on_ragged_boxes(oracle, shape, form):
     U = physical_state(rng, sb_lo, sb_hi, smooth=False, vel=1.5)
     kw = dict(dx=(0.02, 0.017, 0.023))
     outs = {}
+    old = {k: os.environ.get(k) for k in ("CASTRO_AMD_FOLD_TILE", "CASTRO_AMD_FINAL_TILE")}
     try:
         for name, (ft, fin) in (("rows", ("0", "0")), ("tile", env)):
             os.environ["CASTRO_AMD_FOLD_TILE"], os.environ["CASTRO_AMD_FINAL_TILE"] = ft, fin
-            hip = HipHydro(0, numerics="contract")          # the knobs are read when a context is created
+            hip = HipHydro(0, numerics="contract")          # the knobs are read when a context is created, for that context only
             outs[name] = _run_both(hip, oracle, bxlo, bxhi, U, sb_lo, sb_hi, 6.0e-4, **kw)
             hip.close()
     finally:
-        os.environ["CASTRO_AMD_FOLD_TILE"], os.environ["CASTRO_AMD_FINAL_TILE"] = "-1", "0"
-        HipHydro(0, numerics="contract").close()           # back to the defaults for the tests that follow
-        del os.environ["CASTRO_AMD_FOLD_TILE"], os.environ["CASTRO_AMD_FINAL_TILE"]
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
     dev = _outputs_deviation(outs["tile"])
     worst = max(dev, key=dev.get)
     print("contract %s vs oracle, box %s: max deviation %.2e (%s)" % (form, shape, dev[worst], worst))

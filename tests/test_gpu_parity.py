@@ -27,11 +27,6 @@ def hip():
     h.close()
 
 
-LIB_DEFAULT_FOLD_R1 = "2"        # g_fold_r1 of ctu_kernels.hip
-LIB_DEFAULT_WG = "256"           # g_wg (g_final_wg follows it)
-LIB_DEFAULT_FUSED_WG = "128"     # g_fused_wg
-
-
 def _to_dev(h, a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a)).to(h.device)
@@ -2451,7 +2446,7 @@ def test_alternative_final_stage_kernels_are_bit_exact(oracle, env):
     old = {k: os.environ.get(k) for k in keys}
     try:
         os.environ.update(env)
-        h = HipHydro(0)                       # the knobs are read when a context is created
+        h = HipHydro(0)                       # the knobs are read when a context is created, for that context only
         for shape, seed in (((37, 9, 11), 5), ((8, 8, 8), 6), ((1, 5, 3), 7), ((130, 4, 3), 8)):
             rng = np.random.default_rng(seed)
             bxlo = (2, -3, 1)
@@ -2476,15 +2471,52 @@ def test_alternative_final_stage_kernels_are_bit_exact(oracle, env):
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
-        os.environ.setdefault("CASTRO_AMD_XPAD", "0")
-        os.environ["CASTRO_AMD_FUSE_CONSUP"] = "1"
-        os.environ["CASTRO_AMD_FOLD_R1"] = old["CASTRO_AMD_FOLD_R1"] if old["CASTRO_AMD_FOLD_R1"] is not None else LIB_DEFAULT_FOLD_R1
-        for k, v in (("CASTRO_AMD_WG", LIB_DEFAULT_WG), ("CASTRO_AMD_FINAL_WG", LIB_DEFAULT_WG), ("CASTRO_AMD_FUSED_WG", LIB_DEFAULT_FUSED_WG)):
-            os.environ[k] = old[k] if old[k] is not None else v
-        HipHydro(0).close()                   # restore the library's defaults for the tests that follow
+
+
+def test_launch_knobs_belong_to_the_context_that_read_them(oracle):
+    """The CASTRO_AMD_* launch variables are read when a context is created and hold for that context only: context A from a
+    clean environment and context B from one with padded scratch rows, one-wave workgroups, the plain final stage and the first
+    y / z solves as launches of their own live side by side.  The same odd-extent box through A, B and A again: every call
+    bit-equal to the oracle, and each context's profile names the kernels of its own forms and none of the other's."""
+    from castro_amd.hydro import HipHydro
+    theirs = {"CASTRO_AMD_XPAD": "12", "CASTRO_AMD_WG": "64", "CASTRO_AMD_FUSE_CONSUP": "0", "CASTRO_AMD_FOLD_R1": "0"}
+    keys = ["CASTRO_AMD_" + k for k in ("TILE_ROWS", "TRACE_TILE_ROWS", "FOLD_TILE_ROWS", "FUSED_TILE_ROWS", "WG", "FINAL_WG", "FUSED_WG",
+                                        "XPAD", "FUSE_CONSUP", "FOLD_R1", "FOLD_TILE", "FINAL_TILE", "GL_SOURCES", "GL_PLM",
+                                        "DIVU_IN_TRACE", "TRACE_ONE_ZONE", "SIDE_STREAM")]
+    old = {k: os.environ.get(k) for k in keys}
+    a = b = None
+    try:
         for k in keys:
-            if old[k] is None:
+            os.environ.pop(k, None)
+        a = HipHydro(0, numerics="exact")
+        os.environ.update(theirs)
+        b = HipHydro(0, numerics="exact")
+        for k in theirs:
+            del os.environ[k]
+        for h in (a, b):
+            h.profile(True)
+        rng = np.random.default_rng(5)
+        shape, bxlo = (37, 9, 11), (2, -3, 1)
+        bxhi = tuple(bxlo[d] + shape[d] - 1 for d in range(3))
+        sb_lo, sb_hi = tuple(x - 4 for x in bxlo), tuple(x + 4 for x in bxhi)
+        U = physical_state(rng, sb_lo, sb_hi, jump=True)
+        for h, who in ((a, "A"), (b, "B"), (a, "A again")):
+            out = _run_both(h, oracle, bxlo, bxhi, U, sb_lo, sb_hi, 6.0e-4, dx=(0.02, 0.015, 0.03))
+            _assert_exact(out, "context %s" % who)
+        fused, plain = {"k_finalx_consup", "k_trans1_fold"}, {"k_consup", "k_trans1"}
+        ra, rb = set(a.profile_report()), set(b.profile_report())
+        print("context A launched %s\ncontext B launched %s" % (sorted(ra), sorted(rb)))
+        assert fused <= ra and not (plain & ra), sorted(ra)
+        assert plain <= rb and not (fused & rb), sorted(rb)
+    finally:
+        for h in (a, b):
+            if h is not None:
+                h.close()
+        for k, v in old.items():
+            if v is None:
                 os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
 
 
 def test_colella_glaz_nan_sign_seeds_are_bit_exact():

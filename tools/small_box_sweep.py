@@ -62,7 +62,6 @@ def measure(n, env):
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
-        # the knobs are process-wide and re-read (unset = default) by the next context creation
 
 
 for n in sizes:
