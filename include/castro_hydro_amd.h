@@ -412,7 +412,11 @@ typedef struct castro_amd_diffusion {
     double diffuse_cond_scale_fac;      /* castro.diffuse_cond_scale_fac (default 1.0) */
 } castro_amd_diffusion;
 /* source(UEDEN) += mult * DiffTerm(state), source(UEINT) += mult * DiffTerm(state) on [lo, hi] (add_temp_diffusion_to_source);
- * diff_term (one component, or NULL): the bare DiffTerm as well (the reference's `diff_term` derive); source may be NULL then. */
+ * diff_term (one component, or NULL): the bare DiffTerm as well (the reference's `diff_term` derive); source may be NULL then.
+ * Only those two components of source and the one of diff_term are written, and only on [lo, hi].  An empty box (hi[d] < lo[d]
+ * in some direction) launches nothing and returns CASTRO_AMD_OK.  CASTRO_AMD_ERR_ARG, with nothing written: state not of 8
+ * components or not holding [lo, hi] grown by one; source of fewer than 6 components, diff_term not of exactly one, or either
+ * not holding [lo, hi]; source and diff_term both NULL (_mf: any box without a source). */
 int castro_amd_temp_diffusion_fab(castro_amd_ctx *ctx, const castro_amd_fab *state, const castro_amd_fab *source /* or NULL */,
                                   const castro_amd_fab *diff_term /* or NULL */, const int lo[3], const int hi[3],
                                   const castro_amd_diffusion *diff, const castro_amd_geom *geom, double mult, void *stream);
@@ -450,7 +454,11 @@ int castro_amd_estdt_temp_diffusion_mf(castro_amd_ctx *ctx, int nboxes, const ca
  * (diff_src, grav_src, rot_src: Castro_sources.cpp): stage 0 adds DiffTerm(S_old), stage 1 adds 0.5 * DiffTerm(S_new) and then
  * -0.5 * DiffTerm(S_old) to UEDEN and UEINT of the zeroed source before the other terms.  Two launches per stage: the stencil
  * goes first (the one-pass kernel writes S_new in place, and the new-time term reads the neighbours' S_new), the one-pass kernel
- * continues from the two components it left.  S_old (stage 1: S_new too) needs one filled ghost zone around [lo, hi].
+ * continues from the two components it left.  S_old needs one filled ghost zone around [lo, hi] at both stages (stage 1 reads
+ * it for the old-time half of the corrector); S_new needs one at stage 1 only -- stage 0 writes its valid zones and reads none of
+ * it.  A FAB without that zone is CASTRO_AMD_ERR_ARG, unsupported boundaries are CASTRO_AMD_ERR_UNSUPPORTED; every box of the
+ * table is checked before the first launch, so a refused call has written nothing.  The source FAB need not be initialised: the
+ * two energy components start from zero, the other components and the ghost zones of the FAB are zeroed.
  * diff == NULL: castro_amd_sources_mf, the same bits. */
 int castro_amd_sources_mf_ex(castro_amd_ctx *ctx, int stage, int nboxes, const castro_amd_source_box *boxes,
                              const double *grav /* [3] or NULL */, int grav_source_type, const castro_amd_rotation *rot /* or NULL */,

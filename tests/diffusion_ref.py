@@ -82,6 +82,84 @@ def estdt_temp_diffusion(U, box, lo, hi, geom, params, diff, max_dt):
     return float(np.nanmin(v))
 
 
+# ---- inputs and restatements of the unit tests -------------------------------------------------------------------------------
+def grow(lo, hi, g):
+    return tuple(x - g for x in lo), tuple(x + g for x in hi)
+
+
+def shape_of(box):
+    """(nz, ny, nx) of an array on `box`"""
+    return tuple(box[1][a] - box[0][a] + 1 for a in (2, 1, 0))
+
+
+def region(box, lo, hi):
+    """the slices (z, y, x) of [lo, hi] in an array on `box`"""
+    return tuple(slice(lo[a] - box[0][a], hi[a] - box[0][a] + 1) for a in (2, 1, 0))
+
+
+def random_state(rng, shape):
+    """the recipe of the unit case: every component uniform in (0.5, 3.5), so that with a cutoff of 1 and a cutoff_hi of 2.5
+    a sixth of the densities lies at or below the cutoff, half on the ramp and a third above it; T uniform in (1, 2)"""
+    U = rng.uniform(0.5, 3.5, size=(8,) + tuple(shape))
+    U[UTEMP] = rng.uniform(1.0, 2.0, size=tuple(shape))
+    return U
+
+
+def fill_ghosts(U, lo, hi, g, geom):
+    """what the ghost zones of a FAB on grow([lo, hi], g) hold in front of the term: the periodic image where the box spans a
+    periodic direction, NaN behind a physical face (the operator must not use it), and the values U came with (finite: the
+    neighbour box's data) wherever the edge of the box is interior to the domain"""
+    for d in range(3):
+        ax = 3 - d
+        n = hi[d] - lo[d] + 1
+        at_lo, at_hi = lo[d] == geom.domlo[d], hi[d] == geom.domhi[d]
+        if geom.lo_bc[d] == 0 and geom.hi_bc[d] == 0:
+            if at_lo and at_hi:
+                U[...] = np.take(U, g + (np.arange(-g, n + g) % n), axis=ax)
+            continue
+        idx = [slice(None)] * 4
+        if at_lo and geom.lo_bc[d] != 0:
+            idx[ax] = slice(0, g)
+            U[tuple(idx)] = np.nan
+        if at_hi and geom.hi_bc[d] != 0:
+            idx[ax] = slice(n + g, n + 2 * g)
+            U[tuple(idx)] = np.nan
+    return U
+
+
+def ghosted_state(rng, lo, hi, g, geom):
+    """(U, box): a random state (random_state) on grow([lo, hi], g) with the ghost zones of fill_ghosts"""
+    box = grow(lo, hi, g)
+    return fill_ghosts(random_state(rng, shape_of(box)), lo, hi, g, geom), box
+
+
+def source_stage(stage, S_old, old_box, S_new, new_box, src_box, src_ncomp, lo, hi, geom, diff, dt):
+    """castro_amd_sources_mf_ex without gravity, rotation and clean_state, for one box: (source, S_new after the stage, A).
+      stage 0: source(UEDEN, UEINT) = 0 + 1.0 * D(S_old);                        S_new = S_old + dt * source on [lo, hi]
+      stage 1: source(UEDEN, UEINT) = (0 + 0.5 * D(S_new)) + (-0.5) * D(S_old);  S_new += dt * source
+    every other component and every zone of the source FAB outside [lo, hi] is zero; A: the |m|-weighted sum of the terms' A"""
+    Do, Ao = diffusion_term(S_old, old_box, lo, hi, geom, diff)
+    nv = (slice(None),) + region(new_box, lo, hi)
+    if stage == 0:
+        term = 0.0 + 1.0 * Do
+        A = Ao
+        base = S_old[(slice(None),) + region(old_box, lo, hi)]
+    else:
+        Dn, An = diffusion_term(S_new, new_box, lo, hi, geom, diff)
+        term = (0.0 + 0.5 * Dn) + (-0.5) * Do
+        A = 0.5 * An + 0.5 * Ao
+        base = S_new[nv]
+    src = np.zeros((src_ncomp,) + shape_of(src_box))
+    sv = region(src_box, lo, hi)
+    src[UEDEN][sv] = term
+    src[UEINT][sv] = term
+    upd = base.copy()
+    upd[:7] = base[:7] + dt * src[(slice(0, 7),) + sv]
+    out = S_new.copy()
+    out[nv] = upd
+    return src, out, A
+
+
 class DiffusionOracleBackend(OracleBackend):
     """OracleBackend + the diffusion methods, in numpy"""
 

@@ -57,6 +57,128 @@ def test_restatement_against_a_hand_computed_zone():
     assert not R.supported(_G(g.dx, g.domlo, g.domhi, (1, 0, 0), (2, 0, 0))) and not R.supported(_G(g.dx, g.domlo, g.domhi, (2, 0, 0), (2, 3, 0)))
 
 
+# ---- the restatement against a manufactured solution -----------------------------------------------------------------------
+# T = a x^2 + b y^2 + c z^2 + p x + q y + r z + s at the zone centres of an anisotropic index space that does not start at zero.
+# The second difference of a quadratic is exact, so with a constant conductivity k every direction contributes 2 k a away from
+# a physical face; on a Neumann face the flux through the face is dropped and the normal part is the one-sided difference
+#   low face:  k (T+ - T0) / dx^2 =  k (a (2 x0 + dx) + p) / dx,      high face:  -k (T0 - T-) / dx^2 = -k (a (2 x0 - dx) + p) / dx
+# Nothing here is taken from the restatement: a dh on the wrong axis or the wrong side of a face is an O(1) error.
+MS_N, MS_DOMLO = (70, 9, 40), (-5, 3, 100)
+MS_PROB_LO, MS_PROB_HI = (0.0, -1.0, 2.0), (1.4, -0.1, 2.5)
+MS_K, MS_QUAD, MS_LIN, MS_CONST = 3.0, (1.3, -0.7, 2.1), (0.4, -1.1, 0.6), 5.0
+# the issue's boundaries (x periodic: four physical faces), and a mixed pair in x -- outflow low, interior high: each side is a
+# flag of its own in the operator -- for a fifth
+MS_BCS = {"periodic-x": ((0, 2, 4), (0, 2, 2)), "outflow-low-x": ((2, 2, 4), (0, 2, 2))}
+
+
+def _manufactured(lo_bc, hi_bc):
+    n, g = MS_N, 1
+    dx = tuple((MS_PROB_HI[d] - MS_PROB_LO[d]) / n[d] for d in range(3))
+    domhi = tuple(MS_DOMLO[d] + n[d] - 1 for d in range(3))
+    geom = _G(dx, MS_DOMLO, domhi, lo_bc, hi_bc)
+    x = [MS_PROB_LO[d] + (np.arange(-g, n[d] + g) + 0.5) * dx[d] for d in range(3)]            # ghost zones included
+    X, Y, Z = x[0][None, None, :], x[1][None, :, None], x[2][:, None, None]
+    T = (MS_QUAD[0] * X * X + MS_QUAD[1] * Y * Y + MS_QUAD[2] * Z * Z + MS_LIN[0] * X + MS_LIN[1] * Y + MS_LIN[2] * Z + MS_CONST)
+    box = R.grow(MS_DOMLO, domhi, g)
+    U = np.zeros((8,) + R.shape_of(box))
+    U[R.URHO], U[R.UTEMP] = 1.0, T
+    # the closed form, direction by direction
+    part = []
+    for d in range(3):
+        xc = x[d][g:-g]
+        e = np.full(n[d], 2.0 * MS_K * MS_QUAD[d])
+        if lo_bc[d] != 0:
+            e[0] = MS_K * (MS_QUAD[d] * (2.0 * xc[0] + dx[d]) + MS_LIN[d]) / dx[d]
+        if hi_bc[d] != 0:
+            e[-1] = -MS_K * (MS_QUAD[d] * (2.0 * xc[-1] - dx[d]) + MS_LIN[d]) / dx[d]
+        shape = [1, 1, 1]
+        shape[2 - d] = n[d]
+        part.append(e.reshape(shape))
+    want = part[0] + part[1] + part[2]
+    # the inputs are polynomials rounded to double: every T carries eps / 2 |T|, a face difference eps max|T|, six of them per
+    # zone weighted k / dx_d^2, the products, the sums and the closed form's own rounding on top -- 16 eps k max|T| sum_d 1 / dx_d^2
+    tol = 16.0 * np.finfo(float).eps * MS_K * float(np.abs(T).max()) * sum(1.0 / (h * h) for h in dx)
+    return geom, U, box, domhi, want, tol
+
+
+@pytest.mark.parametrize("bcs", sorted(MS_BCS))
+def test_restatement_against_a_manufactured_solution(bcs):
+    from castro_amd import _lib
+    lo_bc, hi_bc = MS_BCS[bcs]
+    geom, U, box, domhi, want, tol = _manufactured(lo_bc, hi_bc)
+    D, A = R.diffusion_term(U, box, MS_DOMLO, domhi, geom, _lib.make_diffusion(MS_K))
+    assert D.shape == MS_N[::-1] and tol < 1e-8
+    inner = tuple(slice(1 if lo_bc[d] != 0 else 0, -1 if hi_bc[d] != 0 else None) for d in (2, 1, 0))
+    err = float(np.abs(D[inner] - 2.0 * MS_K * sum(MS_QUAD)).max())
+    print("%s: away from the physical faces max |D - %.17g| = %.3e (bound %.3e)" % (bcs, 2.0 * MS_K * sum(MS_QUAD), err, tol))
+    assert abs(2.0 * MS_K * sum(MS_QUAD) - 16.2) < 1e-14 and np.array_equal(want[inner], np.full_like(D[inner], 2.0 * MS_K * sum(MS_QUAD)))
+    assert err <= tol
+    faces = 0
+    for d in range(3):
+        for side, bc in ((0, lo_bc[d]), (-1, hi_bc[d])):
+            if bc == 0:
+                continue
+            idx = [slice(None)] * 3
+            idx[2 - d] = side
+            idx = tuple(idx)
+            w = np.broadcast_to(want, D.shape)[idx]
+            ferr = float(np.abs(D[idx] - w).max())
+            print("%s: %s face of direction %d max |D - closed form| = %.3e" % (bcs, "high" if side else "low", d, ferr))
+            assert ferr <= tol, (d, side)
+            assert float(np.abs(w - 2.0 * MS_K * sum(MS_QUAD)).min()) > 1.0          # the one-sided form is nowhere near the interior's
+            faces += 1
+    assert faces == (4 if bcs == "periodic-x" else 5)
+    assert float(np.abs(D - want).max()) <= tol                                     # edges and corners: two and three faces at once
+    assert (A >= np.abs(D) * (1.0 - 1e-12)).all()                                    # the scale of the face contributions
+
+
+def test_restatement_constant_temperature_gives_an_exact_zero():
+    """densities across the ramp (below the cutoff, on it, above cutoff_hi) under a constant T: every face difference is an exact
+    zero whatever the face conductivity, so the term and its scale A are 0.0 in every zone, physical faces included"""
+    from castro_amd import _lib
+    lo_bc, hi_bc = MS_BCS["periodic-x"]
+    geom, U, box, domhi, _, _ = _manufactured(lo_bc, hi_bc)
+    rng = np.random.default_rng(11)
+    U[R.URHO] = rng.uniform(0.5, 3.5, size=U[R.URHO].shape)
+    U[R.UTEMP] = 1.75
+    rho = U[R.URHO]
+    assert (rho <= 1.0).mean() > 0.1 and ((rho > 1.0) & (rho < 2.5)).mean() > 0.3 and (rho >= 2.5).mean() > 0.2
+    D, A = R.diffusion_term(U, box, MS_DOMLO, domhi, geom, _lib.make_diffusion(MS_K, 1.0, 2.5, 0.7))
+    assert np.array_equal(D, np.zeros_like(D)) and np.array_equal(A, np.zeros_like(A))
+
+
+def test_unit_test_inputs():
+    """the input helpers of the GPU tests: the periodic image, NaN behind a physical face, neighbour data at an interior edge"""
+    rng = np.random.default_rng(3)
+    lo, hi, g = (-5, 3, 100), (-5, 5, 103), 2                       # one zone wide in x
+    geom = _G((1.0, 1.0, 1.0), (-5, 3, 90), (-5, 5, 103), (0, 2, 4), (0, 2, 2))
+    U, box = R.ghosted_state(rng, lo, hi, g, geom)
+    assert box == ((-7, 1, 98), (-3, 7, 105)) and U.shape == (8, 8, 7, 5)
+    v = U[:, g:-g, g:-g, g:-g]
+    assert np.isfinite(v).all()
+    for i in range(5):                                            # every x ghost zone is the image of the single valid column
+        assert np.array_equal(U[:, g:-g, g:-g, i:i + 1], v)
+    assert np.isnan(U[:, :, :g]).all() and np.isnan(U[:, :, -g:]).all()            # y: both faces physical
+    assert np.isnan(U[:, -g:]).all() and np.isfinite(U[:, :g, g:-g]).all()       # z: high face physical, low edge interior
+    assert R.region(box, lo, hi) == (slice(2, 6), slice(2, 5), slice(2, 3))
+    # the stage restatement: zero outside [lo, hi] and outside the two energies, and S_new = S_old + dt * source
+    U[np.isnan(U)] = 1.0
+    from castro_amd import _lib
+    diff = _lib.make_diffusion(3.0, 1.0, 2.5, 0.7)
+    sbox = R.grow(lo, hi, 3)
+    src, Sn, A = R.source_stage(0, U, box, np.full_like(U, -3.0), box, sbox, 7, lo, hi, geom, diff, 0.25)
+    D, A0 = R.diffusion_term(U, box, lo, hi, geom, diff)
+    sv = R.region(sbox, lo, hi)
+    assert np.array_equal(src[R.UEDEN][sv], D) and np.array_equal(src[R.UEINT][sv], D) and np.array_equal(A, A0)
+    src[R.UEDEN][sv] = src[R.UEINT][sv] = 0.0
+    assert not src.any()
+    assert np.array_equal(Sn[R.UEDEN][g:-g, g:-g, g:-g], v[R.UEDEN] + 0.25 * D) and np.array_equal(Sn[R.URHO][g:-g, g:-g, g:-g], v[R.URHO])
+    assert (Sn[:, :g] == -3.0).all() and (Sn[:, :, :, -g:] == -3.0).all()
+    # stage 1 with S_new = S_old: 0.5 D - 0.5 D is an exact zero
+    src1, Sn1, A1 = R.source_stage(1, U, box, U, box, (lo, hi), 7, lo, hi, geom, diff, 0.25)
+    assert not src1.any() and np.array_equal(Sn1, U) and np.array_equal(A1, 0.5 * A0 + 0.5 * A0)
+
+
 def test_diffusion_struct_and_symbols_in_both_builds():
     from castro_amd import _lib
     assert C.sizeof(_lib.Diffusion) == 4 * 8
