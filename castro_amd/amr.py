@@ -41,7 +41,7 @@ import torch
 
 from . import _lib as L
 from . import cluster as CL
-from .castro import Castro, NUM_GROW, NUM_STATE, checked_estimate
+from .castro import Castro, NUM_GROW, NUM_STATE, checked_estimate, density_failure, shell_slabs
 
 NSRC = 7                     # components of Source_Type (Castro_setup.cpp:317-327)
 
@@ -73,11 +73,7 @@ class _Patch(Castro):
         # coarse zones under the grown fine box, grown by one for the slopes
         self.cbox = (tuple(_coarsen(self.glo[d]) - 1 for d in range(3)), tuple(_coarsen(self.ghi[d]) + 1 for d in range(3)))
         self.ctmp = self.hydro.alloc(NUM_STATE, *self.cbox) if self.owned else None
-        lo, hi = self.lo, self.hi
-        glo, ghi = self.glo, self.ghi
-        self.shell = [((glo[0], glo[1], glo[2]), (ghi[0], ghi[1], lo[2] - 1)), ((glo[0], glo[1], hi[2] + 1), (ghi[0], ghi[1], ghi[2])),
-                      ((glo[0], glo[1], lo[2]), (ghi[0], lo[1] - 1, hi[2])), ((glo[0], hi[1] + 1, lo[2]), (ghi[0], ghi[1], hi[2])),
-                      ((glo[0], lo[1], lo[2]), (lo[0] - 1, hi[1], hi[2])), ((hi[0] + 1, lo[1], lo[2]), (ghi[0], hi[1], hi[2]))]
+        self.shell = shell_slabs(self.gbox, self.bx)
         if self.have_sources:
             self._bind_sources()
         # flux registers: the coarse faces on the six sides of this box
@@ -95,10 +91,7 @@ class _Patch(Castro):
         self.scbox = (tuple(_coarsen(slo[d]) - 1 for d in range(3)), tuple(_coarsen(shi[d]) + 1 for d in range(3)))
         self.stmp = self.hydro.alloc(NSRC, *self.scbox) if self.owned else None
         self.new_source_g = self.hydro.alloc(NSRC, *self.sbox) if self.owned else None
-        lo, hi = self.lo, self.hi
-        self.sshell = [((slo[0], slo[1], slo[2]), (shi[0], shi[1], lo[2] - 1)), ((slo[0], slo[1], hi[2] + 1), (shi[0], shi[1], shi[2])),
-                       ((slo[0], slo[1], lo[2]), (shi[0], lo[1] - 1, hi[2])), ((slo[0], hi[1] + 1, lo[2]), (shi[0], shi[1], hi[2])),
-                       ((slo[0], lo[1], lo[2]), (lo[0] - 1, hi[1], hi[2])), ((hi[0] + 1, lo[1], lo[2]), (shi[0], hi[1], hi[2]))]
+        self.sshell = shell_slabs(self.sbox, self.bx)
 
     def expand_state(self, S, box=None, neighbors=None):
         assert box is None, "the Source_Type FillPatch of a refined level is level-wide: _Level.fill_source"
@@ -153,11 +146,12 @@ class _Level:
             b.sib = [(s, it, sh) for s in self.boxes for sh in shifts if not (s is b and sh == (0, 0, 0))
                      for it in [CL.intersect(b.gbox, _shift(s.bx, sh))] if it]
             b.at_domain_edge = any(b.glo[d] < b.geom.domlo[d] or b.ghi[d] > b.geom.domhi[d] for d in range(3))
+            if self.have_sources:                                # the same table for the Source_Type FillPatch
+                b.ssib = [(sb, it, sh) for sb in self.boxes for sh in shifts if not (sb is b and sh == (0, 0, 0))
+                          for it in [CL.intersect(b.sbox, _shift(sb.bx, sh))] if it]
             if self.l == 0:                    # no coarser level: no coarse data, no flux registers, nothing to average onto
                 b.csrc, b.csrc_valid, b.crse_init, b.reflux_to, b.avg_to = [], [], {}, {}, []
                 if self.have_sources:
-                    b.ssib = [(sb, it, sh) for sb in self.boxes for sh in shifts if not (sb is b and sh == (0, 0, 0))
-                              for it in [CL.intersect(b.sbox, _shift(sb.bx, sh))] if it]
                     b.ssrc, b.ssrc_valid, b.sshell = [], [], []
                 continue
             b.csrc = [(p, it) for p in parents for it in [CL.intersect(b.cbox, p.gbox)] if it]
@@ -200,8 +194,6 @@ class _Level:
                     "belong to no box of that level" % (b.bx, self.l, self.l - 1, "xyz"[d] + "-+"[side])
             b.avg_to = [(p, it) for p in parents for it in [CL.intersect(b.pbox, p.bx)] if it]
             if self.have_sources:                                # the same tables for the Source_Type FillPatch
-                b.ssib = [(sb, it, sh) for sb in self.boxes for sh in shifts if not (sb is b and sh == (0, 0, 0))
-                          for it in [CL.intersect(b.sbox, _shift(sb.bx, sh))] if it]
                 b.ssrc = [(p, it) for p in parents for it in [CL.intersect(b.scbox, p.sbox)] if it]
                 b.ssrc_valid = [(p, it) for p in parents for it in [CL.intersect(b.scbox, p.bx)] if it]
         self._op_cache = {}
@@ -226,10 +218,7 @@ class _Level:
         if hasattr(h, "fillpatch_shell"):                       # both passes over the six slabs in one launch
             h.fillpatch_shell(b.ctmp, b.cbox, S, b.gbox, b.lo, b.hi, NUM_GROW, b.params, ntimes=1)
             return
-        for lo, hi in b.shell:
-            h.cc_interp(b.ctmp, b.cbox, S, b.gbox, lo, hi, NUM_STATE)
-        for lo, hi in b.shell:                                 # clean_state(Sborder) reaches the ghost zones too
-            h.clean_state(S, b.gbox, lo, hi, b.params, ntimes=1)
+        self._interp_shell(b, S)
 
     def _copy_siblings(self, b, S, which):
         h = self.hydro
@@ -313,7 +302,7 @@ class _Level:
     def _interp_shell(self, b, S):
         for lo, hi in b.shell:
             self.hydro.cc_interp(b.ctmp, b.cbox, S, b.gbox, lo, hi, NUM_STATE)
-        for lo, hi in b.shell:
+        for lo, hi in b.shell:                                 # clean_state(Sborder) reaches the ghost zones too
             self.hydro.clean_state(S, b.gbox, lo, hi, b.params, ntimes=1)
 
     def fill_box(self, b, S):
@@ -409,30 +398,21 @@ class _Level:
         return self._advance_with_sources_impl(time, dt)
 
     def _advance_with_sources_impl(self, time, dt):
-        """do_advance_ctu with old- and new-time gravity / rotation sources (Castro_advance_ctu.cpp:94-143, 156-274),
-        stage by stage over the boxes of the level; the per-box arithmetic is Castro._do_advance_with_sources'."""
+        """do_advance_ctu with old- and new-time gravity / rotation sources (Castro_advance_ctu.cpp:94-143, 156-274), stage by
+        stage over the boxes of the level.  The source stages are the single-level driver's own: Castro._source_stage box by
+        box, or Castro._sources_one_pass over the level's boxes."""
         h = self.hydro
-        fused = hasattr(h, "apply_source")
-        lvl = self._source_level_calls()        # the per-box stages below as one library call per level (castro_amd_sources_mf)
-        if lvl is not None:
+        lvl = self._source_level_calls()        # the per-box stages as one library call per level (castro_amd_sources_mf)
+
+        def sources(stage):
+            if lvl is None:
+                for b in self.mine:
+                    b._source_stage(stage, dt)
+                return
             sp = tuple(t.data_ptr() for b in self.mine for t in (b.S_old_b, b.S_new_b))
-            h.sources_mf(0, self._cached_ops(("src_old",), sp, lambda: h.make_source_boxes(
-                [(b.lo, b.hi, (b.S_old_b, b.gbox), (b.S_new_b, b.gbox), (b.old_source, b.sbox), b.mass_fluxes, b.flux_boxes)
-                 for b in self.mine])), lvl.grav if lvl.do_grav else None, lvl.grav_source_type if lvl.do_grav else 4, lvl.rotation,
-                         lvl.geom, self.params, dt, ntimes=1)
-        for b in (self.mine if lvl is None else ()):
-            S, lo, hi = b.S_old_b, b.lo, b.hi
-            b.old_source.zero_()
-            if b.do_grav:
-                h.old_gravity_source(S, b.gbox, b.old_source, b.sbox, lo, hi, b.grav, b.grav_source_type, dt)
-            if b.rotation is not None:
-                h.old_rotation_source(S, b.gbox, b.old_source, b.sbox, lo, hi, b.rotation, b.geom, dt)
-            if fused:
-                h.apply_source(b.S_new_b, b.gbox, S, b.gbox, dt, b.old_source, b.sbox, NSRC, lo, hi, b.params, ntimes=1)
-            else:
-                h.copy(b.S_new_b, b.gbox, S, b.gbox, lo, hi)
-                h.saxpy(b.S_new_b, b.gbox, dt, b.old_source, b.sbox, NSRC, lo, hi)
-                h.clean_state(b.S_new_b, b.gbox, lo, hi, b.params, ntimes=1)
+            lvl._sources_one_pass(stage, dt, self._cached_ops((("src_old", "src_new")[stage],), sp, lambda: h.make_source_boxes(
+                [b._source_spec(stage) for b in self.mine])))
+        sources(0)
         self.fill_source("old_source")
         predictor = self.params.source_term_predictor == 1
         def hydro(b):
@@ -449,29 +429,10 @@ class _Level:
             self._hydro_calls(hydro)
         self._clean_reduce_new()
         self.amr.comm.allreduce_min(self.red)
-        _, rho_min, _ = self.red.tolist()
-        if rho_min < self.params.small_dens:
-            return False, ("negative density" if rho_min < 0.0 else "small density") + " (density = %e)" % rho_min, None
-        if lvl is not None:
-            sp = tuple(t.data_ptr() for b in self.mine for t in (b.S_old_b, b.S_new_b))
-            h.sources_mf(1, self._cached_ops(("src_new",), sp, lambda: h.make_source_boxes(
-                [(b.lo, b.hi, (b.S_old_b, b.gbox), (b.S_new_b, b.gbox), (b.new_source, (b.lo, b.hi)), b.mass_fluxes, b.flux_boxes)
-                 for b in self.mine])), lvl.grav if lvl.do_grav else None, lvl.grav_source_type if lvl.do_grav else 4, lvl.rotation,
-                         lvl.geom, self.params, dt, ntimes=1)
-        for b in (self.mine if lvl is None else ()):
-            S, lo, hi = b.S_old_b, b.lo, b.hi
-            b.new_source.zero_()
-            if b.do_grav:
-                h.new_gravity_source(S, b.gbox, b.S_new_b, b.gbox, b.new_source, (lo, hi), b.mass_fluxes, b.flux_boxes,
-                                     lo, hi, b.grav, b.grav_source_type, dt, b.geom)
-            if b.rotation is not None:
-                h.new_rotation_source(S, b.gbox, b.S_new_b, b.gbox, b.new_source, (lo, hi), b.mass_fluxes, b.flux_boxes,
-                                      lo, hi, b.rotation, b.geom, dt)
-            if fused:
-                h.apply_source(b.S_new_b, b.gbox, b.S_new_b, b.gbox, dt, b.new_source, (lo, hi), NSRC, lo, hi, b.params, ntimes=1)
-            else:
-                h.saxpy(b.S_new_b, b.gbox, dt, b.new_source, (lo, hi), NSRC, lo, hi)
-                h.clean_state(b.S_new_b, b.gbox, lo, hi, b.params, ntimes=1)
+        bad = density_failure(self.red.tolist()[1], self.params)
+        if bad:
+            return bad
+        sources(1)
         new_dt = self.estTimeStep()
         if self.params.change_max * new_dt < dt:
             return False, "timestep validity check failed", None
@@ -577,8 +538,9 @@ class _Level:
             # the state leaves this advance as post_timestep will leave it (finest level, whole-step attempt): its CFL
             # estimate is what estTimeStep would reduce again from the same zones (Castro.step: _next_est)
             self._cached_est = est_last
-        if rho_min < self.params.small_dens:
-            return False, ("negative density" if rho_min < 0.0 else "small density") + " (density = %e)" % rho_min, None
+        bad = density_failure(rho_min, self.params)
+        if bad:
+            return bad
         new_dt = self.fixed_dt if self.fixed_dt > 0.0 else min(self.max_dt, est * self.params.cfl)
         if self.params.change_max * new_dt < dt:
             return False, "timestep validity check failed", None
@@ -627,8 +589,9 @@ class _Level:
         """The hydro update of every box of the level through ONE library call (the MFIter loop of
         construct_ctu_hydro_source in C++: boxes dealt round robin to the contexts / streams of the box-stream pool, forked
         from and joined to the current stream inside the call).  False: not applicable, the caller loops over the boxes.
-        with_src (_advance_with_sources_impl): every box hands its old-time source FAB to the call, which traces it and adds
-        the hydro update to the S_new the caller has prepared; the new-time sources follow, so nothing is fused behind it."""
+        with_src (_advance_with_sources_impl, between the two source stages): every box hands its old-time source FAB to the
+        call, which traces it and adds the hydro update to the S_new that stage 0 has prepared; the new-time stage follows, so
+        nothing is fused behind it."""
         if not self._level_calls() or not self.mine:
             return False
         fa = [bool(b.flux_assign and b._flux_clear) for b in self.mine]

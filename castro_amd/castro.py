@@ -208,6 +208,26 @@ class AdvanceFailure(RuntimeError):
     pass
 
 
+def density_reason(rho_min):
+    return ("negative density" if rho_min < 0.0 else "small density") + " (density = %e)" % rho_min
+
+
+def density_failure(rho_min, params):
+    """The S_new.min(URHO) verdict of an attempt (Castro_advance_ctu.cpp:168-216): the failure triple of do_advance_ctu, or
+    None.  retry_small_density_cutoff keeps its default (-1e200): every such step is rejected."""
+    return (False, density_reason(rho_min), None) if rho_min < params.small_dens else None
+
+
+def shell_slabs(outer, inner):
+    """The box `outer` minus the box `inner` inside it as six slabs (lo, hi), in the order z-, z+, y-, y+, x-, x+: the z slabs
+    take the full x,y extent, the y slabs the inner z range, the x slabs the inner y,z range.  The order is the order of the
+    launches and of the operation-table entries made from the list."""
+    (olo, ohi), (ilo, ihi) = outer, inner
+    return [((olo[0], olo[1], olo[2]), (ohi[0], ohi[1], ilo[2] - 1)), ((olo[0], olo[1], ihi[2] + 1), (ohi[0], ohi[1], ohi[2])),
+            ((olo[0], olo[1], ilo[2]), (ohi[0], ilo[1] - 1, ihi[2])), ((olo[0], ihi[1] + 1, ilo[2]), (ohi[0], ohi[1], ihi[2])),
+            ((olo[0], ilo[1], ilo[2]), (ilo[0] - 1, ihi[1], ihi[2])), ((ihi[0] + 1, ilo[1], ilo[2]), (ohi[0], ihi[1], ihi[2]))]
+
+
 # smallest box side from which the halo overlap is on by default in a multi-rank run.  Round 6: the LIGHT split (ctoprim with the
 # pending cleans on the valid zones beside the exchange, the ghost shell as one launch, everything downstream un-split) is host-free
 # under castro.use_retry and lives inside the per-rank step graph, so it is compared graph against graph: with all 26 regions
@@ -700,16 +720,7 @@ class Castro:
         ihi = tuple(self.hi[d] - g for d in range(3))
         if any(ihi[d] < ilo[d] for d in range(3)):
             return None, [self.bx]
-        shells = []
-        lo, hi = list(self.lo), list(self.hi)
-        # z slabs take the full x,y extent; y slabs the remaining z; x slabs the remaining y,z
-        shells.append(((lo[0], lo[1], lo[2]), (hi[0], hi[1], ilo[2] - 1)))
-        shells.append(((lo[0], lo[1], ihi[2] + 1), (hi[0], hi[1], hi[2])))
-        shells.append(((lo[0], lo[1], ilo[2]), (hi[0], ilo[1] - 1, ihi[2])))
-        shells.append(((lo[0], ihi[1] + 1, ilo[2]), (hi[0], hi[1], ihi[2])))
-        shells.append(((lo[0], ilo[1], ilo[2]), (ilo[0] - 1, ihi[1], ihi[2])))
-        shells.append(((ihi[0] + 1, ilo[1], ilo[2]), (hi[0], ihi[1], ihi[2])))
-        return (ilo, ihi), shells
+        return (ilo, ihi), shell_slabs(self.bx, (ilo, ihi))
 
     # ---- Castro::do_advance_ctu (Source/driver/Castro_advance_ctu.cpp:15-397) -----------------
     def do_advance_ctu(self, time, dt):
@@ -779,9 +790,9 @@ class Castro:
             h.clean_state_reduce(self.S_new_b, self.gbox, self.lo, self.hi, self.geom, self.params, self.red, ntimes=1)
         self.comm.allreduce_min(self.red)
         est, rho_min, est1 = self.red.tolist()
-        if rho_min < self.params.small_dens:
-            # retry_small_density_cutoff keeps its default (-1e200): every such step is rejected
-            return False, ("negative density" if rho_min < 0.0 else "small density") + " (density = %e)" % rho_min, None
+        bad = density_failure(rho_min, self.params)
+        if bad:
+            return bad
         # the validity check sees S_new cleaned once (Castro_advance_ctu.cpp:221-225, 386-392); what is handed on as the
         # next step's estimate is the one of the state as the step leaves it (post_timestep's clean_state included when
         # it rode along), which is what estTimeStep would return at the start of the next coarse step
@@ -808,9 +819,58 @@ class Castro:
         cur.wait_stream(self._comm_stream)
         self.construct_ctu_hydro_source(time, dt, fuse_clean=fuse, stage="rest", sborder_clean=sb_clean, bc_fill=bc_h, **kw)
 
+    def _source_spec(self, stage):
+        """This box as one entry of make_source_boxes for the old-time (0) / new-time (1) source stage: the old-time source
+        has NUM_GROW_SRC ghost zones for the tracing, the new-time corrector none."""
+        src = (self.old_source, self.sbox) if stage == 0 else (self.new_source, self.bx)
+        return (self.lo, self.hi, (self.S_old_b, self.gbox), (self.S_new_b, self.gbox), src, self.mass_fluxes, self.flux_boxes)
+
+    def _sources_one_pass(self, stage, dt, boxes=None):
+        """_source_stage in one pass (castro_amd_sources_mf, round 6): zero + diffusion + gravity + rotation + apply + clean_state
+        in one kernel -- the separate calls read and write the source and the state three to four times.  `boxes`: the
+        make_source_boxes table of a level whose boxes share the settings of this one (castro_amd/amr.py)."""
+        h = self.hydro
+        dkw = {} if self.diffusion is None else {"diffusion": self.diffusion}      # diff_src goes first (Castro_sources.cpp)
+        h.sources_mf(stage, boxes or h.make_source_boxes([self._source_spec(stage)]), self.grav if self.do_grav else None,
+                     self.grav_source_type if self.do_grav else 4, self.rotation, self.geom, self.params, dt, ntimes=1, **dkw)
+
+    def _source_stage(self, stage, dt):
+        """A source stage of this box by separate backend calls.  stage 0: MultiFab::Copy(S_new, Sborder) (Castro_advance_ctu.cpp:94)
+        and do_old_sources (:127-131) -- construct at t^n, apply with the full dt, clean_state; stage 1: do_new_sources (:262-268)
+        -- corrector from the new state, apply, clean_state (Source/sources/Castro_sources.cpp:230-349)."""
+        h = self.hydro
+        lo, hi, g = self.lo, self.hi, self.gbox
+        S, Sn = self.S_old_b, self.S_new_b
+        src, sbx = self._source_spec(stage)[4]
+        src.zero_()
+        if stage == 0:
+            if self.diffusion is not None:              # construct_old_diff_source: + 1.0 x DiffTerm(Sborder)
+                h.temp_diffusion(S, g, src, sbx, lo, hi, self.diffusion, self.geom, 1.0)
+            if self.do_grav:
+                h.old_gravity_source(S, g, src, sbx, lo, hi, self.grav, self.grav_source_type, dt)
+            if self.rotation is not None:
+                h.old_rotation_source(S, g, src, sbx, lo, hi, self.rotation, self.geom, dt)
+        else:
+            if self.diffusion is not None:              # construct_new_diff_source: + 0.5 x DiffTerm(S_new) - 0.5 x DiffTerm(Sborder)
+                h.temp_diffusion(Sn, g, src, sbx, lo, hi, self.diffusion, self.geom, 0.5)
+                h.temp_diffusion(S, g, src, sbx, lo, hi, self.diffusion, self.geom, -0.5)
+            if self.do_grav:
+                h.new_gravity_source(S, g, Sn, g, src, sbx, self.mass_fluxes, self.flux_boxes, lo, hi, self.grav,
+                                     self.grav_source_type, dt, self.geom)
+            if self.rotation is not None:
+                h.new_rotation_source(S, g, Sn, g, src, sbx, self.mass_fluxes, self.flux_boxes, lo, hi, self.rotation, self.geom, dt)
+        # S_new = (S_old | S_new) + dt x source, clean_state: in one pass where the backend has it
+        if hasattr(h, "apply_source"):
+            h.apply_source(Sn, g, S if stage == 0 else Sn, g, dt, src, sbx, 7, lo, hi, self.params, ntimes=1)
+        else:
+            if stage == 0:              # writes S_new only, the calls above the source only: their order is free
+                h.copy(Sn, g, S, g, lo, hi)
+            h.saxpy(Sn, g, dt, src, sbx, 7, lo, hi)
+            h.clean_state(Sn, g, lo, hi, self.params, ntimes=1)
+
     def _do_advance_with_sources(self, time, dt, S):
-        """do_advance_ctu with old- and new-time gravity / rotation sources (Castro_advance_ctu.cpp:94-143, 156-274;
-        construct_old_source / construct_new_source, Source/sources/Castro_sources.cpp:230-349)."""
+        """do_advance_ctu with old- and new-time diffusion / gravity / rotation sources (Castro_advance_ctu.cpp:94-143, 156-274);
+        the stages themselves are _source_stage / _sources_one_pass, shared with the levels of CastroAmr."""
         h = self.hydro
         lo, hi = self.lo, self.hi
         self.expand_state(S)
@@ -820,33 +880,9 @@ class Castro:
             if not self._in_retry:
                 self.create_source_corrector()
             h.set_source_corrector(self.source_corrector, self.sbox)
-        # MultiFab::Copy(S_new, Sborder) (:94); do_old_sources (:127-131): construct at t^n, apply with the full dt,
-        # clean_state -- the copy, the update and the cleaning in one pass where the backend has it
-        fused = hasattr(h, "apply_source")
-        # one pass (castro_amd_sources_mf, round 6): zero + gravity + rotation + apply + clean_state of a stage in one kernel
-        # -- the separate calls below read and write the source and the state three to four times
         one_pass = hasattr(h, "sources_mf") and os.environ.get("CASTRO_AMD_SOURCES_ONE_PASS", "1") != "0"
-        dkw = {} if self.diffusion is None else {"diffusion": self.diffusion}      # diff_src goes first (Castro_sources.cpp)
-        if one_pass:
-            h.sources_mf(0, h.make_source_boxes([(lo, hi, (S, self.gbox), (self.S_new_b, self.gbox), (self.old_source, self.sbox),
-                                                  self.mass_fluxes, self.flux_boxes)]),
-                         self.grav if self.do_grav else None, self.grav_source_type if self.do_grav else 4, self.rotation, self.geom,
-                         self.params, dt, ntimes=1, **dkw)
-        elif not fused:
-            h.copy(self.S_new_b, self.gbox, S, self.gbox, lo, hi)
-        if not one_pass:
-            self.old_source.zero_()
-            if self.diffusion is not None:              # construct_old_diff_source: + 1.0 x DiffTerm(Sborder)
-                h.temp_diffusion(S, self.gbox, self.old_source, self.sbox, lo, hi, self.diffusion, self.geom, 1.0)
-            if self.do_grav:
-                h.old_gravity_source(S, self.gbox, self.old_source, self.sbox, lo, hi, self.grav, self.grav_source_type, dt)
-            if self.rotation is not None:
-                h.old_rotation_source(S, self.gbox, self.old_source, self.sbox, lo, hi, self.rotation, self.geom, dt)
-            if fused:
-                h.apply_source(self.S_new_b, self.gbox, S, self.gbox, dt, self.old_source, self.sbox, 7, lo, hi, self.params, ntimes=1)
-            else:
-                h.saxpy(self.S_new_b, self.gbox, dt, self.old_source, self.sbox, 7, lo, hi)
-                h.clean_state(self.S_new_b, self.gbox, lo, hi, self.params, ntimes=1)
+        sources = self._sources_one_pass if one_pass else self._source_stage
+        sources(0, dt)
         if self.do_hydro:
             # FillPatch of the source for the tracing
             self.expand_state(self.old_source, self.sbox, self.src_neighbors)
@@ -860,9 +896,9 @@ class Castro:
             # S_new.min(URHO) (:168-216), clean_state(S_new) (:221-225)
             h.clean_state_reduce(self.S_new_b, self.gbox, lo, hi, self.geom, self.params, self.red, ntimes=1)
             self.comm.allreduce_min(self.red)
-            _, rho_min, _ = self.red.tolist()
-            if rho_min < self.params.small_dens:
-                return False, ("negative density" if rho_min < 0.0 else "small density") + " (density = %e)" % rho_min, None
+            bad = density_failure(self.red.tolist()[1], self.params)
+            if bad:
+                return bad
         else:
             # castro.do_hydro = 0 (:137-217): no FillPatch of the old source, no hydro update, no density check;
             # the clean_state(S_new) of :221-225 stays
@@ -874,29 +910,7 @@ class Castro:
             # FillPatches the new state with one ghost zone, Castro_diffusion.cpp:113).  The physical-boundary faces carry no
             # flux whatever their ghost zones hold, so no boundary fill.
             self.expand_state(self.S_new_b, bc=False)
-        # do_new_sources (:262-268): corrector from the new state, apply, clean_state
-        if one_pass:
-            h.sources_mf(1, h.make_source_boxes([(lo, hi, (S, self.gbox), (self.S_new_b, self.gbox), (self.new_source, (lo, hi)),
-                                                  self.mass_fluxes, self.flux_boxes)]),
-                         self.grav if self.do_grav else None, self.grav_source_type if self.do_grav else 4, self.rotation, self.geom,
-                         self.params, dt, ntimes=1, **dkw)
-        else:
-            self.new_source.zero_()
-            if self.diffusion is not None:              # construct_new_diff_source: + 0.5 x DiffTerm(S_new) - 0.5 x DiffTerm(Sborder)
-                h.temp_diffusion(self.S_new_b, self.gbox, self.new_source, (lo, hi), lo, hi, self.diffusion, self.geom, 0.5)
-                h.temp_diffusion(S, self.gbox, self.new_source, (lo, hi), lo, hi, self.diffusion, self.geom, -0.5)
-            if self.do_grav:
-                h.new_gravity_source(S, self.gbox, self.S_new_b, self.gbox, self.new_source, (lo, hi), self.mass_fluxes,
-                                     self.flux_boxes, lo, hi, self.grav, self.grav_source_type, dt, self.geom)
-            if self.rotation is not None:
-                h.new_rotation_source(S, self.gbox, self.S_new_b, self.gbox, self.new_source, (lo, hi), self.mass_fluxes,
-                                      self.flux_boxes, lo, hi, self.rotation, self.geom, dt)
-            if fused:
-                h.apply_source(self.S_new_b, self.gbox, self.S_new_b, self.gbox, dt, self.new_source, (lo, hi), 7, lo, hi,
-                               self.params, ntimes=1)
-            else:
-                h.saxpy(self.S_new_b, self.gbox, dt, self.new_source, (lo, hi), 7, lo, hi)
-                h.clean_state(self.S_new_b, self.gbox, lo, hi, self.params, ntimes=1)
+        sources(1, dt)
         # timestep validity check (:386-392)
         new_dt = self.estTimeStep()
         if self.params.change_max * new_dt < dt:
@@ -1231,9 +1245,7 @@ class Castro:
             if (nsteps - done) % 2 == 0:
                 self._swap_state_time_levels()
             dt_failed = v[L.CTL_DT]                 # not advanced on a rejected step
-            rho_min = v[L.CTL_RHOMIN]
-            why = ("negative density" if rho_min < 0.0 else "small density") + " (density = %e)" % rho_min if status & 1 \
-                else "timestep validity check failed"
+            why = density_reason(v[L.CTL_RHOMIN]) if status & 1 else "timestep validity check failed"
             if not self.use_retry:
                 raise AdvanceFailure("Advance was unsuccessful: %s (step %d of a host-free batch)" % (why, self.nstep + 1))
             # Castro::retry_advance_ctu on the host: the step again from its (already cleaned) old state; the first

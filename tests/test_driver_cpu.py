@@ -78,6 +78,19 @@ def test_interior_plus_shell_tiles_equal_whole_box(oracle):
         assert np.array_equal(a.mass_fluxes[d].numpy(), b.mass_fluxes[d].numpy())
 
 
+def test_shell_slabs_tile_the_ghost_shell_once():
+    """shell_slabs(grown box, box) of a 16^3 box with 4 ghost zones: every zone of the shell in exactly one slab, the slabs in
+    the order z-, z+, y-, y+, x-, x+ (the order of the launches and operation-table entries made from them)."""
+    from castro_amd.castro import shell_slabs
+    cnt = np.zeros((24, 24, 24), dtype=int)                  # [z, y, x] of the grown box, origin at -4
+    slabs = shell_slabs(((-4, -4, -4), (19, 19, 19)), ((0, 0, 0), (15, 15, 15)))
+    for lo, hi in slabs:
+        cnt[lo[2] + 4:hi[2] + 5, lo[1] + 4:hi[1] + 5, lo[0] + 4:hi[0] + 5] += 1
+    assert cnt[4:20, 4:20, 4:20].sum() == 0 and cnt.sum() == 24 ** 3 - 16 ** 3 == 9728 and cnt.max() == 1
+    sides = [(d, s) for lo, hi in slabs for d in range(3) for s in (0, 1) if (hi[d] == -1, lo[d] == 16)[s]]
+    assert sides == [(2, 0), (2, 1), (1, 0), (1, 1), (0, 0), (0, 1)]
+
+
 def test_default_grid():
     import castro_amd
     assert castro_amd.default_grid(1) == (1, 1, 1)
