@@ -68,6 +68,7 @@ EXPORTED_SYMBOLS = (
     "castro_amd_cmpflx_points", "castro_amd_ppm_points", "castro_amd_flatten_points", "castro_amd_trans_points",
     "castro_amd_temp_diffusion_fab", "castro_amd_temp_diffusion_mf", "castro_amd_estdt_temp_diffusion_fab",
     "castro_amd_estdt_temp_diffusion_mf", "castro_amd_sources_mf_ex",
+    "castro_amd_integrated_quantities_mf", "castro_amd_diag_workgroups",
 )
 
 
@@ -111,6 +112,18 @@ class SourceBox(C.Structure):
 class StateBox(C.Structure):
     """castro_amd_state_box: one box of castro_amd_clean_state_reduce_mf / castro_amd_estdt_mf"""
     _fields_ = [("lo", C.c_int * 3), ("hi", C.c_int * 3), ("state", Fab)]
+
+
+class DiagBox(C.Structure):
+    """castro_amd_diag_box: one box of a castro_amd_integrated_quantities_mf call"""
+    _fields_ = [("lo", C.c_int * 3), ("hi", C.c_int * 3), ("state", Fab), ("mask", C.c_void_p)]
+
+
+# CASTRO_AMD_DIAG_*: the order of the sums castro_amd_integrated_quantities_mf writes (include/castro_hydro_amd.h)
+DIAG_N = 14
+(DIAG_MASS, DIAG_XMOM, DIAG_YMOM, DIAG_ZMOM, DIAG_ANGMOM_X, DIAG_ANGMOM_Y, DIAG_ANGMOM_Z, DIAG_RHO_E_INT, DIAG_RHO_K, DIAG_RHO_E,
+ DIAG_COM_X, DIAG_COM_Y, DIAG_COM_Z, DIAG_SPECIES) = range(DIAG_N)
+M_SOLAR = 1.9884e33        # C::M_solar of the reference's constants, cgs: species_diag.out is in solar masses
 
 
 class Rotation(C.Structure):
@@ -264,6 +277,10 @@ def load(numerics=None):
     L.castro_amd_clean_state_reduce_mf.argtypes = [C.c_void_p, C.c_int, C.POINTER(StateBox), C.POINTER(Geom), C.POINTER(Params),
                                                    C.c_int, C.c_void_p, C.c_void_p]
     L.castro_amd_estdt_mf.argtypes = [C.c_void_p, C.c_int, C.POINTER(StateBox), C.POINTER(Geom), C.POINTER(Params), C.c_void_p, C.c_void_p]
+    if hasattr(L, "castro_amd_integrated_quantities_mf"):   # absent from A/B builds of revisions before the integrated quantities
+        L.castro_amd_integrated_quantities_mf.argtypes = [C.c_void_p, C.c_int, C.POINTER(DiagBox), C.POINTER(Geom),
+                                                          C.POINTER(C.c_double * 3), C.c_void_p, C.c_void_p]
+        L.castro_amd_diag_workgroups.argtypes = [C.c_int, C.POINTER(DiagBox)]
     L.castro_amd_step_control.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_double, C.c_double,
                                           C.c_double, C.c_int, C.c_void_p]
     L.castro_amd_clean_state_fab.argtypes = [C.c_void_p, PF, I3, I3, C.POINTER(Params), C.c_int, C.c_void_p]

@@ -634,8 +634,10 @@ class CastroAmr:
                  params=None, make_hydro=None, make_params=None, refine=None, regrid_int=2, n_error_buf=1,
                  blocking_factor=8, patches=None, max_level=1, cluster=False, grid_eff=0.7, max_grid_size=128,
                  do_grav=False, const_grav=0.0, grav_source_type=4, rotation=None, comm=None, base_grid=None, box_streams=4,
-                 diffusion=None):
-        """base_grid = (gx, gy, gz): level 0 as gx x gy x gz equal boxes instead of one (amr.max_grid_size on the base level);
+                 diffusion=None, sum_interval=-1, show_center_of_mass=False, diag_dir=None):
+        """sum_interval, show_center_of_mass, diag_dir: as in castro_amd.Castro -- sum_integrated_quantities() over the composite
+        grid after initData and after every coarse step with nstep % sum_interval == 0 (self.diag_history, the three data logs).
+        base_grid = (gx, gy, gz): level 0 as gx x gy x gz equal boxes instead of one (amr.max_grid_size on the base level);
         with `comm` they are dealt over the ranks like the boxes of the refined levels.
         comm: a castro_amd.DistComm to spread the boxes of every refined level over its ranks (box i of level l on rank
         (i + l) mod size, level 0 on rank 0 unless base_grid cuts it up): every rank builds the same hierarchy, holds the
@@ -708,6 +710,9 @@ class CastroAmr:
         self.time, self.nstep = 0.0, 0
         self.dt_level = [0.0] * 16
         self.level_count = [0] * 16                                   # Amr::level_count: steps of a level since its last regrid
+        from .diag import DiagLog
+        self.diag = DiagLog(sum_interval, show_center_of_mass, diag_dir, io_rank=self.rank == 0)
+        self._diag_out = None
 
     # views used by the tests and the plotfile writer
     crse = property(lambda self: self.lev[0])
@@ -893,9 +898,11 @@ class CastroAmr:
         lev = self._make_level(len(self.lev), pboxes)
         self.lev.append(lev)
         lev.bind()
+        self._diag_masks, self._diag_tables = {}, {}    # the zones of the level below that are covered have changed
 
     def _drop_fine(self):
         del self.lev[1:]
+        self._diag_masks, self._diag_tables = {}, {}
 
     # ---- Castro::errorEst (Castro.cpp:3131-3164) ---------------------------------------------------
     def _fill_ghosts_new(self, upto, lbase=0, alpha=1.0):
@@ -1095,6 +1102,7 @@ class CastroAmr:
         while keep <= min(len(new), len(self.lev) - 1) and new[keep - 1] == self.boxes[keep]:
             keep += 1
         del self.lev[keep:]
+        self._diag_masks, self._diag_tables = {}, {}
         for l in range(keep, len(new) + 1):
             parent = self.lev[l - 1]
             if l - 1 >= keep:                                   # a level made in this regrid: its ghost zones are not filled yet
@@ -1171,6 +1179,9 @@ class CastroAmr:
             self.avgDown(l)
         self.time, self.nstep = 0.0, 0
         self.level_count = [0] * 16
+        self.diag.reset()
+        if self.diag.sum_interval > 0:                  # Castro::post_init: the entry of time 0, dt reported as 0
+            self.diag.record(self.sum_integrated_quantities(), 0, 0.0, finest_level=len(self.lev) - 1)
 
     # ---- Castro::avgDown (Castro.cpp:3096-3113): level l onto level l-1 ------------------------------
     def invalidate_estimates(self):
@@ -1294,6 +1305,7 @@ class CastroAmr:
 
     # ---- Amr::coarseTimeStep ---------------------------------------------------------------------
     def step(self, stop_time=-1.0):
+        self.diag.begin_steps(1)
         dt0 = self._dt0(stop_time, self.nstep == 0)
         for l in range(len(self.dt_level)):
             self.dt_level[l] = dt0 / (2 ** l)
@@ -1303,6 +1315,8 @@ class CastroAmr:
         self.nstep += 1
         for lev in self.lev:
             lev.time, lev.nstep = self.time, self.nstep
+        if self.diag.due(self.nstep):                   # Castro::post_timestep of level 0
+            self.diag.record(self.sum_integrated_quantities(), self.nstep, dt0, finest_level=len(self.lev) - 1)
         return dt0
 
     def evolve(self, stop_time, max_step=10 ** 9):
@@ -1329,6 +1343,68 @@ class CastroAmr:
                             S[p[2] - o[2]:q[2] - o[2] + 1, p[1] - o[1]:q[1] - o[1] + 1, p[0] - o[0]:q[0] - o[0] + 1] = 0.0
                 tot += S.sum().item() * v
         return tot
+
+    # ---- Castro::sum_integrated_quantities over the hierarchy (Source/driver/sum_integrated_quantities.cpp:60-120) ----------
+    sum_interval = property(lambda self: self.diag.sum_interval)
+    diag_history = property(lambda self: self.diag.history)
+
+    def _diag_mask_key(self, l):
+        """what the byte masks of level l depend on: its own boxes and the coarse zones the next level covers"""
+        return (tuple(self.lev[l].box_list()), tuple(tuple(map(tuple, f.pbox)) for f in self.lev[l + 1].boxes))
+
+    def _diag_level_masks(self, l):
+        """{box: uint8 tensor (nz, ny, nx), 0 where level l + 1 covers the zone} for the boxes of level l this rank owns (the
+        build_fine_mask of sum_utils.cpp:29-33); None for the finest level.  Built once per regrid: regrid, _push_level and
+        _drop_fine empty the cache."""
+        if l + 1 >= len(self.lev):
+            return None
+        cache = self.__dict__.setdefault("_diag_masks", {})
+        key = self._diag_mask_key(l)
+        ent = cache.get(l)
+        if ent is None or ent[0] != key:
+            masks = {}
+            for b in self.lev[l].mine:
+                m = torch.ones((b.n[2], b.n[1], b.n[0]), dtype=torch.uint8, device=b.S_new_b.device)
+                o = b.lo
+                for f in self.lev[l + 1].boxes:
+                    it = CL.intersect(f.pbox, b.bx)
+                    if it:
+                        (p, q) = it
+                        m[p[2] - o[2]:q[2] - o[2] + 1, p[1] - o[1]:q[1] - o[1] + 1, p[0] - o[0]:q[0] - o[0] + 1] = 0
+                masks[b.bx] = m
+            ent = cache[l] = (key, masks)
+        return ent[1]
+
+    def sum_integrated_quantities(self):
+        """The integrated quantities of the composite grid (the finest data wherever a zone is refined): one library call per
+        level -- below the finest with the byte masks of the zones the next level covers --, the 14-vectors of the levels
+        added on the device in level order, then one allreduce(SUM) and one copy to the host for the whole hierarchy."""
+        from . import diag
+        center = diag.domain_center(self.lev[0])
+        tot = None
+        for l, lev in enumerate(self.lev):
+            h = lev.hydro
+            if not hasattr(h, "integrated_quantities_mf"):
+                raise RuntimeError("castro_amd: this backend has no integrated_quantities_mf; there is no host fallback")
+            if self._diag_out is None:
+                self._diag_out = [h.alloc(1, (0, 0, 0), (L.DIAG_N - 1, 0, 0)).reshape(L.DIAG_N) for _ in range(2)]
+            masks = self._diag_level_masks(l)
+            sp = tuple(b.S_new_b.data_ptr() for b in lev.mine) + tuple(m.data_ptr() for m in (masks or {}).values())
+            tables = self.__dict__.setdefault("_diag_tables", {})     # raw pointers: one table per configuration of the state buffers
+            if (l, sp) not in tables:
+                if len(tables) > 64:
+                    tables.clear()
+                tables[(l, sp)] = h.make_diag_boxes(
+                    [(b.lo, b.hi, (b.S_new_b, b.gbox), masks[b.bx] if masks is not None else None) for b in lev.mine])
+            boxes = tables[(l, sp)]
+            out = self._diag_out[0 if l == 0 else 1]
+            h.integrated_quantities_mf(boxes, lev.geom, center, out)
+            if l == 0:
+                tot = out
+            else:
+                tot += out
+        self.comm.allreduce_sum(tot)
+        return diag.quantities(self.time, tot.tolist())
 
     def zones_advanced_per_coarse_step(self):
         """Zone updates of one coarse step (level l advances 2^l times): the reference's FOM numerator."""

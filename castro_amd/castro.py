@@ -70,6 +70,9 @@ class SingleComm:
     def allreduce_min(self, t):
         return t
 
+    def allreduce_sum(self, t):
+        return t
+
     def barrier(self):
         pass
 
@@ -171,6 +174,17 @@ class DistComm:
         self.dist.all_reduce(t, op=self.dist.ReduceOp.MIN, group=self.group)
         return t
 
+    def allreduce_sum(self, t):
+        """ParallelDescriptor::ReduceRealSum of the integrated quantities: torch.distributed all_reduce(SUM) (RCCL on the
+        device; gloo moves host memory, like allreduce_min)"""
+        if t.is_cuda and self.dist.get_backend(self.group) == "gloo":
+            h = t.cpu()
+            self.dist.all_reduce(h, op=self.dist.ReduceOp.SUM, group=self.group)
+            t.copy_(h)
+            return t
+        self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=self.group)
+        return t
+
     def barrier(self):
         self.dist.barrier(group=self.group)
 
@@ -244,8 +258,12 @@ class Castro:
                  params=None, hydro=None, comm=None, grid=None, overlap=None, make_params=None, fuse_clean=True, flux_assign=True,
                  use_retry=True, retry_subcycle_factor=0.5, max_subcycles=10, dt_cutoff=1.e-12,
                  do_grav=False, const_grav=0.0, grav_source_type=4, box=None, rotation=None, fixed_dt=-1.0, initial_dt=-1.0, max_dt=1.e200,
-                 alloc=True, numerics=None, proxy_ranks=1, diffusion=None, do_hydro=True):
-        """diffusion: _lib.make_diffusion(const_conductivity=..., ...) turns on castro.diffuse_temp = 1 (explicit thermal diffusion,
+                 alloc=True, numerics=None, proxy_ranks=1, diffusion=None, do_hydro=True,
+                 sum_interval=-1, show_center_of_mass=False, diag_dir=None):
+        """sum_interval (castro.sum_interval, default -1: never), show_center_of_mass, diag_dir: the integrated quantities of
+        sum_integrated_quantities() after initData and after every coarse step with nstep % sum_interval == 0, kept in
+        self.diag_history and appended to diag_dir/{grid,species,amr}_diag.out by the I/O rank (castro_amd/diag.py).
+        diffusion: _lib.make_diffusion(const_conductivity=..., ...) turns on castro.diffuse_temp = 1 (explicit thermal diffusion,
         Source/diffusion/); do_hydro=False: castro.do_hydro = 0, the source stages without the hydro update.  numerics: "exact" | "contract" for the HipHydro this object creates (castro_amd/_lib.py).  alloc=False: the geometry and bookkeeping of a box another rank owns (castro_amd/amr.py), no device memory."""
         self.n_cell = tuple(int(x) for x in n_cell)
         self.owned = bool(alloc)
@@ -377,6 +395,9 @@ class Castro:
         self.dt = 0.0
         self.nstep = 0
         self.hydro_seconds = 0.0
+        from .diag import DiagLog
+        self.diag = DiagLog(sum_interval, show_center_of_mass, diag_dir, io_rank=self.comm.rank == 0)
+        self._diag_out, self._diag_tables = None, {}
         if hasattr(hydro, "reserve"):
             hydro.reserve(*self.n)
 
@@ -595,6 +616,7 @@ class Castro:
             raise ValueError(problem)
         self.clean_state(self.S_new_b, 1)      # Castro.cpp:1100-1160
         self.time, self.nstep, self.dt = 0.0, 0, 0.0
+        self._diag_post_init()
 
     def diffusion_test_analytic(self, time, diff_coeff=1.0, T1=1.0, T2=2.0, t_0=1.e-3):
         """The temperature of Exec/unit_tests/diffusion_test at `time` on the whole domain, (nz, ny, nx): a Gaussian pulse about
@@ -632,6 +654,40 @@ class Castro:
         self.S_new_b[:, g:g + n[2], g:g + n[1], g:g + n[0]] = part.to(self.S_new_b.device, self.S_new_b.dtype)
         self.clean_state(self.S_new_b, 1)
         self.time, self.nstep, self.dt = 0.0, 0, 0.0
+        self._diag_post_init()
+
+    # ---- Castro::sum_integrated_quantities (Source/driver/sum_integrated_quantities.cpp) ---------------------
+    sum_interval = property(lambda self: self.diag.sum_interval)
+    diag_history = property(lambda self: self.diag.history)
+
+    def sum_integrated_quantities(self):
+        """mass, momenta, angular momenta (about the centre the plotfile derives use), internal / kinetic / total energy,
+        centre of mass and its velocity, species mass (in solar masses) of the whole level at the new time: ONE library call
+        over this rank's box, one allreduce(SUM), one copy of 14 doubles to the host."""
+        from . import diag
+        h = self.hydro
+        if not hasattr(h, "integrated_quantities_mf"):
+            raise RuntimeError("castro_amd: this backend has no integrated_quantities_mf; there is no host fallback")
+        if self._diag_out is None:
+            self._diag_out = h.alloc(1, (0, 0, 0), (L.DIAG_N - 1, 0, 0)).reshape(L.DIAG_N)
+        S = self.S_new_b
+        key = S.data_ptr()                      # the two state buffers swap roles every step: one table each
+        if key not in self._diag_tables:
+            self._diag_tables[key] = h.make_diag_boxes([(self.lo, self.hi, (S, self.gbox), None)])
+        h.integrated_quantities_mf(self._diag_tables[key], self.geom, diag.domain_center(self), self._diag_out)
+        self.comm.allreduce_sum(self._diag_out)
+        return diag.quantities(self.time, self._diag_out.tolist())
+
+    def _diag_post_init(self):
+        """Castro::post_init: the entry of time 0 (dt reported as 0)"""
+        self.diag.reset()
+        if self.diag.sum_interval > 0:
+            self.diag.record(self.sum_integrated_quantities(), self.nstep, 0.0)
+
+    def _diag_post_timestep(self):
+        """Castro::post_timestep: nstep % sum_interval == 0"""
+        if self.diag.due(self.nstep):
+            self.diag.record(self.sum_integrated_quantities(), self.nstep, self.dt)
 
     # ---- Castro::estTimeStep (hydro limiter) -------------------------------------------------
     def _reduce(self):
@@ -1022,6 +1078,7 @@ class Castro:
 
     # ---- Amr::coarseTimeStep loop -----------------------------------------------------------
     def step(self, stop_time=-1.0):
+        self.diag.begin_steps(1)
         if self.nstep == 0:
             self.dt = self.computeInitialDt(stop_time)
         else:
@@ -1032,6 +1089,7 @@ class Castro:
             self._next_est = None                   # computeNewDt estimates from the state post_timestep leaves
         self.time += self.dt
         self.nstep += 1
+        self._diag_post_timestep()
         return self.dt
 
     # ---- host-free stepping: dt, time and the step checks stay on the device -----------------------------------
@@ -1196,6 +1254,7 @@ class Castro:
             for _ in range(nsteps):
                 self.step(stop_time)
             return
+        self.diag.begin_steps(nsteps)
         dt0 = self.computeInitialDt(stop_time) if self.nstep == 0 else self.computeNewDt(self.dt, stop_time, est=self._next_est)
         self._ensure_ctl()
         head = torch.zeros(L.CTL_HIST, dtype=torch.float64)
@@ -1261,6 +1320,9 @@ class Castro:
             self.time += self.dt
             self.nstep += 1
             self.run_steps(nsteps - done - 1, stop_time, graph=graph)
+        # the sum of the step the batch ends on, at the batch's one synchronisation (evolve ends every batch on a multiple of
+        # sum_interval; a caller's own batch that runs past one has kept no state to sum there)
+        self._diag_post_timestep()
 
     def evolve(self, stop_time, max_step=10 ** 9, host_free=None):
         """Amr::coarseTimeStep until stop_time (or max_step).  host_free (default: whenever host_free_ok()): the steps go out
@@ -1282,7 +1344,7 @@ class Castro:
                     k = int(math.floor(math.log(x) / math.log(cm))) if x > 1.0 else 0
                 else:
                     k = int(0.99 * remaining / self.dt)
-                k = min(k, max_step - self.nstep, 4 * L.CTL_NHIST)
+                k = self.diag.cap(min(k, max_step - self.nstep, 4 * L.CTL_NHIST), self.nstep)
             if k >= 2:
                 self.run_steps(k, stop_time)
             else:

@@ -29,6 +29,8 @@ struct castro_amd_ctx {
     FabOpsArena level_arena;                        // device table of a level-wide hydro launch (castro_amd_ctu_hydro_mf)
     FabOpsArena diff_arena;                         // device table of a thermal-diffusion launch (castro_amd_temp_diffusion_*)
     hipEvent_t mf_fork = nullptr, mf_join = nullptr;   // castro_amd_ctu_hydro_mf: fork from / join to the caller's stream
+    FabOpsArena diag_arena;                         // device table of castro_amd_integrated_quantities_mf
+    DiagWorkspace diag_ws;                          // its rows of partial sums, one per workgroup
 };
 
 namespace cad {
@@ -242,6 +244,8 @@ void castro_amd_ctx_destroy(castro_amd_ctx* c)
     if (c->ops_arena.p) hipFree(c->ops_arena.p);
     if (c->level_arena.p) hipFree(c->level_arena.p);
     if (c->diff_arena.p) hipFree(c->diff_arena.p);
+    if (c->diag_arena.p) hipFree(c->diag_arena.p);
+    if (c->diag_ws.p) hipFree(c->diag_ws.p);
     prof_collect(&c->prof);
     for (auto e : c->prof.pool) hipEventDestroy(e);
     if (c->arena) hipFree(c->arena);
@@ -754,6 +758,50 @@ int castro_amd_estdt_mf(castro_amd_ctx* c, int nboxes, const castro_amd_state_bo
         if (rc != CASTRO_AMD_OK) return rc;
     }
     return CASTRO_AMD_OK;
+}
+
+// the checks of castro_amd_integrated_quantities_mf on its box table, and the table the kernels read
+static int diag_table(int nboxes, const castro_amd_diag_box* boxes, std::vector<DiagBoxDev>& tab)
+{
+    if (nboxes < 0 || (nboxes > 0 && !boxes)) return CASTRO_AMD_ERR_ARG;
+    tab.resize((size_t)nboxes);
+    for (int i = 0; i < nboxes; ++i) {
+        const castro_amd_diag_box& b = boxes[i];
+        if (!b.state.p || b.state.ncomp != NUM_STATE || !fab_contains(&b.state, b.lo, b.hi)) return CASTRO_AMD_ERR_ARG;
+        DiagBoxDev& T = tab[(size_t)i];
+        T.U = to_dfab(&b.state);
+        T.mask = b.mask;
+        for (int d = 0; d < 3; ++d) { T.lo[d] = b.lo[d]; T.n[d] = b.hi[d] - b.lo[d] + 1; }
+        T.npr = 0;
+    }
+    return CASTRO_AMD_OK;
+}
+
+int castro_amd_integrated_quantities_mf(castro_amd_ctx* c, int nboxes, const castro_amd_diag_box* boxes, const castro_amd_geom* geom,
+                                        const double center[3], double* d_out, void* stream)
+{
+    if (!c || !geom || !center || !d_out) return CASTRO_AMD_ERR_ARG;
+    if (geom->coord != 0) return CASTRO_AMD_ERR_UNSUPPORTED;
+    std::vector<DiagBoxDev> tab;
+    const int rt = diag_table(nboxes, boxes, tab);
+    if (rt != CASTRO_AMD_OK) return rt;
+    DiagGeom G;
+    for (int d = 0; d < 3; ++d) { G.dx[d] = geom->dx[d]; G.problo[d] = geom->problo[d]; G.center[d] = center[d]; }
+    G.vol = geom->dx[0] * geom->dx[1] * geom->dx[2];
+    hipSetDevice(c->device);
+    return launch_integrated_quantities(nboxes, tab.data(), G, &c->diag_arena, &c->diag_ws, d_out, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_diag_workgroups(int nboxes, const castro_amd_diag_box* boxes)
+{
+    std::vector<DiagBoxDev> tab;
+    const int rt = diag_table(nboxes, boxes, tab);
+    if (rt != CASTRO_AMD_OK) return rt;
+    if (nboxes == 0) return 0;
+    std::vector<int> start;
+    int iters = 0;
+    const int rc = diag_layout(nboxes, tab.data(), start, iters);
+    return rc != 0 ? rc : start.back();
 }
 
 int castro_amd_saxpy_fab(castro_amd_ctx* c, const castro_amd_fab* dst, double a, const castro_amd_fab* src, int ncomp,

@@ -166,6 +166,17 @@ int launch_temp_diffusion(int nbox, DiffBoxDev* boxes, bool two, const DiffDev& 
                           FabOpsArena* arena, hipStream_t stream, Profiler* prof);
 int launch_estdt_temp_diffusion(const DFab& U, const int lo[3], const int hi[3], const double dx[3], const DevParams& P,
                                 double cond, double cutoff, double below, double* d_out, hipStream_t stream, Profiler* prof);
+// integrated quantities (diag_kernels.hip).  One box of a castro_amd_integrated_quantities_mf launch: the valid zones
+// [lo, lo + n) of U, the byte mask of those zones (nullptr: every zone counts); npr: pairs of x-adjacent zones per row, set by
+// diag_layout
+struct DiagBoxDev { DFab U; const unsigned char* mask; int lo[3], n[3]; int npr; };
+struct DiagGeom { double dx[3], problo[3], center[3], vol; };
+// rows of partial sums of the context: reserved at first use, grown only by a launch with more workgroups than any before
+struct DiagWorkspace { double* p = nullptr; size_t rows = 0; };
+// start[r]: first workgroup of box r (start[nbox]: all of them); iters: pairs a thread takes.  Returns 0 or CASTRO_AMD_ERR_ARG
+int diag_layout(int nbox, DiagBoxDev* boxes, std::vector<int>& start, int& iters);
+int launch_integrated_quantities(int nbox, DiagBoxDev* boxes, const DiagGeom& G, FabOpsArena* arena, DiagWorkspace* ws,
+                                 double* d_out, hipStream_t stream, Profiler* prof);
 int launch_saxpy(const DFab& D, const DFab& S, const int lo[3], const int hi[3], double a, int ncomp,
                  hipStream_t stream, Profiler* prof);
 int launch_fab_ops(int nops, const DFab* D, const DFab* X, const DFab* Y, const int* lo, const int* hi, const int* kind,

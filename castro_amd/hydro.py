@@ -395,6 +395,44 @@ class HipHydro:
             L.check(self.lib.castro_amd_estdt_mf(self.h, n, arr, C.byref(geom), C.byref(params), C.c_void_p(out.data_ptr()),
                                                  _stream_ptr(stream)), "estdt_mf")
 
+    # ---- Castro::sum_integrated_quantities (Source/driver/sum_integrated_quantities.cpp) ---------------------------
+    @staticmethod
+    def make_diag_boxes(specs):
+        """ctypes array of castro_amd_diag_box from (lo, hi, (state, box), mask) -- mask: a uint8 tensor shaped (nz, ny, nx) like
+        [lo, hi] on the device of the state (0 = the zone is covered by a finer level), or None.  The array keeps the masks alive."""
+        arr = (L.DiagBox * max(len(specs), 1))()
+        keep = []
+        for db, (lo, hi, st, mask) in zip(arr, specs):
+            for d in range(3):
+                db.lo[d], db.hi[d] = lo[d], hi[d]
+            db.state = L.fab_of(st[0], *st[1])
+            if mask is not None:
+                shape = (hi[2] - lo[2] + 1, hi[1] - lo[1] + 1, hi[0] - lo[0] + 1)
+                if mask.dtype != torch.uint8 or tuple(mask.shape) != shape or not mask.is_contiguous():
+                    raise AssertionError("a diag mask is a contiguous uint8 tensor shaped (nz, ny, nx) of its box: %s %s for %s"
+                                         % (mask.dtype, tuple(mask.shape), shape))
+                db.mask = mask.data_ptr()
+                keep.append(mask)
+        arr._masks = keep
+        return arr, len(specs)
+
+    def integrated_quantities_mf(self, boxes, geom, center, out, stream=None):
+        """castro_amd_integrated_quantities_mf: the 14 sums (_lib.DIAG_*) over the valid zones of every box of `boxes`
+        (make_diag_boxes), masked zones skipped, into `out` (a device tensor of _lib.DIAG_N doubles, overwritten; no boxes:
+        zeros).  Deterministic: the same boxes give the same bits."""
+        arr, n = boxes
+        ctr = (C.c_double * 3)(*[float(x) for x in center])
+        L.check(self.lib.castro_amd_integrated_quantities_mf(self.h, n, arr, C.byref(geom), C.byref(ctr), C.c_void_p(out.data_ptr()),
+                                                             _stream_ptr(stream)), "integrated_quantities_mf")
+
+    def diag_workgroups(self, boxes):
+        """workgroups (= rows of partial sums) integrated_quantities_mf launches for `boxes`"""
+        arr, n = boxes
+        nb = int(self.lib.castro_amd_diag_workgroups(n, arr))
+        if nb < 0:
+            L.check(nb, "diag_workgroups")
+        return nb
+
     def lincomb(self, dst, dst_box, a, x, x_box, b, y, y_box, ncomp, lo, hi, stream=None):
         L.check(self.lib.castro_amd_lincomb_fab(self.h, C.byref(L.fab_of(dst, *dst_box)), float(a), C.byref(L.fab_of(x, *x_box)),
                                                 float(b), C.byref(L.fab_of(y, *y_box)), int(ncomp), L.i3(lo), L.i3(hi),

@@ -56,7 +56,7 @@ extern "C" {
  *      castro_amd_clean_state_reduce_mf, castro_amd_estdt_mf.
  *   5 (not bumped: new entry points and a new struct only, nothing an existing caller allocates changes size or meaning):
  *      castro_amd_diffusion, castro_amd_temp_diffusion_fab / _mf, castro_amd_estdt_temp_diffusion_fab / _mf,
- *      castro_amd_sources_mf_ex.
+ *      castro_amd_sources_mf_ex; castro_amd_integrated_quantities_mf, castro_amd_diag_workgroups (struct castro_amd_diag_box).
  * A caller checks `castro_amd_abi_version() == CASTRO_AMD_ABI_VERSION` once after loading the library; a mismatch means
  * the library was built from another revision of this header (a 0.2 caller with 2-double vectors would be written 8 bytes
  * out of bounds by a 0.3 library). */
@@ -464,6 +464,54 @@ int castro_amd_sources_mf_ex(castro_amd_ctx *ctx, int stage, int nboxes, const c
                              const double *grav /* [3] or NULL */, int grav_source_type, const castro_amd_rotation *rot /* or NULL */,
                              const castro_amd_diffusion *diff /* or NULL */, const castro_amd_geom *geom,
                              const castro_amd_params *params, double dt, int clean_ntimes, void *stream);
+
+/* The integrated quantities of Castro::sum_integrated_quantities (Source/driver/sum_integrated_quantities.cpp:60-230, built on
+ * volWgtSum / locWgtSum, sum_utils.cpp:17-205) over the valid zones [lo, hi] of every box of a level, in ONE call:
+ * d_out[CASTRO_AMD_DIAG_*] = sum over the zones of the quantity times vol = dx * dy * dz (coord 0 only).  With
+ * loc_d = problo_d + (0.5 + index_d) * dx_d:
+ *   MASS            rho                                      volWgtSum("density")
+ *   XMOM .. ZMOM    (rho u)_d                                "xmom", "ymom", "zmom"
+ *   ANGMOM_X .. _Z  ((loc - center) x (rho u))_d, the expression of the angular_momentum_* derives (CASTRO_AMD_DER_ANGMOM_*)
+ *   RHO_E_INT       (rho e)                                  "rho_e"
+ *   RHO_K           0.5 / rho * |rho u|^2, the expression of the kineng derive (CASTRO_AMD_DER_KINENG)
+ *   RHO_E           (rho E)                                  "rho_E"
+ *   COM_X .. _Z     (rho * loc_d)                            locWgtSum("density", d); the centre of mass is this over MASS
+ *   SPECIES         (rho X)                                  volWgtSum("rho_" + species), NOT divided by M_solar
+ * mask (or NULL: every zone counts): one byte per valid zone, shaped like [lo, hi], x fastest; a zero byte marks a zone
+ * covered by a finer level.  The reference multiplies the derived field by build_fine_mask()'s 0 / 1 MultiFab
+ * (sum_utils.cpp:29-33); here a covered zone is SKIPPED instead, so a NaN or Inf under a fine patch cannot poison the sum
+ * (0 * NaN would) -- for finite data the two are the same number.  Ghost zones of the FABs are never read.
+ * d_out is OVERWRITTEN (the caller initialises nothing; nboxes == 0 writes zeros).  The sum is taken in a fixed order --
+ * per thread, across the lanes of a wave, across the waves of a workgroup, then over the workgroups' rows of partial sums
+ * by a second launch -- and never through floating-point atomics: the same boxes give the same bits on every call and on
+ * every stream.  The rows of partial sums live in the context (reserved at the first call, grown only by a call with more
+ * workgroups than any before); apart from that the call neither allocates nor synchronises.
+ * castro_amd_diag_workgroups: the number of workgroups (= rows of partial sums) the call launches for these boxes, or a
+ * negative error; host arithmetic only. */
+#define CASTRO_AMD_DIAG_N 14
+#define CASTRO_AMD_DIAG_MASS 0
+#define CASTRO_AMD_DIAG_XMOM 1
+#define CASTRO_AMD_DIAG_YMOM 2
+#define CASTRO_AMD_DIAG_ZMOM 3
+#define CASTRO_AMD_DIAG_ANGMOM_X 4
+#define CASTRO_AMD_DIAG_ANGMOM_Y 5
+#define CASTRO_AMD_DIAG_ANGMOM_Z 6
+#define CASTRO_AMD_DIAG_RHO_E_INT 7
+#define CASTRO_AMD_DIAG_RHO_K 8
+#define CASTRO_AMD_DIAG_RHO_E 9
+#define CASTRO_AMD_DIAG_COM_X 10
+#define CASTRO_AMD_DIAG_COM_Y 11
+#define CASTRO_AMD_DIAG_COM_Z 12
+#define CASTRO_AMD_DIAG_SPECIES 13
+typedef struct castro_amd_diag_box {
+    int lo[3], hi[3];
+    castro_amd_fab state;
+    const unsigned char *mask;
+} castro_amd_diag_box;
+int castro_amd_integrated_quantities_mf(castro_amd_ctx *ctx, int nboxes, const castro_amd_diag_box *boxes,
+                                        const castro_amd_geom *geom, const double center[3],
+                                        double *d_out /* CASTRO_AMD_DIAG_N device doubles, overwritten */, void *stream);
+int castro_amd_diag_workgroups(int nboxes, const castro_amd_diag_box *boxes);
 
 /* Two-level AMR building blocks, refinement ratio 2 (first slice).  The reference calls AMReX for
  * all of these [3P, not in the reference tree]; the arithmetic is restated from the published descriptions and is
