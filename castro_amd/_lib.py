@@ -69,6 +69,8 @@ EXPORTED_SYMBOLS = (
     "castro_amd_temp_diffusion_fab", "castro_amd_temp_diffusion_mf", "castro_amd_estdt_temp_diffusion_fab",
     "castro_amd_estdt_temp_diffusion_mf", "castro_amd_sources_mf_ex",
     "castro_amd_integrated_quantities_mf", "castro_amd_diag_workgroups",
+    "castro_amd_radial_mass_mf", "castro_amd_radial_gravity", "castro_amd_monopole_grav_fab",
+    "castro_amd_old_gravity_source_gfab", "castro_amd_new_gravity_source_gfab",
 )
 
 
@@ -124,6 +126,47 @@ DIAG_N = 14
 (DIAG_MASS, DIAG_XMOM, DIAG_YMOM, DIAG_ZMOM, DIAG_ANGMOM_X, DIAG_ANGMOM_Y, DIAG_ANGMOM_Z, DIAG_RHO_E_INT, DIAG_RHO_K, DIAG_RHO_E,
  DIAG_COM_X, DIAG_COM_Y, DIAG_COM_Z, DIAG_SPECIES) = range(DIAG_N)
 M_SOLAR = 1.9884e33        # C::M_solar of the reference's constants, cgs: species_diag.out is in solar masses
+
+
+class MonopoleParams(C.Structure):
+    """castro_amd_monopole_params"""
+    _fields_ = [("n1d", C.c_int), ("drdxfac", C.c_int), ("center", C.c_double * 3), ("max_radius_all_in_domain", C.c_double),
+                ("Gconst", C.c_double)]
+
+
+# C::Gconst of the reference comes from its Microphysics constants; the cgs value of that release
+GCONST = 6.67428e-8
+# castro_amd_radial_mass_mf: a brick of 8 x 8 x 4 zones must fit a window of 64 bins (include/castro_hydro_amd.h)
+MONOPOLE_BRICK, MONOPOLE_WINDOW = (8, 8, 4), 64
+
+
+def monopole_n1d(n_cell, drdxfac):
+    """bins of the radial arrays: drdxfac * (int(sqrt(nx^2 + ny^2 + nz^2)) + 2 * NUM_GROW) of the domain (Castro.cpp:3887-3913,
+    Gravity.cpp:315)"""
+    import math
+    return int(drdxfac) * (int(math.sqrt(float(sum(int(n) * int(n) for n in n_cell)))) + 2 * NUM_GROW)
+
+
+def monopole_max_drdxfac(dx):
+    """the largest gravity.drdxfac the binning kernel takes for zones of size dx: drdxfac * (brick diagonal) / dx[0] + 3 <= 64"""
+    import math
+    diag = math.sqrt(sum((b * float(d)) ** 2 for b, d in zip(MONOPOLE_BRICK, dx)))
+    return int((MONOPOLE_WINDOW - 3.0) * float(dx[0]) / diag)
+
+
+def make_monopole(n_cell, geom, center, drdxfac=1, Gconst=GCONST, n1d=None):
+    """castro_amd_monopole_params of a domain of n_cell zones: n1d (monopole_n1d unless given) and max_radius_all_in_domain =
+    min over d of probhi[d] - center[d] (Gravity.cpp:333-338)"""
+    if int(drdxfac) < 1:
+        raise ValueError("gravity.drdxfac must be at least 1, not %r" % (drdxfac,))
+    m = MonopoleParams()
+    m.n1d = monopole_n1d(n_cell, drdxfac) if n1d is None else int(n1d)
+    m.drdxfac = int(drdxfac)
+    for d in range(3):
+        m.center[d] = float(center[d])
+    m.max_radius_all_in_domain = min(geom.probhi[d] - float(center[d]) for d in range(3))
+    m.Gconst = float(Gconst)
+    return m
 
 
 class Rotation(C.Structure):
@@ -281,6 +324,14 @@ def load(numerics=None):
         L.castro_amd_integrated_quantities_mf.argtypes = [C.c_void_p, C.c_int, C.POINTER(DiagBox), C.POINTER(Geom),
                                                           C.POINTER(C.c_double * 3), C.c_void_p, C.c_void_p]
         L.castro_amd_diag_workgroups.argtypes = [C.c_int, C.POINTER(DiagBox)]
+    if hasattr(L, "castro_amd_radial_mass_mf"):             # absent from A/B builds of revisions before monopole gravity
+        PM = C.POINTER(MonopoleParams)
+        L.castro_amd_radial_mass_mf.argtypes = [C.c_void_p, C.c_int, C.POINTER(DiagBox), C.POINTER(Geom), PM, C.c_void_p, C.c_void_p]
+        L.castro_amd_radial_gravity.argtypes = [C.c_void_p, PM, C.POINTER(Geom), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.castro_amd_monopole_grav_fab.argtypes = [C.c_void_p, C.c_void_p, PM, C.POINTER(Geom), PF, C.c_void_p]
+        L.castro_amd_old_gravity_source_gfab.argtypes = [C.c_void_p, PF, PF, I3, I3, PF, C.c_int, C.c_double, C.c_void_p]
+        L.castro_amd_new_gravity_source_gfab.argtypes = [C.c_void_p, PF, PF, PF, PF, I3, I3, PF, PF, C.c_int, C.c_double,
+                                                         C.POINTER(Geom), C.c_void_p]
     L.castro_amd_step_control.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_double, C.c_double,
                                           C.c_double, C.c_int, C.c_void_p]
     L.castro_amd_clean_state_fab.argtypes = [C.c_void_p, PF, I3, I3, C.POINTER(Params), C.c_int, C.c_void_p]

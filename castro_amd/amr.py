@@ -634,8 +634,9 @@ class CastroAmr:
                  params=None, make_hydro=None, make_params=None, refine=None, regrid_int=2, n_error_buf=1,
                  blocking_factor=8, patches=None, max_level=1, cluster=False, grid_eff=0.7, max_grid_size=128,
                  do_grav=False, const_grav=0.0, grav_source_type=4, rotation=None, comm=None, base_grid=None, box_streams=4,
-                 diffusion=None, sum_interval=-1, show_center_of_mass=False, diag_dir=None):
-        """sum_interval, show_center_of_mass, diag_dir: as in castro_amd.Castro -- sum_integrated_quantities() over the composite
+                 diffusion=None, sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant"):
+        """gravity_type: "constant" only ("monopole" is refused: single level, castro_amd.Castro).
+        sum_interval, show_center_of_mass, diag_dir: as in castro_amd.Castro -- sum_integrated_quantities() over the composite
         grid after initData and after every coarse step with nstep % sum_interval == 0 (self.diag_history, the three data logs).
         base_grid = (gx, gy, gz): level 0 as gx x gy x gz equal boxes instead of one (amr.max_grid_size on the base level);
         with `comm` they are dealt over the ranks like the boxes of the refined levels.
@@ -656,6 +657,12 @@ class CastroAmr:
             # the operator of a refined level needs AMReX's coarse-fine boundary stencil [3P], which is not restated
             raise NotImplementedError("CastroAmr: thermal diffusion (diffusion=...) is built for a single level only; "
                                       "use castro_amd.Castro")
+        if gravity_type not in ("constant", "monopole"):
+            raise ValueError("gravity_type must be \"constant\" or \"monopole\", not %r" % (gravity_type,))
+        if gravity_type == "monopole":
+            raise NotImplementedError("CastroAmr: monopole gravity is built for a single level only (castro_amd.Castro): the level "
+                                      "combination and the time interpolation of Gravity::make_radial_gravity "
+                                      "(Gravity.cpp:2962-3127) are not built")
         if patch_crse is not None:
             assert patches is None
             patches = [patch_crse]

@@ -259,8 +259,12 @@ class Castro:
                  use_retry=True, retry_subcycle_factor=0.5, max_subcycles=10, dt_cutoff=1.e-12,
                  do_grav=False, const_grav=0.0, grav_source_type=4, box=None, rotation=None, fixed_dt=-1.0, initial_dt=-1.0, max_dt=1.e200,
                  alloc=True, numerics=None, proxy_ranks=1, diffusion=None, do_hydro=True,
-                 sum_interval=-1, show_center_of_mass=False, diag_dir=None):
-        """sum_interval (castro.sum_interval, default -1: never), show_center_of_mass, diag_dir: the integrated quantities of
+                 sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", drdxfac=1, Gconst=L.GCONST):
+        """gravity_type (gravity.gravity_type): "constant" (ConstantGrav: const_grav along z) | "monopole" (MonopoleGrav: the radial
+        self-gravity of the state about the centre sum_integrated_quantities uses -- the `center` attribute, else the middle of the
+        domain; 3-D Cartesian, non-periodic, single level); drdxfac: gravity.drdxfac; Gconst: the reference takes C::Gconst from
+        its Microphysics constants, the default is the cgs value of that release.
+        sum_interval (castro.sum_interval, default -1: never), show_center_of_mass, diag_dir: the integrated quantities of
         sum_integrated_quantities() after initData and after every coarse step with nstep % sum_interval == 0, kept in
         self.diag_history and appended to diag_dir/{grid,species,amr}_diag.out by the I/O rank (castro_amd/diag.py).
         diffusion: _lib.make_diffusion(const_conductivity=..., ...) turns on castro.diffuse_temp = 1 (explicit thermal diffusion,
@@ -370,6 +374,12 @@ class Castro:
         self.max_dt = float(max_dt)                             # castro.max_dt (Castro.cpp:1515-1530)
         # castro.do_grav with gravity.gravity_type = "ConstantGrav": g along the last dimension (Gravity.cpp:860-866)
         self.do_grav, self.grav, self.grav_source_type = bool(do_grav), (0.0, 0.0, float(const_grav)), int(grav_source_type)
+        if gravity_type not in ("constant", "monopole"):
+            raise ValueError("gravity_type must be \"constant\" or \"monopole\", not %r" % (gravity_type,))
+        self.gravity_type, self.drdxfac, self.Gconst = gravity_type, int(drdxfac), float(Gconst)
+        self.monopole = self.do_grav and gravity_type == "monopole"
+        if self.monopole:
+            self._init_monopole(hydro_alloc, box)
         # castro.do_rotation: `rotation` = _lib.make_rotation(rotational_period, rot_axis, ...)
         self.rotation = rotation
         # castro.diffuse_temp = 1: `diffusion` = _lib.make_diffusion(const_conductivity, ...); castro.do_hydro
@@ -612,6 +622,8 @@ class Castro:
             h.sod_init(self.S_new_b, self.gbox, self.lo, self.hi, self.geom, self.params, **kw)
         elif problem == "diffusion_test":
             return self.set_state(self.diffusion_test_state(**kw))
+        elif problem == "dust_collapse":
+            return self.set_state(self.dust_collapse_state(**kw))
         else:
             raise ValueError(problem)
         self.clean_state(self.S_new_b, 1)      # Castro.cpp:1100-1160
@@ -655,6 +667,93 @@ class Castro:
         self.clean_state(self.S_new_b, 1)
         self.time, self.nstep, self.dt = 0.0, 0, 0.0
         self._diag_post_init()
+
+    def dust_collapse_state(self, rho_0=1.e9, r_0=6.5e8, p_0=1.e10, rho_ambient=1.0, smooth_delta=1.e-5, nsub=5):
+        """problem_initialize_state_data of Exec/gravity_tests/DustCollapse (no r_offset) on the whole domain: the density of a
+        tanh-smoothed sphere of radius r_0 about the problem centre, averaged over nsub^3 points per zone; pressure p_0 everywhere,
+        e = p / ((gamma - 1) rho) (eos_input_rp of the gamma law), no motion, one species.  The defaults are those of _prob_params."""
+        import numpy as np
+        from . import diag
+        g = self.geom
+        ctr = diag.domain_center(self)
+        sub = [None] * 3
+        for d in range(3):
+            lo = g.problo[d] + np.arange(self.n_cell[d], dtype=np.float64) * g.dx[d]
+            dsub = g.dx[d] / float(nsub)
+            sub[d] = [(lo + (float(m) + 0.5) * dsub) - ctr[d] for m in range(nsub)]
+        avg = np.zeros(self.n_cell[::-1])
+        for kk in range(nsub):
+            zz = sub[2][kk][:, None, None]
+            for jj in range(nsub):
+                yy = sub[1][jj][None, :, None]
+                for ii in range(nsub):
+                    xx = sub[0][ii][None, None, :]
+                    dist = np.sqrt(xx * xx + yy * yy + zz * zz)
+                    avg += rho_0 - 0.5 * (rho_0 - rho_ambient) * (1.0 + np.tanh((dist - r_0) / smooth_delta))
+        volinv = 1.0
+        for _ in range(3):
+            volinv /= float(nsub)
+        rho = avg * volinv
+        eint = p_0 / ((self.params.eos_gamma - 1.0) * rho)
+        U = np.zeros((NUM_STATE,) + rho.shape)
+        U[L.URHO] = rho
+        U[L.UEDEN] = rho * eint
+        U[L.UEINT] = rho * eint
+        U[L.UTEMP] = eint / L.gamma_law_cv(self.params)
+        U[L.UFS] = rho
+        return U
+
+    # ---- gravity.gravity_type = MonopoleGrav (Source/gravity/Gravity.cpp) --------------------------------------------
+    def _init_monopole(self, hydro_alloc, box):
+        if box is not None:
+            raise NotImplementedError("monopole gravity on a refined patch: the level combination and the time interpolation of "
+                                      "Gravity::make_radial_gravity (Gravity.cpp:2962-3127) are not built")
+        if all(self.periodic):
+            raise ValueError("monopole gravity needs a non-periodic domain: a fully periodic one has no isolated mass to take "
+                             "the radial profile of")
+        if self.drdxfac < 1:
+            raise ValueError("gravity.drdxfac must be at least 1, not %d" % self.drdxfac)
+        dmax = L.monopole_max_drdxfac([self.geom.dx[d] for d in range(3)])
+        if self.drdxfac > dmax:
+            raise ValueError("gravity.drdxfac = %d is above the %d this geometry allows: the binning kernel holds the sub-zones of a "
+                             "brick of 8 x 8 x 4 zones in a window of 64 bins (drdxfac <= 5 for cubic zones)" % (self.drdxfac, dmax))
+        self.n1d = L.monopole_n1d(self.n_cell, self.drdxfac)
+        # Gravity_Type old / new data with the one ghost zone the grav_source_type = 4 energy term reads
+        self.gravbox = (tuple(x - 1 for x in self.lo), tuple(x + 1 for x in self.hi))
+        self.grav_old = hydro_alloc(3, *self.gravbox)
+        self.grav_new = hydro_alloc(3, *self.gravbox)
+        self._radial_mv = hydro_alloc(1, (0, 0, 0), (2 * self.n1d - 1, 0, 0))
+        self._radial_g = hydro_alloc(1, (0, 0, 0), (self.n1d - 1, 0, 0))
+        self._mono_tables = {}
+
+    def monopole_params(self):
+        """castro_amd_monopole_params of this run: n1d of the domain, max_radius_all_in_domain about the problem centre"""
+        from . import diag
+        return L.make_monopole(self.n_cell, self.geom, diag.domain_center(self), self.drdxfac, self.Gconst)
+
+    def _monopole_gravity(self, S, grav):
+        """Gravity::construct_old_gravity / construct_new_gravity for MonopoleGrav (Castro_advance_ctu.cpp:122, 258): bin the valid
+        zones of S, sum over the ranks, integrate outwards, interpolate onto `grav` (ghost zone included) -- all on the device.
+        The reference bins the State_Type data, not Sborder: at the old-time point that is S_old_b, whose valid zones are the
+        cleaned old state (the FillPatch only adds ghost zones around them), at the new-time point S_new_b after the hydro
+        update and its clean_state."""
+        h = self.hydro
+        mono = self.monopole_params()
+        key = S.data_ptr()                      # the two state buffers swap roles every step: one table each
+        if key not in self._mono_tables:
+            self._mono_tables[key] = h.make_diag_boxes([(self.lo, self.hi, (S, self.gbox), None)])
+        mv = self._radial_mv.reshape(-1)
+        h.radial_mass_mf(self._mono_tables[key], self.geom, mono, mv)
+        self.comm.allreduce_sum(mv)
+        h.radial_gravity(mono, self.geom, mv, self._radial_g.reshape(-1))
+        h.monopole_grav(self._radial_g.reshape(-1), mono, self.geom, grav, self.gravbox)
+
+    def radial_gravity(self):
+        """(radial_mass, radial_vol, radial_grav) of the last gravity construction, as numpy arrays of n1d entries"""
+        if not self.monopole:
+            raise RuntimeError("radial_gravity() needs Castro(do_grav=True, gravity_type=\"monopole\")")
+        mv = self._radial_mv.reshape(-1).cpu().numpy()
+        return mv[:self.n1d].copy(), mv[self.n1d:].copy(), self._radial_g.reshape(-1).cpu().numpy().copy()
 
     # ---- Castro::sum_integrated_quantities (Source/driver/sum_integrated_quantities.cpp) ---------------------
     sum_interval = property(lambda self: self.diag.sum_interval)
@@ -902,7 +1001,10 @@ class Castro:
         if stage == 0:
             if self.diffusion is not None:              # construct_old_diff_source: + 1.0 x DiffTerm(Sborder)
                 h.temp_diffusion(S, g, src, sbx, lo, hi, self.diffusion, self.geom, 1.0)
-            if self.do_grav:
+            if self.monopole:
+                self._monopole_gravity(S, self.grav_old)
+                h.old_gravity_source_gfab(S, g, src, sbx, lo, hi, self.grav_old, self.gravbox, self.grav_source_type, dt)
+            elif self.do_grav:
                 h.old_gravity_source(S, g, src, sbx, lo, hi, self.grav, self.grav_source_type, dt)
             if self.rotation is not None:
                 h.old_rotation_source(S, g, src, sbx, lo, hi, self.rotation, self.geom, dt)
@@ -910,7 +1012,11 @@ class Castro:
             if self.diffusion is not None:              # construct_new_diff_source: + 0.5 x DiffTerm(S_new) - 0.5 x DiffTerm(Sborder)
                 h.temp_diffusion(Sn, g, src, sbx, lo, hi, self.diffusion, self.geom, 0.5)
                 h.temp_diffusion(S, g, src, sbx, lo, hi, self.diffusion, self.geom, -0.5)
-            if self.do_grav:
+            if self.monopole:
+                self._monopole_gravity(Sn, self.grav_new)
+                h.new_gravity_source_gfab(S, g, Sn, g, src, sbx, self.mass_fluxes, self.flux_boxes, lo, hi, self.grav_old,
+                                          self.grav_new, self.gravbox, self.grav_source_type, dt, self.geom)
+            elif self.do_grav:
                 h.new_gravity_source(S, g, Sn, g, src, sbx, self.mass_fluxes, self.flux_boxes, lo, hi, self.grav,
                                      self.grav_source_type, dt, self.geom)
             if self.rotation is not None:
@@ -936,7 +1042,9 @@ class Castro:
             if not self._in_retry:
                 self.create_source_corrector()
             h.set_source_corrector(self.source_corrector, self.sbox)
-        one_pass = hasattr(h, "sources_mf") and os.environ.get("CASTRO_AMD_SOURCES_ONE_PASS", "1") != "0"
+        # monopole gravity reads a per-zone vector: the one-pass table (castro_amd_sources_mf) carries one vector per call
+        one_pass = (hasattr(h, "sources_mf") and os.environ.get("CASTRO_AMD_SOURCES_ONE_PASS", "1") != "0"
+                    and not getattr(self, "monopole", False))
         sources = self._sources_one_pass if one_pass else self._source_stage
         sources(0, dt)
         if self.do_hydro:

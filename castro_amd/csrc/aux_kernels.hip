@@ -227,8 +227,20 @@ int launch_estdt(const DFab& U, const int lo[3], const int hi[3], const DevGeom&
 // ---------------------------------------------------------------------------------------
 constexpr int NSRC = 7;
 
+// where a zone's gravity comes from: one vector for every zone (ConstantGrav), or a 3-component FAB (MonopoleGrav: gold(i,j,k,n) /
+// gnew(i,j,k,n) of the reference; the grav_source_type = 4 energy term reads the six neighbours, so the FAB has one ghost zone)
+struct GravConst {
+    double g[3];
+    __device__ __forceinline__ double operator()(int, int, int, int n) const { return g[n]; }
+};
+struct GravFab {
+    DFab G;
+    __device__ __forceinline__ double operator()(int i, int j, int k, int n) const { return G.p[fidx(G, i, j, k, n)]; }
+};
+
 // the source of one zone (src[0 .. NSRC-1], every component set); the kernels below accumulate it into the Source_Type FAB
-__device__ __forceinline__ void old_grav_zone(const DFab& U, int i, int j, int k, const double grav[3], int type, double dt, double src[7])
+template <class GRAV>
+__device__ __forceinline__ void old_grav_zone_g(const DFab& U, int i, int j, int k, const GRAV& grav, int type, double dt, double src[7])
 {
     constexpr int NSRC_ = 7;
     double snew[NUM_STATE];
@@ -243,7 +255,7 @@ __device__ __forceinline__ void old_grav_zone(const DFab& U, int i, int j, int k
 
     double Sr[3];
     for (int n = 0; n < 3; ++n) {
-        Sr[n] = rho * grav[n];
+        Sr[n] = rho * grav(i, j, k, n);
         src[UMX + n] = Sr[n];
         snew[UMX + n] += dt * src[UMX + n];
     }
@@ -260,6 +272,22 @@ __device__ __forceinline__ void old_grav_zone(const DFab& U, int i, int j, int k
     src[UEDEN] = SrE;
 }
 
+__device__ __forceinline__ void old_grav_zone(const DFab& U, int i, int j, int k, const double grav[3], int type, double dt, double src[7])
+{
+    const GravConst g = { { grav[0], grav[1], grav[2] } };
+    old_grav_zone_g(U, i, j, k, g, type, dt, src);
+}
+
+__global__ void __launch_bounds__(256) k_old_grav_source_gfab(DFab U, DFab SRC, Box3 b, GravFab gold, int type, double dt)
+{
+    int i, j, k;
+    if (!box_thread3(b.lo, b.n, i, j, k)) return;
+    double src[NSRC];
+    old_grav_zone_g(U, i, j, k, gold, type, dt, src);
+    const long cs = fidx(SRC, i, j, k, 0);
+    for (int n = 0; n < NSRC; ++n) SRC.p[cs + SRC.sn * n] += src[n];
+}
+
 __global__ void __launch_bounds__(256) k_old_grav_source(DFab U, DFab SRC, Box3 b, double g0, double g1, double g2,
                                                          int type, double dt)
 {
@@ -272,8 +300,10 @@ __global__ void __launch_bounds__(256) k_old_grav_source(DFab U, DFab SRC, Box3 
     for (int n = 0; n < NSRC; ++n) SRC.p[cs + SRC.sn * n] += src[n];
 }
 
-__device__ __forceinline__ void new_grav_zone(const DFab& UO, const DFab& UN, const DFab& M0, const DFab& M1, const DFab& M2, int i, int j, int k,
-                                              const double grav[3], int type, double dt, double dx0, double dx1, double dx2, double src[7])
+template <class GOLD, class GNEW>
+__device__ __forceinline__ void new_grav_zone_g(const DFab& UO, const DFab& UN, const DFab& M0, const DFab& M1, const DFab& M2, int i, int j, int k,
+                                                const GOLD& gold, const GNEW& gnew, int type, double dt, double dx0, double dx1, double dx2,
+                                                double src[7])
 {
     constexpr int NSRC = 7;
     const double vol = dx0 * dx1 * dx2;
@@ -293,11 +323,11 @@ __device__ __forceinline__ void new_grav_zone(const DFab& UO, const DFab& UN, co
 
     double vold[3], Sr_old[3], vnew[3], Sr_new[3];
     for (int n = 0; n < 3; ++n) vold[n] = UO.p[co + UO.sn * (UMX + n)] * rhooinv;
-    for (int n = 0; n < 3; ++n) Sr_old[n] = rhoo * grav[n];
+    for (int n = 0; n < 3; ++n) Sr_old[n] = rhoo * gold(i, j, k, n);
     double SrE_old = vold[0] * Sr_old[0] + vold[1] * Sr_old[1] + vold[2] * Sr_old[2];
 
     for (int n = 0; n < 3; ++n) vnew[n] = snew[UMX + n] * rhoninv;
-    for (int n = 0; n < 3; ++n) Sr_new[n] = rhon * grav[n];
+    for (int n = 0; n < 3; ++n) Sr_new[n] = rhon * gnew(i, j, k, n);
     double SrE_new = vnew[0] * Sr_new[0] + vnew[1] * Sr_new[1] + vnew[2] * Sr_new[2];
 
     double Srcorr[3];
@@ -319,15 +349,15 @@ __device__ __forceinline__ void new_grav_zone(const DFab& UO, const DFab& UN, co
         SrEcorr = new_ke - old_ke;
     } else {
         SrEcorr = -SrE_old;
-        // time-averaged edge-centred gravity; gold == gnew == grav in every zone
+        // time-averaged edge-centred gravity (Castro_gravity.cpp:562-574); ConstantGrav: gold == gnew == grav in every zone
         double g[3];
-        for (int n = 0; n < 3; ++n) g[n] = 0.5 * (grav[n] + grav[n]);
-        double gxl = 0.5 * (g[0] + 0.5 * (grav[0] + grav[0]));
-        double gxr = 0.5 * (g[0] + 0.5 * (grav[0] + grav[0]));
-        double gyl = 0.5 * (g[1] + 0.5 * (grav[1] + grav[1]));
-        double gyr = 0.5 * (g[1] + 0.5 * (grav[1] + grav[1]));
-        double gzl = 0.5 * (g[2] + 0.5 * (grav[2] + grav[2]));
-        double gzr = 0.5 * (g[2] + 0.5 * (grav[2] + grav[2]));
+        for (int n = 0; n < 3; ++n) g[n] = 0.5 * (gnew(i, j, k, n) + gold(i, j, k, n));
+        double gxl = 0.5 * (g[0] + 0.5 * (gnew(i - 1, j, k, 0) + gold(i - 1, j, k, 0)));
+        double gxr = 0.5 * (g[0] + 0.5 * (gnew(i + 1, j, k, 0) + gold(i + 1, j, k, 0)));
+        double gyl = 0.5 * (g[1] + 0.5 * (gnew(i, j - 1, k, 1) + gold(i, j - 1, k, 1)));
+        double gyr = 0.5 * (g[1] + 0.5 * (gnew(i, j + 1, k, 1) + gold(i, j + 1, k, 1)));
+        double gzl = 0.5 * (g[2] + 0.5 * (gnew(i, j, k - 1, 2) + gold(i, j, k - 1, 2)));
+        double gzr = 0.5 * (g[2] + 0.5 * (gnew(i, j, k + 1, 2) + gold(i, j, k + 1, 2)));
 
         SrEcorr += hdtInv * (M0.p[fidx(M0, i, j, k, 0)] * gxl * dx0 +
                              M0.p[fidx(M0, i + 1, j, k, 0)] * gxr * dx0 +
@@ -337,6 +367,25 @@ __device__ __forceinline__ void new_grav_zone(const DFab& UO, const DFab& UN, co
                              M2.p[fidx(M2, i, j, k + 1, 0)] * gzr * dx2) / vol;
     }
     src[UEDEN] = SrEcorr;
+}
+
+__device__ __forceinline__ void new_grav_zone(const DFab& UO, const DFab& UN, const DFab& M0, const DFab& M1, const DFab& M2, int i, int j, int k,
+                                              const double grav[3], int type, double dt, double dx0, double dx1, double dx2, double src[7])
+{
+    const GravConst g = { { grav[0], grav[1], grav[2] } };
+    new_grav_zone_g(UO, UN, M0, M1, M2, i, j, k, g, g, type, dt, dx0, dx1, dx2, src);
+}
+
+__global__ void __launch_bounds__(256) k_new_grav_source_gfab(DFab UO, DFab UN, DFab SRC, DFab M0, DFab M1, DFab M2, Box3 b,
+                                                              GravFab gold, GravFab gnew, int type, double dt,
+                                                              double dx0, double dx1, double dx2)
+{
+    int i, j, k;
+    if (!box_thread3(b.lo, b.n, i, j, k)) return;
+    double src[NSRC];
+    new_grav_zone_g(UO, UN, M0, M1, M2, i, j, k, gold, gnew, type, dt, dx0, dx1, dx2, src);
+    const long cs = fidx(SRC, i, j, k, 0);
+    for (int n = 0; n < NSRC; ++n) SRC.p[cs + SRC.sn * n] += src[n];
 }
 
 __global__ void __launch_bounds__(256) k_new_grav_source(DFab UO, DFab UN, DFab SRC, DFab M0, DFab M1, DFab M2, Box3 b,
@@ -602,6 +651,36 @@ int launch_old_grav_source(const DFab& U, const DFab& SRC, const int lo[3], cons
     prof_begin(prof, "k_old_grav_source", stream);
     hipLaunchKernelGGL(k_old_grav_source, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, U, SRC, b,
                        grav[0], grav[1], grav[2], type, dt);
+    prof_end(prof, stream);
+    return launch_status();
+}
+
+int launch_old_grav_source_gfab(const DFab& U, const DFab& SRC, const int lo[3], const int hi[3], const DFab& GO,
+                                int type, double dt, hipStream_t stream, Profiler* prof)
+{
+    Box3 b;
+    long n = 1;
+    for (int d = 0; d < 3; ++d) { b.lo[d] = lo[d]; b.n[d] = hi[d] - lo[d] + 1; n *= b.n[d]; }
+    if (n <= 0) return 0;
+    const GravFab gold = { GO };
+    prof_begin(prof, "k_old_grav_source_gfab", stream);
+    hipLaunchKernelGGL(k_old_grav_source_gfab, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, U, SRC, b, gold, type, dt);
+    prof_end(prof, stream);
+    return launch_status();
+}
+
+int launch_new_grav_source_gfab(const DFab& UO, const DFab& UN, const DFab& SRC, const DFab M[3], const int lo[3], const int hi[3],
+                                const DFab& GO, const DFab& GN, int type, double dt, const double dx[3], hipStream_t stream,
+                                Profiler* prof)
+{
+    Box3 b;
+    long n = 1;
+    for (int d = 0; d < 3; ++d) { b.lo[d] = lo[d]; b.n[d] = hi[d] - lo[d] + 1; n *= b.n[d]; }
+    if (n <= 0) return 0;
+    const GravFab gold = { GO }, gnew = { GN };
+    prof_begin(prof, "k_new_grav_source_gfab", stream);
+    hipLaunchKernelGGL(k_new_grav_source_gfab, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, UO, UN, SRC, M[0], M[1], M[2], b,
+                       gold, gnew, type, dt, dx[0], dx[1], dx[2]);
     prof_end(prof, stream);
     return launch_status();
 }

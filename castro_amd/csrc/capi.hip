@@ -31,6 +31,7 @@ struct castro_amd_ctx {
     hipEvent_t mf_fork = nullptr, mf_join = nullptr;   // castro_amd_ctu_hydro_mf: fork from / join to the caller's stream
     FabOpsArena diag_arena;                         // device table of castro_amd_integrated_quantities_mf
     DiagWorkspace diag_ws;                          // its rows of partial sums, one per workgroup
+    MonoWorkspace mono_ws;                          // castro_amd_radial_mass_mf: rows, counts and device box tables
 };
 
 namespace cad {
@@ -246,6 +247,7 @@ void castro_amd_ctx_destroy(castro_amd_ctx* c)
     if (c->diff_arena.p) hipFree(c->diff_arena.p);
     if (c->diag_arena.p) hipFree(c->diag_arena.p);
     if (c->diag_ws.p) hipFree(c->diag_ws.p);
+    mono_workspace_free(&c->mono_ws);
     prof_collect(&c->prof);
     for (auto e : c->prof.pool) hipEventDestroy(e);
     if (c->arena) hipFree(c->arena);
@@ -802,6 +804,114 @@ int castro_amd_diag_workgroups(int nboxes, const castro_amd_diag_box* boxes)
     int iters = 0;
     const int rc = diag_layout(nboxes, tab.data(), start, iters);
     return rc != 0 ? rc : start.back();
+}
+
+// castro_amd_monopole_params + castro_amd_geom as the kernels read them
+static int mono_geom(const castro_amd_geom* geom, const castro_amd_monopole_params* mp, MonoGeom& G)
+{
+    if (!geom || !mp || mp->n1d < 2 || mp->drdxfac < 1) return CASTRO_AMD_ERR_ARG;
+    if (geom->coord != 0) return CASTRO_AMD_ERR_UNSUPPORTED;
+    bool octant = true;
+    for (int d = 0; d < 3; ++d) {
+        if (!(geom->dx[d] > 0.0)) return CASTRO_AMD_ERR_ARG;
+        G.dx[d] = geom->dx[d]; G.problo[d] = geom->problo[d]; G.center[d] = mp->center[d];
+        octant = octant && std::fabs(mp->center[d] - geom->problo[d]) < 1.e-2 * geom->dx[d];        // Gravity.cpp:1439-1447
+    }
+    G.octant_factor = octant ? 8.0 : 1.0;
+    G.max_radius = mp->max_radius_all_in_domain;
+    G.Gconst = mp->Gconst;
+    G.n1d = mp->n1d; G.drdxfac = mp->drdxfac;
+    return CASTRO_AMD_OK;
+}
+
+int castro_amd_radial_mass_mf(castro_amd_ctx* c, int nboxes, const castro_amd_diag_box* boxes, const castro_amd_geom* geom,
+                              const castro_amd_monopole_params* params, double* d_mass_vol, void* stream)
+{
+    if (!c || !d_mass_vol || nboxes < 0 || (nboxes > 0 && !boxes)) return CASTRO_AMD_ERR_ARG;
+    MonoGeom G;
+    const int rg = mono_geom(geom, params, G);
+    if (rg != CASTRO_AMD_OK) return rg;
+    // the table is compared byte by byte with the ones already on the device: every byte of it is set here
+    std::vector<MonoBoxDev> tab((size_t)nboxes);
+    if (nboxes > 0) std::memset((void*)tab.data(), 0, (size_t)nboxes * sizeof(MonoBoxDev));
+    for (int i = 0; i < nboxes; ++i) {
+        const castro_amd_diag_box& b = boxes[i];
+        if (!b.state.p || b.state.ncomp != NUM_STATE || !fab_contains(&b.state, b.lo, b.hi)) return CASTRO_AMD_ERR_ARG;
+        MonoBoxDev& T = tab[(size_t)i];
+        const DFab U = to_dfab(&b.state);
+        T.U.p = U.p; T.U.sy = U.sy; T.U.sz = U.sz; T.U.sn = U.sn;
+        T.mask = b.mask;
+        for (int d = 0; d < 3; ++d) { T.U.lo[d] = U.lo[d]; T.lo[d] = b.lo[d]; T.n[d] = b.hi[d] - b.lo[d] + 1; }
+    }
+    hipSetDevice(c->device);
+    return launch_radial_mass(nboxes, tab.data(), G, &c->mono_ws, d_mass_vol, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_radial_gravity(castro_amd_ctx* c, const castro_amd_monopole_params* params, const castro_amd_geom* geom,
+                              const double* d_mass_vol, double* d_radial_grav, void* stream)
+{
+    if (!c || !d_mass_vol || !d_radial_grav) return CASTRO_AMD_ERR_ARG;
+    MonoGeom G;
+    const int rg = mono_geom(geom, params, G);
+    if (rg != CASTRO_AMD_OK) return rg;
+    hipSetDevice(c->device);
+    return launch_radial_gravity(G, d_mass_vol, d_radial_grav, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_monopole_grav_fab(castro_amd_ctx* c, const double* d_radial_grav, const castro_amd_monopole_params* params,
+                                 const castro_amd_geom* geom, const castro_amd_fab* grav_fab, void* stream)
+{
+    if (!c || !d_radial_grav || !grav_fab || !grav_fab->p || grav_fab->ncomp != 3) return CASTRO_AMD_ERR_ARG;
+    MonoGeom G;
+    const int rg = mono_geom(geom, params, G);
+    if (rg != CASTRO_AMD_OK) return rg;
+    hipSetDevice(c->device);
+    return launch_monopole_grav(d_radial_grav, G, to_dfab(grav_fab), grav_fab->lo, grav_fab->hi, (hipStream_t)stream, &c->prof);
+}
+
+// a gravity FAB of the _gfab source calls: 3 components, one ghost zone around [lo, hi] where the energy term reads neighbours
+static bool grav_fab_ok(const castro_amd_fab* g, const int lo[3], const int hi[3], int grav_source_type)
+{
+    if (!g || !g->p || g->ncomp != 3) return false;
+    const int ng = grav_source_type == 4 ? 1 : 0;
+    const int glo[3] = { lo[0] - ng, lo[1] - ng, lo[2] - ng }, ghi[3] = { hi[0] + ng, hi[1] + ng, hi[2] + ng };
+    return fab_contains(g, glo, ghi);
+}
+
+int castro_amd_old_gravity_source_gfab(castro_amd_ctx* c, const castro_amd_fab* state, const castro_amd_fab* source,
+                                       const int lo[3], const int hi[3], const castro_amd_fab* grav_old, int grav_source_type,
+                                       double dt, void* stream)
+{
+    if (!c || !state || !state->p || !source || !source->p) return CASTRO_AMD_ERR_ARG;
+    if (state->ncomp != NUM_STATE || source->ncomp < 7 || grav_source_type < 1 || grav_source_type > 4) return CASTRO_AMD_ERR_ARG;
+    if (!fab_contains(state, lo, hi) || !fab_contains(source, lo, hi) || !grav_fab_ok(grav_old, lo, hi, 1)) return CASTRO_AMD_ERR_ARG;
+    hipSetDevice(c->device);
+    return launch_old_grav_source_gfab(to_dfab(state), to_dfab(source), lo, hi, to_dfab(grav_old), grav_source_type, dt,
+                                       (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_new_gravity_source_gfab(castro_amd_ctx* c, const castro_amd_fab* state_old, const castro_amd_fab* state_new,
+                                       const castro_amd_fab* source, const castro_amd_fab mass_fluxes[3],
+                                       const int lo[3], const int hi[3], const castro_amd_fab* grav_old,
+                                       const castro_amd_fab* grav_new, int grav_source_type,
+                                       double dt, const castro_amd_geom* geom, void* stream)
+{
+    if (!c || !state_old || !state_old->p || !state_new || !state_new->p || !source || !source->p || !mass_fluxes || !geom)
+        return CASTRO_AMD_ERR_ARG;
+    if (state_old->ncomp != NUM_STATE || state_new->ncomp != NUM_STATE || source->ncomp < 7) return CASTRO_AMD_ERR_ARG;
+    if (grav_source_type < 1 || grav_source_type > 4 || geom->coord != 0) return CASTRO_AMD_ERR_ARG;
+    if (!fab_contains(state_old, lo, hi) || !fab_contains(state_new, lo, hi) || !fab_contains(source, lo, hi)) return CASTRO_AMD_ERR_ARG;
+    if (!grav_fab_ok(grav_old, lo, hi, grav_source_type) || !grav_fab_ok(grav_new, lo, hi, grav_source_type)) return CASTRO_AMD_ERR_ARG;
+    DFab M[3];
+    for (int d = 0; d < 3; ++d) {
+        int fhi[3] = { hi[0], hi[1], hi[2] };
+        fhi[d] += 1;
+        if (!mass_fluxes[d].p || mass_fluxes[d].ncomp != 1 || !fab_contains(&mass_fluxes[d], lo, fhi)) return CASTRO_AMD_ERR_ARG;
+        M[d] = to_dfab(&mass_fluxes[d]);
+    }
+    hipSetDevice(c->device);
+    return launch_new_grav_source_gfab(to_dfab(state_old), to_dfab(state_new), to_dfab(source), M, lo, hi, to_dfab(grav_old),
+                                       to_dfab(grav_new), grav_source_type, dt, geom->dx, (hipStream_t)stream, &c->prof);
 }
 
 int castro_amd_saxpy_fab(castro_amd_ctx* c, const castro_amd_fab* dst, double a, const castro_amd_fab* src, int ncomp,

@@ -177,6 +177,34 @@ struct DiagWorkspace { double* p = nullptr; size_t rows = 0; };
 int diag_layout(int nbox, DiagBoxDev* boxes, std::vector<int>& start, int& iters);
 int launch_integrated_quantities(int nbox, DiagBoxDev* boxes, const DiagGeom& G, FabOpsArena* arena, DiagWorkspace* ws,
                                  double* d_out, hipStream_t stream, Profiler* prof);
+// monopole gravity (monopole_kernels.hip).  One box of a castro_amd_radial_mass_mf launch: the valid zones [lo, lo + n) of U, the
+// byte mask of those zones (nullptr: every zone counts); nb: bricks per direction, set by the launcher.  A table is compared
+// byte by byte with the ones the context has on the device: fill it field by field over zeroed storage
+struct MonoBoxDev { DFab U; const unsigned char* mask; int lo[3], n[3], nb[3]; };
+// octant_factor: 8 when the centre sits on problo (Gravity.cpp:1439-1447), else 1; max_radius: max_radius_all_in_domain
+struct MonoGeom { double dx[3], problo[3], center[3]; double octant_factor, max_radius, Gconst; int n1d, drdxfac; };
+// what a context keeps for the binning: one row of 64 bins and its first bin per workgroup, the integer counts per bin, and the
+// box tables it has copied to the device (by content).  Reserved at first use; grown only by a call with more workgroups,
+// more bins or a table not seen before -- any other call neither allocates nor synchronises
+struct MonoWorkspace {
+    double* rows = nullptr; int* rbase = nullptr; size_t nrows = 0;
+    unsigned long long* count = nullptr; size_t ncount = 0;
+    struct Table { std::vector<char> host; void* dev = nullptr; };
+    std::vector<Table> tables;
+};
+bool radial_window_ok(const MonoGeom& G);
+void mono_workspace_free(MonoWorkspace* ws);
+int launch_radial_mass(int nbox, MonoBoxDev* boxes, const MonoGeom& G, MonoWorkspace* ws, double* d_out, hipStream_t stream,
+                       Profiler* prof);
+int launch_radial_gravity(const MonoGeom& G, const double* d_mass_vol, double* d_radial_grav, hipStream_t stream, Profiler* prof);
+int launch_monopole_grav(const double* d_radial_grav, const MonoGeom& G, const DFab& F, const int lo[3], const int hi[3],
+                         hipStream_t stream, Profiler* prof);
+// the gravity sources with a per-zone vector: GO / GN are 3-component FABs with one ghost zone around [lo, hi] (type 4)
+int launch_old_grav_source_gfab(const DFab& U, const DFab& SRC, const int lo[3], const int hi[3], const DFab& GO,
+                                int type, double dt, hipStream_t stream, Profiler* prof);
+int launch_new_grav_source_gfab(const DFab& UO, const DFab& UN, const DFab& SRC, const DFab M[3], const int lo[3], const int hi[3],
+                                const DFab& GO, const DFab& GN, int type, double dt, const double dx[3], hipStream_t stream,
+                                Profiler* prof);
 int launch_saxpy(const DFab& D, const DFab& S, const int lo[3], const int hi[3], double a, int ncomp,
                  hipStream_t stream, Profiler* prof);
 int launch_fab_ops(int nops, const DFab* D, const DFab* X, const DFab* Y, const int* lo, const int* hi, const int* kind,

@@ -194,6 +194,42 @@ class HipHydro:
                                                            int(grav_source_type), float(dt), C.byref(geom), _stream_ptr(stream)),
                 "new_gravity_source_fab")
 
+    # ---- monopole gravity (Source/gravity/Gravity.cpp) and the gravity sources with a per-zone vector -------------------
+    def radial_mass_mf(self, boxes, geom, mono, out, stream=None):
+        """castro_amd_radial_mass_mf: Gravity::compute_radial_mass over the valid zones of `boxes` (make_diag_boxes) into `out`, a
+        device tensor of 2 * n1d doubles (mass, then volume), overwritten.  Deterministic: the same boxes give the same bits."""
+        arr, n = boxes
+        L.check(self.lib.castro_amd_radial_mass_mf(self.h, n, arr, C.byref(geom), C.byref(mono), C.c_void_p(out.data_ptr()),
+                                                   _stream_ptr(stream)), "radial_mass_mf")
+
+    def radial_gravity(self, mono, geom, mass_vol, radial_grav, stream=None):
+        """castro_amd_radial_gravity: the outward integration of make_radial_gravity, mass_vol (2 * n1d) -> radial_grav (n1d)"""
+        L.check(self.lib.castro_amd_radial_gravity(self.h, C.byref(mono), C.byref(geom), C.c_void_p(mass_vol.data_ptr()),
+                                                   C.c_void_p(radial_grav.data_ptr()), _stream_ptr(stream)), "radial_gravity")
+
+    def monopole_grav(self, radial_grav, mono, geom, grav, grav_box, stream=None):
+        """castro_amd_monopole_grav_fab: interpolate_monopole_grav onto the whole box of the 3-component FAB `grav`"""
+        L.check(self.lib.castro_amd_monopole_grav_fab(self.h, C.c_void_p(radial_grav.data_ptr()), C.byref(mono), C.byref(geom),
+                                                      C.byref(L.fab_of(grav, *grav_box)), _stream_ptr(stream)), "monopole_grav_fab")
+
+    def old_gravity_source_gfab(self, state, box, source, src_box, lo, hi, grav_old, grav_box, grav_source_type, dt, stream=None):
+        L.check(self.lib.castro_amd_old_gravity_source_gfab(self.h, C.byref(L.fab_of(state, *box)), C.byref(L.fab_of(source, *src_box)),
+                                                            L.i3(lo), L.i3(hi), C.byref(L.fab_of(grav_old, *grav_box)),
+                                                            int(grav_source_type), float(dt), _stream_ptr(stream)),
+                "old_gravity_source_gfab")
+
+    def new_gravity_source_gfab(self, state_old, old_box, state_new, new_box, source, src_box, mass_fluxes, flux_boxes, lo, hi,
+                                grav_old, grav_new, grav_box, grav_source_type, dt, geom, stream=None):
+        mb = (L.Fab * 3)()
+        for d in range(3):
+            mb[d] = L.fab_of(mass_fluxes[d], *flux_boxes[d])
+        L.check(self.lib.castro_amd_new_gravity_source_gfab(self.h, C.byref(L.fab_of(state_old, *old_box)),
+                                                            C.byref(L.fab_of(state_new, *new_box)),
+                                                            C.byref(L.fab_of(source, *src_box)), mb, L.i3(lo), L.i3(hi),
+                                                            C.byref(L.fab_of(grav_old, *grav_box)), C.byref(L.fab_of(grav_new, *grav_box)),
+                                                            int(grav_source_type), float(dt), C.byref(geom), _stream_ptr(stream)),
+                "new_gravity_source_gfab")
+
     def old_rotation_source(self, state, box, source, src_box, lo, hi, rot, geom, dt, stream=None):
         L.check(self.lib.castro_amd_old_rotation_source_fab(self.h, C.byref(L.fab_of(state, *box)), C.byref(L.fab_of(source, *src_box)),
                                                             L.i3(lo), L.i3(hi), C.byref(rot), C.byref(geom), float(dt),

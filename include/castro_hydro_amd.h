@@ -56,7 +56,9 @@ extern "C" {
  *      castro_amd_clean_state_reduce_mf, castro_amd_estdt_mf.
  *   5 (not bumped: new entry points and a new struct only, nothing an existing caller allocates changes size or meaning):
  *      castro_amd_diffusion, castro_amd_temp_diffusion_fab / _mf, castro_amd_estdt_temp_diffusion_fab / _mf,
- *      castro_amd_sources_mf_ex; castro_amd_integrated_quantities_mf, castro_amd_diag_workgroups (struct castro_amd_diag_box).
+ *      castro_amd_sources_mf_ex; castro_amd_integrated_quantities_mf, castro_amd_diag_workgroups (struct castro_amd_diag_box);
+ *      castro_amd_radial_mass_mf, castro_amd_radial_gravity, castro_amd_monopole_grav_fab (struct castro_amd_monopole_params),
+ *      castro_amd_old_gravity_source_gfab, castro_amd_new_gravity_source_gfab.
  * A caller checks `castro_amd_abi_version() == CASTRO_AMD_ABI_VERSION` once after loading the library; a mismatch means
  * the library was built from another revision of this header (a 0.2 caller with 2-double vectors would be written 8 bytes
  * out of bounds by a 0.3 library). */
@@ -512,6 +514,53 @@ int castro_amd_integrated_quantities_mf(castro_amd_ctx *ctx, int nboxes, const c
                                         const castro_amd_geom *geom, const double center[3],
                                         double *d_out /* CASTRO_AMD_DIAG_N device doubles, overwritten */, void *stream);
 int castro_amd_diag_workgroups(int nboxes, const castro_amd_diag_box *boxes);
+
+/* Monopole self-gravity, gravity.gravity_type = "MonopoleGrav" (Source/gravity/Gravity.cpp), 3-D Cartesian, one level, no
+ * GR_GRAV.  n1d: bins of the radial arrays, drdxfac * (int(sqrt(nx^2 + ny^2 + nz^2)) + 2 * NUM_GROW) of the domain
+ * (Castro.cpp:3887-3913, Gravity.cpp:315); drdxfac: gravity.drdxfac, the bins are dx[0] / drdxfac wide; center: problem::center;
+ * max_radius_all_in_domain: min over d of probhi[d] - center[d] (Gravity.cpp:333-338); Gconst: the reference takes C::Gconst
+ * from its Microphysics constants (cgs, 6.67428e-8 in that release) -- here it is the caller's. */
+typedef struct castro_amd_monopole_params {
+    int n1d, drdxfac;
+    double center[3];
+    double max_radius_all_in_domain;
+    double Gconst;
+} castro_amd_monopole_params;
+/* Gravity::compute_radial_mass (Gravity.cpp:1409-1576) over the valid zones of every box: a zone under a zero mask byte (mask
+ * as in castro_amd_diag_box), with rho == 0 (:1491) or whose centre lies beyond bin n1d - 1 (:1514) is skipped; every other
+ * zone is split into drdxfac^3 sub-zones with the expressions of :1474-1541, and a sub-zone of bin index <= n1d - 1 adds
+ * vol_frac * rho to the mass of its bin and counts one towards its volume; octant_factor = 8 when center sits on problo within
+ * 1e-2 dx in all three directions (:1439-1447).  d_mass_vol: 2 * n1d device doubles, OVERWRITTEN: radial_mass, then radial_vol =
+ * count * vol_frac (the reference adds vol_frac count times).  The bins are found without contraction in both builds, and the
+ * masses are summed in an order fixed by the box table alone, never through floating-point atomics: the same boxes give
+ * the same bits on every call and on every stream.  The result of a rank is ready for a sum over the ranks.  The rows of
+ * partial sums and the device copy of the box table live in the context: a call with more workgroups or bins than any before,
+ * or with a table the context has not seen, allocates and synchronises; any other call does neither and can be captured.
+ * CASTRO_AMD_ERR_UNSUPPORTED: geom.coord != 0, or drdxfac above what a window of 64 bins per brick of 8 x 8 x 4 zones holds:
+ * drdxfac * sqrt((8 dx)^2 + (8 dy)^2 + (4 dz)^2) / dx + 3 <= 64, i.e. drdxfac <= 5 for cubic zones. */
+int castro_amd_radial_mass_mf(castro_amd_ctx *ctx, int nboxes, const castro_amd_diag_box *boxes, const castro_amd_geom *geom,
+                              const castro_amd_monopole_params *params, double *d_mass_vol, void *stream);
+/* The outward integration of Gravity::make_radial_gravity (Gravity.cpp:3170-3274) by one device thread: den = mass / vol where
+ * vol > 0, the three branches around max_radius_all_in_domain, radial_grav[i] = -Gconst * mass_encl / rc^2.  d_mass_vol as
+ * above (after the sum over the ranks), d_radial_grav: n1d device doubles.  No contraction in either build. */
+int castro_amd_radial_gravity(castro_amd_ctx *ctx, const castro_amd_monopole_params *params, const castro_amd_geom *geom,
+                              const double *d_mass_vol, double *d_radial_grav, void *stream);
+/* Gravity::interpolate_monopole_grav (Gravity.cpp:1300-1406) onto the WHOLE box of grav_fab (3 components), ghost zones
+ * included (:1322-1323): linear in bin 0 and in bin n1d - 1, quadratic with the min / max clamp between; a zone beyond bin
+ * n1d - 1 is left as it is. */
+int castro_amd_monopole_grav_fab(castro_amd_ctx *ctx, const double *d_radial_grav, const castro_amd_monopole_params *params,
+                                 const castro_amd_geom *geom, const castro_amd_fab *grav_fab, void *stream);
+/* castro_amd_old_gravity_source_fab / castro_amd_new_gravity_source_fab with the gravity of a zone read from 3-component FABs,
+ * gold(i,j,k,n) and gnew(i,j,k,n) of Castro_gravity.cpp:234-362 and :384-596.  grav_source_type = 4 reads the six neighbours of
+ * a zone (:564-574): grav_old and grav_new then hold one ghost zone around [lo, hi]. */
+int castro_amd_old_gravity_source_gfab(castro_amd_ctx *ctx, const castro_amd_fab *state, const castro_amd_fab *source,
+                                       const int lo[3], const int hi[3], const castro_amd_fab *grav_old, int grav_source_type,
+                                       double dt, void *stream);
+int castro_amd_new_gravity_source_gfab(castro_amd_ctx *ctx, const castro_amd_fab *state_old, const castro_amd_fab *state_new,
+                                       const castro_amd_fab *source, const castro_amd_fab mass_fluxes[3],
+                                       const int lo[3], const int hi[3], const castro_amd_fab *grav_old,
+                                       const castro_amd_fab *grav_new, int grav_source_type,
+                                       double dt, const castro_amd_geom *geom, void *stream);
 
 /* Two-level AMR building blocks, refinement ratio 2 (first slice).  The reference calls AMReX for
  * all of these [3P, not in the reference tree]; the arithmetic is restated from the published descriptions and is
