@@ -71,6 +71,7 @@ EXPORTED_SYMBOLS = (
     "castro_amd_integrated_quantities_mf", "castro_amd_diag_workgroups",
     "castro_amd_radial_mass_mf", "castro_amd_radial_gravity", "castro_amd_monopole_grav_fab",
     "castro_amd_old_gravity_source_gfab", "castro_amd_new_gravity_source_gfab",
+    "castro_amd_radial_mass_mf_ex", "castro_amd_radial_combine", "castro_amd_grav_bc_fill_fab", "castro_amd_sources_mf_g",
 )
 
 
@@ -132,6 +133,15 @@ class MonopoleParams(C.Structure):
     """castro_amd_monopole_params"""
     _fields_ = [("n1d", C.c_int), ("drdxfac", C.c_int), ("center", C.c_double * 3), ("max_radius_all_in_domain", C.c_double),
                 ("Gconst", C.c_double)]
+
+
+class RadialBox(C.Structure):
+    """castro_amd_radial_box: one box of a castro_amd_radial_mass_mf_ex call"""
+    _fields_ = [("lo", C.c_int * 3), ("hi", C.c_int * 3), ("state_old", Fab), ("state_new", Fab), ("mask", C.c_void_p),
+                ("omalpha", C.c_double), ("alpha", C.c_double)]
+
+
+MONOPOLE_MAX_LEVELS = 16       # castro_amd_radial_combine
 
 
 # C::Gconst of the reference comes from its Microphysics constants; the cgs value of that release
@@ -332,6 +342,13 @@ def load(numerics=None):
         L.castro_amd_old_gravity_source_gfab.argtypes = [C.c_void_p, PF, PF, I3, I3, PF, C.c_int, C.c_double, C.c_void_p]
         L.castro_amd_new_gravity_source_gfab.argtypes = [C.c_void_p, PF, PF, PF, PF, I3, I3, PF, PF, C.c_int, C.c_double,
                                                          C.POINTER(Geom), C.c_void_p]
+    if hasattr(L, "castro_amd_radial_combine"):             # absent from A/B builds of revisions before monopole gravity on AMR levels
+        PM = C.POINTER(MonopoleParams)
+        L.castro_amd_radial_mass_mf_ex.argtypes = [C.c_void_p, C.c_int, C.POINTER(RadialBox), C.POINTER(Geom), PM, C.c_void_p, C.c_void_p]
+        L.castro_amd_radial_combine.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
+        L.castro_amd_grav_bc_fill_fab.argtypes = [C.c_void_p, PF, C.POINTER(Geom), C.c_void_p]
+        L.castro_amd_sources_mf_g.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(SourceBox), PF, PF, C.c_int,
+                                              C.POINTER(Rotation), C.POINTER(Geom), C.POINTER(Params), C.c_double, C.c_int, C.c_void_p]
     L.castro_amd_step_control.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_double, C.c_double,
                                           C.c_double, C.c_int, C.c_void_p]
     L.castro_amd_clean_state_fab.argtypes = [C.c_void_p, PF, I3, I3, C.POINTER(Params), C.c_int, C.c_void_p]

@@ -29,7 +29,8 @@ Fixed hierarchies: `patches=[...]`, one entry per refined level: a box (lo, hi) 
 the level below.  Level 0 is one box (per rank; this driver is single-rank).
 Periodic domains: the periodic images of the boxes of a level enter the same-level copies and the reflux as boxes shifted
 by the domain extent.  Constant gravity and rotation sources on every level (the Source_Type FillPatch of a refined level
-interpolates the coarse sources like the state).  Not provided: multi-rank AMR.  The interpolation,
+interpolates the coarse sources like the state); monopole self-gravity with gravity=MonopoleGravity(...) (castro_amd/gravity.py:
+the radial arrays span the levels, _Level.fill_grav is the Gravity_Type FillPatch).  Not provided: multi-rank AMR.  The interpolation,
 flux-register and clustering arithmetic is AMReX's, restated from its published description
 (include/castro_hydro_amd.h, castro_amd/cluster.py): parity with an AMReX build is unpinned.
 """
@@ -69,6 +70,8 @@ class _Patch(Castro):
             self.cbox, self.ctmp, self.shell, self.regs = None, None, [], {}
             if self.have_sources:
                 self.new_source_g = self.hydro.alloc(NSRC, *self.sbox) if self.owned else None
+            if self.monopole:
+                self.gcbox, self.gctmp, self.gshell = None, None, []
             return
         # coarse zones under the grown fine box, grown by one for the slopes
         self.cbox = (tuple(_coarsen(self.glo[d]) - 1 for d in range(3)), tuple(_coarsen(self.ghi[d]) + 1 for d in range(3)))
@@ -76,6 +79,8 @@ class _Patch(Castro):
         self.shell = shell_slabs(self.gbox, self.bx)
         if self.have_sources:
             self._bind_sources()
+        if self.monopole:
+            self._bind_gravity()
         # flux registers: the coarse faces on the six sides of this box
         plo, phi = pbox
         self.regs = {}
@@ -92,6 +97,16 @@ class _Patch(Castro):
         self.stmp = self.hydro.alloc(NSRC, *self.scbox) if self.owned else None
         self.new_source_g = self.hydro.alloc(NSRC, *self.sbox) if self.owned else None
         self.sshell = shell_slabs(self.sbox, self.bx)
+
+    def _bind_gravity(self):
+        """Gravity_Type data (one ghost zone): the ghost shell inside the domain -- the zones outside it get the boundary fill --
+        and the coarse zones under it, grown by one for the slopes."""
+        g = self.geom
+        ilo = tuple(max(self.gravbox[0][d], g.domlo[d]) for d in range(3))
+        ihi = tuple(min(self.gravbox[1][d], g.domhi[d]) for d in range(3))
+        self.gcbox = (tuple(_coarsen(ilo[d]) - 1 for d in range(3)), tuple(_coarsen(ihi[d]) + 1 for d in range(3)))
+        self.gctmp = self.hydro.alloc(3, *self.gcbox) if self.owned else None
+        self.gshell = [sl for sl in shell_slabs((ilo, ihi), self.bx) if all(sl[1][d] >= sl[0][d] for d in range(3))]
 
     def expand_state(self, S, box=None, neighbors=None):
         assert box is None, "the Source_Type FillPatch of a refined level is level-wide: _Level.fill_source"
@@ -149,6 +164,19 @@ class _Level:
             if self.have_sources:                                # the same table for the Source_Type FillPatch
                 b.ssib = [(sb, it, sh) for sb in self.boxes for sh in shifts if not (sb is b and sh == (0, 0, 0))
                           for it in [CL.intersect(b.sbox, _shift(sb.bx, sh))] if it]
+            if b.monopole:                                       # the same table for the Gravity_Type FillPatch (one ghost zone)
+                b.gsib = [(sb, it, sh) for sb in self.boxes for sh in shifts if not (sb is b and sh == (0, 0, 0))
+                          for it in [CL.intersect(b.gravbox, _shift(sb.bx, sh))] if it]
+                b.grav_at_edge = any(b.gravbox[0][d] < b.geom.domlo[d] or b.gravbox[1][d] > b.geom.domhi[d] for d in range(3))
+                b.gsrc = [(p, it) for p in parents for it in [CL.intersect(b.gcbox, p.gravbox)] if it] if self.l > 0 else []
+                b.gsrc_valid = [(p, it) for p in parents for it in [CL.intersect(b.gcbox, p.bx)] if it] if self.l > 0 else []
+                if self.l > 0:
+                    cov = np.zeros(tuple(b.gcbox[1][d] - b.gcbox[0][d] + 1 for d in (2, 1, 0)), dtype=bool)
+                    o = b.gcbox[0]
+                    for _, (lo, hi) in b.gsrc:
+                        cov[lo[2] - o[2]:hi[2] - o[2] + 1, lo[1] - o[1]:hi[1] - o[1] + 1, lo[0] - o[0]:hi[0] - o[0] + 1] = True
+                    assert cov.all(), "box %s of level %d not properly nested: the coarse zones under its gravity ghost zones " \
+                        "reach beyond the gravity data of level %d" % (b.bx, self.l, self.l - 1)
             if self.l == 0:                    # no coarser level: no coarse data, no flux registers, nothing to average onto
                 b.csrc, b.csrc_valid, b.crse_init, b.reflux_to, b.avg_to = [], [], {}, {}, []
                 if self.have_sources:
@@ -373,6 +401,61 @@ class _Level:
             h.copy(b.new_source_g, b.sbox, b.new_source, b.bx, b.lo, b.hi)
         self.fill_source("new_source_g")
 
+    # ---- AmrLevel::FillPatch of Gravity_Type (Gravity.cpp:894-900, 967-973) ------------------------------------
+    def fill_grav(self, name, a):
+        """Ghost zones of grav_old / grav_new (`name`) of every box, after interpolate_monopole_grav has filled the whole FABs.
+        A ghost zone under a sibling's valid zone already holds the sibling's bits (same level, same radial array, same function
+        of the index).  Ghost zones covered only by the coarser level: the coarse Gravity_Type data -- grav_old / grav_new of its
+        last advance -- interpolated in time ((1 - a) old + a new) and space (cell_cons_interp, Castro_setup.cpp:352-364,
+        414-416); the interpolation runs over the whole ghost shell inside the domain and the siblings' valid zones are copied
+        over it, as FillPatch does.  Ghost zones outside the domain: the Gravity_Type boundary fill (Castro_setup.cpp:614-622)."""
+        h = self.hydro
+        if self.plain_base:
+            for b in self.mine:
+                h.grav_bc_fill(getattr(b, name), b.gravbox, b.geom)
+            return
+        if self.amr.nranks > 1:
+            X = self.amr._xrun
+            X([("grav_lincomb", b, p, lo, hi, a) for b in self.boxes for p, (lo, hi) in b.gsrc + b.gsrc_valid], 3)
+            for b in (self.mine if self.l > 0 else ()):
+                for lo, hi in b.gshell:
+                    h.cc_interp(b.gctmp, b.gcbox, getattr(b, name), b.gravbox, lo, hi, 3)
+            if self.l > 0:
+                X([("grav_copy", b, sb, lo, hi, (name, sh)) for b in self.boxes for sb, (lo, hi), sh in b.gsib], 3)
+            for b in self.mine:
+                h.grav_bc_fill(getattr(b, name), b.gravbox, b.geom)
+            return
+        if self.batched and self._level_calls():
+            mk, P = h.make_ops, self.params
+            if self.l > 0:
+                for key, attr in (("grav_lincomb_ghost", "gsrc"), ("grav_lincomb_valid", "gsrc_valid")):
+                    ops = self._cached_ops((key,), (), lambda attr=attr: mk(
+                        [(L.OP_LINCOMB, 0, 3, lo, hi, 0.0, 0.0, (b.gctmp, b.gcbox), (p.grav_old, p.gravbox), (p.grav_new, p.gravbox))
+                         for b in self.boxes for p, (lo, hi) in getattr(b, attr)]))
+                    arr, n = ops
+                    for i in range(n):
+                        arr[i].a, arr[i].b = 1.0 - a, a
+                    h.fab_ops(ops, params=P)
+                h.fab_ops(self._cached_ops(("grav_shell", name), (), lambda: mk(
+                    [(L.OP_INTERP, 0, 3, lo, hi, 0.0, 0.0, (getattr(b, name), b.gravbox), (b.gctmp, b.gcbox), None)
+                     for b in self.boxes for lo, hi in b.gshell])), params=P)
+                h.fab_ops(self._cached_ops(("grav_sib", name), (), lambda: mk(
+                    [(L.OP_COPY, 0, 3, lo, hi, 0.0, 0.0, (getattr(b, name), b.gravbox), (getattr(sb, name), _shift(sb.gravbox, sh)), None)
+                     for b in self.boxes for sb, (lo, hi), sh in b.gsib])), params=P)
+            for b in self.boxes:
+                if b.grav_at_edge:
+                    h.grav_bc_fill(getattr(b, name), b.gravbox, b.geom)
+            return
+        for b in (self.boxes if self.l > 0 else ()):
+            for p, (lo, hi) in b.gsrc + b.gsrc_valid:           # ghost zones of the parents first, valid zones last
+                h.lincomb(b.gctmp, b.gcbox, 1.0 - a, p.grav_old, p.gravbox, a, p.grav_new, p.gravbox, 3, lo, hi)
+            for lo, hi in b.gshell:
+                h.cc_interp(b.gctmp, b.gcbox, getattr(b, name), b.gravbox, lo, hi, 3)
+        for b in self.boxes:
+            for sb, (lo, hi), sh in (b.gsib if self.l > 0 else ()):
+                h.copy(getattr(b, name), b.gravbox, getattr(sb, name), _shift(sb.gravbox, sh), lo, hi)
+            h.grav_bc_fill(getattr(b, name), b.gravbox, b.geom)
+
     def create_source_corrector(self):
         """Castro::create_source_corrector on a level of boxes (Castro.cpp:3780-3818): AmrLevel::FillPatch(Source_Type at its old
         time -- after the swap that is the new-time corrector of the LAST advance --, components UMX .. UMZ, NUM_GROW_SRC ghost
@@ -403,15 +486,27 @@ class _Level:
         box, or Castro._sources_one_pass over the level's boxes."""
         h = self.hydro
         lvl = self._source_level_calls()        # the per-box stages as one library call per level (castro_amd_sources_mf)
+        G = self.amr.gravity
 
         def sources(stage):
+            if G is not None:
+                # construct_old_gravity in front of the old-time sources (Castro_advance_ctu.cpp:122), construct_new_gravity in
+                # front of the new-time ones (:258): level-wide, every coarser level at this level's time
+                if stage == 0:
+                    G.get_old_grav_vector(self.l, time, self.alpha)
+                else:
+                    G.get_new_grav_vector(self.l, time + dt, self.alpha + dt / self._dt_parent if self.l > 0 else 1.0)
             if lvl is None:
                 for b in self.mine:
                     b._source_stage(stage, dt)
                 return
             sp = tuple(t.data_ptr() for b in self.mine for t in (b.S_old_b, b.S_new_b))
+            gf = None
+            if G is not None:                   # Gravity_Type FABs keep their storage between regrids
+                gf = self._cached_ops(("grav_fabs",), (), lambda: (h.make_grav_fabs([(b.grav_old, b.gravbox) for b in self.mine]),
+                                                                   h.make_grav_fabs([(b.grav_new, b.gravbox) for b in self.mine])))
             lvl._sources_one_pass(stage, dt, self._cached_ops((("src_old", "src_new")[stage],), sp, lambda: h.make_source_boxes(
-                [b._source_spec(stage) for b in self.mine])))
+                [b._source_spec(stage) for b in self.mine])), **({} if gf is None else {"grav_fabs": gf}))
         sources(0)
         self.fill_source("old_source")
         predictor = self.params.source_term_predictor == 1
@@ -444,9 +539,13 @@ class _Level:
         None: box by box."""
         if not (self._level_calls() and self.mine and hasattr(self.hydro, "sources_mf")):
             return None
+        if os.environ.get("CASTRO_AMD_SOURCES_ONE_PASS", "1") == "0" and self.amr.gravity is not None:
+            return None                         # the separate-call form of the gravity sources (A/B and tests)
         b0 = self.mine[0]
+        if b0.monopole and not hasattr(self.hydro, "sources_mf_g"):
+            return None
         for b in self.mine:
-            if (b.do_grav != b0.do_grav or (b.do_grav and (tuple(b.grav) != tuple(b0.grav) or b.grav_source_type != b0.grav_source_type))
+            if (b.do_grav != b0.do_grav or b.monopole != b0.monopole or (b.do_grav and (tuple(b.grav) != tuple(b0.grav) or b.grav_source_type != b0.grav_source_type))
                     or b.rotation is not b0.rotation):
                 return None
         return b0
@@ -634,8 +733,10 @@ class CastroAmr:
                  params=None, make_hydro=None, make_params=None, refine=None, regrid_int=2, n_error_buf=1,
                  blocking_factor=8, patches=None, max_level=1, cluster=False, grid_eff=0.7, max_grid_size=128,
                  do_grav=False, const_grav=0.0, grav_source_type=4, rotation=None, comm=None, base_grid=None, box_streams=4,
-                 diffusion=None, sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant"):
-        """gravity_type: "constant" only ("monopole" is refused: single level, castro_amd.Castro).
+                 diffusion=None, sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", gravity=None):
+        """gravity: castro_amd.MonopoleGravity(drdxfac=..., Gconst=...) with do_grav=True -- monopole self-gravity on every
+        level (castro_amd/gravity.py: the object spans the levels like the reference's Gravity).
+        gravity_type: "constant" only (the bare string "monopole" carries neither drdxfac nor Gconst and is refused).
         sum_interval, show_center_of_mass, diag_dir: as in castro_amd.Castro -- sum_integrated_quantities() over the composite
         grid after initData and after every coarse step with nstep % sum_interval == 0 (self.diag_history, the three data logs).
         base_grid = (gx, gy, gz): level 0 as gx x gy x gz equal boxes instead of one (amr.max_grid_size on the base level);
@@ -660,9 +761,18 @@ class CastroAmr:
         if gravity_type not in ("constant", "monopole"):
             raise ValueError("gravity_type must be \"constant\" or \"monopole\", not %r" % (gravity_type,))
         if gravity_type == "monopole":
-            raise NotImplementedError("CastroAmr: monopole gravity is built for a single level only (castro_amd.Castro): the level "
+            raise NotImplementedError("CastroAmr: gravity_type=\"monopole\" is the single-level form (castro_amd.Castro); the level "
                                       "combination and the time interpolation of Gravity::make_radial_gravity "
-                                      "(Gravity.cpp:2962-3127) are not built")
+                                      "(Gravity.cpp:2962-3127) are reached with gravity=castro_amd.MonopoleGravity(drdxfac=..., "
+                                      "Gconst=...)")
+        if gravity is not None:
+            from .gravity import MonopoleGravity
+            if not isinstance(gravity, MonopoleGravity):
+                raise TypeError("gravity must be a castro_amd.MonopoleGravity, not %r" % (type(gravity),))
+            if not do_grav:
+                raise ValueError("gravity=MonopoleGravity(...) needs do_grav=True")
+            gravity.bind(self, lo_bc, hi_bc)
+        self.gravity = gravity
         if patch_crse is not None:
             assert patches is None
             patches = [patch_crse]
@@ -674,6 +784,8 @@ class CastroAmr:
         self.params = params if params is not None else (make_params() if make_params else L.default_params())
         self._kw = dict(prob_lo=prob_lo, prob_hi=prob_hi, lo_bc=lo_bc, hi_bc=hi_bc, params=self.params, overlap=False,
                         do_grav=do_grav, const_grav=const_grav, grav_source_type=grav_source_type, rotation=rotation)
+        if gravity is not None:
+            self._kw["gravity"] = gravity
         self.n_cell = tuple(n_cell)
         self.periodic = tuple(lo_bc[d] == 0 and hi_bc[d] == 0 for d in range(3))
         # boxes of a level whose hydro updates may be in flight at once (device backend); CASTRO_AMD_BOX_STREAMS overrides
@@ -686,6 +798,8 @@ class CastroAmr:
                 base.new_source_g = base.hydro.alloc(NSRC, *base.sbox)
             self.lev = [_Level(self, 0, [base])]                      # lev[0] covers the domain
             self.lev[0].bind()
+            if gravity is not None:
+                gravity.check_level(0, base.geom)
         else:
             gx = tuple(int(x) for x in base_grid)
             assert all(self.n_cell[d] % gx[d] == 0 and self.n_cell[d] // gx[d] >= 2 * NUM_GROW for d in range(3)), \
@@ -705,6 +819,8 @@ class CastroAmr:
                 b.bind(lev0, None)
             self.lev.append(lev0)
             lev0.bind()
+            if gravity is not None:
+                gravity.check_level(0, lev0.geom)
         self.refine = refine
         self.regrid_int, self.n_error_buf, self.blocking_factor = int(regrid_int), int(n_error_buf), int(blocking_factor)
         self.cluster = bool(cluster)
@@ -815,8 +931,15 @@ class CastroAmr:
 
     def _xstage(self, kind, D, S, lo, hi, extra):
         h = S.hydro
-        t = h.alloc(NSRC if kind.startswith("src_") else NUM_STATE, lo, hi)
+        t = h.alloc(NSRC if kind.startswith("src_") else (3 if kind.startswith("grav_") else NUM_STATE), lo, hi)
         box = (tuple(lo), tuple(hi))
+        if kind == "grav_lincomb":             # Gravity_Type data of a parent, interpolated in time
+            h.lincomb(t, box, 1.0 - extra, S.grav_old, S.gravbox, extra, S.grav_new, S.gravbox, 3, lo, hi)
+            return t
+        if kind == "grav_copy":
+            name, sh = extra
+            h.copy(t, box, getattr(S, name), _shift(S.gravbox, sh), lo, hi)
+            return t
         if kind == "src_lincomb":              # Source_Type data of a parent, interpolated in time
             h.lincomb(t, box, 1.0 - extra, S.old_source, S.sbox, extra, S.new_source_g, S.sbox, NSRC, lo, hi)
             return t
@@ -848,7 +971,18 @@ class CastroAmr:
         """the operation on this rank's box D; `buf` holds the staged source when S lives elsewhere"""
         h = D.hydro
         box = (tuple(lo), tuple(hi))
-        if kind == "src_lincomb":
+        if kind == "grav_lincomb":
+            if buf is None:
+                h.lincomb(D.gctmp, D.gcbox, 1.0 - extra, S.grav_old, S.gravbox, extra, S.grav_new, S.gravbox, 3, lo, hi)
+            else:
+                h.copy(D.gctmp, D.gcbox, buf, box, lo, hi)
+        elif kind == "grav_copy":
+            name, sh = extra
+            if buf is None:
+                h.copy(getattr(D, name), D.gravbox, getattr(S, name), _shift(S.gravbox, sh), lo, hi)
+            else:
+                h.copy(getattr(D, name), D.gravbox, buf, box, lo, hi)
+        elif kind == "src_lincomb":
             if buf is None:
                 h.lincomb(D.stmp, D.scbox, 1.0 - extra, S.old_source, S.sbox, extra, S.new_source_g, S.sbox, NSRC, lo, hi)
             else:
@@ -903,13 +1037,19 @@ class CastroAmr:
 
     def _push_level(self, pboxes):
         lev = self._make_level(len(self.lev), pboxes)
+        if self.gravity is not None:
+            self.gravity.check_level(len(self.lev), lev.geom)
         self.lev.append(lev)
         lev.bind()
         self._diag_masks, self._diag_tables = {}, {}    # the zones of the level below that are covered have changed
+        if self.gravity is not None:
+            self.gravity.reset(len(self.lev) - 1)
 
     def _drop_fine(self):
         del self.lev[1:]
         self._diag_masks, self._diag_tables = {}, {}
+        if self.gravity is not None:
+            self.gravity.reset(1)
 
     # ---- Castro::errorEst (Castro.cpp:3131-3164) ---------------------------------------------------
     def _fill_ghosts_new(self, upto, lbase=0, alpha=1.0):
@@ -1110,6 +1250,8 @@ class CastroAmr:
             keep += 1
         del self.lev[keep:]
         self._diag_masks, self._diag_tables = {}, {}
+        if self.gravity is not None:
+            self.gravity.reset(keep)
         for l in range(keep, len(new) + 1):
             parent = self.lev[l - 1]
             if l - 1 >= keep:                                   # a level made in this regrid: its ghost zones are not filled yet
@@ -1252,6 +1394,7 @@ class CastroAmr:
         h = lev.hydro
         lev.alpha = alpha
         lev._t0, lev._alpha0, lev._dt_parent = t, alpha, 2.0 * dt
+        lev.t_old, lev.t_new = t, t + dt        # StateData::prevTime / curTime of the level (Gravity::make_radial_gravity)
         lev.fuse_post_level = l == finest and os.environ.get("CASTRO_AMD_FUSE_POST_FINEST", "1") != "0"
         lev.advance(t, dt)
         self.level_count[l] += 1

@@ -259,8 +259,11 @@ class Castro:
                  use_retry=True, retry_subcycle_factor=0.5, max_subcycles=10, dt_cutoff=1.e-12,
                  do_grav=False, const_grav=0.0, grav_source_type=4, box=None, rotation=None, fixed_dt=-1.0, initial_dt=-1.0, max_dt=1.e200,
                  alloc=True, numerics=None, proxy_ranks=1, diffusion=None, do_hydro=True,
-                 sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", drdxfac=1, Gconst=L.GCONST):
-        """gravity_type (gravity.gravity_type): "constant" (ConstantGrav: const_grav along z) | "monopole" (MonopoleGrav: the radial
+                 sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", drdxfac=1, Gconst=L.GCONST,
+                 gravity=None):
+        """gravity: the castro_amd.MonopoleGravity of the CastroAmr hierarchy this box belongs to (set by CastroAmr: the object
+        spans the levels and constructs grav_old / grav_new of every box; a single-level run uses gravity_type="monopole").
+        gravity_type (gravity.gravity_type): "constant" (ConstantGrav: const_grav along z) | "monopole" (MonopoleGrav: the radial
         self-gravity of the state about the centre sum_integrated_quantities uses -- the `center` attribute, else the middle of the
         domain; 3-D Cartesian, non-periodic, single level); drdxfac: gravity.drdxfac; Gconst: the reference takes C::Gconst from
         its Microphysics constants, the default is the cgs value of that release.
@@ -377,8 +380,17 @@ class Castro:
         if gravity_type not in ("constant", "monopole"):
             raise ValueError("gravity_type must be \"constant\" or \"monopole\", not %r" % (gravity_type,))
         self.gravity_type, self.drdxfac, self.Gconst = gravity_type, int(drdxfac), float(Gconst)
-        self.monopole = self.do_grav and gravity_type == "monopole"
-        if self.monopole:
+        self.monopole = self.do_grav and (gravity_type == "monopole" or gravity is not None)
+        self.level_gravity = gravity if self.do_grav else None
+        if self.level_gravity is not None:
+            # a box of a CastroAmr level: Gravity_Type old / new data with one ghost zone; the radial arrays live in `gravity`
+            self.gravity_type, self.drdxfac, self.Gconst = "monopole", gravity.drdxfac, gravity.Gconst
+            self.gravbox = (tuple(x - 1 for x in self.lo), tuple(x + 1 for x in self.hi))
+            self.grav_old = hydro_alloc(3, *self.gravbox)
+            self.grav_new = hydro_alloc(3, *self.gravbox)
+            if gravity.center is not None:
+                self.center = gravity.center
+        elif self.monopole:
             self._init_monopole(hydro_alloc, box)
         # castro.do_rotation: `rotation` = _lib.make_rotation(rotational_period, rot_axis, ...)
         self.rotation = rotation
@@ -750,7 +762,7 @@ class Castro:
 
     def radial_gravity(self):
         """(radial_mass, radial_vol, radial_grav) of the last gravity construction, as numpy arrays of n1d entries"""
-        if not self.monopole:
+        if not self.monopole or self.level_gravity is not None:
             raise RuntimeError("radial_gravity() needs Castro(do_grav=True, gravity_type=\"monopole\")")
         mv = self._radial_mv.reshape(-1).cpu().numpy()
         return mv[:self.n1d].copy(), mv[self.n1d:].copy(), self._radial_g.reshape(-1).cpu().numpy().copy()
@@ -980,11 +992,20 @@ class Castro:
         src = (self.old_source, self.sbox) if stage == 0 else (self.new_source, self.bx)
         return (self.lo, self.hi, (self.S_old_b, self.gbox), (self.S_new_b, self.gbox), src, self.mass_fluxes, self.flux_boxes)
 
-    def _sources_one_pass(self, stage, dt, boxes=None):
+    def _sources_one_pass(self, stage, dt, boxes=None, grav_fabs=None):
         """_source_stage in one pass (castro_amd_sources_mf, round 6): zero + diffusion + gravity + rotation + apply + clean_state
         in one kernel -- the separate calls read and write the source and the state three to four times.  `boxes`: the
-        make_source_boxes table of a level whose boxes share the settings of this one (castro_amd/amr.py)."""
+        make_source_boxes table of a level whose boxes share the settings of this one (castro_amd/amr.py); `grav_fabs`: with
+        monopole gravity the (grav_old, grav_new) make_grav_fabs arrays of those boxes (castro_amd_sources_mf_g)."""
         h = self.hydro
+        if self.monopole:
+            if self.level_gravity is None:          # a single level constructs its own gravity; CastroAmr does it level-wide
+                self._monopole_gravity(self.S_old_b if stage == 0 else self.S_new_b, self.grav_old if stage == 0 else self.grav_new)
+            if grav_fabs is None:
+                grav_fabs = (h.make_grav_fabs([(self.grav_old, self.gravbox)]), h.make_grav_fabs([(self.grav_new, self.gravbox)]))
+            h.sources_mf_g(stage, boxes or h.make_source_boxes([self._source_spec(stage)]), grav_fabs[0], grav_fabs[1],
+                           self.grav_source_type, self.rotation, self.geom, self.params, dt, ntimes=1)
+            return
         dkw = {} if self.diffusion is None else {"diffusion": self.diffusion}      # diff_src goes first (Castro_sources.cpp)
         h.sources_mf(stage, boxes or h.make_source_boxes([self._source_spec(stage)]), self.grav if self.do_grav else None,
                      self.grav_source_type if self.do_grav else 4, self.rotation, self.geom, self.params, dt, ntimes=1, **dkw)
@@ -1002,7 +1023,8 @@ class Castro:
             if self.diffusion is not None:              # construct_old_diff_source: + 1.0 x DiffTerm(Sborder)
                 h.temp_diffusion(S, g, src, sbx, lo, hi, self.diffusion, self.geom, 1.0)
             if self.monopole:
-                self._monopole_gravity(S, self.grav_old)
+                if self.level_gravity is None:
+                    self._monopole_gravity(S, self.grav_old)
                 h.old_gravity_source_gfab(S, g, src, sbx, lo, hi, self.grav_old, self.gravbox, self.grav_source_type, dt)
             elif self.do_grav:
                 h.old_gravity_source(S, g, src, sbx, lo, hi, self.grav, self.grav_source_type, dt)
@@ -1013,7 +1035,8 @@ class Castro:
                 h.temp_diffusion(Sn, g, src, sbx, lo, hi, self.diffusion, self.geom, 0.5)
                 h.temp_diffusion(S, g, src, sbx, lo, hi, self.diffusion, self.geom, -0.5)
             if self.monopole:
-                self._monopole_gravity(Sn, self.grav_new)
+                if self.level_gravity is None:
+                    self._monopole_gravity(Sn, self.grav_new)
                 h.new_gravity_source_gfab(S, g, Sn, g, src, sbx, self.mass_fluxes, self.flux_boxes, lo, hi, self.grav_old,
                                           self.grav_new, self.gravbox, self.grav_source_type, dt, self.geom)
             elif self.do_grav:
@@ -1042,9 +1065,10 @@ class Castro:
             if not self._in_retry:
                 self.create_source_corrector()
             h.set_source_corrector(self.source_corrector, self.sbox)
-        # monopole gravity reads a per-zone vector: the one-pass table (castro_amd_sources_mf) carries one vector per call
+        # monopole gravity reads a per-zone vector: castro_amd_sources_mf_g carries the gravity FABs of every box (not together
+        # with the diffusion term, which only castro_amd_sources_mf_ex places in front of the one-pass kernel)
         one_pass = (hasattr(h, "sources_mf") and os.environ.get("CASTRO_AMD_SOURCES_ONE_PASS", "1") != "0"
-                    and not getattr(self, "monopole", False))
+                    and (not getattr(self, "monopole", False) or (hasattr(h, "sources_mf_g") and self.diffusion is None)))
         sources = self._sources_one_pass if one_pass else self._source_stage
         sources(0, dt)
         if self.do_hydro:

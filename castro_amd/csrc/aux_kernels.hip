@@ -3,6 +3,7 @@
 // problem initial data.  Reference locations are cited per kernel.
 #include <hip/hip_runtime.h>
 #include <cstring>
+#include <type_traits>
 #include "../../include/castro_hydro_amd.h"
 #include "hydro_device.h"
 #include "ctu_kernels.h"
@@ -760,8 +761,15 @@ int launch_new_rot_source(const DFab& UO, const DFab& UN, const DFab& SRC, const
 // ---------------------------------------------------------------------------------------
 struct GravDev { double g[3]; int type, on; };
 
-template <int STAGE>
-__global__ void __launch_bounds__(256) k_sources_apply(const SrcBoxDev* __restrict__ tab, const long* __restrict__ start, int nbox,
+// the SrcBoxDev of a table entry: the entry itself, or the front of an entry that carries its gravity FABs as well
+__device__ __forceinline__ const SrcBoxDev& src_box_of(const SrcBoxDev& b) { return b; }
+__device__ __forceinline__ const SrcBoxDev& src_box_of(const SrcBoxGDev& b) { return b.box; }
+
+// GFAB = false (BOX = SrcBoxDev): the one vector of the call through GravConst.  GFAB = true (BOX = SrcBoxGDev,
+// castro_amd_sources_mf_g): the gravity of a zone through GravFab from the box's grav_old / grav_new FABs, the zone functions
+// of k_old_grav_source_gfab / k_new_grav_source_gfab
+template <int STAGE, bool GFAB, class BOX>
+__global__ void __launch_bounds__(256) k_sources_apply(const BOX* __restrict__ tab, const long* __restrict__ start, int nbox,
                                                        GravDev G, RotDev R, int rot_on, double dt, double dx0, double dx1, double dx2,
                                                        DevParams P, int ntimes, int diff_on)
 {
@@ -772,7 +780,8 @@ __global__ void __launch_bounds__(256) k_sources_apply(const SrcBoxDev* __restri
         const int mid = (lo_ + hi_ + 1) >> 1;
         if (start[mid] <= t) lo_ = mid; else hi_ = mid - 1;
     }
-    const SrcBoxDev B = tab[lo_];
+    const BOX BX = tab[lo_];
+    const SrcBoxDev& B = src_box_of(BX);
     t -= start[lo_];
     const int i = B.lo[0] + (int)(t % B.n[0]);
     const long q = t / B.n[0];
@@ -791,8 +800,14 @@ __global__ void __launch_bounds__(256) k_sources_apply(const SrcBoxDev* __restri
         acc[UEINT] = B.Src.p[cs + B.Src.sn * UEINT];
     }
     if (G.on) {
-        if (STAGE == 0) old_grav_zone(B.So, i, j, k, G.g, G.type, dt, src);
-        else new_grav_zone(B.So, B.Sn, B.M0, B.M1, B.M2, i, j, k, G.g, G.type, dt, dx0, dx1, dx2, src);
+        if constexpr (GFAB) {
+            const GravFab gold = { BX.GO }, gnew = { BX.GN };
+            if (STAGE == 0) old_grav_zone_g(B.So, i, j, k, gold, G.type, dt, src);
+            else new_grav_zone_g(B.So, B.Sn, B.M0, B.M1, B.M2, i, j, k, gold, gnew, G.type, dt, dx0, dx1, dx2, src);
+        } else {
+            if (STAGE == 0) old_grav_zone(B.So, i, j, k, G.g, G.type, dt, src);
+            else new_grav_zone(B.So, B.Sn, B.M0, B.M1, B.M2, i, j, k, G.g, G.type, dt, dx0, dx1, dx2, src);
+        }
         for (int n = 0; n < NSRC; ++n) acc[n] += src[n];
     }
     if (rot_on) {
@@ -817,19 +832,24 @@ __global__ void __launch_bounds__(256) k_sources_apply(const SrcBoxDev* __restri
 
 static RotDev make_rotdev(const castro_amd_rotation* r, const castro_amd_geom* g, double dt);
 
-int launch_sources_apply(int stage, int nbox, const SrcBoxDev* boxes, const double* grav, int grav_type, const castro_amd_rotation* rot,
-                         const castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
-                         hipStream_t stream, Profiler* prof, int diff_on)
+static const SrcBoxDev& src_box_host(const SrcBoxDev& b) { return b; }
+static const SrcBoxDev& src_box_host(const SrcBoxGDev& b) { return b.box; }
+
+template <class BOX>
+static int launch_sources_apply_t(int stage, int nbox, const BOX* boxes, const double* grav, int grav_type, const castro_amd_rotation* rot,
+                                  const castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
+                                  hipStream_t stream, Profiler* prof, int diff_on)
 {
+    constexpr bool GFAB = std::is_same<BOX, SrcBoxGDev>::value;
     if (nbox < 1 || !boxes || !arena) return 0;
     std::vector<long> start((size_t)nbox + 1, 0);
     for (int r = 0; r < nbox; ++r) {
         long n = 1;
-        for (int d = 0; d < 3; ++d) n *= boxes[r].n[d] > 0 ? boxes[r].n[d] : 0;
+        for (int d = 0; d < 3; ++d) n *= src_box_host(boxes[r]).n[d] > 0 ? src_box_host(boxes[r]).n[d] : 0;
         start[(size_t)r + 1] = start[(size_t)r] + n;
     }
     if (start.back() <= 0) return 0;
-    const size_t bo = (size_t)nbox * sizeof(SrcBoxDev), bs = start.size() * sizeof(long);
+    const size_t bo = (size_t)nbox * sizeof(BOX), bs = start.size() * sizeof(long);
     const size_t need = ((bo + 255) & ~(size_t)255) + bs;
     if (need > arena->bytes) {
         if (arena->p) { (void)hipStreamSynchronize(stream); (void)hipFree(arena->p); arena->p = nullptr; arena->bytes = 0; }
@@ -841,19 +861,40 @@ int launch_sources_apply(int stage, int nbox, const SrcBoxDev* boxes, const doub
     if (hipMemcpyAsync(base, boxes, bo, hipMemcpyHostToDevice, stream) != hipSuccess) return -4;
     if (hipMemcpyAsync(dstart, start.data(), bs, hipMemcpyHostToDevice, stream) != hipSuccess) return -4;
     GravDev G;
-    G.on = grav ? 1 : 0; G.type = grav_type;
+    G.on = (grav || GFAB) ? 1 : 0; G.type = grav_type;
     for (int d = 0; d < 3; ++d) G.g[d] = grav ? grav[d] : 0.0;
     RotDev R;
     std::memset(&R, 0, sizeof(R));
     if (rot) R = make_rotdev(rot, geom, dt);
     const unsigned nb = (unsigned)((start.back() + 255) / 256);
     prof_begin(prof, stage == 0 ? "k_sources_old" : "k_sources_new", stream);
-    if (stage == 0) hipLaunchKernelGGL(k_sources_apply<0>, dim3(nb), dim3(256), 0, stream, (const SrcBoxDev*)base, (const long*)dstart, nbox, G, R,
+    if constexpr (GFAB) {
+        if (stage == 0) hipLaunchKernelGGL((k_sources_apply<0, true, SrcBoxGDev>), dim3(nb), dim3(256), 0, stream, (const SrcBoxGDev*)base, (const long*)dstart, nbox, G, R,
+                                           rot ? 1 : 0, dt, geom->dx[0], geom->dx[1], geom->dx[2], P, ntimes, diff_on);
+        else hipLaunchKernelGGL((k_sources_apply<1, true, SrcBoxGDev>), dim3(nb), dim3(256), 0, stream, (const SrcBoxGDev*)base, (const long*)dstart, nbox, G, R,
+                                rot ? 1 : 0, dt, geom->dx[0], geom->dx[1], geom->dx[2], P, ntimes, diff_on);
+    } else {
+    if (stage == 0) hipLaunchKernelGGL((k_sources_apply<0, false, SrcBoxDev>), dim3(nb), dim3(256), 0, stream, (const SrcBoxDev*)base, (const long*)dstart, nbox, G, R,
                                        rot ? 1 : 0, dt, geom->dx[0], geom->dx[1], geom->dx[2], P, ntimes, diff_on);
-    else hipLaunchKernelGGL(k_sources_apply<1>, dim3(nb), dim3(256), 0, stream, (const SrcBoxDev*)base, (const long*)dstart, nbox, G, R,
+    else hipLaunchKernelGGL((k_sources_apply<1, false, SrcBoxDev>), dim3(nb), dim3(256), 0, stream, (const SrcBoxDev*)base, (const long*)dstart, nbox, G, R,
                             rot ? 1 : 0, dt, geom->dx[0], geom->dx[1], geom->dx[2], P, ntimes, diff_on);
+    }
     prof_end(prof, stream);
     return launch_status();
+}
+
+int launch_sources_apply(int stage, int nbox, const SrcBoxDev* boxes, const double* grav, int grav_type, const castro_amd_rotation* rot,
+                         const castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
+                         hipStream_t stream, Profiler* prof, int diff_on)
+{
+    return launch_sources_apply_t(stage, nbox, boxes, grav, grav_type, rot, geom, P, dt, ntimes, arena, stream, prof, diff_on);
+}
+
+int launch_sources_apply_gfab(int stage, int nbox, const SrcBoxGDev* boxes, int grav_type, const castro_amd_rotation* rot,
+                              const castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
+                              hipStream_t stream, Profiler* prof, int diff_on)
+{
+    return launch_sources_apply_t(stage, nbox, boxes, nullptr, grav_type, rot, geom, P, dt, ntimes, arena, stream, prof, diff_on);
 }
 
 int launch_saxpy(const DFab& D, const DFab& S, const int lo[3], const int hi[3], double a, int ncomp,

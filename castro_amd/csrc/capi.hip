@@ -740,6 +740,58 @@ int castro_amd_sources_mf_ex(castro_amd_ctx* c, int stage, int nboxes, const cas
     return rc == 0 ? CASTRO_AMD_OK : (rc < 0 ? CASTRO_AMD_ERR_HIP : rc);
 }
 
+static bool grav_fab_ok(const castro_amd_fab* g, const int lo[3], const int hi[3], int grav_source_type);
+
+int castro_amd_sources_mf_g(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
+                            const castro_amd_fab* grav_old, const castro_amd_fab* grav_new, int grav_source_type,
+                            const castro_amd_rotation* rot, const castro_amd_geom* geom, const castro_amd_params* params,
+                            double dt, int clean_ntimes, void* stream)
+{
+    if (!c || (stage != 0 && stage != 1) || nboxes < 0 || (nboxes > 0 && !boxes) || !geom || !params || clean_ntimes < 0) return CASTRO_AMD_ERR_ARG;
+    if (nboxes > 0 && (!grav_old || (stage == 1 && !grav_new))) return CASTRO_AMD_ERR_ARG;
+    if (grav_source_type < 1 || grav_source_type > 4) return CASTRO_AMD_ERR_ARG;
+    if (rot && (rot->rot_source_type < 1 || rot->rot_source_type > 4)) return CASTRO_AMD_ERR_ARG;
+    if ((rot || stage == 1) && geom->coord != 0) return CASTRO_AMD_ERR_ARG;
+    if (rot && stage == 1 && !(dt > 0.0)) return CASTRO_AMD_ERR_ARG;
+    if (nboxes == 0) return CASTRO_AMD_OK;
+    std::vector<SrcBoxGDev> tab((size_t)nboxes);
+    for (int i = 0; i < nboxes; ++i) {
+        const castro_amd_source_box& b = boxes[i];
+        if (!b.S_old.p || !b.S_new.p || !b.source.p || b.S_old.ncomp != NUM_STATE || b.S_new.ncomp != NUM_STATE || b.source.ncomp < 7)
+            return CASTRO_AMD_ERR_ARG;
+        if (!fab_contains(&b.S_old, b.lo, b.hi) || !fab_contains(&b.S_new, b.lo, b.hi) || !fab_contains(&b.source, b.lo, b.hi)) return CASTRO_AMD_ERR_ARG;
+        // stage 0 reads the zone itself, stage 1 with grav_source_type 4 its six neighbours as well
+        if (!grav_fab_ok(&grav_old[i], b.lo, b.hi, stage == 1 ? grav_source_type : 1)) return CASTRO_AMD_ERR_ARG;
+        if (stage == 1 && !grav_fab_ok(&grav_new[i], b.lo, b.hi, grav_source_type)) return CASTRO_AMD_ERR_ARG;
+        SrcBoxGDev& TG = tab[(size_t)i];
+        SrcBoxDev& T = TG.box;
+        T.So = to_dfab(&b.S_old); T.Sn = to_dfab(&b.S_new); T.Src = to_dfab(&b.source);
+        T.M0 = T.M1 = T.M2 = to_dfab(nullptr);
+        if (stage == 1) {
+            DFab M[3];
+            for (int d = 0; d < 3; ++d) {
+                int fhi[3] = { b.hi[0], b.hi[1], b.hi[2] };
+                fhi[d] += 1;
+                if (!b.mass_flux[d].p || b.mass_flux[d].ncomp != 1 || !fab_contains(&b.mass_flux[d], b.lo, fhi)) return CASTRO_AMD_ERR_ARG;
+                M[d] = to_dfab(&b.mass_flux[d]);
+            }
+            T.M0 = M[0]; T.M1 = M[1]; T.M2 = M[2];
+        }
+        for (int d = 0; d < 3; ++d) {
+            if (b.source.hi[d] < b.source.lo[d]) return CASTRO_AMD_ERR_ARG;
+            T.lo[d] = b.source.lo[d]; T.n[d] = b.source.hi[d] - b.source.lo[d] + 1;
+            T.vlo[d] = b.lo[d]; T.vhi[d] = b.hi[d];
+        }
+        T.nsc = b.source.ncomp;
+        TG.GO = to_dfab(&grav_old[i]);
+        TG.GN = to_dfab(stage == 1 ? &grav_new[i] : &grav_old[i]);
+    }
+    hipSetDevice(c->device);
+    const int rc = launch_sources_apply_gfab(stage, nboxes, tab.data(), grav_source_type, rot, geom, to_devparams(params), dt, clean_ntimes,
+                                             &c->ops_arena, (hipStream_t)stream, &c->prof, 0);
+    return rc == 0 ? CASTRO_AMD_OK : (rc < 0 ? CASTRO_AMD_ERR_HIP : rc);
+}
+
 int castro_amd_clean_state_reduce_mf(castro_amd_ctx* c, int nboxes, const castro_amd_state_box* boxes, const castro_amd_geom* geom,
                                      const castro_amd_params* params, int ntimes, double* d_out, void* stream)
 {
@@ -845,6 +897,51 @@ int castro_amd_radial_mass_mf(castro_amd_ctx* c, int nboxes, const castro_amd_di
     }
     hipSetDevice(c->device);
     return launch_radial_mass(nboxes, tab.data(), G, &c->mono_ws, d_mass_vol, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_radial_mass_mf_ex(castro_amd_ctx* c, int nboxes, const castro_amd_radial_box* boxes, const castro_amd_geom* geom,
+                                 const castro_amd_monopole_params* params, double* d_mass_vol, void* stream)
+{
+    if (!c || !d_mass_vol || nboxes < 0 || (nboxes > 0 && !boxes)) return CASTRO_AMD_ERR_ARG;
+    MonoGeom G;
+    const int rg = mono_geom(geom, params, G);
+    if (rg != CASTRO_AMD_OK) return rg;
+    // compared byte by byte with the tables already on the device: every byte is set here
+    std::vector<MonoBoxDevEx> tab((size_t)nboxes);
+    if (nboxes > 0) std::memset((void*)tab.data(), 0, (size_t)nboxes * sizeof(MonoBoxDevEx));
+    for (int i = 0; i < nboxes; ++i) {
+        const castro_amd_radial_box& b = boxes[i];
+        if (!b.state_old.p || b.state_old.ncomp != NUM_STATE || !fab_contains(&b.state_old, b.lo, b.hi)) return CASTRO_AMD_ERR_ARG;
+        if (!b.state_new.p || b.state_new.ncomp != NUM_STATE || !fab_contains(&b.state_new, b.lo, b.hi)) return CASTRO_AMD_ERR_ARG;
+        MonoBoxDevEx& T = tab[(size_t)i];
+        const DFab U = to_dfab(&b.state_old), U2 = to_dfab(&b.state_new);
+        T.U.p = U.p; T.U.sy = U.sy; T.U.sz = U.sz; T.U.sn = U.sn;
+        T.U2.p = U2.p; T.U2.sy = U2.sy; T.U2.sz = U2.sz; T.U2.sn = U2.sn;
+        T.mask = b.mask;
+        T.omalpha = b.omalpha; T.alpha = b.alpha;
+        for (int d = 0; d < 3; ++d) { T.U.lo[d] = U.lo[d]; T.U2.lo[d] = U2.lo[d]; T.lo[d] = b.lo[d]; T.n[d] = b.hi[d] - b.lo[d] + 1; }
+    }
+    hipSetDevice(c->device);
+    return launch_radial_mass_ex(nboxes, tab.data(), G, &c->mono_ws, d_mass_vol, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_radial_combine(castro_amd_ctx* c, int level, const double* const* d_mass_vol, const int* n1d, double* d_out, void* stream)
+{
+    if (!c || level < 0 || level >= MONO_MAX_LEVELS || !d_mass_vol || !n1d || !d_out) return CASTRO_AMD_ERR_ARG;
+    MonoCombine A;
+    std::memset(&A, 0, sizeof(A));
+    A.level = level;
+    for (int l = 0; l <= level; ++l) { A.mv[l] = d_mass_vol[l]; A.n1d[l] = n1d[l]; }
+    hipSetDevice(c->device);
+    return launch_radial_combine(A, d_out, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_grav_bc_fill_fab(castro_amd_ctx* c, const castro_amd_fab* grav_fab, const castro_amd_geom* geom, void* stream)
+{
+    if (!c || !grav_fab || !grav_fab->p || grav_fab->ncomp != 3 || !geom) return CASTRO_AMD_ERR_ARG;
+    hipSetDevice(c->device);
+    return launch_grav_bc_fill(to_dfab(grav_fab), grav_fab->lo, grav_fab->hi, geom->domlo, geom->domhi, geom->lo_bc, geom->hi_bc,
+                               (hipStream_t)stream, &c->prof);
 }
 
 int castro_amd_radial_gravity(castro_amd_ctx* c, const castro_amd_monopole_params* params, const castro_amd_geom* geom,

@@ -153,6 +153,11 @@ int launch_new_rot_source(const DFab& UO, const DFab& UN, const DFab& SRC, const
 // one box of castro_amd_sources_mf: states, Source_Type FAB (nsc components), mass fluxes; [lo, lo + n): the zones of the source FAB
 // (thread range), [vlo, vhi]: the valid zones
 struct SrcBoxDev { DFab So, Sn, Src, M0, M1, M2; int lo[3], n[3]; int vlo[3], vhi[3]; int nsc; };
+// one box of castro_amd_sources_mf_g: the same, and its Gravity_Type FABs (3 components, one ghost zone around [vlo, vhi])
+struct SrcBoxGDev { SrcBoxDev box; DFab GO, GN; };
+int launch_sources_apply_gfab(int stage, int nbox, const SrcBoxGDev* boxes, int grav_type, const ::castro_amd_rotation* rot,
+                              const ::castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
+                              hipStream_t stream, Profiler* prof, int diff_on = 0);
 int launch_sources_apply(int stage, int nbox, const SrcBoxDev* boxes, const double* grav, int grav_type, const ::castro_amd_rotation* rot,
                          const ::castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
                          hipStream_t stream, Profiler* prof, int diff_on = 0);
@@ -181,6 +186,12 @@ int launch_integrated_quantities(int nbox, DiagBoxDev* boxes, const DiagGeom& G,
 // byte mask of those zones (nullptr: every zone counts); nb: bricks per direction, set by the launcher.  A table is compared
 // byte by byte with the ones the context has on the device: fill it field by field over zeroed storage
 struct MonoBoxDev { DFab U; const unsigned char* mask; int lo[3], n[3], nb[3]; };
+// one box of a castro_amd_radial_mass_mf_ex launch: MonoBoxDev's fields in MonoBoxDev's order, then the new-time state and the
+// weights of the time interpolation, rho = (U(URHO) * omalpha) + (U2(URHO) * alpha)
+struct MonoBoxDevEx { DFab U; const unsigned char* mask; int lo[3], n[3], nb[3]; DFab U2; double omalpha, alpha; };
+// castro_amd_radial_combine: the mass / volume arrays (2 * n1d[lev] doubles each) of levels 0 .. level
+constexpr int MONO_MAX_LEVELS = 16;
+struct MonoCombine { const double* mv[MONO_MAX_LEVELS]; int n1d[MONO_MAX_LEVELS]; int level; };
 // octant_factor: 8 when the centre sits on problo (Gravity.cpp:1439-1447), else 1; max_radius: max_radius_all_in_domain
 struct MonoGeom { double dx[3], problo[3], center[3]; double octant_factor, max_radius, Gconst; int n1d, drdxfac; };
 // what a context keeps for the binning: one row of 64 bins and its first bin per workgroup, the integer counts per bin, and the
@@ -196,6 +207,12 @@ bool radial_window_ok(const MonoGeom& G);
 void mono_workspace_free(MonoWorkspace* ws);
 int launch_radial_mass(int nbox, MonoBoxDev* boxes, const MonoGeom& G, MonoWorkspace* ws, double* d_out, hipStream_t stream,
                        Profiler* prof);
+int launch_radial_mass_ex(int nbox, MonoBoxDevEx* boxes, const MonoGeom& G, MonoWorkspace* ws, double* d_out, hipStream_t stream,
+                          Profiler* prof);
+int launch_radial_combine(const MonoCombine& A, double* d_out, hipStream_t stream, Profiler* prof);
+// Gravity_Type boundary fill of the zones of [flo, fhi] outside the domain (3 components)
+int launch_grav_bc_fill(const DFab& F, const int flo[3], const int fhi[3], const int domlo[3], const int domhi[3],
+                        const int lo_bc[3], const int hi_bc[3], hipStream_t stream, Profiler* prof);
 int launch_radial_gravity(const MonoGeom& G, const double* d_mass_vol, double* d_radial_grav, hipStream_t stream, Profiler* prof);
 int launch_monopole_grav(const double* d_radial_grav, const MonoGeom& G, const DFab& F, const int lo[3], const int hi[3],
                          hipStream_t stream, Profiler* prof);

@@ -1,5 +1,8 @@
-// monopole_kernels.hip -- gravity.gravity_type = "MonopoleGrav" (Source/gravity/Gravity.cpp), 3-D Cartesian, one level:
-//   k_radial_partial + k_radial_final   Gravity::compute_radial_mass (:1409-1576): the radial histogram of mass and volume
+// monopole_kernels.hip -- gravity.gravity_type = "MonopoleGrav" (Source/gravity/Gravity.cpp), 3-D Cartesian:
+//   k_radial_partial + k_radial_final   Gravity::compute_radial_mass (:1409-1576): the radial histogram of mass and volume;
+//                                       k_radial_partial<true, MonoBoxDevEx>: of a state between two time levels (:2987-3000)
+//   k_radial_combine                    the level combination of make_radial_gravity (:3103-3168)
+//   k_grav_bc_fill                      the physical-boundary fill of Gravity_Type (Castro_setup.cpp:614-622)
 //   k_radial_gravity                    the outward integration of make_radial_gravity (:3170-3274, no GR_GRAV)
 //   k_monopole_grav                     interpolate_monopole_grav (:1300-1406) onto a grown 3-component gravity FAB
 // Everything here is compiled with contraction off in BOTH builds (the Makefile gives this file -ffp-contract=off in the
@@ -60,7 +63,12 @@ __device__ __forceinline__ double mono_readlane(double v, int s)
     return __hiloint2double(hi, lo);
 }
 
-__global__ void __launch_bounds__(MONO_WG) k_radial_partial(const MonoBoxDev* __restrict__ tab, const int* __restrict__ start, int nbox,
+// The body of the binning kernels.  INTERP = false (BOX = MonoBoxDev): the density of a zone is U(URHO).  INTERP = true
+// (BOX = MonoBoxDevEx): the state of a coarser level between its two time levels (Gravity.cpp:2987-3000, S = S_old * omalpha,
+// S_new * alpha, S = S + S_new): rho = (rho_old * omalpha) + (rho_new * alpha), the two products rounded, then the sum -- this
+// file is compiled without contraction --, and the rho == 0 test of :1491 is made on that value.
+template <bool INTERP, class BOX>
+__global__ void __launch_bounds__(MONO_WG) k_radial_partial(const BOX* __restrict__ tab, const int* __restrict__ start, int nbox,
                                                            MonoGeom G, double* __restrict__ rows, int* __restrict__ rbase,
                                                            unsigned long long* __restrict__ count)
 {
@@ -70,7 +78,7 @@ __global__ void __launch_bounds__(MONO_WG) k_radial_partial(const MonoBoxDev* __
         const int mid = (b0 + b1 + 1) >> 1;
         if ((unsigned)start[mid] <= bid) b0 = mid; else b1 = mid - 1;
     }
-    const MonoBoxDev B = tab[b0];
+    const BOX B = tab[b0];
     const int lb = (int)(bid - (unsigned)start[b0]);
     const int bx = lb % B.nb[0], by = (lb / B.nb[0]) % B.nb[1], bz = lb / (B.nb[0] * B.nb[1]);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -99,6 +107,11 @@ __global__ void __launch_bounds__(MONO_WG) k_radial_partial(const MonoBoxDev* __
     double rho = 0.0;
     if (ok) {
         rho = B.U.p[(long)(i - B.U.lo[0]) + B.U.sy * (long)(j - B.U.lo[1]) + B.U.sz * (long)(k - B.U.lo[2]) + B.U.sn * URHO];
+        if constexpr (INTERP) {
+            const double rho_new = B.U2.p[(long)(i - B.U2.lo[0]) + B.U2.sy * (long)(j - B.U2.lo[1]) + B.U2.sz * (long)(k - B.U2.lo[2]) + B.U2.sn * URHO];
+            const double so = rho * B.omalpha, sn = rho_new * B.alpha;
+            rho = so + sn;
+        }
         ok = rho != 0.0;                                  // a zone masked out by a zeroed density (:1491)
     }
 
@@ -275,12 +288,13 @@ __global__ void __launch_bounds__(256) k_monopole_grav(const double* __restrict_
 }
 
 // bricks per direction and the first workgroup of every box; returns the number of workgroups or a negative error
-static long mono_layout(int nbox, MonoBoxDev* boxes, std::vector<int>& start)
+template <class BOX>
+static long mono_layout(int nbox, BOX* boxes, std::vector<int>& start)
 {
     start.assign((size_t)nbox + 1, 0);
     long tot = 0;
     for (int r = 0; r < nbox; ++r) {
-        MonoBoxDev& B = boxes[r];
+        BOX& B = boxes[r];
         B.nb[0] = (B.n[0] + MONO_BX - 1) / MONO_BX; B.nb[1] = (B.n[1] + MONO_BY - 1) / MONO_BY; B.nb[2] = (B.n[2] + MONO_BZ - 1) / MONO_BZ;
         if (B.n[0] > 0 && B.n[1] > 0 && B.n[2] > 0) tot += (long)B.nb[0] * B.nb[1] * B.nb[2];
         else B.nb[0] = B.nb[1] = B.nb[2] = 0;
@@ -300,8 +314,26 @@ void mono_workspace_free(MonoWorkspace* ws)
     ws->tables.clear();
 }
 
-int launch_radial_mass(int nbox, MonoBoxDev* boxes, const MonoGeom& G, MonoWorkspace* ws, double* d_out, hipStream_t stream,
-                       Profiler* prof)
+static void radial_partial_launch(const MonoBoxDev* tab, const int* start, int nbox, const MonoGeom& G, MonoWorkspace* ws, int nb,
+                                  hipStream_t stream, Profiler* prof)
+{
+    prof_begin(prof, "k_radial_partial", stream);
+    hipLaunchKernelGGL((k_radial_partial<false, MonoBoxDev>), dim3((unsigned)nb), dim3(MONO_WG), 0, stream, tab, start, nbox, G, ws->rows, ws->rbase, ws->count);
+    prof_end(prof, stream);
+}
+
+static void radial_partial_launch(const MonoBoxDevEx* tab, const int* start, int nbox, const MonoGeom& G, MonoWorkspace* ws, int nb,
+                                  hipStream_t stream, Profiler* prof)
+{
+    prof_begin(prof, "k_radial_partial_interp", stream);
+    hipLaunchKernelGGL((k_radial_partial<true, MonoBoxDevEx>), dim3((unsigned)nb), dim3(MONO_WG), 0, stream, tab, start, nbox, G, ws->rows, ws->rbase,
+                       ws->count);
+    prof_end(prof, stream);
+}
+
+template <class BOX>
+static int launch_radial_mass_t(int nbox, BOX* boxes, const MonoGeom& G, MonoWorkspace* ws, double* d_out, hipStream_t stream,
+                                Profiler* prof)
 {
     if (G.n1d < 2 || G.drdxfac < 1) return CASTRO_AMD_ERR_ARG;
     if (!radial_window_ok(G)) return CASTRO_AMD_ERR_UNSUPPORTED;
@@ -324,10 +356,10 @@ int launch_radial_mass(int nbox, MonoBoxDev* boxes, const MonoGeom& G, MonoWorks
     // the box table on the device: kept per content (a driver alternates between the tables of its two state buffers), so a
     // table that has been seen before costs no copy -- an asynchronous copy from this call's host vector could not be
     // captured into a graph
-    const MonoBoxDev* dtab = nullptr;
+    const BOX* dtab = nullptr;
     const int* dstart = nullptr;
     if (nb > 0) {
-        const size_t bo = (size_t)nbox * sizeof(MonoBoxDev), bs = start.size() * sizeof(int);
+        const size_t bo = (size_t)nbox * sizeof(BOX), bs = start.size() * sizeof(int);
         const size_t off = (bo + 255) & ~(size_t)255;
         std::vector<char> key(off + bs, 0);
         std::memcpy(key.data(), boxes, bo);
@@ -348,14 +380,12 @@ int launch_radial_mass(int nbox, MonoBoxDev* boxes, const MonoGeom& G, MonoWorks
             ws->tables.back().dev = d;
             hit = &ws->tables.back();
         }
-        dtab = (const MonoBoxDev*)hit->dev;
+        dtab = (const BOX*)hit->dev;
         dstart = (const int*)((const char*)hit->dev + off);
     }
     if (hipMemsetAsync(ws->count, 0, (size_t)G.n1d * sizeof(unsigned long long), stream) != hipSuccess) return CASTRO_AMD_ERR_HIP;
     if (nb > 0) {
-        prof_begin(prof, "k_radial_partial", stream);
-        hipLaunchKernelGGL(k_radial_partial, dim3((unsigned)nb), dim3(MONO_WG), 0, stream, dtab, dstart, nbox, G, ws->rows, ws->rbase, ws->count);
-        prof_end(prof, stream);
+        radial_partial_launch(dtab, dstart, nbox, G, ws, nb, stream, prof);
         if (hipGetLastError() != hipSuccess) return CASTRO_AMD_ERR_HIP;
     }
     const double fac = (double)G.drdxfac;
@@ -364,6 +394,123 @@ int launch_radial_mass(int nbox, MonoBoxDev* boxes, const MonoGeom& G, MonoWorks
     prof_begin(prof, "k_radial_final", stream);
     hipLaunchKernelGGL(k_radial_final, dim3((unsigned)((G.n1d + MONO_WIN - 1) / MONO_WIN)), dim3(MONO_WIN * MONO_FINAL_GROUPS), 0, stream,
                        (const double*)ws->rows, (const int*)ws->rbase, nb, (const unsigned long long*)ws->count, G.n1d, vol_frac, d_out);
+    prof_end(prof, stream);
+    return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
+}
+
+int launch_radial_mass(int nbox, MonoBoxDev* boxes, const MonoGeom& G, MonoWorkspace* ws, double* d_out, hipStream_t stream,
+                       Profiler* prof)
+{
+    return launch_radial_mass_t(nbox, boxes, G, ws, d_out, stream, prof);
+}
+
+int launch_radial_mass_ex(int nbox, MonoBoxDevEx* boxes, const MonoGeom& G, MonoWorkspace* ws, double* d_out, hipStream_t stream,
+                          Profiler* prof)
+{
+    return launch_radial_mass_t(nbox, boxes, G, ws, d_out, stream, prof);
+}
+
+// The level combination of make_radial_gravity (Gravity.cpp:3103-3168), one thread per bin i of `level`: the level's own entry,
+// then for lev = level - 1 down to 0, ratio = 2^(level - lev), the bins i < ratio * (n1d / ratio) add
+// (1. / double(ratio)) * array[lev][i / ratio] -- the reference's sequence of additions to radial_mass_summed[i], and the same
+// for the volumes.  out[0 .. n1d): mass, out[n1d .. 2 n1d): volume
+__global__ void __launch_bounds__(256) k_radial_combine(MonoCombine A, double* __restrict__ out)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    const int n1d = A.n1d[A.level];
+    if (i >= n1d) return;
+    double m = A.mv[A.level][i], v = A.mv[A.level][n1d + i];
+    int ratio = 1;
+    for (int lev = A.level - 1; lev >= 0; --lev) {
+        ratio *= 2;
+        if (i < ratio * (n1d / ratio)) {
+            const double w = 1. / (double)ratio;
+            const int ci = i / ratio;
+            const double tm = w * A.mv[lev][ci], tv = w * A.mv[lev][A.n1d[lev] + ci];
+            m += tm;
+            v += tv;
+        }
+    }
+    out[i] = m;
+    out[n1d + i] = v;
+}
+
+int launch_radial_combine(const MonoCombine& A, double* d_out, hipStream_t stream, Profiler* prof)
+{
+    if (A.level < 0 || A.level >= MONO_MAX_LEVELS) return CASTRO_AMD_ERR_ARG;
+    int ratio = 1;
+    for (int lev = A.level; lev >= 0; --lev) {
+        if (!A.mv[lev] || A.n1d[lev] < 2) return CASTRO_AMD_ERR_ARG;
+        // the coarse index of the last bin that receives a share must exist in the coarser array
+        if (lev < A.level && A.n1d[A.level] / ratio > A.n1d[lev]) return CASTRO_AMD_ERR_UNSUPPORTED;
+        ratio *= 2;
+    }
+    const int n1d = A.n1d[A.level];
+    prof_begin(prof, "k_radial_combine", stream);
+    hipLaunchKernelGGL(k_radial_combine, dim3((unsigned)((n1d + 255) / 256)), dim3(256), 0, stream, A, d_out);
+    prof_end(prof, stream);
+    return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
+}
+
+// The physical-boundary fill of Gravity_Type (Castro_setup.cpp:614-622): components 0 / 1 / 2 carry the x / y / z velocity BC
+// records with inflow replaced -- first-order extrapolation at inflow and outflow faces, reflection at symmetry faces and walls
+// with the component normal to a mirrored face negated.  One thread per zone of [flo, flo + n); a zone inside the domain in
+// every non-periodic direction is left alone.  The x, y, z sweeps of the boundary functions compose to an independent index map
+// per direction (k_bc_fill of aux_kernels.hip), so every zone reads a zone inside the domain: no zone written here is read here.
+struct MonoBcMap { int lo[3], hi[3]; int kind_lo[3], kind_hi[3]; };    // kind 0: leave, 1: extrapolate, 2: mirror
+
+__global__ void __launch_bounds__(256) k_grav_bc_fill(DFab F, int lo0, int lo1, int lo2, int n0, int n1, int n2, MonoBcMap M)
+{
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= (long)n0 * n1 * n2) return;
+    int ijk[3], s[3];
+    bool flip[3], outside = false;
+    ijk[0] = lo0 + (int)(tid % n0);
+    const long rr = tid / n0;
+    ijk[1] = lo1 + (int)(rr % n1);
+    ijk[2] = lo2 + (int)(rr / n1);
+    for (int d = 0; d < 3; ++d) {
+        s[d] = ijk[d];
+        flip[d] = false;
+        if (ijk[d] < M.lo[d] && M.kind_lo[d] != 0) {
+            outside = true;
+            if (M.kind_lo[d] == 1) s[d] = M.lo[d];
+            else { s[d] = 2 * M.lo[d] - ijk[d] - 1; flip[d] = true; }
+        } else if (ijk[d] > M.hi[d] && M.kind_hi[d] != 0) {
+            outside = true;
+            if (M.kind_hi[d] == 1) s[d] = M.hi[d];
+            else { s[d] = 2 * M.hi[d] - ijk[d] + 1; flip[d] = true; }
+        }
+    }
+    if (!outside) return;
+    const long cd = (long)(ijk[0] - F.lo[0]) + F.sy * (long)(ijk[1] - F.lo[1]) + F.sz * (long)(ijk[2] - F.lo[2]);
+    const long cs = (long)(s[0] - F.lo[0]) + F.sy * (long)(s[1] - F.lo[1]) + F.sz * (long)(s[2] - F.lo[2]);
+    for (int n = 0; n < 3; ++n) {
+        const double v = F.p[cs + F.sn * n];
+        F.p[cd + F.sn * n] = flip[n] ? -v : v;
+    }
+}
+
+int launch_grav_bc_fill(const DFab& F, const int flo[3], const int fhi[3], const int domlo[3], const int domhi[3],
+                        const int lo_bc[3], const int hi_bc[3], hipStream_t stream, Profiler* prof)
+{
+    MonoBcMap M;
+    long n = 1;
+    for (int d = 0; d < 3; ++d) {
+        M.lo[d] = domlo[d]; M.hi[d] = domhi[d];
+        M.kind_lo[d] = lo_bc[d] == 0 ? 0 : (lo_bc[d] >= 3 ? 2 : 1);      // Symmetry, SlipWall, NoSlipWall mirror
+        M.kind_hi[d] = hi_bc[d] == 0 ? 0 : (hi_bc[d] >= 3 ? 2 : 1);
+        if (fhi[d] < flo[d]) return 0;
+        n *= fhi[d] - flo[d] + 1;
+        // every zone outside the domain must find its image inside the FAB and inside the domain
+        const int elo = M.kind_lo[d] != 0 && flo[d] < domlo[d] ? domlo[d] - flo[d] : 0;
+        const int ehi = M.kind_hi[d] != 0 && fhi[d] > domhi[d] ? fhi[d] - domhi[d] : 0;
+        if (elo > 0 && (fhi[d] < domlo[d] || (M.kind_lo[d] == 2 && domlo[d] + elo - 1 > (fhi[d] < domhi[d] ? fhi[d] : domhi[d])))) return CASTRO_AMD_ERR_ARG;
+        if (ehi > 0 && (flo[d] > domhi[d] || (M.kind_hi[d] == 2 && domhi[d] - ehi + 1 < (flo[d] > domlo[d] ? flo[d] : domlo[d])))) return CASTRO_AMD_ERR_ARG;
+    }
+    prof_begin(prof, "k_grav_bc_fill", stream);
+    hipLaunchKernelGGL(k_grav_bc_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, F, flo[0], flo[1], flo[2],
+                       fhi[0] - flo[0] + 1, fhi[1] - flo[1] + 1, fhi[2] - flo[2] + 1, M);
     prof_end(prof, stream);
     return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
 }

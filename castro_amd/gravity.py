@@ -1,0 +1,172 @@
+"""gravity.gravity_type = "MonopoleGrav" on the levels of CastroAmr: the part of the reference's Gravity object that spans the levels
+(Source/gravity/Gravity.cpp).  castro_amd.CastroAmr(do_grav=True, gravity=MonopoleGravity(drdxfac=..., Gconst=...)).
+
+  make_radial_gravity(level, time)   Gravity::make_radial_gravity (:2962-3274): every level lev <= level binned at `time` -- old,
+                                     new or time-interpolated data (the eps tests of :2966-3001), the zones under level lev + 1
+                                     masked for lev < level --, one sum over the ranks per level array, the level combination
+                                     of :3103-3168 and the outward integration, all on the device
+  get_old_grav_vector(level) /       Gravity::get_old_grav_vector / get_new_grav_vector (:832-973): make_radial_gravity at the
+  get_new_grav_vector(level)         level's old / new time, interpolate_monopole_grav onto grav_old / grav_new of every box of
+                                     the level, then the FillPatch of Gravity_Type (_Level.fill_grav: coarse data interpolated in
+                                     time and space, siblings, physical boundaries)
+
+Levels finer than `level` do not enter.  Not provided: GR_GRAV, the point mass, gravity.max_solve_level, domains with a periodic
+direction (the Gravity_Type FillPatch across a periodic boundary is not built), thermal diffusion on AMR levels.
+"""
+from . import _lib as L
+
+
+def time_branch(time, t_old, t_new):
+    """Which data of a level make_radial_gravity bins at `time` (Gravity.cpp:2966-3004): ("new", 1.0) | ("old", 0.0) |
+    ("interp", alpha) with alpha = (time - t_old) / (t_new - t_old); outside [t_old, t_new] the reference aborts."""
+    eps = (t_new - t_old) * 1.e-6
+    if eps == 0.0:
+        return "new", 1.0
+    if abs(time - t_old) < eps:
+        return "old", 0.0
+    if abs(time - t_new) < eps:
+        return "new", 1.0
+    if time > t_old and time < t_new:
+        return "interp", (time - t_old) / (t_new - t_old)
+    raise RuntimeError("Problem in Gravity::make_radial_gravity: time %r is outside the level's old / new times %r / %r"
+                       % (time, t_old, t_new))
+
+
+class MonopoleGravity:
+    def __init__(self, drdxfac=1, Gconst=L.GCONST, center=None):
+        """drdxfac: gravity.drdxfac; Gconst: the reference takes C::Gconst from its Microphysics constants (the default is the cgs
+        value of that release); center: problem::center, default the middle of the domain."""
+        self.drdxfac, self.Gconst = int(drdxfac), float(Gconst)
+        self.center = None if center is None else tuple(float(x) for x in center)
+        if self.drdxfac < 1:
+            raise ValueError("gravity.drdxfac must be at least 1, not %d" % self.drdxfac)
+        self.amr = None
+        self._lev = {}
+
+    # ---- the hierarchy this object belongs to ---------------------------------------------------------------
+    def bind(self, amr, lo_bc, hi_bc):
+        if any(lo_bc[d] == 0 or hi_bc[d] == 0 for d in range(3)):
+            raise (ValueError if all(lo_bc[d] == 0 and hi_bc[d] == 0 for d in range(3)) else NotImplementedError)(
+                "monopole gravity needs a non-periodic domain: a fully periodic one has no isolated mass to take the radial "
+                "profile of, and the Gravity_Type FillPatch across a periodic boundary of a partly periodic one is not built")
+        if self.amr is not None and self.amr is not amr:
+            raise ValueError("a MonopoleGravity object belongs to one CastroAmr")
+        self.amr = amr
+
+    def check_level(self, l, geom):
+        """the checks of the single-level driver with this level's dx"""
+        dmax = L.monopole_max_drdxfac([geom.dx[d] for d in range(3)])
+        if self.drdxfac > dmax:
+            raise ValueError("gravity.drdxfac = %d is above the %d the geometry of level %d allows: the binning kernel holds the "
+                             "sub-zones of a brick of 8 x 8 x 4 zones in a window of 64 bins (drdxfac <= 5 for cubic zones)"
+                             % (self.drdxfac, dmax, l))
+        if l >= L.MONOPOLE_MAX_LEVELS:
+            raise ValueError("monopole gravity: at most %d levels" % L.MONOPOLE_MAX_LEVELS)
+
+    def reset(self, from_level=0):
+        """regrid / _push_level / _drop_fine: the box tables and masks of levels >= from_level - 1 hold pointers into boxes that
+        are gone, or describe a coverage that has changed"""
+        for l in list(self._lev):
+            if l >= from_level:
+                del self._lev[l]
+            else:
+                self._lev[l]["tables"] = {}
+
+    def n1d(self, l):
+        """bins of level l: monopole_n1d of the level's domain (Gravity.cpp:315, Castro.cpp:3887-3913)"""
+        return L.monopole_n1d(tuple((2 ** l) * x for x in self.amr.n_cell), self.drdxfac)
+
+    def problem_center(self):
+        if self.center is not None:
+            return list(self.center)
+        g = self.amr.lev[0].geom
+        return [0.5 * (g.problo[d] + g.probhi[d]) for d in range(3)]
+
+    def params(self, l):
+        """castro_amd_monopole_params of level l"""
+        lev = self.amr.lev[l]
+        return L.make_monopole(tuple((2 ** l) * x for x in self.amr.n_cell), lev.geom, self.problem_center(), self.drdxfac,
+                               self.Gconst, n1d=self.n1d(l))
+
+    def _arrays(self, l):
+        """radial_mass / radial_vol of level l (one array of 2 n1d), the combined arrays, radial_grav_old / radial_grav_new"""
+        ent = self._lev.get(l)
+        if ent is None:
+            h, n = self.amr.lev[l].hydro, self.n1d(l)
+            vec = lambda m: h.alloc(1, (0, 0, 0), (m - 1, 0, 0)).reshape(-1)
+            ent = self._lev[l] = dict(mv=vec(2 * n), summed=vec(2 * n), old=vec(n), new=vec(n), tables={})
+        return ent
+
+    # ---- Gravity::make_radial_gravity ---------------------------------------------------------------------------
+    def _bin_level(self, lev_i, level, time, which):
+        """radial_mass[lev_i], radial_vol[lev_i] at `time`, summed over the ranks"""
+        amr = self.amr
+        lev = amr.lev[lev_i]
+        h = lev.hydro
+        ent = self._arrays(lev_i)
+        if lev_i == level:
+            branch, alpha = ("old", 0.0) if which == "old" else ("new", 1.0)       # the level's own advance: its own old / new data
+        else:
+            branch, alpha = time_branch(time, lev.t_old, lev.t_new)
+        masks = amr._diag_level_masks(lev_i) if lev_i < level else None
+        mkey = tuple(m.data_ptr() for m in (masks or {}).values())
+        mask_of = lambda b: masks[b.bx] if masks is not None else None
+        tables = ent["tables"]
+        if len(tables) > 32:
+            tables.clear()
+        geom, mono = lev.geom, self.params(lev_i)
+        if branch == "interp":
+            if not hasattr(h, "radial_mass_mf_ex"):
+                raise RuntimeError("castro_amd: this backend has no radial_mass_mf_ex; there is no host fallback")
+            key = ("ex", mkey) + tuple(t.data_ptr() for b in lev.mine for t in (b.S_old_b, b.S_new_b))
+            if key not in tables:
+                tables[key] = h.make_radial_boxes([(b.lo, b.hi, (b.S_old_b, b.gbox), (b.S_new_b, b.gbox), mask_of(b)) for b in lev.mine])
+            h.radial_mass_mf_ex(tables[key], 1.0 - alpha, alpha, geom, mono, ent["mv"])
+        else:
+            name = "S_old_b" if branch == "old" else "S_new_b"
+            key = (name, mkey) + tuple(getattr(b, name).data_ptr() for b in lev.mine)
+            if key not in tables:
+                tables[key] = h.make_diag_boxes([(b.lo, b.hi, (getattr(b, name), b.gbox), mask_of(b)) for b in lev.mine])
+            h.radial_mass_mf(tables[key], geom, mono, ent["mv"])
+        amr.comm.allreduce_sum(ent["mv"])               # ParallelDescriptor::ReduceRealSum of the level's arrays
+        return branch
+
+    def make_radial_gravity(self, level, time, which="new"):
+        """radial_grav_old[level] (which = "old") or radial_grav_new[level] at `time`; returns the data each level was binned
+        from ("old" | "new" | "interp"), coarsest first"""
+        branches = [self._bin_level(l, level, time, which) for l in range(level + 1)]
+        h = self.amr.lev[level].hydro
+        ent = self._arrays(level)
+        if level == 0:
+            summed = ent["mv"]
+        else:
+            if not hasattr(h, "radial_combine"):
+                raise RuntimeError("castro_amd: this backend has no radial_combine; there is no host fallback")
+            summed = ent["summed"]
+            h.radial_combine(level, [self._arrays(l)["mv"] for l in range(level + 1)], [self.n1d(l) for l in range(level + 1)], summed)
+        ent["last_summed"] = summed
+        h.radial_gravity(self.params(level), self.amr.lev[level].geom, summed, ent[which])
+        return branches
+
+    # ---- Gravity::get_old_grav_vector / get_new_grav_vector -----------------------------------------------------
+    def _grav_vector(self, level, which, time, a):
+        lev = self.amr.lev[level]
+        self.make_radial_gravity(level, time, which)
+        rg, mono = self._arrays(level)[which], self.params(level)
+        name = "grav_" + which
+        for b in lev.mine:
+            lev.hydro.monopole_grav(rg, mono, lev.geom, getattr(b, name), b.gravbox)
+        lev.fill_grav(name, a)
+
+    def get_old_grav_vector(self, level, time=None, a=0.0):
+        """grav_old of every box of `level` at the level's old time; a: where that time lies in the parent's [old, new]"""
+        self._grav_vector(level, "old", self.amr.lev[level].t_old if time is None else time, a)
+
+    def get_new_grav_vector(self, level, time=None, a=1.0):
+        self._grav_vector(level, "new", self.amr.lev[level].t_new if time is None else time, a)
+
+    def radial_gravity(self, level):
+        """(radial_mass_summed, radial_vol_summed, radial_grav_old, radial_grav_new) of `level` after its last construction, numpy"""
+        ent, n = self._arrays(level), self.n1d(level)
+        mv = ent.get("last_summed", ent["mv"]).cpu().numpy()
+        return mv[:n].copy(), mv[n:].copy(), ent["old"].cpu().numpy().copy(), ent["new"].cpu().numpy().copy()

@@ -212,6 +212,64 @@ class HipHydro:
         L.check(self.lib.castro_amd_monopole_grav_fab(self.h, C.c_void_p(radial_grav.data_ptr()), C.byref(mono), C.byref(geom),
                                                       C.byref(L.fab_of(grav, *grav_box)), _stream_ptr(stream)), "monopole_grav_fab")
 
+    @staticmethod
+    def make_radial_boxes(specs):
+        """ctypes array of castro_amd_radial_box from (lo, hi, (S_old, box), (S_new, box), mask) -- mask as in make_diag_boxes; the
+        weights are set per call (radial_mass_mf_ex)."""
+        arr = (L.RadialBox * max(len(specs), 1))()
+        keep = []
+        for rb, (lo, hi, so, sn, mask) in zip(arr, specs):
+            for d in range(3):
+                rb.lo[d], rb.hi[d] = lo[d], hi[d]
+            rb.state_old, rb.state_new = L.fab_of(so[0], *so[1]), L.fab_of(sn[0], *sn[1])
+            if mask is not None:
+                shape = (hi[2] - lo[2] + 1, hi[1] - lo[1] + 1, hi[0] - lo[0] + 1)
+                if mask.dtype != torch.uint8 or tuple(mask.shape) != shape or not mask.is_contiguous():
+                    raise AssertionError("a mask is a contiguous uint8 tensor shaped (nz, ny, nx) of its box: %s %s for %s"
+                                         % (mask.dtype, tuple(mask.shape), shape))
+                rb.mask = mask.data_ptr()
+                keep.append(mask)
+        arr._masks = keep
+        return arr, len(specs)
+
+    def radial_mass_mf_ex(self, boxes, omalpha, alpha, geom, mono, out, stream=None):
+        """castro_amd_radial_mass_mf_ex: radial_mass_mf over rho = (rho_old * omalpha) + (rho_new * alpha) of `boxes`
+        (make_radial_boxes): a coarser level between its two time levels (Gravity.cpp:2987-3000)"""
+        arr, n = boxes
+        for i in range(n):
+            arr[i].omalpha, arr[i].alpha = float(omalpha), float(alpha)
+        L.check(self.lib.castro_amd_radial_mass_mf_ex(self.h, n, arr, C.byref(geom), C.byref(mono), C.c_void_p(out.data_ptr()),
+                                                      _stream_ptr(stream)), "radial_mass_mf_ex")
+
+    def radial_combine(self, level, mass_vols, n1ds, out, stream=None):
+        """castro_amd_radial_combine: radial_mass_summed / radial_vol_summed of `level` from the arrays of levels 0 .. level
+        (device tensors of 2 * n1ds[lev] doubles, summed over the ranks) into `out` (2 * n1ds[level])"""
+        ptrs = (C.c_void_p * (level + 1))(*[t.data_ptr() for t in mass_vols[:level + 1]])
+        ns = (C.c_int * (level + 1))(*[int(x) for x in n1ds[:level + 1]])
+        L.check(self.lib.castro_amd_radial_combine(self.h, int(level), ptrs, ns, C.c_void_p(out.data_ptr()), _stream_ptr(stream)),
+                "radial_combine")
+
+    def grav_bc_fill(self, grav, grav_box, geom, stream=None):
+        """castro_amd_grav_bc_fill_fab: the Gravity_Type boundary fill of the zones of `grav` (3 components) outside the domain"""
+        L.check(self.lib.castro_amd_grav_bc_fill_fab(self.h, C.byref(L.fab_of(grav, *grav_box)), C.byref(geom), _stream_ptr(stream)),
+                "grav_bc_fill_fab")
+
+    @staticmethod
+    def make_grav_fabs(specs):
+        """ctypes array of castro_amd_fab from (grav, box): the grav_old or grav_new FABs of the boxes of a sources_mf_g call"""
+        arr = (L.Fab * max(len(specs), 1))()
+        for i, (g, box) in enumerate(specs):
+            arr[i] = L.fab_of(g, *box)
+        return arr
+
+    def sources_mf_g(self, stage, boxes, grav_old, grav_new, grav_source_type, rot, geom, params, dt, ntimes=1, stream=None):
+        """castro_amd_sources_mf_g: sources_mf with the gravity of box i read from grav_old[i] / grav_new[i] (make_grav_fabs)"""
+        arr, n = boxes
+        if n:
+            L.check(self.lib.castro_amd_sources_mf_g(self.h, int(stage), n, arr, grav_old, grav_new, int(grav_source_type),
+                                                     C.byref(rot) if rot is not None else None, C.byref(geom), C.byref(params),
+                                                     float(dt), int(ntimes), _stream_ptr(stream)), "sources_mf_g")
+
     def old_gravity_source_gfab(self, state, box, source, src_box, lo, hi, grav_old, grav_box, grav_source_type, dt, stream=None):
         L.check(self.lib.castro_amd_old_gravity_source_gfab(self.h, C.byref(L.fab_of(state, *box)), C.byref(L.fab_of(source, *src_box)),
                                                             L.i3(lo), L.i3(hi), C.byref(L.fab_of(grav_old, *grav_box)),

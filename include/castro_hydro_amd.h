@@ -562,6 +562,51 @@ int castro_amd_new_gravity_source_gfab(castro_amd_ctx *ctx, const castro_amd_fab
                                        const castro_amd_fab *grav_new, int grav_source_type,
                                        double dt, const castro_amd_geom *geom, void *stream);
 
+/* Monopole gravity on the levels of an AMR hierarchy: Gravity::make_radial_gravity(level, time) (Gravity.cpp:2962-3168) bins
+ * every level lev <= level at `time`, the zones under level lev + 1 masked for lev < level, and combines the arrays.
+ *
+ * castro_amd_radial_mass_mf_ex: castro_amd_radial_mass_mf over a state between two time levels, the branch
+ * time > t_old && time < t_new of :2987-3000 (S = S_old * omalpha; S_new * alpha; S = S + S_new with alpha = (time - t_old) /
+ * (t_new - t_old), omalpha = 1.0 - alpha): per box, rho = (state_old(URHO) * omalpha) + (state_new(URHO) * alpha), rounded in
+ * that order with nothing fused, and the rho == 0 test of :1491 on that value.  Bricks, windows, summation orders, integer
+ * volume counts, the drdxfac limit and its error code are castro_amd_radial_mass_mf's; a zone under a zero mask byte is
+ * skipped (the reference multiplies the state by build_fine_mask and then skips on rho == 0: the same zones).  Which of old,
+ * new or interpolated applies (the eps = (t_new - t_old) * 1e-6 tests of :2966-2986 and the abort of :3001) is the caller's
+ * decision; for one time level it calls castro_amd_radial_mass_mf. */
+typedef struct castro_amd_radial_box {
+    int lo[3], hi[3];
+    castro_amd_fab state_old, state_new;
+    const unsigned char *mask;
+    double omalpha, alpha;
+} castro_amd_radial_box;
+int castro_amd_radial_mass_mf_ex(castro_amd_ctx *ctx, int nboxes, const castro_amd_radial_box *boxes, const castro_amd_geom *geom,
+                                 const castro_amd_monopole_params *params, double *d_mass_vol, void *stream);
+/* The level combination of :3103-3168.  d_mass_vol[lev], lev = 0 .. level: the 2 * n1d[lev] device doubles of
+ * castro_amd_radial_mass_mf(_ex) of level lev, already summed over the ranks.  d_out (2 * n1d[level] device doubles,
+ * overwritten): radial_mass_summed, then radial_vol_summed of `level`: the level's own array, then for lev = level - 1 down
+ * to 0, ratio = the product of the refinement ratios between lev and level (2 each), every bin i < n1d[level] / ratio of lev
+ * adds (1. / double(ratio)) * array[lev][i] to the fine bins ratio * i .. ratio * i + ratio - 1.  One thread per fine bin
+ * makes the reference's additions to that bin in the reference's order.  n1d differs per level (monopole_n1d of the level's
+ * domain) and is no exact multiple of the coarser one: CASTRO_AMD_ERR_UNSUPPORTED when n1d[level] / ratio exceeds n1d[lev];
+ * level < 16.  d_out feeds castro_amd_radial_gravity (geometry and n1d of `level`) and castro_amd_monopole_grav_fab. */
+int castro_amd_radial_combine(castro_amd_ctx *ctx, int level, const double *const *d_mass_vol, const int *n1d, double *d_out,
+                              void *stream);
+/* The physical-boundary part of AmrLevel::FillPatch(Gravity_Type) (Gravity.cpp:894-900, 967-973): the zones of grav_fab (3
+ * components) outside the domain in a non-periodic direction.  Components 0 / 1 / 2 carry the x / y / z velocity BC records
+ * with inflow replaced (Castro_setup.cpp:614-622): first-order extrapolation at inflow and outflow faces, reflection at
+ * symmetry faces and walls with the component normal to the face negated.  The image of a mirrored zone must lie inside
+ * grav_fab (CASTRO_AMD_ERR_ARG otherwise).  The coarse-fine part of that FillPatch is CASTRO_AMD_OP_INTERP /
+ * castro_amd_cc_interp_fab with 3 components. */
+int castro_amd_grav_bc_fill_fab(castro_amd_ctx *ctx, const castro_amd_fab *grav_fab, const castro_amd_geom *geom, void *stream);
+/* castro_amd_sources_mf with the gravity of every box read from its Gravity_Type FABs: grav_old[i] / grav_new[i] (3
+ * components, one ghost zone around [lo, hi] of box i for grav_source_type = 4; grav_new is read by stage 1 only and may be
+ * NULL for stage 0) take the place of the one vector -- the zone functions of castro_amd_old/new_gravity_source_gfab inside
+ * the one-pass kernel.  Everything else as castro_amd_sources_mf. */
+int castro_amd_sources_mf_g(castro_amd_ctx *ctx, int stage, int nboxes, const castro_amd_source_box *boxes,
+                            const castro_amd_fab *grav_old, const castro_amd_fab *grav_new, int grav_source_type,
+                            const castro_amd_rotation *rot /* or NULL */, const castro_amd_geom *geom,
+                            const castro_amd_params *params, double dt, int clean_ntimes, void *stream);
+
 /* Two-level AMR building blocks, refinement ratio 2 (first slice).  The reference calls AMReX for
  * all of these [3P, not in the reference tree]; the arithmetic is restated from the published descriptions and is
  * NOT pinned against an AMReX build:
