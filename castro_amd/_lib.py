@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = (
     "castro_amd_radial_mass_mf", "castro_amd_radial_gravity", "castro_amd_monopole_grav_fab",
     "castro_amd_old_gravity_source_gfab", "castro_amd_new_gravity_source_gfab",
     "castro_amd_radial_mass_mf_ex", "castro_amd_radial_combine", "castro_amd_grav_bc_fill_fab", "castro_amd_sources_mf_g",
+    "castro_amd_new_sponge_source_fab", "castro_amd_sources_mf_opts",
 )
 
 
@@ -200,6 +201,35 @@ def make_rotation(rotational_period, rot_axis=3, center=(0.5, 0.5, 0.5), include
     return R
 
 
+class Sponge(C.Structure):
+    """castro_amd_sponge"""
+    _fields_ = [("lower_radius", C.c_double), ("upper_radius", C.c_double), ("lower_density", C.c_double),
+                ("upper_density", C.c_double), ("lower_pressure", C.c_double), ("upper_pressure", C.c_double),
+                ("lower_factor", C.c_double), ("upper_factor", C.c_double), ("target_velocity", C.c_double * 3),
+                ("timescale", C.c_double), ("center", C.c_double * 3), ("implicit", C.c_int)]
+
+
+def make_sponge(timescale, lower_radius=-1.0, upper_radius=-1.0, lower_density=-1.0, upper_density=-1.0, lower_pressure=-1.0,
+                upper_pressure=-1.0, lower_factor=0.0, upper_factor=1.0, target_velocity=(0.0, 0.0, 0.0), center=None, implicit=1):
+    """castro.do_sponge = 1 with the castro.sponge_* parameters and their defaults (Source/driver/_cpp_parameters:177-181,
+    483-520) and the checks of Castro.cpp:475-488.  center: problem::center; None leaves it to the driver (its `center`
+    attribute, else the middle of the domain) -- a direct caller of HipHydro.new_sponge_source gives it."""
+    if not float(timescale) > 0.0:
+        raise ValueError("If using the sponge, the sponge_timescale must be positive.")
+    if max(float(upper_radius), float(upper_density), float(upper_pressure)) < 0.0:
+        raise ValueError("If using the sponge, at least one of the upper radius, density, or pressure must be non-negative.")
+    if max(float(lower_radius), float(lower_density), float(lower_pressure)) < 0.0:
+        raise ValueError("If using the sponge, at least one of the lower radius, density, or pressure must be non-negative.")
+    S = Sponge(float(lower_radius), float(upper_radius), float(lower_density), float(upper_density), float(lower_pressure),
+               float(upper_pressure), float(lower_factor), float(upper_factor))
+    for d in range(3):
+        S.target_velocity[d] = float(target_velocity[d])
+        S.center[d] = float(center[d]) if center is not None else float("nan")
+    S.timescale, S.implicit = float(timescale), int(implicit)
+    S.center_given = center is not None
+    return S
+
+
 class Diffusion(C.Structure):
     """castro_amd_diffusion"""
     _fields_ = [("const_conductivity", C.c_double), ("diffuse_cutoff_density", C.c_double),
@@ -217,6 +247,12 @@ def make_diffusion(const_conductivity, diffuse_cutoff_density=-1.e200, diffuse_c
 class DiffusionBox(C.Structure):
     """castro_amd_diffusion_box: one box of a castro_amd_temp_diffusion_mf call"""
     _fields_ = [("lo", C.c_int * 3), ("hi", C.c_int * 3), ("state", Fab), ("source", Fab)]
+
+
+class SourceOpts(C.Structure):
+    """castro_amd_source_opts"""
+    _fields_ = [("grav", C.POINTER(C.c_double)), ("grav_old", C.POINTER(Fab)), ("grav_new", C.POINTER(Fab)),
+                ("grav_source_type", C.c_int), ("rot", C.POINTER(Rotation)), ("diff", C.POINTER(Diffusion)), ("sponge", C.POINTER(Sponge))]
 
 
 # CODATA-2010 cgs constants of the gamma-law restatement (castro_amd/csrc/hydro_device.h)
@@ -349,6 +385,11 @@ def load(numerics=None):
         L.castro_amd_grav_bc_fill_fab.argtypes = [C.c_void_p, PF, C.POINTER(Geom), C.c_void_p]
         L.castro_amd_sources_mf_g.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(SourceBox), PF, PF, C.c_int,
                                               C.POINTER(Rotation), C.POINTER(Geom), C.POINTER(Params), C.c_double, C.c_int, C.c_void_p]
+    if hasattr(L, "castro_amd_sources_mf_opts"):            # absent from A/B builds of revisions before the sponge
+        L.castro_amd_new_sponge_source_fab.argtypes = [C.c_void_p, PF, PF, I3, I3, C.POINTER(Sponge), C.POINTER(Geom),
+                                                       C.POINTER(Params), C.c_double, C.c_void_p]
+        L.castro_amd_sources_mf_opts.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(SourceBox), C.POINTER(SourceOpts),
+                                                 C.POINTER(Geom), C.POINTER(Params), C.c_double, C.c_int, C.c_void_p]
     L.castro_amd_step_control.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_double, C.c_double,
                                           C.c_double, C.c_int, C.c_void_p]
     L.castro_amd_clean_state_fab.argtypes = [C.c_void_p, PF, I3, I3, C.POINTER(Params), C.c_int, C.c_void_p]

@@ -539,14 +539,14 @@ class _Level:
         None: box by box."""
         if not (self._level_calls() and self.mine and hasattr(self.hydro, "sources_mf")):
             return None
-        if os.environ.get("CASTRO_AMD_SOURCES_ONE_PASS", "1") == "0" and self.amr.gravity is not None:
-            return None                         # the separate-call form of the gravity sources (A/B and tests)
+        if os.environ.get("CASTRO_AMD_SOURCES_ONE_PASS", "1") == "0" and (self.amr.gravity is not None or self.mine[0].sponge is not None):
+            return None                         # the separate-call form of the gravity / sponge sources (A/B and tests)
         b0 = self.mine[0]
         if b0.monopole and not hasattr(self.hydro, "sources_mf_g"):
             return None
         for b in self.mine:
             if (b.do_grav != b0.do_grav or b.monopole != b0.monopole or (b.do_grav and (tuple(b.grav) != tuple(b0.grav) or b.grav_source_type != b0.grav_source_type))
-                    or b.rotation is not b0.rotation):
+                    or b.rotation is not b0.rotation or b.sponge is not b0.sponge):
                 return None
         return b0
 
@@ -733,8 +733,11 @@ class CastroAmr:
                  params=None, make_hydro=None, make_params=None, refine=None, regrid_int=2, n_error_buf=1,
                  blocking_factor=8, patches=None, max_level=1, cluster=False, grid_eff=0.7, max_grid_size=128,
                  do_grav=False, const_grav=0.0, grav_source_type=4, rotation=None, comm=None, base_grid=None, box_streams=4,
-                 diffusion=None, sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", gravity=None):
-        """gravity: castro_amd.MonopoleGravity(drdxfac=..., Gconst=...) with do_grav=True -- monopole self-gravity on every
+                 diffusion=None, sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", gravity=None,
+                 sponge=None):
+        """sponge: _lib.make_sponge(timescale, ...) -- castro.do_sponge = 1 on every box of every level (zone-local: a refined
+        level needs nothing from the coarser one), as in castro_amd.Castro.
+        gravity: castro_amd.MonopoleGravity(drdxfac=..., Gconst=...) with do_grav=True -- monopole self-gravity on every
         level (castro_amd/gravity.py: the object spans the levels like the reference's Gravity).
         gravity_type: "constant" only (the bare string "monopole" carries neither drdxfac nor Gconst and is refused).
         sum_interval, show_center_of_mass, diag_dir: as in castro_amd.Castro -- sum_integrated_quantities() over the composite
@@ -786,6 +789,8 @@ class CastroAmr:
                         do_grav=do_grav, const_grav=const_grav, grav_source_type=grav_source_type, rotation=rotation)
         if gravity is not None:
             self._kw["gravity"] = gravity
+        if sponge is not None:
+            self._kw["sponge"] = sponge
         self.n_cell = tuple(n_cell)
         self.periodic = tuple(lo_bc[d] == 0 and hi_bc[d] == 0 for d in range(3))
         # boxes of a level whose hydro updates may be in flight at once (device backend); CASTRO_AMD_BOX_STREAMS overrides

@@ -260,8 +260,11 @@ class Castro:
                  do_grav=False, const_grav=0.0, grav_source_type=4, box=None, rotation=None, fixed_dt=-1.0, initial_dt=-1.0, max_dt=1.e200,
                  alloc=True, numerics=None, proxy_ranks=1, diffusion=None, do_hydro=True,
                  sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", drdxfac=1, Gconst=L.GCONST,
-                 gravity=None):
-        """gravity: the castro_amd.MonopoleGravity of the CastroAmr hierarchy this box belongs to (set by CastroAmr: the object
+                 gravity=None, sponge=None):
+        """sponge: _lib.make_sponge(timescale, ...) turns on castro.do_sponge = 1 (Source/sources/Castro_sponge.cpp): a new-time
+        source that damps the momentum where the radius, the density or the pressure says so; a sponge made without a center
+        takes the `center` attribute of this object, else the middle of the domain, whenever a step needs it.
+        gravity: the castro_amd.MonopoleGravity of the CastroAmr hierarchy this box belongs to (set by CastroAmr: the object
         spans the levels and constructs grav_old / grav_new of every box; a single-level run uses gravity_type="monopole").
         gravity_type (gravity.gravity_type): "constant" (ConstantGrav: const_grav along z) | "monopole" (MonopoleGrav: the radial
         self-gravity of the state about the centre sum_integrated_quantities uses -- the `center` attribute, else the middle of the
@@ -399,7 +402,10 @@ class Castro:
         if diffusion is not None and box is not None:
             raise NotImplementedError("thermal diffusion on a refined patch needs the coarse-fine boundary of the operator")
         self.dt_limiter = ""                    # "hydro" | "diffusion" | "castro.max_dt": what the last estTimeStep was limited by
-        self.have_sources = self.do_grav or rotation is not None or diffusion is not None or not self.do_hydro
+        # castro.do_sponge: `sponge` = _lib.make_sponge(timescale, ...)
+        self.sponge = sponge
+        self.have_sources = (self.do_grav or rotation is not None or diffusion is not None or sponge is not None
+                             or not self.do_hydro)
         if self.have_sources:
             NSRC, NGS = 7, 3            # NSRC, NUM_GROW_SRC (Castro_setup.cpp:317-327)
             self.sbox = (tuple(x - NGS for x in self.lo), tuple(x + NGS for x in self.hi))
@@ -992,21 +998,33 @@ class Castro:
         src = (self.old_source, self.sbox) if stage == 0 else (self.new_source, self.bx)
         return (self.lo, self.hi, (self.S_old_b, self.gbox), (self.S_new_b, self.gbox), src, self.mass_fluxes, self.flux_boxes)
 
+    def _sponge_params(self):
+        """the castro_amd_sponge of this box, or None: a sponge made without a center gets problem::center as monopole gravity
+        and the integrated quantities take it (the `center` attribute, else the middle of the domain)"""
+        sp = self.sponge
+        if sp is not None and not getattr(sp, "center_given", True):
+            from . import diag
+            ctr = diag.domain_center(self)
+            for d in range(3):
+                sp.center[d] = float(ctr[d])
+        return sp
+
     def _sources_one_pass(self, stage, dt, boxes=None, grav_fabs=None):
-        """_source_stage in one pass (castro_amd_sources_mf, round 6): zero + diffusion + gravity + rotation + apply + clean_state
-        in one kernel -- the separate calls read and write the source and the state three to four times.  `boxes`: the
+        """_source_stage in one pass (castro_amd_sources_mf, round 6): zero + diffusion + gravity + rotation + sponge + apply +
+        clean_state in one kernel -- the separate calls read and write the source and the state three to four times.  `boxes`: the
         make_source_boxes table of a level whose boxes share the settings of this one (castro_amd/amr.py); `grav_fabs`: with
         monopole gravity the (grav_old, grav_new) make_grav_fabs arrays of those boxes (castro_amd_sources_mf_g)."""
         h = self.hydro
+        skw = {} if self.sponge is None else {"sponge": self._sponge_params()}     # sponge_src goes last
         if self.monopole:
             if self.level_gravity is None:          # a single level constructs its own gravity; CastroAmr does it level-wide
                 self._monopole_gravity(self.S_old_b if stage == 0 else self.S_new_b, self.grav_old if stage == 0 else self.grav_new)
             if grav_fabs is None:
                 grav_fabs = (h.make_grav_fabs([(self.grav_old, self.gravbox)]), h.make_grav_fabs([(self.grav_new, self.gravbox)]))
             h.sources_mf_g(stage, boxes or h.make_source_boxes([self._source_spec(stage)]), grav_fabs[0], grav_fabs[1],
-                           self.grav_source_type, self.rotation, self.geom, self.params, dt, ntimes=1)
+                           self.grav_source_type, self.rotation, self.geom, self.params, dt, ntimes=1, **skw)
             return
-        dkw = {} if self.diffusion is None else {"diffusion": self.diffusion}      # diff_src goes first (Castro_sources.cpp)
+        dkw = dict(skw) if self.diffusion is None else dict(skw, diffusion=self.diffusion)      # diff_src goes first (Castro_sources.cpp)
         h.sources_mf(stage, boxes or h.make_source_boxes([self._source_spec(stage)]), self.grav if self.do_grav else None,
                      self.grav_source_type if self.do_grav else 4, self.rotation, self.geom, self.params, dt, ntimes=1, **dkw)
 
@@ -1044,6 +1062,8 @@ class Castro:
                                      self.grav_source_type, dt, self.geom)
             if self.rotation is not None:
                 h.new_rotation_source(S, g, Sn, g, src, sbx, self.mass_fluxes, self.flux_boxes, lo, hi, self.rotation, self.geom, dt)
+            if self.sponge is not None:                 # construct_new_sponge_source; there is no old-time sponge
+                h.new_sponge_source(Sn, g, src, sbx, lo, hi, self._sponge_params(), self.geom, self.params, dt)
         # S_new = (S_old | S_new) + dt x source, clean_state: in one pass where the backend has it
         if hasattr(h, "apply_source"):
             h.apply_source(Sn, g, S if stage == 0 else Sn, g, dt, src, sbx, 7, lo, hi, self.params, ntimes=1)
@@ -1054,7 +1074,7 @@ class Castro:
             h.clean_state(Sn, g, lo, hi, self.params, ntimes=1)
 
     def _do_advance_with_sources(self, time, dt, S):
-        """do_advance_ctu with old- and new-time diffusion / gravity / rotation sources (Castro_advance_ctu.cpp:94-143, 156-274);
+        """do_advance_ctu with old- and new-time diffusion / gravity / rotation / sponge sources (Castro_advance_ctu.cpp:94-143, 156-274);
         the stages themselves are _source_stage / _sources_one_pass, shared with the levels of CastroAmr."""
         h = self.hydro
         lo, hi = self.lo, self.hi

@@ -635,6 +635,76 @@ __global__ void __launch_bounds__(256) k_new_rot_source(DFab UO, DFab UN, DFab S
     for (int n = 0; n < NSRC; ++n) SRC.p[cs + SRC.sn * n] += src[n];
 }
 
+// ---------------------------------------------------------------------------------------
+// the sponge (castro.do_sponge, Source/sources/Castro_sponge.cpp:55-249): momentum is damped towards rho * target velocity where
+// the radius, the density or the pressure of a zone says so; a new-time source only (construct_old_sponge_source is empty)
+// ---------------------------------------------------------------------------------------
+struct SpongeDev {
+    double lower_radius, upper_radius, lower_density, upper_density, lower_pressure, upper_pressure;
+    double lower_factor, upper_factor, target[3], alpha;
+    double center[3], problo[3], dx[3];
+    int implicit;
+};
+
+// lower_factor + 0.5 (upper_factor - lower_factor) (1 - cos(pi (x - lo) / delta)); lo == hi at x == lo is cos(pi 0/0), as in the reference
+__device__ __forceinline__ double sponge_ramp(const SpongeDev& S, double x, double lo, double delta)
+{
+    return S.lower_factor + 0.5 * (S.upper_factor - S.lower_factor) * (1.0 - cos(M_PI * (x - lo) / delta));
+}
+
+// the sponge source of one zone from its NEW state (rho, momenta, T, rho X): Sr[3] for UMX..UMZ and SrE for UEDEN, the
+// only components the sponge has
+__device__ __forceinline__ void sponge_zone(const SpongeDev& S, const DevParams& P, int i, int j, int k, double rho, const double mom[3],
+                                            double T, double rhoX, double dt, double Sr[3], double& SrE)
+{
+    const int idx[3] = { i, j, k };
+    double r[3];
+    for (int d = 0; d < 3; ++d) r[d] = S.problo[d] + ((double)idx[d] + 0.5) * S.dx[d] - S.center[d];
+    const double rhoInv = 1.0 / rho;
+    const double delta_r = S.upper_radius - S.lower_radius;
+    const double delta_rho = S.lower_density - S.upper_density;
+    const double delta_p = S.lower_pressure - S.upper_pressure;
+    double f = 0.0;
+    if (S.lower_radius >= 0.0 && S.upper_radius > S.lower_radius) {
+        const double rad = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+        if (rad < S.lower_radius) f = S.lower_factor;
+        else if (rad >= S.lower_radius && rad <= S.upper_radius) f = sponge_ramp(S, rad, S.lower_radius, delta_r);
+        else f = S.upper_factor;
+    }
+    // the density sponge takes priority over the radial one, the pressure sponge over both
+    if (S.upper_density > 0.0 && S.lower_density > 0.0) {
+        if (rho > S.upper_density) f = S.lower_factor;
+        else if (rho <= S.upper_density && rho >= S.lower_density) f = sponge_ramp(S, rho, S.upper_density, delta_rho);
+        else f = S.upper_factor;
+    }
+    if (S.upper_pressure > 0.0 && S.lower_pressure >= 0.0) {
+        const double e = eos_e_of_T(P, T, rhoX * rhoInv);               // eos(eos_input_rt) of (rho, T, X)
+        const double p = (P.gamma - 1.0) * rho * e;
+        if (p > S.upper_pressure) f = S.lower_factor;
+        else if (p <= S.upper_pressure && p >= S.lower_pressure) f = sponge_ramp(S, p, S.upper_pressure, delta_p);
+        else f = S.upper_factor;
+    }
+    double fac;
+    if (S.implicit == 1) fac = -(1.0 - 1.0 / (1.0 + S.alpha * f));
+    else fac = -S.alpha * f;
+    for (int n = 0; n < 3; ++n) Sr[n] = (mom[n] - rho * S.target[n]) * fac / dt;
+    SrE = 0.0;
+    for (int n = 0; n < 3; ++n) SrE += mom[n] * rhoInv * Sr[n];
+}
+
+__global__ void __launch_bounds__(256) k_new_sponge_source(DFab UN, DFab SRC, Box3 b, SpongeDev S, DevParams P, double dt)
+{
+    int i, j, k;
+    if (!box_thread3(b.lo, b.n, i, j, k)) return;
+    const long c = fidx(UN, i, j, k, 0);
+    const double mom[3] = { UN.p[c + UN.sn * UMX], UN.p[c + UN.sn * UMY], UN.p[c + UN.sn * UMZ] };
+    double Sr[3], SrE;
+    sponge_zone(S, P, i, j, k, UN.p[c + UN.sn * URHO], mom, UN.p[c + UN.sn * UTEMP], UN.p[c + UN.sn * UFS], dt, Sr, SrE);
+    const long cs = fidx(SRC, i, j, k, 0);
+    for (int n = 0; n < 3; ++n) SRC.p[cs + SRC.sn * (UMX + n)] += Sr[n];
+    SRC.p[cs + SRC.sn * UEDEN] += SrE;
+}
+
 
 static Box3 make_box3(const int lo[3], const int hi[3], long& n)
 {
@@ -752,6 +822,34 @@ int launch_new_rot_source(const DFab& UO, const DFab& UN, const DFab& SRC, const
     return launch_status();
 }
 
+static SpongeDev make_spongedev(const castro_amd_sponge* s, const castro_amd_geom* g, double dt)
+{
+    SpongeDev S;
+    S.lower_radius = s->lower_radius; S.upper_radius = s->upper_radius;
+    S.lower_density = s->lower_density; S.upper_density = s->upper_density;
+    S.lower_pressure = s->lower_pressure; S.upper_pressure = s->upper_pressure;
+    S.lower_factor = s->lower_factor; S.upper_factor = s->upper_factor;
+    // alpha = dt / sponge_timescale (Castro_sponge.cpp:64-69), the same in every zone
+    S.alpha = s->timescale > 0.0 ? dt / s->timescale : 0.0;
+    for (int d = 0; d < 3; ++d) {
+        S.target[d] = s->target_velocity[d]; S.center[d] = s->center[d];
+        S.problo[d] = g->problo[d]; S.dx[d] = g->dx[d];
+    }
+    S.implicit = s->implicit;
+    return S;
+}
+
+int launch_new_sponge_source(const DFab& UN, const DFab& SRC, const int lo[3], const int hi[3], const castro_amd_sponge* s,
+                             const castro_amd_geom* g, const DevParams& P, double dt, hipStream_t stream, Profiler* prof)
+{
+    long n; Box3 b = make_box3(lo, hi, n);
+    if (n <= 0) return 0;
+    prof_begin(prof, "k_new_sponge_source", stream);
+    hipLaunchKernelGGL(k_new_sponge_source, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, UN, SRC, b, make_spongedev(s, g, dt), P, dt);
+    prof_end(prof, stream);
+    return launch_status();
+}
+
 // ---------------------------------------------------------------------------------------
 // castro_amd_sources_mf (round 6): a source stage of do_advance_ctu for every box of a level in ONE launch.  Per zone of the
 // Source_Type FAB of its box a thread does what memset + k_old/new_grav_source + k_old/new_rot_source + k_apply_source did in
@@ -768,11 +866,17 @@ __device__ __forceinline__ const SrcBoxDev& src_box_of(const SrcBoxGDev& b) { re
 // GFAB = false (BOX = SrcBoxDev): the one vector of the call through GravConst.  GFAB = true (BOX = SrcBoxGDev,
 // castro_amd_sources_mf_g): the gravity of a zone through GravFab from the box's grav_old / grav_new FABs, the zone functions
 // of k_old_grav_source_gfab / k_new_grav_source_gfab
-template <int STAGE, bool GFAB, class BOX>
+// SP: nothing, or one SpongeDev (STAGE 1 only) -- the sponge after rotation, sponge_zone on the S_new values this thread loads for
+// the apply anyway.  Without it the kernel has the arguments and the code it had before there was a sponge.
+__device__ __forceinline__ const SpongeDev& sponge_arg(const SpongeDev& s) { return s; }
+
+template <int STAGE, bool GFAB, class BOX, class... SP>
 __global__ void __launch_bounds__(256) k_sources_apply(const BOX* __restrict__ tab, const long* __restrict__ start, int nbox,
                                                        GravDev G, RotDev R, int rot_on, double dt, double dx0, double dx1, double dx2,
-                                                       DevParams P, int ntimes, int diff_on)
+                                                       DevParams P, int ntimes, int diff_on, SP... sp)
 {
+    constexpr bool SPONGE = sizeof...(SP) == 1;
+    static_assert(sizeof...(SP) <= 1 && (!SPONGE || STAGE == 1), "the sponge is one argument of the new-time stage");
     long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= start[nbox]) return;
     int lo_ = 0, hi_ = nbox - 1;
@@ -815,14 +919,25 @@ __global__ void __launch_bounds__(256) k_sources_apply(const BOX* __restrict__ t
         else new_rot_zone(B.So, B.Sn, B.M0, B.M1, B.M2, i, j, k, R, dt, src);
         for (int n = 0; n < NSRC; ++n) acc[n] += src[n];
     }
+    double u[NUM_STATE];
+    if constexpr (SPONGE) {
+        // the base of the apply is S_new, the state the sponge is made from: loaded once, in front of the store of the source
+        const long cn = fidx(B.Sn, i, j, k, 0);
+#pragma unroll
+        for (int n = 0; n < NUM_STATE; ++n) u[n] = B.Sn.p[cn + B.Sn.sn * n];
+        const double mom[3] = { u[UMX], u[UMY], u[UMZ] };
+        double Sr[3], SrE;
+        sponge_zone(sponge_arg(sp...), P, i, j, k, u[URHO], mom, u[UTEMP], u[UFS], dt, Sr, SrE);
+        for (int n = 0; n < 3; ++n) acc[UMX + n] += Sr[n];
+        acc[UEDEN] += SrE;
+    }
     for (int n = 0; n < B.nsc; ++n) B.Src.p[cs + B.Src.sn * n] = n < NSRC ? acc[n] : 0.0;
     // k_apply_source: S_new = (S_old | S_new) + dt * source, clean_state x ntimes
     const DFab& Bs = STAGE == 0 ? B.So : B.Sn;
     const long cd = fidx(B.Sn, i, j, k, 0), cb = fidx(Bs, i, j, k, 0);
-    double u[NUM_STATE];
 #pragma unroll
     for (int n = 0; n < NUM_STATE; ++n) {
-        u[n] = Bs.p[cb + Bs.sn * n];
+        if constexpr (!SPONGE) u[n] = Bs.p[cb + Bs.sn * n];
         if (n < NSRC) u[n] += dt * acc[n];
     }
     if (ntimes > 0) clean_zone(P, ntimes, u[URHO], u[UMX], u[UMY], u[UMZ], u[UEDEN], u[UEINT], u[UTEMP], u[UFS]);
@@ -838,7 +953,7 @@ static const SrcBoxDev& src_box_host(const SrcBoxGDev& b) { return b.box; }
 template <class BOX>
 static int launch_sources_apply_t(int stage, int nbox, const BOX* boxes, const double* grav, int grav_type, const castro_amd_rotation* rot,
                                   const castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
-                                  hipStream_t stream, Profiler* prof, int diff_on)
+                                  hipStream_t stream, Profiler* prof, int diff_on, const castro_amd_sponge* sponge)
 {
     constexpr bool GFAB = std::is_same<BOX, SrcBoxGDev>::value;
     if (nbox < 1 || !boxes || !arena) return 0;
@@ -867,6 +982,14 @@ static int launch_sources_apply_t(int stage, int nbox, const BOX* boxes, const d
     std::memset(&R, 0, sizeof(R));
     if (rot) R = make_rotdev(rot, geom, dt);
     const unsigned nb = (unsigned)((start.back() + 255) / 256);
+    if (sponge && stage == 1) {
+        // the sponge has no old-time source: stage 0 with a sponge is the launch below
+        prof_begin(prof, "k_sources_new_sponge", stream);
+        hipLaunchKernelGGL((k_sources_apply<1, GFAB, BOX, SpongeDev>), dim3(nb), dim3(256), 0, stream, (const BOX*)base, (const long*)dstart, nbox, G, R,
+                           rot ? 1 : 0, dt, geom->dx[0], geom->dx[1], geom->dx[2], P, ntimes, diff_on, make_spongedev(sponge, geom, dt));
+        prof_end(prof, stream);
+        return launch_status();
+    }
     prof_begin(prof, stage == 0 ? "k_sources_old" : "k_sources_new", stream);
     if constexpr (GFAB) {
         if (stage == 0) hipLaunchKernelGGL((k_sources_apply<0, true, SrcBoxGDev>), dim3(nb), dim3(256), 0, stream, (const SrcBoxGDev*)base, (const long*)dstart, nbox, G, R,
@@ -885,16 +1008,16 @@ static int launch_sources_apply_t(int stage, int nbox, const BOX* boxes, const d
 
 int launch_sources_apply(int stage, int nbox, const SrcBoxDev* boxes, const double* grav, int grav_type, const castro_amd_rotation* rot,
                          const castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
-                         hipStream_t stream, Profiler* prof, int diff_on)
+                         hipStream_t stream, Profiler* prof, int diff_on, const castro_amd_sponge* sponge)
 {
-    return launch_sources_apply_t(stage, nbox, boxes, grav, grav_type, rot, geom, P, dt, ntimes, arena, stream, prof, diff_on);
+    return launch_sources_apply_t(stage, nbox, boxes, grav, grav_type, rot, geom, P, dt, ntimes, arena, stream, prof, diff_on, sponge);
 }
 
 int launch_sources_apply_gfab(int stage, int nbox, const SrcBoxGDev* boxes, int grav_type, const castro_amd_rotation* rot,
                               const castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
-                              hipStream_t stream, Profiler* prof, int diff_on)
+                              hipStream_t stream, Profiler* prof, int diff_on, const castro_amd_sponge* sponge)
 {
-    return launch_sources_apply_t(stage, nbox, boxes, nullptr, grav_type, rot, geom, P, dt, ntimes, arena, stream, prof, diff_on);
+    return launch_sources_apply_t(stage, nbox, boxes, nullptr, grav_type, rot, geom, P, dt, ntimes, arena, stream, prof, diff_on, sponge);
 }
 
 int launch_saxpy(const DFab& D, const DFab& S, const int lo[3], const int hi[3], double a, int ncomp,

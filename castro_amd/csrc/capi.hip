@@ -570,6 +570,19 @@ int castro_amd_new_rotation_source_fab(castro_amd_ctx* c, const castro_amd_fab* 
                                  (hipStream_t)stream, &c->prof);
 }
 
+int castro_amd_new_sponge_source_fab(castro_amd_ctx* c, const castro_amd_fab* state_new, const castro_amd_fab* source,
+                                     const int lo[3], const int hi[3], const castro_amd_sponge* sponge,
+                                     const castro_amd_geom* geom, const castro_amd_params* params, double dt, void* stream)
+{
+    if (!c || !state_new || !state_new->p || !source || !source->p || !lo || !hi || !sponge || !geom || !params) return CASTRO_AMD_ERR_ARG;
+    if (state_new->ncomp != NUM_STATE || source->ncomp < 7) return CASTRO_AMD_ERR_ARG;
+    if (geom->coord != 0 || !(dt > 0.0) || !(sponge->timescale > 0.0)) return CASTRO_AMD_ERR_ARG;
+    if (!fab_contains(state_new, lo, hi) || !fab_contains(source, lo, hi)) return CASTRO_AMD_ERR_ARG;
+    hipSetDevice(c->device);
+    return launch_new_sponge_source(to_dfab(state_new), to_dfab(source), lo, hi, sponge, geom, to_devparams(params), dt,
+                                    (hipStream_t)stream, &c->prof);
+}
+
 // ---- the source stages and the level reductions for every box of a level in one call (include/castro_hydro_amd.h) ----
 // ---- thermal diffusion (diffusion_kernels.hip) ----
 // the operator's boundary conditions (Diffusion.cpp:99-126): Neumann, except Dirichlet for Inflow on a low face and for Symmetry
@@ -677,12 +690,32 @@ int castro_amd_sources_mf(castro_amd_ctx* c, int stage, int nboxes, const castro
     return castro_amd_sources_mf_ex(c, stage, nboxes, boxes, grav, grav_source_type, rot, nullptr, geom, params, dt, clean_ntimes, stream);
 }
 
+// the checks of castro_amd_new_sponge_source_fab; stage 0 takes a sponge and adds nothing
+static bool sponge_ok(const castro_amd_sponge* sponge, const castro_amd_geom* geom, double dt)
+{
+    return !sponge || (geom->coord == 0 && dt > 0.0 && sponge->timescale > 0.0);
+}
+
+static int sources_mf_vec(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
+                          const double* grav, int grav_source_type, const castro_amd_rotation* rot,
+                          const castro_amd_diffusion* diff, const castro_amd_sponge* sponge, const castro_amd_geom* geom,
+                          const castro_amd_params* params, double dt, int clean_ntimes, void* stream);
+
 int castro_amd_sources_mf_ex(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
                              const double* grav, int grav_source_type, const castro_amd_rotation* rot,
                              const castro_amd_diffusion* diff, const castro_amd_geom* geom, const castro_amd_params* params,
                              double dt, int clean_ntimes, void* stream)
 {
+    return sources_mf_vec(c, stage, nboxes, boxes, grav, grav_source_type, rot, diff, nullptr, geom, params, dt, clean_ntimes, stream);
+}
+
+static int sources_mf_vec(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
+                          const double* grav, int grav_source_type, const castro_amd_rotation* rot,
+                          const castro_amd_diffusion* diff, const castro_amd_sponge* sponge, const castro_amd_geom* geom,
+                          const castro_amd_params* params, double dt, int clean_ntimes, void* stream)
+{
     if (!c || (stage != 0 && stage != 1) || nboxes < 0 || (nboxes > 0 && !boxes) || !geom || !params || clean_ntimes < 0) return CASTRO_AMD_ERR_ARG;
+    if (!sponge_ok(sponge, geom, dt)) return CASTRO_AMD_ERR_ARG;
     // the checks of the single-box entry points (castro_amd_old/new_gravity_source_fab, _rotation_source_fab, _apply_source_fab)
     if (grav && (grav_source_type < 1 || grav_source_type > 4)) return CASTRO_AMD_ERR_ARG;
     if (rot && (rot->rot_source_type < 1 || rot->rot_source_type > 4)) return CASTRO_AMD_ERR_ARG;
@@ -736,18 +769,47 @@ int castro_amd_sources_mf_ex(castro_amd_ctx* c, int stage, int nboxes, const cas
         if (rd != 0) return rd < 0 ? rd : CASTRO_AMD_ERR_HIP;
     }
     const int rc = launch_sources_apply(stage, nboxes, tab.data(), grav, grav_source_type, rot, geom, to_devparams(params), dt, clean_ntimes,
-                                        &c->ops_arena, (hipStream_t)stream, &c->prof, diff ? 1 : 0);
+                                        &c->ops_arena, (hipStream_t)stream, &c->prof, diff ? 1 : 0, sponge);
     return rc == 0 ? CASTRO_AMD_OK : (rc < 0 ? CASTRO_AMD_ERR_HIP : rc);
 }
 
 static bool grav_fab_ok(const castro_amd_fab* g, const int lo[3], const int hi[3], int grav_source_type);
+
+static int sources_mf_gfab(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
+                           const castro_amd_fab* grav_old, const castro_amd_fab* grav_new, int grav_source_type,
+                           const castro_amd_rotation* rot, const castro_amd_sponge* sponge, const castro_amd_geom* geom,
+                           const castro_amd_params* params, double dt, int clean_ntimes, void* stream);
 
 int castro_amd_sources_mf_g(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
                             const castro_amd_fab* grav_old, const castro_amd_fab* grav_new, int grav_source_type,
                             const castro_amd_rotation* rot, const castro_amd_geom* geom, const castro_amd_params* params,
                             double dt, int clean_ntimes, void* stream)
 {
+    return sources_mf_gfab(c, stage, nboxes, boxes, grav_old, grav_new, grav_source_type, rot, nullptr, geom, params, dt, clean_ntimes, stream);
+}
+
+int castro_amd_sources_mf_opts(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
+                               const castro_amd_source_opts* o, const castro_amd_geom* geom, const castro_amd_params* params,
+                               double dt, int clean_ntimes, void* stream)
+{
+    if (!o) return CASTRO_AMD_ERR_ARG;
+    if (o->grav_old || o->grav_new) {
+        if (o->grav) return CASTRO_AMD_ERR_ARG;
+        if (o->diff) return CASTRO_AMD_ERR_UNSUPPORTED;
+        return sources_mf_gfab(c, stage, nboxes, boxes, o->grav_old, o->grav_new, o->grav_source_type, o->rot, o->sponge, geom, params, dt,
+                               clean_ntimes, stream);
+    }
+    return sources_mf_vec(c, stage, nboxes, boxes, o->grav, o->grav_source_type, o->rot, o->diff, o->sponge, geom, params, dt, clean_ntimes,
+                          stream);
+}
+
+static int sources_mf_gfab(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
+                           const castro_amd_fab* grav_old, const castro_amd_fab* grav_new, int grav_source_type,
+                           const castro_amd_rotation* rot, const castro_amd_sponge* sponge, const castro_amd_geom* geom,
+                           const castro_amd_params* params, double dt, int clean_ntimes, void* stream)
+{
     if (!c || (stage != 0 && stage != 1) || nboxes < 0 || (nboxes > 0 && !boxes) || !geom || !params || clean_ntimes < 0) return CASTRO_AMD_ERR_ARG;
+    if (!sponge_ok(sponge, geom, dt)) return CASTRO_AMD_ERR_ARG;
     if (nboxes > 0 && (!grav_old || (stage == 1 && !grav_new))) return CASTRO_AMD_ERR_ARG;
     if (grav_source_type < 1 || grav_source_type > 4) return CASTRO_AMD_ERR_ARG;
     if (rot && (rot->rot_source_type < 1 || rot->rot_source_type > 4)) return CASTRO_AMD_ERR_ARG;
@@ -788,7 +850,7 @@ int castro_amd_sources_mf_g(castro_amd_ctx* c, int stage, int nboxes, const cast
     }
     hipSetDevice(c->device);
     const int rc = launch_sources_apply_gfab(stage, nboxes, tab.data(), grav_source_type, rot, geom, to_devparams(params), dt, clean_ntimes,
-                                             &c->ops_arena, (hipStream_t)stream, &c->prof, 0);
+                                             &c->ops_arena, (hipStream_t)stream, &c->prof, 0, sponge);
     return rc == 0 ? CASTRO_AMD_OK : (rc < 0 ? CASTRO_AMD_ERR_HIP : rc);
 }
 

@@ -6,6 +6,7 @@
 #include "hydro_device.h"
 
 struct castro_amd_rotation;      // include/castro_hydro_amd.h
+struct castro_amd_sponge;
 struct castro_amd_geom;
 
 namespace cad {
@@ -150,6 +151,9 @@ int launch_old_rot_source(const DFab& U, const DFab& SRC, const int lo[3], const
                           const ::castro_amd_geom* g, double dt, hipStream_t stream, Profiler* prof);
 int launch_new_rot_source(const DFab& UO, const DFab& UN, const DFab& SRC, const DFab M[3], const int lo[3], const int hi[3],
                           const ::castro_amd_rotation* r, const ::castro_amd_geom* g, double dt, hipStream_t stream, Profiler* prof);
+// the sponge (Castro_sponge.cpp): a new-time source made from S_new alone, added to UMX..UMZ and UEDEN of SRC on [lo, hi]
+int launch_new_sponge_source(const DFab& UN, const DFab& SRC, const int lo[3], const int hi[3], const ::castro_amd_sponge* s,
+                             const ::castro_amd_geom* g, const DevParams& P, double dt, hipStream_t stream, Profiler* prof);
 // one box of castro_amd_sources_mf: states, Source_Type FAB (nsc components), mass fluxes; [lo, lo + n): the zones of the source FAB
 // (thread range), [vlo, vhi]: the valid zones
 struct SrcBoxDev { DFab So, Sn, Src, M0, M1, M2; int lo[3], n[3]; int vlo[3], vhi[3]; int nsc; };
@@ -157,10 +161,10 @@ struct SrcBoxDev { DFab So, Sn, Src, M0, M1, M2; int lo[3], n[3]; int vlo[3], vh
 struct SrcBoxGDev { SrcBoxDev box; DFab GO, GN; };
 int launch_sources_apply_gfab(int stage, int nbox, const SrcBoxGDev* boxes, int grav_type, const ::castro_amd_rotation* rot,
                               const ::castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
-                              hipStream_t stream, Profiler* prof, int diff_on = 0);
+                              hipStream_t stream, Profiler* prof, int diff_on = 0, const ::castro_amd_sponge* sponge = nullptr);
 int launch_sources_apply(int stage, int nbox, const SrcBoxDev* boxes, const double* grav, int grav_type, const ::castro_amd_rotation* rot,
                          const ::castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
-                         hipStream_t stream, Profiler* prof, int diff_on = 0);
+                         hipStream_t stream, Profiler* prof, int diff_on = 0, const ::castro_amd_sponge* sponge = nullptr);
 // thermal diffusion (diffusion_kernels.hip).  One box of a castro_amd_temp_diffusion_* launch: U (and U2, the old state of the
 // time-centred corrector) with at least one ghost zone around [lo, hi]; Src: the Source_Type FAB (p == nullptr: none);
 // Out: a one-component FAB for the bare term (p == nullptr: none); nt: tiles per direction, set by the launcher

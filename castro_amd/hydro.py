@@ -262,9 +262,15 @@ class HipHydro:
             arr[i] = L.fab_of(g, *box)
         return arr
 
-    def sources_mf_g(self, stage, boxes, grav_old, grav_new, grav_source_type, rot, geom, params, dt, ntimes=1, stream=None):
-        """castro_amd_sources_mf_g: sources_mf with the gravity of box i read from grav_old[i] / grav_new[i] (make_grav_fabs)"""
+    def sources_mf_g(self, stage, boxes, grav_old, grav_new, grav_source_type, rot, geom, params, dt, ntimes=1, stream=None,
+                     sponge=None):
+        """castro_amd_sources_mf_g: sources_mf with the gravity of box i read from grav_old[i] / grav_new[i] (make_grav_fabs).
+        sponge (_lib.make_sponge with a center): castro_amd_sources_mf_opts, the sponge after rotation in stage 1."""
         arr, n = boxes
+        if n and sponge is not None:
+            self._sources_mf_opts(stage, arr, n, L.SourceOpts(None, grav_old, grav_new, int(grav_source_type)), rot, None, sponge,
+                                  geom, params, dt, ntimes, stream)
+            return
         if n:
             L.check(self.lib.castro_amd_sources_mf_g(self.h, int(stage), n, arr, grav_old, grav_new, int(grav_source_type),
                                                      C.byref(rot) if rot is not None else None, C.byref(geom), C.byref(params),
@@ -303,6 +309,23 @@ class HipHydro:
                                                             C.byref(L.fab_of(source, *src_box)), mb, L.i3(lo), L.i3(hi),
                                                             C.byref(rot), C.byref(geom), float(dt), _stream_ptr(stream)),
                 "new_rotation_source_fab")
+
+    def new_sponge_source(self, state_new, new_box, source, src_box, lo, hi, sponge, geom, params, dt, stream=None):
+        """castro_amd_new_sponge_source_fab: Castro::construct_new_sponge_source on [lo, hi] (sponge: _lib.make_sponge with a center)"""
+        L.check(self.lib.castro_amd_new_sponge_source_fab(self.h, C.byref(L.fab_of(state_new, *new_box)),
+                                                          C.byref(L.fab_of(source, *src_box)), L.i3(lo), L.i3(hi), C.byref(sponge),
+                                                          C.byref(geom), C.byref(params), float(dt), _stream_ptr(stream)),
+                "new_sponge_source_fab")
+
+    def _sources_mf_opts(self, stage, arr, n, opts, rot, diffusion, sponge, geom, params, dt, ntimes, stream):
+        """castro_amd_sources_mf_opts with the gravity fields of `opts` set by the caller"""
+        if rot is not None:
+            opts.rot = C.pointer(rot)
+        if diffusion is not None:
+            opts.diff = C.pointer(diffusion)
+        opts.sponge = C.pointer(sponge)
+        L.check(self.lib.castro_amd_sources_mf_opts(self.h, int(stage), n, arr, C.byref(opts), C.byref(geom), C.byref(params),
+                                                    float(dt), int(ntimes), _stream_ptr(stream)), "sources_mf_opts")
 
     def saxpy(self, dst, dst_box, a, src, src_box, ncomp, lo, hi, stream=None):
         """dst[:ncomp] += a * src[:ncomp] on [lo,hi] (Castro::apply_source_to_state)."""
@@ -407,13 +430,19 @@ class HipHydro:
             sb.S_old, sb.S_new, sb.source = L.fab_of(so[0], *so[1]), L.fab_of(sn[0], *sn[1]), L.fab_of(src[0], *src[1])
         return arr, len(specs)
 
-    def sources_mf(self, stage, boxes, grav, grav_source_type, rot, geom, params, dt, ntimes=1, stream=None, diffusion=None):
+    def sources_mf(self, stage, boxes, grav, grav_source_type, rot, geom, params, dt, ntimes=1, stream=None, diffusion=None,
+                   sponge=None):
         """castro_amd_sources_mf: stage 0 = old-time sources + S_new = S_old + dt * source + clean_state, stage 1 = new-time
         sources + S_new += dt * source + clean_state, for every box of `boxes` (make_source_boxes).  diffusion
-        (_lib.make_diffusion): castro_amd_sources_mf_ex, the thermal-diffusion term in front of gravity and rotation."""
+        (_lib.make_diffusion): castro_amd_sources_mf_ex, the thermal-diffusion term in front of gravity and rotation.
+        sponge (_lib.make_sponge with a center): castro_amd_sources_mf_opts, the sponge after rotation in stage 1."""
         arr, n = boxes
         if n:
             g = (C.c_double * 3)(*[float(x) for x in grav]) if grav is not None else None
+            if sponge is not None:
+                opts = L.SourceOpts(C.cast(g, C.POINTER(C.c_double)) if g is not None else None, None, None, int(grav_source_type))
+                self._sources_mf_opts(stage, arr, n, opts, rot, diffusion, sponge, geom, params, dt, ntimes, stream)
+                return
             if diffusion is not None:
                 L.check(self.lib.castro_amd_sources_mf_ex(self.h, int(stage), n, arr, g, int(grav_source_type),
                                                           C.byref(rot) if rot is not None else None, C.byref(diffusion),

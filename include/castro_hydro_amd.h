@@ -58,7 +58,8 @@ extern "C" {
  *      castro_amd_diffusion, castro_amd_temp_diffusion_fab / _mf, castro_amd_estdt_temp_diffusion_fab / _mf,
  *      castro_amd_sources_mf_ex; castro_amd_integrated_quantities_mf, castro_amd_diag_workgroups (struct castro_amd_diag_box);
  *      castro_amd_radial_mass_mf, castro_amd_radial_gravity, castro_amd_monopole_grav_fab (struct castro_amd_monopole_params),
- *      castro_amd_old_gravity_source_gfab, castro_amd_new_gravity_source_gfab.
+ *      castro_amd_old_gravity_source_gfab, castro_amd_new_gravity_source_gfab;
+ *      castro_amd_new_sponge_source_fab (struct castro_amd_sponge), castro_amd_sources_mf_opts (struct castro_amd_source_opts).
  * A caller checks `castro_amd_abi_version() == CASTRO_AMD_ABI_VERSION` once after loading the library; a mismatch means
  * the library was built from another revision of this header (a 0.2 caller with 2-double vectors would be written 8 bytes
  * out of bounds by a 0.3 library). */
@@ -606,6 +607,55 @@ int castro_amd_sources_mf_g(castro_amd_ctx *ctx, int stage, int nboxes, const ca
                             const castro_amd_fab *grav_old, const castro_amd_fab *grav_new, int grav_source_type,
                             const castro_amd_rotation *rot /* or NULL */, const castro_amd_geom *geom,
                             const castro_amd_params *params, double dt, int clean_ntimes, void *stream);
+
+/* The sponge (castro.do_sponge = 1, Source/sources/Castro_sponge.cpp): momentum is damped towards rho * target_velocity on the
+ * time scale `timescale` wherever a sponge factor f in [lower_factor, upper_factor] is non-zero.  Per zone, from the NEW state:
+ *   radial   (lower_radius >= 0 and upper_radius > lower_radius), r = |problo + (i + 1/2) dx - center|:
+ *            f = lower_factor below lower_radius, upper_factor above upper_radius, between them
+ *            lower_factor + 0.5 (upper_factor - lower_factor) (1 - cos(pi (r - lower_radius) / (upper_radius - lower_radius)))
+ *   density  (both densities > 0; overrides the radial factor): lower_factor where rho > upper_density, upper_factor where
+ *            rho < lower_density, the cosine ramp in (rho - upper_density) / (lower_density - upper_density) between them
+ *   pressure (upper_pressure > 0 and lower_pressure >= 0; overrides both): the same in p = eos(rho, T, X) of the gamma law
+ *   alpha = dt / timescale;  fac = -(1 - 1 / (1 + alpha f)) if implicit == 1, else -alpha f
+ *   Sr[n] = (U[UMX + n] - rho * target_velocity[n]) * fac / dt;   SrE = sum_n U[UMX + n] * (1 / rho) * Sr[n]
+ * and source(UMX + n) += Sr[n], source(UEDEN) += SrE; no other component is touched.  With lower == upper of a pair a zone
+ * exactly on the threshold evaluates cos(pi * 0/0), as in the reference.  The sponge has no old-time source
+ * (construct_old_sponge_source is empty).  The defaults of _cpp_parameters: radii, densities, pressures -1 (off),
+ * lower_factor 0, upper_factor 1, target_velocity 0, implicit 1; the reference refuses timescale <= 0, and all three upper (or
+ * all three lower) limits negative (Castro.cpp:475-488). */
+typedef struct castro_amd_sponge {
+    double lower_radius, upper_radius;          /* castro.sponge_lower_radius / _upper_radius */
+    double lower_density, upper_density;        /* castro.sponge_lower_density / _upper_density */
+    double lower_pressure, upper_pressure;      /* castro.sponge_lower_pressure / _upper_pressure */
+    double lower_factor, upper_factor;          /* castro.sponge_lower_factor / _upper_factor */
+    double target_velocity[3];                  /* castro.sponge_target_{x,y,z}_velocity */
+    double timescale;                           /* castro.sponge_timescale */
+    double center[3];                           /* problem::center */
+    int implicit;                               /* castro.sponge_implicit */
+} castro_amd_sponge;
+/* Castro::construct_new_sponge_source / apply_sponge on [lo, hi] of one box: needs the new state and the Source_Type FAB only.
+ * CASTRO_AMD_ERR_ARG unless geom->coord == 0, dt > 0 and sponge->timescale > 0. */
+int castro_amd_new_sponge_source_fab(castro_amd_ctx *ctx, const castro_amd_fab *state_new, const castro_amd_fab *source,
+                                     const int lo[3], const int hi[3], const castro_amd_sponge *sponge,
+                                     const castro_amd_geom *geom, const castro_amd_params *params, double dt, void *stream);
+/* The one-pass source stages with every source term of the three forms above behind one options struct, and the sponge:
+ *   grav (a vector: castro_amd_sources_mf) or grav_old / grav_new (one FAB per box: castro_amd_sources_mf_g), not both;
+ *   rot; diff (castro_amd_sources_mf_ex; not together with gravity FABs: CASTRO_AMD_ERR_UNSUPPORTED); sponge.
+ * Every pointer may be NULL; with sponge == NULL the call IS the matching one of the three, the same bits.  With a sponge,
+ * stage 1 adds its source after rotation (the dispatch order of Castro_sources.cpp:290-347) inside the one kernel, from the
+ * S_new values the kernel loads for the apply -- the bits of castro_amd_new_sponge_source_fab called after the others; stage 0
+ * accepts a sponge and adds nothing.  Argument checks as above. */
+typedef struct castro_amd_source_opts {
+    const double *grav;                         /* [3] or NULL */
+    const castro_amd_fab *grav_old, *grav_new;  /* [nboxes] or NULL */
+    int grav_source_type;
+    const castro_amd_rotation *rot;
+    const castro_amd_diffusion *diff;
+    const castro_amd_sponge *sponge;
+} castro_amd_source_opts;
+int castro_amd_sources_mf_opts(castro_amd_ctx *ctx, int stage, int nboxes, const castro_amd_source_box *boxes,
+                               const castro_amd_source_opts *opts, const castro_amd_geom *geom, const castro_amd_params *params,
+                               double dt, int clean_ntimes, void *stream);
 
 /* Two-level AMR building blocks, refinement ratio 2 (first slice).  The reference calls AMReX for
  * all of these [3P, not in the reference tree]; the arithmetic is restated from the published descriptions and is
