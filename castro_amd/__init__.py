@@ -6,16 +6,16 @@ Layout:
   hydro.py         HipHydro: the reference's per-FAB hydro interface over the C ABI
   castro.py        Castro: single-level driver (FillPatch halo exchange over RCCL, dt control, retry, gravity, rotation, thermal diffusion, sponge)
   amr.py           CastroAmr: coarse level + one refined patch with subcycling, reflux, avgDown
-  gravity.py       MonopoleGravity: monopole self-gravity over the levels of CastroAmr (radial arrays, level combination)
+  gravity.py       MonopoleGravity: monopole self-gravity over the levels of CastroAmr (radial arrays, level combination); PointMass: the central point mass
   plotfile.py      Castro plotfile writer / reader
 """
 from ._lib import (NUM_STATE, NGDNV, NUM_GROW, URHO, UMX, UMY, UMZ, UEDEN, UEINT, UTEMP, UFS,
                    default_params, make_geom, make_rotation, make_diffusion, make_sponge, LIB_PATH)
 from .castro import Castro, DistComm, SingleComm, AdvanceFailure, default_grid
 from .amr import CastroAmr
-from .gravity import MonopoleGravity
+from .gravity import MonopoleGravity, PointMass
 
-__all__ = ["Castro", "CastroAmr", "MonopoleGravity", "DistComm", "SingleComm", "AdvanceFailure", "default_grid", "default_params", "make_geom", "make_rotation", "make_diffusion", "make_sponge",
+__all__ = ["Castro", "CastroAmr", "MonopoleGravity", "PointMass", "DistComm", "SingleComm", "AdvanceFailure", "default_grid", "default_params", "make_geom", "make_rotation", "make_diffusion", "make_sponge",
            "NUM_STATE", "NGDNV", "NUM_GROW", "LIB_PATH"]
 
 

@@ -73,6 +73,7 @@ EXPORTED_SYMBOLS = (
     "castro_amd_old_gravity_source_gfab", "castro_amd_new_gravity_source_gfab",
     "castro_amd_radial_mass_mf_ex", "castro_amd_radial_combine", "castro_amd_grav_bc_fill_fab", "castro_amd_sources_mf_g",
     "castro_amd_new_sponge_source_fab", "castro_amd_sources_mf_opts",
+    "castro_amd_add_pointmass_fab", "castro_amd_add_pointmass_mf", "castro_amd_pointmass_delta_mf", "castro_amd_pointmass_apply_mf",
 )
 
 
@@ -228,6 +229,33 @@ def make_sponge(timescale, lower_radius=-1.0, upper_radius=-1.0, lower_density=-
     S.timescale, S.implicit = float(timescale), int(implicit)
     S.center_given = center is not None
     return S
+
+
+class PointMassParams(C.Structure):
+    """castro_amd_pointmass_params"""
+    _fields_ = [("center", C.c_double * 3), ("Gconst", C.c_double)]
+
+
+class PointMassBox(C.Structure):
+    """castro_amd_pointmass_box: one box of castro_amd_pointmass_delta_mf / castro_amd_pointmass_apply_mf"""
+    _fields_ = [("lo", C.c_int * 3), ("hi", C.c_int * 3), ("state_old", Fab), ("state_new", Fab)]
+
+
+def make_pointmass(center, Gconst=GCONST):
+    """castro_amd_pointmass_params: problem::center and C::Gconst"""
+    p = PointMassParams()
+    for d in range(3):
+        p.center[d] = float(center[d])
+    p.Gconst = float(Gconst)
+    return p
+
+
+def pointmass_cube(center, geom):
+    """(lo, hi) of the 4 x 4 x 4 zones Castro::pointmass_update sums over and restores (Castro_pointmass.cpp:38-65), before the
+    clipping to a box: icen = floor((center - problo) / dx + 1e-8), icen - 2 .. icen + 1"""
+    import math
+    icen = [int(math.floor((float(center[d]) - geom.problo[d]) / geom.dx[d] + 1.e-8)) for d in range(3)]
+    return tuple(i - 2 for i in icen), tuple(i + 1 for i in icen)
 
 
 class Diffusion(C.Structure):
@@ -390,6 +418,14 @@ def load(numerics=None):
                                                        C.POINTER(Params), C.c_double, C.c_void_p]
         L.castro_amd_sources_mf_opts.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(SourceBox), C.POINTER(SourceOpts),
                                                  C.POINTER(Geom), C.POINTER(Params), C.c_double, C.c_int, C.c_void_p]
+    if hasattr(L, "castro_amd_add_pointmass_mf"):           # absent from A/B builds of revisions before the point mass
+        PP = C.POINTER(PointMassParams)
+        L.castro_amd_add_pointmass_fab.argtypes = [C.c_void_p, PF, PP, C.POINTER(Geom), C.c_void_p, C.c_void_p]
+        L.castro_amd_add_pointmass_mf.argtypes = [C.c_void_p, C.c_int, PF, PP, C.POINTER(Geom), C.c_void_p, C.c_void_p]
+        L.castro_amd_pointmass_delta_mf.argtypes = [C.c_void_p, C.c_int, C.POINTER(PointMassBox), PP, C.POINTER(Geom), C.c_void_p,
+                                                    C.c_void_p]
+        L.castro_amd_pointmass_apply_mf.argtypes = [C.c_void_p, C.c_int, C.POINTER(PointMassBox), PP, C.POINTER(Geom), C.c_void_p,
+                                                    C.c_void_p, C.c_void_p]
     L.castro_amd_step_control.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_double, C.c_double,
                                           C.c_double, C.c_int, C.c_void_p]
     L.castro_amd_clean_state_fab.argtypes = [C.c_void_p, PF, I3, I3, C.POINTER(Params), C.c_int, C.c_void_p]

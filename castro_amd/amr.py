@@ -583,6 +583,19 @@ class _Level:
     advance = Castro.advance
     subcycle_advance_ctu = Castro.subcycle_advance_ctu
 
+    def _pointmass_update(self):
+        """Castro::pointmass_update at the end of this level's advance (Castro_advance.cpp:102-107): it acts on the finest EXISTING
+        level only (level == parent->finestLevel()) -- on every one of its subcycles, and on level 0 while nothing finer exists.
+        S_old_b of every box is the old state of the whole advance.  Collective over the ranks.  True if it ran."""
+        pm = self.amr.pm
+        if pm is None or not pm.fix_solution or self.l != len(self.amr.lev) - 1:
+            return False
+        h = self.hydro
+        specs = [(b.lo, b.hi, (b.S_old_b, b.gbox), (b.S_new_b, b.gbox)) for b in self.mine]
+        pm.update(h, self.amr.comm, h.make_pointmass_boxes(specs), self.amr.gravity.problem_center(), self.geom)
+        self.invalidate_estimate()              # S_new has been written outside the update pass
+        return True
+
     def _hydro_calls(self, fn):
         """fn(b) -- the hydro update of one box -- for every box of this rank.  The boxes of a level are independent
         there, and one small box fills a fraction of the chip (a 32^3 box is 64 workgroups of 256 CUs' worth), so with
@@ -734,8 +747,12 @@ class CastroAmr:
                  blocking_factor=8, patches=None, max_level=1, cluster=False, grid_eff=0.7, max_grid_size=128,
                  do_grav=False, const_grav=0.0, grav_source_type=4, rotation=None, comm=None, base_grid=None, box_streams=4,
                  diffusion=None, sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", gravity=None,
-                 sponge=None):
-        """sponge: _lib.make_sponge(timescale, ...) -- castro.do_sponge = 1 on every box of every level (zone-local: a refined
+                 sponge=None, use_point_mass=False, point_mass=0.0, point_mass_fix_solution=False):
+        """use_point_mass, point_mass, point_mass_fix_solution: as in castro_amd.Castro, with gravity=MonopoleGravity(...) -- ONE
+        point mass per hierarchy (self.point_mass reads the device value), its field added after the Gravity_Type FillPatch of
+        every level, Castro::pointmass_update after every advance of the finest existing level.  Constant gravity plus a point
+        mass is not built for AMR levels (the Gravity_Type FillPatch tables exist for monopole gravity only).
+        sponge: _lib.make_sponge(timescale, ...) -- castro.do_sponge = 1 on every box of every level (zone-local: a refined
         level needs nothing from the coarser one), as in castro_amd.Castro.
         gravity: castro_amd.MonopoleGravity(drdxfac=..., Gconst=...) with do_grav=True -- monopole self-gravity on every
         level (castro_amd/gravity.py: the object spans the levels like the reference's Gravity).
@@ -776,6 +793,14 @@ class CastroAmr:
                 raise ValueError("gravity=MonopoleGravity(...) needs do_grav=True")
             gravity.bind(self, lo_bc, hi_bc)
         self.gravity = gravity
+        self.pm = None
+        if use_point_mass:
+            if not do_grav:
+                raise ValueError("use_point_mass needs do_grav=True: the point mass is a term of the gravity vector")
+            if gravity is None:
+                raise NotImplementedError("CastroAmr: a point mass with constant gravity is not built for AMR levels (their "
+                                          "Gravity_Type FillPatch exists for gravity=MonopoleGravity(...) only); use "
+                                          "castro_amd.Castro, or monopole gravity")
         if patch_crse is not None:
             assert patches is None
             patches = [patch_crse]
@@ -826,6 +851,9 @@ class CastroAmr:
             lev0.bind()
             if gravity is not None:
                 gravity.check_level(0, lev0.geom)
+        if use_point_mass:
+            from .gravity import PointMass
+            self.pm = gravity.point_mass = PointMass(self._hydro_for(0), point_mass, point_mass_fix_solution, gravity.Gconst)
         self.refine = refine
         self.regrid_int, self.n_error_buf, self.blocking_factor = int(regrid_int), int(n_error_buf), int(blocking_factor)
         self.cluster = bool(cluster)
@@ -842,6 +870,9 @@ class CastroAmr:
         self.diag = DiagLog(sum_interval, show_center_of_mass, diag_dir, io_rank=self.rank == 0)
         self._diag_out = None
 
+    use_point_mass = property(lambda self: self.pm is not None)
+    point_mass = property(lambda self: self.pm.value() if self.pm is not None else None,
+                          doc="castro::point_mass as the device holds it (None without use_point_mass)")
     # views used by the tests and the plotfile writer
     crse = property(lambda self: self.lev[0])
     fine = property(lambda self: self.lev[1] if len(self.lev) > 1 else None)

@@ -260,8 +260,16 @@ class Castro:
                  do_grav=False, const_grav=0.0, grav_source_type=4, box=None, rotation=None, fixed_dt=-1.0, initial_dt=-1.0, max_dt=1.e200,
                  alloc=True, numerics=None, proxy_ranks=1, diffusion=None, do_hydro=True,
                  sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", drdxfac=1, Gconst=L.GCONST,
-                 gravity=None, sponge=None):
-        """sponge: _lib.make_sponge(timescale, ...) turns on castro.do_sponge = 1 (Source/sources/Castro_sponge.cpp): a new-time
+                 gravity=None, sponge=None, use_point_mass=False, point_mass=0.0, point_mass_fix_solution=False):
+        """use_point_mass, point_mass, point_mass_fix_solution (castro.use_point_mass / point_mass / point_mass_fix_solution): a
+        mass M at problem::center -- the `center` attribute, else the middle of the domain -- whose field is added to the gravity
+        vector of either gravity_type (Gravity::add_pointmass_to_gravity); needs do_grav.  M lives in one device double
+        (self.point_mass reads it).  With "constant" the gravity is then no longer one vector: the box gets grav_old / grav_new
+        FABs (const_grav in z, zero elsewhere, plus the point mass) and takes the path of the per-zone gravity sources.
+        point_mass_fix_solution: after every advance the mass that arrived in the 4 x 4 x 4 zones around the centre is moved into
+        M and those zones are put back to the step's old state (Castro::pointmass_update); the next time step is then
+        estimated afresh from the final state.
+        sponge: _lib.make_sponge(timescale, ...) turns on castro.do_sponge = 1 (Source/sources/Castro_sponge.cpp): a new-time
         source that damps the momentum where the radius, the density or the pressure says so; a sponge made without a center
         takes the `center` attribute of this object, else the middle of the domain, whenever a step needs it.
         gravity: the castro_amd.MonopoleGravity of the CastroAmr hierarchy this box belongs to (set by CastroAmr: the object
@@ -385,6 +393,10 @@ class Castro:
         self.gravity_type, self.drdxfac, self.Gconst = gravity_type, int(drdxfac), float(Gconst)
         self.monopole = self.do_grav and (gravity_type == "monopole" or gravity is not None)
         self.level_gravity = gravity if self.do_grav else None
+        self.use_point_mass = bool(use_point_mass)
+        if self.use_point_mass and not self.do_grav:
+            raise ValueError("use_point_mass needs do_grav=True: the point mass is a term of the gravity vector")
+        self.pm = None
         if self.level_gravity is not None:
             # a box of a CastroAmr level: Gravity_Type old / new data with one ghost zone; the radial arrays live in `gravity`
             self.gravity_type, self.drdxfac, self.Gconst = "monopole", gravity.drdxfac, gravity.Gconst
@@ -395,6 +407,20 @@ class Castro:
                 self.center = gravity.center
         elif self.monopole:
             self._init_monopole(hydro_alloc, box)
+        if self.use_point_mass and self.level_gravity is None:
+            if box is not None:
+                raise NotImplementedError("a point mass on a refined patch belongs to the hierarchy: CastroAmr(use_point_mass=True, "
+                                          "gravity=MonopoleGravity(...))")
+            if alloc:
+                from .gravity import PointMass
+                self.pm = PointMass(hydro, point_mass, point_mass_fix_solution, self.Gconst)
+            if not self.monopole:
+                # ConstantGrav plus a point mass: Gravity_Type data like monopole gravity's (Gravity.cpp:859-866, 902-907)
+                self.gravbox = (tuple(x - 1 for x in self.lo), tuple(x + 1 for x in self.hi))
+                self.grav_old = hydro_alloc(3, *self.gravbox)
+                self.grav_new = hydro_alloc(3, *self.gravbox)
+        # the gravity of a zone comes from grav_old / grav_new instead of the one vector self.grav
+        self.grav_fab = self.monopole or (self.use_point_mass and self.do_grav)
         # castro.do_rotation: `rotation` = _lib.make_rotation(rotational_period, rot_axis, ...)
         self.rotation = rotation
         # castro.diffuse_temp = 1: `diffusion` = _lib.make_diffusion(const_conductivity, ...); castro.do_hydro
@@ -766,6 +792,35 @@ class Castro:
         h.radial_gravity(mono, self.geom, mv, self._radial_g.reshape(-1))
         h.monopole_grav(self._radial_g.reshape(-1), mono, self.geom, grav, self.gravbox)
 
+    def _construct_gravity(self, S, grav):
+        """get_old_grav_vector / get_new_grav_vector of a single level (Gravity.cpp:837-980) into `grav`: the constant vector or
+        the monopole interpolation, then -- last -- the point mass over the whole grown FAB."""
+        if self.monopole:
+            self._monopole_gravity(S, grav)
+        else:
+            grav.zero_()                        # grav.setVal(0.0, ng); grav.setVal(const_grav, AMREX_SPACEDIM - 1, 1, ng)
+            grav[2].fill_(self.grav[2])
+        if self.pm is not None:
+            from . import diag
+            self.pm.add(self.hydro, self.hydro.make_grav_fabs([(grav, self.gravbox)]), diag.domain_center(self), self.geom)
+
+    point_mass = property(lambda self: self.pm.value() if self.pm is not None else None,
+                          doc="castro::point_mass as the device holds it (None without use_point_mass)")
+
+    def _pointmass_update(self):
+        """Castro::pointmass_update (Castro_pointmass.cpp) after the advance of a single level -- the finest one: S_old_b is the
+        old state of the whole step (the restored original after retry subcycles).  True if it ran."""
+        pm = self.pm
+        if pm is None or not pm.fix_solution or self.level_gravity is not None:
+            return False
+        from . import diag
+        key = (self.S_old_b.data_ptr(), self.S_new_b.data_ptr())
+        tabs = self.__dict__.setdefault("_pm_tables", {})
+        if key not in tabs:
+            tabs[key] = self.hydro.make_pointmass_boxes([(self.lo, self.hi, (self.S_old_b, self.gbox), (self.S_new_b, self.gbox))])
+        pm.update(self.hydro, self.comm, tabs[key], diag.domain_center(self), self.geom)
+        return True
+
     def radial_gravity(self):
         """(radial_mass, radial_vol, radial_grav) of the last gravity construction, as numpy arrays of n1d entries"""
         if not self.monopole or self.level_gravity is not None:
@@ -1016,9 +1071,9 @@ class Castro:
         monopole gravity the (grav_old, grav_new) make_grav_fabs arrays of those boxes (castro_amd_sources_mf_g)."""
         h = self.hydro
         skw = {} if self.sponge is None else {"sponge": self._sponge_params()}     # sponge_src goes last
-        if self.monopole:
+        if self.grav_fab:
             if self.level_gravity is None:          # a single level constructs its own gravity; CastroAmr does it level-wide
-                self._monopole_gravity(self.S_old_b if stage == 0 else self.S_new_b, self.grav_old if stage == 0 else self.grav_new)
+                self._construct_gravity(self.S_old_b if stage == 0 else self.S_new_b, self.grav_old if stage == 0 else self.grav_new)
             if grav_fabs is None:
                 grav_fabs = (h.make_grav_fabs([(self.grav_old, self.gravbox)]), h.make_grav_fabs([(self.grav_new, self.gravbox)]))
             h.sources_mf_g(stage, boxes or h.make_source_boxes([self._source_spec(stage)]), grav_fabs[0], grav_fabs[1],
@@ -1040,9 +1095,9 @@ class Castro:
         if stage == 0:
             if self.diffusion is not None:              # construct_old_diff_source: + 1.0 x DiffTerm(Sborder)
                 h.temp_diffusion(S, g, src, sbx, lo, hi, self.diffusion, self.geom, 1.0)
-            if self.monopole:
+            if self.grav_fab:
                 if self.level_gravity is None:
-                    self._monopole_gravity(S, self.grav_old)
+                    self._construct_gravity(S, self.grav_old)
                 h.old_gravity_source_gfab(S, g, src, sbx, lo, hi, self.grav_old, self.gravbox, self.grav_source_type, dt)
             elif self.do_grav:
                 h.old_gravity_source(S, g, src, sbx, lo, hi, self.grav, self.grav_source_type, dt)
@@ -1052,9 +1107,9 @@ class Castro:
             if self.diffusion is not None:              # construct_new_diff_source: + 0.5 x DiffTerm(S_new) - 0.5 x DiffTerm(Sborder)
                 h.temp_diffusion(Sn, g, src, sbx, lo, hi, self.diffusion, self.geom, 0.5)
                 h.temp_diffusion(S, g, src, sbx, lo, hi, self.diffusion, self.geom, -0.5)
-            if self.monopole:
+            if self.grav_fab:
                 if self.level_gravity is None:
-                    self._monopole_gravity(Sn, self.grav_new)
+                    self._construct_gravity(Sn, self.grav_new)
                 h.new_gravity_source_gfab(S, g, Sn, g, src, sbx, self.mass_fluxes, self.flux_boxes, lo, hi, self.grav_old,
                                           self.grav_new, self.gravbox, self.grav_source_type, dt, self.geom)
             elif self.do_grav:
@@ -1088,7 +1143,7 @@ class Castro:
         # monopole gravity reads a per-zone vector: castro_amd_sources_mf_g carries the gravity FABs of every box (not together
         # with the diffusion term, which only castro_amd_sources_mf_ex places in front of the one-pass kernel)
         one_pass = (hasattr(h, "sources_mf") and os.environ.get("CASTRO_AMD_SOURCES_ONE_PASS", "1") != "0"
-                    and (not getattr(self, "monopole", False) or (hasattr(h, "sources_mf_g") and self.diffusion is None)))
+                    and (not getattr(self, "grav_fab", False) or (hasattr(h, "sources_mf_g") and self.diffusion is None)))
         sources = self._sources_one_pass if one_pass else self._source_stage
         sources(0, dt)
         if self.do_hydro:
@@ -1170,8 +1225,14 @@ class Castro:
             if not ok:
                 raise AdvanceFailure("Advance was unsuccessful: " + reason)      # amrex::Abort in the reference
             self.lastDt = dt
-            return new_dt
-        return self.subcycle_advance_ctu(time, dt)
+        else:
+            new_dt = self.subcycle_advance_ctu(time, dt)
+        # pointmass_update (Castro_advance.cpp:102-107): after the advance or its retry subcycles, before finalize_advance.  It
+        # rewrites zones of S_new: the estimate the advance made is not the one of the state it leaves, and the caller estimates
+        # the next time step afresh (step(): computeNewDt without `est`)
+        if self._pointmass_update():
+            new_dt = None
+        return new_dt
 
     # ---- Castro::subcycle_advance_ctu + retry_advance_ctu (Castro_advance_ctu.cpp:403-768) ------
     def subcycle_advance_ctu(self, time, dt):
@@ -1399,7 +1460,9 @@ class Castro:
         is raised here.  With graph (default: at least 4 steps; a single rank, or RCCL ranks whose collectives the kernel library
         issues itself: _rank_graph_ok) a pair of steps -- the two roles of the ping-pong state buffers -- is captured in a
         hipGraph once, per rank, and replayed.  Falls back to step() when host_free_ok()
-        is false.  Bit-identical to step(): the same kernels with the same dt, computed by the same expressions."""
+        is false -- every run with source terms, so also every run with a point mass: its steps go out stream-ordered through
+        step(), and no graph is captured (the point mass lives on the device all the same, so the accretion itself needs no
+        host round trip).  Bit-identical to step(): the same kernels with the same dt, computed by the same expressions."""
         if nsteps <= 0:
             return
         if not self.host_free_ok():

@@ -32,6 +32,7 @@ struct castro_amd_ctx {
     FabOpsArena diag_arena;                         // device table of castro_amd_integrated_quantities_mf
     DiagWorkspace diag_ws;                          // its rows of partial sums, one per workgroup
     MonoWorkspace mono_ws;                          // castro_amd_radial_mass_mf: rows, counts and device box tables
+    MonoWorkspace pm_ws;                            // castro_amd_add_pointmass_mf / castro_amd_pointmass_*_mf: device tables only
 };
 
 namespace cad {
@@ -248,6 +249,7 @@ void castro_amd_ctx_destroy(castro_amd_ctx* c)
     if (c->diag_arena.p) hipFree(c->diag_arena.p);
     if (c->diag_ws.p) hipFree(c->diag_ws.p);
     mono_workspace_free(&c->mono_ws);
+    mono_workspace_free(&c->pm_ws);
     prof_collect(&c->prof);
     for (auto e : c->prof.pool) hipEventDestroy(e);
     if (c->arena) hipFree(c->arena);
@@ -1071,6 +1073,106 @@ int castro_amd_new_gravity_source_gfab(castro_amd_ctx* c, const castro_amd_fab* 
     hipSetDevice(c->device);
     return launch_new_grav_source_gfab(to_dfab(state_old), to_dfab(state_new), to_dfab(source), M, lo, hi, to_dfab(grav_old),
                                        to_dfab(grav_new), grav_source_type, dt, geom->dx, (hipStream_t)stream, &c->prof);
+}
+
+// ---- the central point mass (pointmass_kernels.hip) -----------------------------------------------------------------------------
+static int pm_geom(const castro_amd_pointmass_params* pm, const castro_amd_geom* geom, PmGeom& G)
+{
+    if (!pm || !geom) return CASTRO_AMD_ERR_ARG;
+    if (geom->coord != 0) return CASTRO_AMD_ERR_UNSUPPORTED;
+    for (int d = 0; d < 3; ++d) {
+        if (!(geom->dx[d] > 0.0)) return CASTRO_AMD_ERR_ARG;
+        G.dx[d] = geom->dx[d]; G.problo[d] = geom->problo[d]; G.center[d] = pm->center[d];
+    }
+    G.Gconst = pm->Gconst;
+    return CASTRO_AMD_OK;
+}
+
+int castro_amd_add_pointmass_mf(castro_amd_ctx* c, int nfabs, const castro_amd_fab* grav_fabs, const castro_amd_pointmass_params* pm,
+                                const castro_amd_geom* geom, const double* d_point_mass, void* stream)
+{
+    if (!c || nfabs < 0 || (nfabs > 0 && !grav_fabs) || !d_point_mass) return CASTRO_AMD_ERR_ARG;
+    PmGeom G;
+    const int rg = pm_geom(pm, geom, G);
+    if (rg != CASTRO_AMD_OK) return rg;
+    // compared byte by byte with the tables already on the device: every byte is set here
+    std::vector<PmFabDev> tab((size_t)nfabs);
+    if (nfabs > 0) std::memset((void*)tab.data(), 0, (size_t)nfabs * sizeof(PmFabDev));
+    for (int i = 0; i < nfabs; ++i) {
+        const castro_amd_fab& f = grav_fabs[i];
+        if (!f.p || f.ncomp != 3) return CASTRO_AMD_ERR_ARG;
+        const DFab F = to_dfab(&f);
+        PmFabDev& T = tab[(size_t)i];
+        T.F.p = F.p; T.F.sy = F.sy; T.F.sz = F.sz; T.F.sn = F.sn;
+        for (int d = 0; d < 3; ++d) {
+            if (f.hi[d] < f.lo[d]) return CASTRO_AMD_ERR_ARG;
+            T.F.lo[d] = F.lo[d]; T.lo[d] = f.lo[d]; T.n[d] = f.hi[d] - f.lo[d] + 1;
+        }
+    }
+    hipSetDevice(c->device);
+    return launch_add_pointmass(nfabs, tab.data(), G, d_point_mass, &c->pm_ws, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_add_pointmass_fab(castro_amd_ctx* c, const castro_amd_fab* grav_fab, const castro_amd_pointmass_params* pm,
+                                 const castro_amd_geom* geom, const double* d_point_mass, void* stream)
+{
+    if (!grav_fab) return CASTRO_AMD_ERR_ARG;
+    return castro_amd_add_pointmass_mf(c, 1, grav_fab, pm, geom, d_point_mass, stream);
+}
+
+// the checks of the two halves of pointmass_update on their box table, the table the kernels read and the cube's low corner
+static int pm_boxes(int nboxes, const castro_amd_pointmass_box* boxes, const castro_amd_pointmass_params* pm,
+                    const castro_amd_geom* geom, std::vector<PmBoxDev>& tab, int clo[3])
+{
+    if (nboxes < 0 || (nboxes > 0 && !boxes)) return CASTRO_AMD_ERR_ARG;
+    PmGeom G;
+    const int rg = pm_geom(pm, geom, G);
+    if (rg != CASTRO_AMD_OK) return rg;
+    for (int d = 0; d < 3; ++d) {
+        // the zone whose lower left corner is at the centre (Castro_pointmass.cpp:38-52); box_size = 2
+        const double q = std::floor((pm->center[d] - geom->problo[d]) / geom->dx[d] + 1.e-8);
+        if (!(std::fabs(q) < 1.0e9)) return CASTRO_AMD_ERR_ARG;
+        clo[d] = (int)q - 2;
+    }
+    tab.resize((size_t)nboxes);
+    if (nboxes > 0) std::memset((void*)tab.data(), 0, (size_t)nboxes * sizeof(PmBoxDev));
+    for (int i = 0; i < nboxes; ++i) {
+        const castro_amd_pointmass_box& b = boxes[i];
+        if (!b.state_old.p || b.state_old.ncomp != NUM_STATE || !fab_contains(&b.state_old, b.lo, b.hi)) return CASTRO_AMD_ERR_ARG;
+        if (!b.state_new.p || b.state_new.ncomp != NUM_STATE || !fab_contains(&b.state_new, b.lo, b.hi)) return CASTRO_AMD_ERR_ARG;
+        const DFab So = to_dfab(&b.state_old), Sn = to_dfab(&b.state_new);
+        PmBoxDev& T = tab[(size_t)i];
+        T.So.p = So.p; T.So.sy = So.sy; T.So.sz = So.sz; T.So.sn = So.sn;
+        T.Sn.p = Sn.p; T.Sn.sy = Sn.sy; T.Sn.sz = Sn.sz; T.Sn.sn = Sn.sn;
+        for (int d = 0; d < 3; ++d) { T.So.lo[d] = So.lo[d]; T.Sn.lo[d] = Sn.lo[d]; T.lo[d] = b.lo[d]; T.hi[d] = b.hi[d]; }
+    }
+    return CASTRO_AMD_OK;
+}
+
+int castro_amd_pointmass_delta_mf(castro_amd_ctx* c, int nboxes, const castro_amd_pointmass_box* boxes,
+                                  const castro_amd_pointmass_params* pm, const castro_amd_geom* geom, double* d_delta, void* stream)
+{
+    if (!c || !d_delta) return CASTRO_AMD_ERR_ARG;
+    std::vector<PmBoxDev> tab;
+    int clo[3];
+    const int rt = pm_boxes(nboxes, boxes, pm, geom, tab, clo);
+    if (rt != CASTRO_AMD_OK) return rt;
+    hipSetDevice(c->device);
+    return launch_pointmass_delta(nboxes, tab.data(), clo, geom->dx[0] * geom->dx[1] * geom->dx[2], d_delta, &c->pm_ws,
+                                  (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_pointmass_apply_mf(castro_amd_ctx* c, int nboxes, const castro_amd_pointmass_box* boxes,
+                                  const castro_amd_pointmass_params* pm, const castro_amd_geom* geom, const double* d_delta,
+                                  double* d_point_mass, void* stream)
+{
+    if (!c || !d_delta || !d_point_mass) return CASTRO_AMD_ERR_ARG;
+    std::vector<PmBoxDev> tab;
+    int clo[3];
+    const int rt = pm_boxes(nboxes, boxes, pm, geom, tab, clo);
+    if (rt != CASTRO_AMD_OK) return rt;
+    hipSetDevice(c->device);
+    return launch_pointmass_apply(nboxes, tab.data(), clo, d_delta, d_point_mass, &c->pm_ws, (hipStream_t)stream, &c->prof);
 }
 
 int castro_amd_saxpy_fab(castro_amd_ctx* c, const castro_amd_fab* dst, double a, const castro_amd_fab* src, int ncomp,

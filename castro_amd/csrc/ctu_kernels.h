@@ -220,6 +220,20 @@ int launch_grav_bc_fill(const DFab& F, const int flo[3], const int fhi[3], const
 int launch_radial_gravity(const MonoGeom& G, const double* d_mass_vol, double* d_radial_grav, hipStream_t stream, Profiler* prof);
 int launch_monopole_grav(const double* d_radial_grav, const MonoGeom& G, const DFab& F, const int lo[3], const int hi[3],
                          hipStream_t stream, Profiler* prof);
+// the central point mass (pointmass_kernels.hip).  One gravity FAB of a castro_amd_add_pointmass_* launch: its whole box
+// [lo, lo + n), ghost zones included; start: the first thread of the FAB, set by the launcher.  One box of a
+// castro_amd_pointmass_delta_mf / _apply_mf launch: the valid zones [lo, hi] of the old and the new state.  Both tables are
+// compared byte by byte with the ones the context has on the device: fill them field by field over zeroed storage
+struct PmFabDev { DFab F; int lo[3], n[3]; long start; };
+struct PmBoxDev { DFab So, Sn; int lo[3], hi[3]; };
+struct PmGeom { double dx[3], problo[3], center[3]; double Gconst; };
+int launch_add_pointmass(int nfab, PmFabDev* fabs, const PmGeom& G, const double* d_mass, MonoWorkspace* ws, hipStream_t stream,
+                         Profiler* prof);
+// clo: the low corner of the 4 x 4 x 4 cube (icen - 2 of Castro_pointmass.cpp:43-65)
+int launch_pointmass_delta(int nbox, const PmBoxDev* boxes, const int clo[3], double vol, double* d_delta, MonoWorkspace* ws,
+                           hipStream_t stream, Profiler* prof);
+int launch_pointmass_apply(int nbox, const PmBoxDev* boxes, const int clo[3], const double* d_delta, double* d_mass,
+                           MonoWorkspace* ws, hipStream_t stream, Profiler* prof);
 // the gravity sources with a per-zone vector: GO / GN are 3-component FABs with one ghost zone around [lo, hi] (type 4)
 int launch_old_grav_source_gfab(const DFab& U, const DFab& SRC, const int lo[3], const int hi[3], const DFab& GO,
                                 int type, double dt, hipStream_t stream, Profiler* prof);

@@ -10,8 +10,19 @@
                                      the level, then the FillPatch of Gravity_Type (_Level.fill_grav: coarse data interpolated in
                                      time and space, siblings, physical boundaries)
 
-Levels finer than `level` do not enter.  Not provided: GR_GRAV, the point mass, gravity.max_solve_level, domains with a periodic
-direction (the Gravity_Type FillPatch across a periodic boundary is not built), thermal diffusion on AMR levels.
+  PointMass                          castro.use_point_mass / castro.point_mass / castro.point_mass_fix_solution: a mass M at
+                                     problem::center, ONE device double per run (per CastroAmr hierarchy: castro::point_mass is
+                                     one global shared by the levels).  add(): Gravity::add_pointmass_to_gravity (:2903-2948) over
+                                     the grown gravity FABs, called at the END of get_old / get_new_grav_vector (:902-907,
+                                     :975-980) -- after the interpolation and after the Gravity_Type FillPatch, so a coarse-fine
+                                     ghost zone of a refined level holds the coarse level's data, which already carry the coarse
+                                     level's point-mass term, PLUS the level's own term: the reference's result, reproduced.
+                                     update(): Castro::pointmass_update (Source/gravity/Castro_pointmass.cpp), two launches with
+                                     the sum over the ranks between them and no host round trip.
+
+Levels finer than `level` do not enter.  Not provided: GR_GRAV, gravity.max_solve_level, a potential (phiGrav), checkpoint / restart
+of the point mass, domains with a periodic direction (the Gravity_Type FillPatch across a periodic boundary is not built), thermal
+diffusion on AMR levels, constant gravity plus a point mass on AMR levels.
 """
 from . import _lib as L
 
@@ -32,6 +43,40 @@ def time_branch(time, t_old, t_new):
                        % (time, t_old, t_new))
 
 
+class PointMass:
+    """The central point mass of a run.  buf: two device doubles, [point_mass, mass_change_at_center]."""
+
+    def __init__(self, hydro, mass, fix_solution=False, Gconst=L.GCONST):
+        for name in ("add_pointmass_mf", "pointmass_delta_mf", "pointmass_apply_mf"):
+            if not hasattr(hydro, name):
+                raise RuntimeError("castro_amd: this backend has no %s; there is no host fallback" % name)
+        self.fix_solution, self.Gconst = bool(fix_solution), float(Gconst)
+        self.buf = hydro.alloc(1, (0, 0, 0), (1, 0, 0)).reshape(2)
+        self.buf[0] = float(mass)
+        self.mass, self.delta = self.buf[:1], self.buf[1:]
+        self.nupdates = 0                       # pointmass_update calls that ran (whatever the sign of the change)
+
+    def value(self):
+        """the point mass as the device holds it (one copy to the host)"""
+        return float(self.buf[0])
+
+    def params(self, center):
+        return L.make_pointmass(center, self.Gconst)
+
+    def add(self, hydro, fabs, center, geom):
+        """Gravity::add_pointmass_to_gravity over every FAB of `fabs` (HipHydro.make_grav_fabs): their whole boxes"""
+        hydro.add_pointmass_mf(fabs, self.params(center), geom, self.mass)
+
+    def update(self, hydro, comm, boxes, center, geom):
+        """Castro::pointmass_update over `boxes` (HipHydro.make_pointmass_boxes): the caller has checked level == finest_level
+        and point_mass_fix_solution"""
+        pm = self.params(center)
+        hydro.pointmass_delta_mf(boxes, pm, geom, self.delta)
+        comm.allreduce_sum(self.delta)          # ParallelDescriptor::ReduceRealSum(mass_change_at_center)
+        hydro.pointmass_apply_mf(boxes, pm, geom, self.delta, self.mass)
+        self.nupdates += 1
+
+
 class MonopoleGravity:
     def __init__(self, drdxfac=1, Gconst=L.GCONST, center=None):
         """drdxfac: gravity.drdxfac; Gconst: the reference takes C::Gconst from its Microphysics constants (the default is the cgs
@@ -41,6 +86,7 @@ class MonopoleGravity:
         if self.drdxfac < 1:
             raise ValueError("gravity.drdxfac must be at least 1, not %d" % self.drdxfac)
         self.amr = None
+        self.point_mass = None                  # the PointMass of the hierarchy (CastroAmr(use_point_mass=True))
         self._lev = {}
 
     # ---- the hierarchy this object belongs to ---------------------------------------------------------------
@@ -157,6 +203,12 @@ class MonopoleGravity:
         for b in lev.mine:
             lev.hydro.monopole_grav(rg, mono, lev.geom, getattr(b, name), b.gravbox)
         lev.fill_grav(name, a)
+        if self.point_mass is not None and lev.mine:
+            # add_pointmass_to_gravity comes last (Gravity.cpp:902-907, 975-980): on top of whatever the FillPatch has put into
+            # the ghost zones -- on a refined level the coarse data with the coarse level's point-mass term
+            h = lev.hydro
+            fabs = h.make_grav_fabs([(getattr(b, name), b.gravbox) for b in lev.mine])       # descriptors are memoised
+            self.point_mass.add(h, fabs, self.problem_center(), lev.geom)
 
     def get_old_grav_vector(self, level, time=None, a=0.0):
         """grav_old of every box of `level` at the level's old time; a: where that time lies in the parent's [old, new]"""

@@ -262,6 +262,42 @@ class HipHydro:
             arr[i] = L.fab_of(g, *box)
         return arr
 
+    # ---- the central point mass (castro.use_point_mass; Gravity.cpp:2903-2948, Castro_pointmass.cpp) ---------------------
+    def add_pointmass(self, grav, grav_box, pm, geom, mass, stream=None):
+        """castro_amd_add_pointmass_fab: Gravity::add_pointmass_to_gravity over the whole box of the 3-component FAB `grav`; pm:
+        _lib.make_pointmass(center, Gconst); mass: a device tensor whose first double is the point mass"""
+        L.check(self.lib.castro_amd_add_pointmass_fab(self.h, C.byref(L.fab_of(grav, *grav_box)), C.byref(pm), C.byref(geom),
+                                                      C.c_void_p(mass.data_ptr()), _stream_ptr(stream)), "add_pointmass_fab")
+
+    def add_pointmass_mf(self, fabs, pm, geom, mass, stream=None):
+        """castro_amd_add_pointmass_mf: add_pointmass for every FAB of `fabs` (make_grav_fabs) in one launch"""
+        if len(fabs):
+            L.check(self.lib.castro_amd_add_pointmass_mf(self.h, len(fabs), fabs, C.byref(pm), C.byref(geom),
+                                                         C.c_void_p(mass.data_ptr()), _stream_ptr(stream)), "add_pointmass_mf")
+
+    @staticmethod
+    def make_pointmass_boxes(specs):
+        """ctypes array of castro_amd_pointmass_box from (lo, hi, (S_old, box), (S_new, box))."""
+        arr = (L.PointMassBox * max(len(specs), 1))()
+        for pb, (lo, hi, so, sn) in zip(arr, specs):
+            for d in range(3):
+                pb.lo[d], pb.hi[d] = lo[d], hi[d]
+            pb.state_old, pb.state_new = L.fab_of(so[0], *so[1]), L.fab_of(sn[0], *sn[1])
+        return arr, len(specs)
+
+    def pointmass_delta_mf(self, boxes, pm, geom, delta, stream=None):
+        """castro_amd_pointmass_delta_mf: the mass that arrived in the 4 x 4 x 4 zones around the centre, over the boxes of `boxes`
+        (make_pointmass_boxes), into the first double of the device tensor `delta` (overwritten).  Deterministic."""
+        arr, n = boxes
+        L.check(self.lib.castro_amd_pointmass_delta_mf(self.h, n, arr, C.byref(pm), C.byref(geom), C.c_void_p(delta.data_ptr()),
+                                                       _stream_ptr(stream)), "pointmass_delta_mf")
+
+    def pointmass_apply_mf(self, boxes, pm, geom, delta, mass, stream=None):
+        """castro_amd_pointmass_apply_mf: if delta > 0, mass += delta and the cube zones of S_new take S_old's values"""
+        arr, n = boxes
+        L.check(self.lib.castro_amd_pointmass_apply_mf(self.h, n, arr, C.byref(pm), C.byref(geom), C.c_void_p(delta.data_ptr()),
+                                                       C.c_void_p(mass.data_ptr()), _stream_ptr(stream)), "pointmass_apply_mf")
+
     def sources_mf_g(self, stage, boxes, grav_old, grav_new, grav_source_type, rot, geom, params, dt, ntimes=1, stream=None,
                      sponge=None):
         """castro_amd_sources_mf_g: sources_mf with the gravity of box i read from grav_old[i] / grav_new[i] (make_grav_fabs).

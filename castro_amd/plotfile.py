@@ -9,6 +9,9 @@ Reference behaviour restated:
                                            raw little-endian doubles, i fastest, component slowest); format per
                                            SURVEY.md D.4 -- it cannot be checked against an AMReX reader here.
 
+With castro.use_point_mass the plotfile directory also holds the file `point_mass`: the value as one line, %.17g
+(Castro_io.cpp:1137-1150); the readers return it as "point_mass" (None when the file is absent).
+
 The field data are produced on the device (state copy + castro_amd_derive_fab); this module only does the
 host-side file layout.  One rank = one box = one Cell_D file; rank 0 writes Header and Cell_H.
 """
@@ -35,6 +38,21 @@ def _g(x):
 
 def _box(lo, hi):
     return "((%d,%d,%d) (%d,%d,%d) (0,0,0))" % (lo[0], lo[1], lo[2], hi[0], hi[1], hi[2])
+
+
+def write_point_mass(dirname, driver):
+    """the `point_mass` file of plotFileOutput (Castro_io.cpp:1137-1150), by the I/O rank, when castro.use_point_mass is set"""
+    if getattr(driver, "use_point_mass", False):
+        with open(os.path.join(dirname, "point_mass"), "w") as f:
+            f.write(_g(driver.point_mass) + "\n")
+
+
+def read_point_mass(dirname):
+    path = os.path.join(dirname, "point_mass")
+    if not os.path.exists(path):
+        return None
+    with open(path) as f:
+        return float(f.read().split()[0])
 
 
 def plot_data(castro, derive=None):
@@ -136,6 +154,11 @@ def write_plotfile(dirname, castro, derive=None, job_info=None):
                 f.write("castro.%s = %s\n" % (fld, getattr(castro.params, fld)))
             if job_info:
                 f.write(str(job_info) + "\n")
+    if getattr(castro, "use_point_mass", False):
+        pm = castro.point_mass                  # every rank reads its device copy; the I/O rank writes
+        if rank == 0:
+            with open(os.path.join(dirname, "point_mass"), "w") as f:
+                f.write(_g(pm) + "\n")
     comm.barrier()
     return names
 
@@ -197,6 +220,7 @@ def write_plotfile_amr(dirname, amr, derive=None):
                 for arr in fabs:
                     f.write("".join("%.16e," % fn(arr[n]) for n in range(ncomp)) + "\n")
                 f.write("\n")
+    write_point_mass(dirname, amr)
     return names
 
 
@@ -238,7 +262,7 @@ def read_plotfile_amr(dirname):
         if ngrids == 1:
             lev.update(box=boxes[0], data=fabs[0])
         out.append(lev)
-    return dict(names=names, time=time, levels=out)
+    return dict(names=names, time=time, levels=out, point_mass=read_point_mass(dirname))
 
 
 def read_plotfile(dirname):
@@ -288,4 +312,4 @@ def read_plotfile(dirname):
         s = [lo[d] - dom_lo[d] for d in range(3)]
         data[:, s[2]:s[2] + m[2], s[1]:s[1] + m[1], s[0]:s[0] + m[0]] = a
     return dict(names=names, time=time, nstep=nstep, prob_lo=prob_lo, prob_hi=prob_hi, domain=(dom_lo, dom_hi),
-                dx=dx, boxes=boxes, data=data)
+                dx=dx, boxes=boxes, data=data, point_mass=read_point_mass(dirname))

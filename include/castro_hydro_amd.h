@@ -59,7 +59,9 @@ extern "C" {
  *      castro_amd_sources_mf_ex; castro_amd_integrated_quantities_mf, castro_amd_diag_workgroups (struct castro_amd_diag_box);
  *      castro_amd_radial_mass_mf, castro_amd_radial_gravity, castro_amd_monopole_grav_fab (struct castro_amd_monopole_params),
  *      castro_amd_old_gravity_source_gfab, castro_amd_new_gravity_source_gfab;
- *      castro_amd_new_sponge_source_fab (struct castro_amd_sponge), castro_amd_sources_mf_opts (struct castro_amd_source_opts).
+ *      castro_amd_new_sponge_source_fab (struct castro_amd_sponge), castro_amd_sources_mf_opts (struct castro_amd_source_opts);
+ *      castro_amd_add_pointmass_fab / _mf, castro_amd_pointmass_delta_mf, castro_amd_pointmass_apply_mf (structs
+ *      castro_amd_pointmass_params, castro_amd_pointmass_box).
  * A caller checks `castro_amd_abi_version() == CASTRO_AMD_ABI_VERSION` once after loading the library; a mismatch means
  * the library was built from another revision of this header (a 0.2 caller with 2-double vectors would be written 8 bytes
  * out of bounds by a 0.3 library). */
@@ -656,6 +658,56 @@ typedef struct castro_amd_source_opts {
 int castro_amd_sources_mf_opts(castro_amd_ctx *ctx, int stage, int nboxes, const castro_amd_source_box *boxes,
                                const castro_amd_source_opts *opts, const castro_amd_geom *geom, const castro_amd_params *params,
                                double dt, int clean_ntimes, void *stream);
+
+/* The central point mass of the gravity module (castro.use_point_mass = 1, castro.point_mass, castro.point_mass_fix_solution):
+ * a mass M at problem::center whose field is added to the gravity vector of every gravity.gravity_type, ConstantGrav included.
+ * M lives in ONE device double of the caller (d_point_mass): the kernels read it there and castro_amd_pointmass_apply_mf adds
+ * to it, so an accreting run needs no host round trip between its steps.  3-D Cartesian: CASTRO_AMD_ERR_UNSUPPORTED unless
+ * geom->coord == 0. */
+typedef struct castro_amd_pointmass_params {
+    double center[3];                           /* problem::center */
+    double Gconst;                              /* C::Gconst */
+} castro_amd_pointmass_params;
+/* Gravity::add_pointmass_to_gravity (Source/gravity/Gravity.cpp:2903-2948, the phi part left out: there is no PhiGrav_Type
+ * here) over the WHOLE box of grav_fab (3 components), ghost zones included -- the reference runs over the grown box.  Per zone
+ *   x, y, z = problo + (i + 1/2) dx - center;  rsq = x*x + y*y + z*z;  radial_force = -Gconst * M / rsq;  rinv = 1 / sqrt(rsq)
+ *   grav(n) += radial_force * (x_n * rinv)
+ * in that order (`exact`: the bits of the expression; `contract`: with the build's FMA contraction).  The reference calls it at
+ * the END of get_old_grav_vector / get_new_grav_vector (:902-907, :975-980): after interpolate_monopole_grav and after the
+ * Gravity_Type FillPatch (castro_amd_grav_bc_fill_fab and the coarse-fine interpolation).  A zone whose centre coincides with
+ * `center` divides by zero, as in the reference. */
+int castro_amd_add_pointmass_fab(castro_amd_ctx *ctx, const castro_amd_fab *grav_fab, const castro_amd_pointmass_params *pm,
+                                 const castro_amd_geom *geom, const double *d_point_mass, void *stream);
+/* The same for grav_fabs[0 .. nfabs) -- the gravity FABs of the boxes of a level -- in one launch; the bits of nfabs
+ * castro_amd_add_pointmass_fab calls.  The table is kept on the device by content: a call with a table the context has seen
+ * neither allocates nor synchronises and can be captured into a graph. */
+int castro_amd_add_pointmass_mf(castro_amd_ctx *ctx, int nfabs, const castro_amd_fab *grav_fabs,
+                                const castro_amd_pointmass_params *pm, const castro_amd_geom *geom, const double *d_point_mass,
+                                void *stream);
+/* One box of Castro::pointmass_update: the valid zones [lo, hi] of the old and the new State_Type data (NUM_STATE components). */
+typedef struct castro_amd_pointmass_box {
+    int lo[3], hi[3];
+    castro_amd_fab state_old, state_new;
+} castro_amd_pointmass_box;
+/* Castro::pointmass_update (Source/gravity/Castro_pointmass.cpp; called from Castro::advance, Castro_advance.cpp:102-107, on
+ * the finest level when castro.point_mass_fix_solution = 1) in two stream-ordered halves with the sum over the ranks between
+ * them.  The cube: icen = floor((center[d] - problo[d]) / dx[d] + 1e-8), the zones icen - 2 .. icen + 1 of every direction,
+ * clipped to each box (:38-65).
+ *   castro_amd_pointmass_delta_mf   *d_delta = sum over the cube zones of the boxes of dx*dy*dz * (state_new(URHO) -
+ *                                   state_old(URHO)) (:67-86), OVERWRITTEN.  No floating-point atomics: one wave, the terms
+ *                                   added in the order of the zone index inside the cube -- the same bits for any cut of the
+ *                                   level into boxes, on every call and on every stream.  The boxes must be disjoint.
+ *   (the caller sums *d_delta over the ranks: ParallelDescriptor::ReduceRealSum, :86)
+ *   castro_amd_pointmass_apply_mf   if *d_delta > 0: *d_point_mass += *d_delta, and every cube zone of every box copies all
+ *                                   NUM_STATE components from state_old to state_new (:88-153); otherwise nothing is written.
+ * nboxes = 0 is accepted by both (a rank without a box of the level: delta 0, and the apply still moves the summed change into
+ * its copy of the point mass).  Tables by content, as above. */
+int castro_amd_pointmass_delta_mf(castro_amd_ctx *ctx, int nboxes, const castro_amd_pointmass_box *boxes,
+                                  const castro_amd_pointmass_params *pm, const castro_amd_geom *geom, double *d_delta,
+                                  void *stream);
+int castro_amd_pointmass_apply_mf(castro_amd_ctx *ctx, int nboxes, const castro_amd_pointmass_box *boxes,
+                                  const castro_amd_pointmass_params *pm, const castro_amd_geom *geom, const double *d_delta,
+                                  double *d_point_mass, void *stream);
 
 /* Two-level AMR building blocks, refinement ratio 2 (first slice).  The reference calls AMReX for
  * all of these [3P, not in the reference tree]; the arithmetic is restated from the published descriptions and is
