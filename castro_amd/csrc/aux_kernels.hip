@@ -952,7 +952,7 @@ static const SrcBoxDev& src_box_host(const SrcBoxGDev& b) { return b.box; }
 
 template <class BOX>
 static int launch_sources_apply_t(int stage, int nbox, const BOX* boxes, const double* grav, int grav_type, const castro_amd_rotation* rot,
-                                  const castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
+                                  const castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, StagedTable* arena,
                                   hipStream_t stream, Profiler* prof, int diff_on, const castro_amd_sponge* sponge)
 {
     constexpr bool GFAB = std::is_same<BOX, SrcBoxGDev>::value;
@@ -964,17 +964,10 @@ static int launch_sources_apply_t(int stage, int nbox, const BOX* boxes, const d
         start[(size_t)r + 1] = start[(size_t)r] + n;
     }
     if (start.back() <= 0) return 0;
-    const size_t bo = (size_t)nbox * sizeof(BOX), bs = start.size() * sizeof(long);
-    const size_t need = ((bo + 255) & ~(size_t)255) + bs;
-    if (need > arena->bytes) {
-        if (arena->p) { (void)hipStreamSynchronize(stream); (void)hipFree(arena->p); arena->p = nullptr; arena->bytes = 0; }
-        if (hipMalloc(&arena->p, 2 * need) != hipSuccess) return -3;
-        arena->bytes = 2 * need;
-    }
-    char* base = (char*)arena->p;
-    long* dstart = (long*)(base + ((bo + 255) & ~(size_t)255));
-    if (hipMemcpyAsync(base, boxes, bo, hipMemcpyHostToDevice, stream) != hipSuccess) return -4;
-    if (hipMemcpyAsync(dstart, start.data(), bs, hipMemcpyHostToDevice, stream) != hipSuccess) return -4;
+    const BOX* dbox;
+    const long* dstart;
+    const int rt = arena->stage(boxes, (size_t)nbox, start.data(), start.size(), stream, dbox, dstart);
+    if (rt != 0) return rt;
     GravDev G;
     G.on = (grav || GFAB) ? 1 : 0; G.type = grav_type;
     for (int d = 0; d < 3; ++d) G.g[d] = grav ? grav[d] : 0.0;
@@ -982,39 +975,29 @@ static int launch_sources_apply_t(int stage, int nbox, const BOX* boxes, const d
     std::memset(&R, 0, sizeof(R));
     if (rot) R = make_rotdev(rot, geom, dt);
     const unsigned nb = (unsigned)((start.back() + 255) / 256);
-    if (sponge && stage == 1) {
-        // the sponge has no old-time source: stage 0 with a sponge is the launch below
-        prof_begin(prof, "k_sources_new_sponge", stream);
-        hipLaunchKernelGGL((k_sources_apply<1, GFAB, BOX, SpongeDev>), dim3(nb), dim3(256), 0, stream, (const BOX*)base, (const long*)dstart, nbox, G, R,
-                           rot ? 1 : 0, dt, geom->dx[0], geom->dx[1], geom->dx[2], P, ntimes, diff_on, make_spongedev(sponge, geom, dt));
-        prof_end(prof, stream);
-        return launch_status();
-    }
-    prof_begin(prof, stage == 0 ? "k_sources_old" : "k_sources_new", stream);
-    if constexpr (GFAB) {
-        if (stage == 0) hipLaunchKernelGGL((k_sources_apply<0, true, SrcBoxGDev>), dim3(nb), dim3(256), 0, stream, (const SrcBoxGDev*)base, (const long*)dstart, nbox, G, R,
-                                           rot ? 1 : 0, dt, geom->dx[0], geom->dx[1], geom->dx[2], P, ntimes, diff_on);
-        else hipLaunchKernelGGL((k_sources_apply<1, true, SrcBoxGDev>), dim3(nb), dim3(256), 0, stream, (const SrcBoxGDev*)base, (const long*)dstart, nbox, G, R,
-                                rot ? 1 : 0, dt, geom->dx[0], geom->dx[1], geom->dx[2], P, ntimes, diff_on);
-    } else {
-    if (stage == 0) hipLaunchKernelGGL((k_sources_apply<0, false, SrcBoxDev>), dim3(nb), dim3(256), 0, stream, (const SrcBoxDev*)base, (const long*)dstart, nbox, G, R,
-                                       rot ? 1 : 0, dt, geom->dx[0], geom->dx[1], geom->dx[2], P, ntimes, diff_on);
-    else hipLaunchKernelGGL((k_sources_apply<1, false, SrcBoxDev>), dim3(nb), dim3(256), 0, stream, (const SrcBoxDev*)base, (const long*)dstart, nbox, G, R,
-                            rot ? 1 : 0, dt, geom->dx[0], geom->dx[1], geom->dx[2], P, ntimes, diff_on);
-    }
+    // the sponge has no old-time source: stage 0 with a sponge is the launch without one
+    const bool sp = sponge && stage == 1;
+    prof_begin(prof, sp ? "k_sources_new_sponge" : stage == 0 ? "k_sources_old" : "k_sources_new", stream);
+    auto launch = [&](auto kernel, auto... tail) {
+        hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, stream, dbox, dstart, nbox, G, R, rot ? 1 : 0, dt, geom->dx[0], geom->dx[1],
+                           geom->dx[2], P, ntimes, diff_on, tail...);
+    };
+    if (sp) launch(k_sources_apply<1, GFAB, BOX, SpongeDev>, make_spongedev(sponge, geom, dt));
+    else if (stage == 0) launch(k_sources_apply<0, GFAB, BOX>);
+    else launch(k_sources_apply<1, GFAB, BOX>);
     prof_end(prof, stream);
     return launch_status();
 }
 
 int launch_sources_apply(int stage, int nbox, const SrcBoxDev* boxes, const double* grav, int grav_type, const castro_amd_rotation* rot,
-                         const castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
+                         const castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, StagedTable* arena,
                          hipStream_t stream, Profiler* prof, int diff_on, const castro_amd_sponge* sponge)
 {
     return launch_sources_apply_t(stage, nbox, boxes, grav, grav_type, rot, geom, P, dt, ntimes, arena, stream, prof, diff_on, sponge);
 }
 
 int launch_sources_apply_gfab(int stage, int nbox, const SrcBoxGDev* boxes, int grav_type, const castro_amd_rotation* rot,
-                              const castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
+                              const castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, StagedTable* arena,
                               hipStream_t stream, Profiler* prof, int diff_on, const castro_amd_sponge* sponge)
 {
     return launch_sources_apply_t(stage, nbox, boxes, nullptr, grav_type, rot, geom, P, dt, ntimes, arena, stream, prof, diff_on, sponge);
@@ -1321,7 +1304,7 @@ __device__ __forceinline__ void fab_op_thread(const FabOp& o, long t, const DevP
 
 int launch_fab_ops(int nops, const DFab* D, const DFab* X, const DFab* Y, const int* lo, const int* hi, const int* kind,
                    const int* dir, const int* side, const int* ncomp, const double* a, const double* b, hipStream_t stream, Profiler* prof,
-                   const DevParams* Pp, FabOpsArena* arena)
+                   const DevParams* Pp, StagedTable* arena)
 {
     DevParams P;
     if (Pp) P = *Pp; else std::memset(&P, 0, sizeof(P));
@@ -1358,23 +1341,16 @@ int launch_fab_ops(int nops, const DFab* D, const DFab* X, const DFab* Y, const 
             start.push_back(start.back() + n);
         }
         if (ops.empty()) return 0;
-        const size_t bo = ops.size() * sizeof(FabOp), bs = start.size() * sizeof(long);
-        const size_t need = ((bo + 255) & ~(size_t)255) + bs;
-        if (need > arena->bytes) {
-            if (arena->p) { hipStreamSynchronize(stream); hipFree(arena->p); arena->p = nullptr; arena->bytes = 0; }
-            if (hipMalloc(&arena->p, 2 * need) != hipSuccess) return -3;
-            arena->bytes = 2 * need;
-        }
-        char* base = (char*)arena->p;
-        long* dstart = (long*)(base + ((bo + 255) & ~(size_t)255));
-        if (hipMemcpyAsync(base, ops.data(), bo, hipMemcpyHostToDevice, stream) != hipSuccess) return -4;
-        if (hipMemcpyAsync(dstart, start.data(), bs, hipMemcpyHostToDevice, stream) != hipSuccess) return -4;
+        const FabOp* dops;
+        const long* dstart;
+        const int rt = arena->stage(ops.data(), ops.size(), start.data(), start.size(), stream, dops, dstart);
+        if (rt != 0) return rt;
         static const char* const kind_name[9] = { "k_fab_ops_copy", "k_fab_ops_lincomb", "k_fab_ops_crse_init", "k_fab_ops_fine_add",
                                                   "k_fab_ops_reflux", "k_fab_ops_clean", "k_fab_ops_interp_clean", "k_fab_ops_avgdown",
                                                   "k_fab_ops_interp" };
         prof_begin(prof, kind_name[ops[0].kind >= 0 && ops[0].kind < 9 ? ops[0].kind : 0], stream);     // tables are built per purpose: one kind each
         hipLaunchKernelGGL(k_fab_ops_mem, dim3((unsigned)((start.back() + 255) / 256)), dim3(256), 0, stream,
-                           (const FabOp*)base, (const long*)dstart, (int)ops.size(), P);
+                           dops, dstart, (int)ops.size(), P);
         prof_end(prof, stream);
         return launch_status();
     }

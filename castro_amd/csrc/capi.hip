@@ -25,14 +25,15 @@ struct castro_amd_ctx {
     // kernel), forked from and joined to the caller's stream with events inside one call: CASTRO_AMD_SIDE_STREAM=0 turns it off
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    FabOpsArena ops_arena;                          // device table of castro_amd_fab_ops_p calls with more than 16 operations
-    FabOpsArena level_arena;                        // device table of a level-wide hydro launch (castro_amd_ctu_hydro_mf)
-    FabOpsArena diff_arena;                         // device table of a thermal-diffusion launch (castro_amd_temp_diffusion_*)
+    // device tables (dev_table.h), one per launch family: a source call with diffusion has two of them in flight
+    StagedTable ops_arena;                          // castro_amd_fab_ops_p calls with more than 16 operations, castro_amd_sources_mf*
+    StagedTable level_arena;                        // a level-wide hydro launch (castro_amd_ctu_hydro_mf)
+    StagedTable diff_arena;                         // a thermal-diffusion launch (castro_amd_temp_diffusion_*)
     hipEvent_t mf_fork = nullptr, mf_join = nullptr;   // castro_amd_ctu_hydro_mf: fork from / join to the caller's stream
-    FabOpsArena diag_arena;                         // device table of castro_amd_integrated_quantities_mf
+    StagedTable diag_arena;                         // castro_amd_integrated_quantities_mf
     DiagWorkspace diag_ws;                          // its rows of partial sums, one per workgroup
     MonoWorkspace mono_ws;                          // castro_amd_radial_mass_mf: rows, counts and device box tables
-    MonoWorkspace pm_ws;                            // castro_amd_add_pointmass_mf / castro_amd_pointmass_*_mf: device tables only
+    TableCache pm_tables{32};                       // castro_amd_add_pointmass_mf / castro_amd_pointmass_*_mf
 };
 
 namespace cad {
@@ -243,13 +244,10 @@ void castro_amd_ctx_destroy(castro_amd_ctx* c)
     if (c->ev_join) hipEventDestroy(c->ev_join);
     if (c->mf_fork) hipEventDestroy(c->mf_fork);
     if (c->mf_join) hipEventDestroy(c->mf_join);
-    if (c->ops_arena.p) hipFree(c->ops_arena.p);
-    if (c->level_arena.p) hipFree(c->level_arena.p);
-    if (c->diff_arena.p) hipFree(c->diff_arena.p);
-    if (c->diag_arena.p) hipFree(c->diag_arena.p);
+    for (StagedTable* t : { &c->ops_arena, &c->level_arena, &c->diff_arena, &c->diag_arena }) t->release();
     if (c->diag_ws.p) hipFree(c->diag_ws.p);
     mono_workspace_free(&c->mono_ws);
-    mono_workspace_free(&c->pm_ws);
+    c->pm_tables.release();
     prof_collect(&c->prof);
     for (auto e : c->prof.pool) hipEventDestroy(e);
     if (c->arena) hipFree(c->arena);
@@ -516,6 +514,18 @@ int castro_amd_old_gravity_source_fab(castro_amd_ctx* c, const castro_amd_fab* s
     return launch_old_grav_source(to_dfab(state), to_dfab(source), lo, hi, grav, grav_source_type, dt, (hipStream_t)stream, &c->prof);
 }
 
+// the three mass-flux FABs of [lo, hi]: one component each, on the faces of their direction
+static bool mass_flux_dfabs(const castro_amd_fab mass_fluxes[3], const int lo[3], const int hi[3], DFab M[3])
+{
+    for (int d = 0; d < 3; ++d) {
+        int fhi[3] = { hi[0], hi[1], hi[2] };
+        fhi[d] += 1;
+        if (!mass_fluxes[d].p || mass_fluxes[d].ncomp != 1 || !fab_contains(&mass_fluxes[d], lo, fhi)) return false;
+        M[d] = to_dfab(&mass_fluxes[d]);
+    }
+    return true;
+}
+
 int castro_amd_new_gravity_source_fab(castro_amd_ctx* c, const castro_amd_fab* state_old, const castro_amd_fab* state_new,
                                       const castro_amd_fab* source, const castro_amd_fab mass_fluxes[3],
                                       const int lo[3], const int hi[3], const double grav[3], int grav_source_type,
@@ -527,12 +537,7 @@ int castro_amd_new_gravity_source_fab(castro_amd_ctx* c, const castro_amd_fab* s
     if (grav_source_type < 1 || grav_source_type > 4 || geom->coord != 0) return CASTRO_AMD_ERR_ARG;
     if (!fab_contains(state_old, lo, hi) || !fab_contains(state_new, lo, hi) || !fab_contains(source, lo, hi)) return CASTRO_AMD_ERR_ARG;
     DFab M[3];
-    for (int d = 0; d < 3; ++d) {
-        int fhi[3] = { hi[0], hi[1], hi[2] };
-        fhi[d] += 1;
-        if (!mass_fluxes[d].p || mass_fluxes[d].ncomp != 1 || !fab_contains(&mass_fluxes[d], lo, fhi)) return CASTRO_AMD_ERR_ARG;
-        M[d] = to_dfab(&mass_fluxes[d]);
-    }
+    if (!mass_flux_dfabs(mass_fluxes, lo, hi, M)) return CASTRO_AMD_ERR_ARG;
     hipSetDevice(c->device);
     return launch_new_grav_source(to_dfab(state_old), to_dfab(state_new), to_dfab(source), M, lo, hi, grav, grav_source_type,
                                   dt, geom->dx, (hipStream_t)stream, &c->prof);
@@ -561,12 +566,7 @@ int castro_amd_new_rotation_source_fab(castro_amd_ctx* c, const castro_amd_fab* 
     if (rot->rot_source_type < 1 || rot->rot_source_type > 4 || geom->coord != 0 || !(dt > 0.0)) return CASTRO_AMD_ERR_ARG;
     if (!fab_contains(state_old, lo, hi) || !fab_contains(state_new, lo, hi) || !fab_contains(source, lo, hi)) return CASTRO_AMD_ERR_ARG;
     DFab M[3];
-    for (int d = 0; d < 3; ++d) {
-        int fhi[3] = { hi[0], hi[1], hi[2] };
-        fhi[d] += 1;
-        if (!mass_fluxes[d].p || mass_fluxes[d].ncomp != 1 || !fab_contains(&mass_fluxes[d], lo, fhi)) return CASTRO_AMD_ERR_ARG;
-        M[d] = to_dfab(&mass_fluxes[d]);
-    }
+    if (!mass_flux_dfabs(mass_fluxes, lo, hi, M)) return CASTRO_AMD_ERR_ARG;
     hipSetDevice(c->device);
     return launch_new_rot_source(to_dfab(state_old), to_dfab(state_new), to_dfab(source), M, lo, hi, rot, geom, dt,
                                  (hipStream_t)stream, &c->prof);
@@ -685,6 +685,94 @@ int castro_amd_estdt_temp_diffusion_mf(castro_amd_ctx* c, int nboxes, const cast
     return CASTRO_AMD_OK;
 }
 
+// the checks of castro_amd_new_sponge_source_fab; stage 0 takes a sponge and adds nothing
+static bool sponge_ok(const castro_amd_sponge* sponge, const castro_amd_geom* geom, double dt)
+{
+    return !sponge || (geom->coord == 0 && dt > 0.0 && sponge->timescale > 0.0);
+}
+
+static bool grav_fab_ok(const castro_amd_fab* g, const int lo[3], const int hi[3], int grav_source_type);
+
+// the checks of one box of the one-pass sources, and the box as the kernel reads it
+static int src_box(SrcBoxDev& T, const castro_amd_source_box& b, bool mass_fluxes)
+{
+    if (!b.S_old.p || !b.S_new.p || !b.source.p || b.S_old.ncomp != NUM_STATE || b.S_new.ncomp != NUM_STATE || b.source.ncomp < 7)
+        return CASTRO_AMD_ERR_ARG;
+    if (!fab_contains(&b.S_old, b.lo, b.hi) || !fab_contains(&b.S_new, b.lo, b.hi) || !fab_contains(&b.source, b.lo, b.hi)) return CASTRO_AMD_ERR_ARG;
+    T.So = to_dfab(&b.S_old); T.Sn = to_dfab(&b.S_new); T.Src = to_dfab(&b.source);
+    T.M0 = T.M1 = T.M2 = to_dfab(nullptr);
+    if (mass_fluxes) {
+        DFab M[3];
+        if (!mass_flux_dfabs(b.mass_flux, b.lo, b.hi, M)) return CASTRO_AMD_ERR_ARG;
+        T.M0 = M[0]; T.M1 = M[1]; T.M2 = M[2];
+    }
+    for (int d = 0; d < 3; ++d) {
+        if (b.source.hi[d] < b.source.lo[d]) return CASTRO_AMD_ERR_ARG;
+        T.lo[d] = b.source.lo[d]; T.n[d] = b.source.hi[d] - b.source.lo[d] + 1;
+        T.vlo[d] = b.lo[d]; T.vhi[d] = b.hi[d];
+    }
+    T.nsc = b.source.ncomp;
+    return CASTRO_AMD_OK;
+}
+
+// The one-pass sources behind their four entry points.  Gravity is a vector for the level (o.grav) or one FAB per box
+// (o.grav_old / o.grav_new), not both; the FABs do not go together with diffusion.
+static int sources_mf_impl(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes, const castro_amd_source_opts& o,
+                           const castro_amd_geom* geom, const castro_amd_params* params, double dt, int clean_ntimes, void* stream)
+{
+    const bool gfab = o.grav_old || o.grav_new, grav_on = gfab || o.grav;
+    if (gfab && o.grav) return CASTRO_AMD_ERR_ARG;
+    if (gfab && o.diff) return CASTRO_AMD_ERR_UNSUPPORTED;
+    if (!c || (stage != 0 && stage != 1) || nboxes < 0 || (nboxes > 0 && !boxes) || !geom || !params || clean_ntimes < 0) return CASTRO_AMD_ERR_ARG;
+    if (!sponge_ok(o.sponge, geom, dt)) return CASTRO_AMD_ERR_ARG;
+    if (gfab && nboxes > 0 && (!o.grav_old || (stage == 1 && !o.grav_new))) return CASTRO_AMD_ERR_ARG;
+    // the checks of the single-box entry points (castro_amd_old/new_gravity_source_fab, _rotation_source_fab, _apply_source_fab)
+    if (grav_on && (o.grav_source_type < 1 || o.grav_source_type > 4)) return CASTRO_AMD_ERR_ARG;
+    if (o.rot && (o.rot->rot_source_type < 1 || o.rot->rot_source_type > 4)) return CASTRO_AMD_ERR_ARG;
+    if ((o.rot || (grav_on && stage == 1)) && geom->coord != 0) return CASTRO_AMD_ERR_ARG;
+    if (o.rot && stage == 1 && !(dt > 0.0)) return CASTRO_AMD_ERR_ARG;
+    if (o.diff) {
+        const int rc = diff_check(o.diff, geom);
+        if (rc != CASTRO_AMD_OK) return rc;
+    }
+    if (nboxes == 0) return CASTRO_AMD_OK;
+    std::vector<SrcBoxDev> tab(gfab ? 0 : (size_t)nboxes);
+    std::vector<SrcBoxGDev> gtab(gfab ? (size_t)nboxes : 0);
+    std::vector<DiffBoxDev> dtab(o.diff ? (size_t)nboxes : 0);
+    for (int i = 0; i < nboxes; ++i) {
+        const castro_amd_source_box& b = boxes[i];
+        const int rb = src_box(gfab ? gtab[(size_t)i].box : tab[(size_t)i], b, stage == 1 && (grav_on || o.rot));
+        if (rb != CASTRO_AMD_OK) return rb;
+        if (gfab) {
+            // stage 0 reads the zone itself, stage 1 with grav_source_type 4 its six neighbours as well
+            if (!grav_fab_ok(&o.grav_old[i], b.lo, b.hi, stage == 1 ? o.grav_source_type : 1)) return CASTRO_AMD_ERR_ARG;
+            if (stage == 1 && !grav_fab_ok(&o.grav_new[i], b.lo, b.hi, o.grav_source_type)) return CASTRO_AMD_ERR_ARG;
+            gtab[(size_t)i].GO = to_dfab(&o.grav_old[i]);
+            gtab[(size_t)i].GN = to_dfab(stage == 1 ? &o.grav_new[i] : &o.grav_old[i]);
+        }
+        // diff_src: stage 0 the term of S_old, stage 1 the corrector 0.5 DiffTerm(S_new) - 0.5 DiffTerm(S_old)
+        if (o.diff) {
+            const int rd = stage == 0 ? diff_box(dtab[(size_t)i], &b.S_old, nullptr, &b.source, nullptr, b.lo, b.hi)
+                                      : diff_box(dtab[(size_t)i], &b.S_new, &b.S_old, &b.source, nullptr, b.lo, b.hi);
+            if (rd != CASTRO_AMD_OK) return rd;
+        }
+    }
+    hipSetDevice(c->device);
+    if (o.diff) {
+        // a launch of its own in front of the one-pass kernel: that kernel writes S_new in place, and the stencil of the
+        // new-time term reads the neighbours' S_new.  It leaves 0 + term in UEDEN / UEINT of the valid zones; the one-pass
+        // kernel starts its sums of those two components from there instead of from zero.
+        const int rd = launch_temp_diffusion(nboxes, dtab.data(), stage == 1, to_diffdev(o.diff, geom), stage == 0 ? 1.0 : 0.5, -0.5, 1,
+                                             &c->diff_arena, (hipStream_t)stream, &c->prof);
+        if (rd != 0) return rd;
+    }
+    const DevParams P = to_devparams(params);
+    return gfab ? launch_sources_apply_gfab(stage, nboxes, gtab.data(), o.grav_source_type, o.rot, geom, P, dt, clean_ntimes, &c->ops_arena,
+                                            (hipStream_t)stream, &c->prof, 0, o.sponge)
+                : launch_sources_apply(stage, nboxes, tab.data(), o.grav, o.grav_source_type, o.rot, geom, P, dt, clean_ntimes, &c->ops_arena,
+                                       (hipStream_t)stream, &c->prof, o.diff ? 1 : 0, o.sponge);
+}
+
 int castro_amd_sources_mf(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
                           const double* grav, int grav_source_type, const castro_amd_rotation* rot,
                           const castro_amd_geom* geom, const castro_amd_params* params, double dt, int clean_ntimes, void* stream)
@@ -692,102 +780,28 @@ int castro_amd_sources_mf(castro_amd_ctx* c, int stage, int nboxes, const castro
     return castro_amd_sources_mf_ex(c, stage, nboxes, boxes, grav, grav_source_type, rot, nullptr, geom, params, dt, clean_ntimes, stream);
 }
 
-// the checks of castro_amd_new_sponge_source_fab; stage 0 takes a sponge and adds nothing
-static bool sponge_ok(const castro_amd_sponge* sponge, const castro_amd_geom* geom, double dt)
-{
-    return !sponge || (geom->coord == 0 && dt > 0.0 && sponge->timescale > 0.0);
-}
-
-static int sources_mf_vec(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
-                          const double* grav, int grav_source_type, const castro_amd_rotation* rot,
-                          const castro_amd_diffusion* diff, const castro_amd_sponge* sponge, const castro_amd_geom* geom,
-                          const castro_amd_params* params, double dt, int clean_ntimes, void* stream);
-
 int castro_amd_sources_mf_ex(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
                              const double* grav, int grav_source_type, const castro_amd_rotation* rot,
                              const castro_amd_diffusion* diff, const castro_amd_geom* geom, const castro_amd_params* params,
                              double dt, int clean_ntimes, void* stream)
 {
-    return sources_mf_vec(c, stage, nboxes, boxes, grav, grav_source_type, rot, diff, nullptr, geom, params, dt, clean_ntimes, stream);
+    const castro_amd_source_opts o = { grav, nullptr, nullptr, grav_source_type, rot, diff, nullptr };
+    return sources_mf_impl(c, stage, nboxes, boxes, o, geom, params, dt, clean_ntimes, stream);
 }
-
-static int sources_mf_vec(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
-                          const double* grav, int grav_source_type, const castro_amd_rotation* rot,
-                          const castro_amd_diffusion* diff, const castro_amd_sponge* sponge, const castro_amd_geom* geom,
-                          const castro_amd_params* params, double dt, int clean_ntimes, void* stream)
-{
-    if (!c || (stage != 0 && stage != 1) || nboxes < 0 || (nboxes > 0 && !boxes) || !geom || !params || clean_ntimes < 0) return CASTRO_AMD_ERR_ARG;
-    if (!sponge_ok(sponge, geom, dt)) return CASTRO_AMD_ERR_ARG;
-    // the checks of the single-box entry points (castro_amd_old/new_gravity_source_fab, _rotation_source_fab, _apply_source_fab)
-    if (grav && (grav_source_type < 1 || grav_source_type > 4)) return CASTRO_AMD_ERR_ARG;
-    if (rot && (rot->rot_source_type < 1 || rot->rot_source_type > 4)) return CASTRO_AMD_ERR_ARG;
-    if ((rot || (grav && stage == 1)) && geom->coord != 0) return CASTRO_AMD_ERR_ARG;
-    if (rot && stage == 1 && !(dt > 0.0)) return CASTRO_AMD_ERR_ARG;
-    if (diff) {
-        const int rc = diff_check(diff, geom);
-        if (rc != CASTRO_AMD_OK) return rc;
-    }
-    if (nboxes == 0) return CASTRO_AMD_OK;
-    std::vector<SrcBoxDev> tab((size_t)nboxes);
-    std::vector<DiffBoxDev> dtab(diff ? (size_t)nboxes : 0);
-    for (int i = 0; i < nboxes; ++i) {
-        const castro_amd_source_box& b = boxes[i];
-        if (!b.S_old.p || !b.S_new.p || !b.source.p || b.S_old.ncomp != NUM_STATE || b.S_new.ncomp != NUM_STATE || b.source.ncomp < 7)
-            return CASTRO_AMD_ERR_ARG;
-        if (!fab_contains(&b.S_old, b.lo, b.hi) || !fab_contains(&b.S_new, b.lo, b.hi) || !fab_contains(&b.source, b.lo, b.hi)) return CASTRO_AMD_ERR_ARG;
-        SrcBoxDev& T = tab[(size_t)i];
-        T.So = to_dfab(&b.S_old); T.Sn = to_dfab(&b.S_new); T.Src = to_dfab(&b.source);
-        T.M0 = T.M1 = T.M2 = to_dfab(nullptr);
-        if (stage == 1 && (grav || rot)) {
-            DFab M[3];
-            for (int d = 0; d < 3; ++d) {
-                int fhi[3] = { b.hi[0], b.hi[1], b.hi[2] };
-                fhi[d] += 1;
-                if (!b.mass_flux[d].p || b.mass_flux[d].ncomp != 1 || !fab_contains(&b.mass_flux[d], b.lo, fhi)) return CASTRO_AMD_ERR_ARG;
-                M[d] = to_dfab(&b.mass_flux[d]);
-            }
-            T.M0 = M[0]; T.M1 = M[1]; T.M2 = M[2];
-        }
-        for (int d = 0; d < 3; ++d) {
-            if (b.source.hi[d] < b.source.lo[d]) return CASTRO_AMD_ERR_ARG;
-            T.lo[d] = b.source.lo[d]; T.n[d] = b.source.hi[d] - b.source.lo[d] + 1;
-            T.vlo[d] = b.lo[d]; T.vhi[d] = b.hi[d];
-        }
-        T.nsc = b.source.ncomp;
-        // diff_src: stage 0 the term of S_old, stage 1 the corrector 0.5 DiffTerm(S_new) - 0.5 DiffTerm(S_old)
-        if (diff) {
-            const int rd = stage == 0 ? diff_box(dtab[(size_t)i], &b.S_old, nullptr, &b.source, nullptr, b.lo, b.hi)
-                                      : diff_box(dtab[(size_t)i], &b.S_new, &b.S_old, &b.source, nullptr, b.lo, b.hi);
-            if (rd != CASTRO_AMD_OK) return rd;
-        }
-    }
-    hipSetDevice(c->device);
-    if (diff) {
-        // a launch of its own in front of the one-pass kernel: that kernel writes S_new in place, and the stencil of the
-        // new-time term reads the neighbours' S_new.  It leaves 0 + term in UEDEN / UEINT of the valid zones; the one-pass
-        // kernel starts its sums of those two components from there instead of from zero.
-        const int rd = launch_temp_diffusion(nboxes, dtab.data(), stage == 1, to_diffdev(diff, geom), stage == 0 ? 1.0 : 0.5, -0.5, 1,
-                                             &c->diff_arena, (hipStream_t)stream, &c->prof);
-        if (rd != 0) return rd < 0 ? rd : CASTRO_AMD_ERR_HIP;
-    }
-    const int rc = launch_sources_apply(stage, nboxes, tab.data(), grav, grav_source_type, rot, geom, to_devparams(params), dt, clean_ntimes,
-                                        &c->ops_arena, (hipStream_t)stream, &c->prof, diff ? 1 : 0, sponge);
-    return rc == 0 ? CASTRO_AMD_OK : (rc < 0 ? CASTRO_AMD_ERR_HIP : rc);
-}
-
-static bool grav_fab_ok(const castro_amd_fab* g, const int lo[3], const int hi[3], int grav_source_type);
-
-static int sources_mf_gfab(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
-                           const castro_amd_fab* grav_old, const castro_amd_fab* grav_new, int grav_source_type,
-                           const castro_amd_rotation* rot, const castro_amd_sponge* sponge, const castro_amd_geom* geom,
-                           const castro_amd_params* params, double dt, int clean_ntimes, void* stream);
 
 int castro_amd_sources_mf_g(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
                             const castro_amd_fab* grav_old, const castro_amd_fab* grav_new, int grav_source_type,
                             const castro_amd_rotation* rot, const castro_amd_geom* geom, const castro_amd_params* params,
                             double dt, int clean_ntimes, void* stream)
 {
-    return sources_mf_gfab(c, stage, nboxes, boxes, grav_old, grav_new, grav_source_type, rot, nullptr, geom, params, dt, clean_ntimes, stream);
+    castro_amd_source_opts o = { nullptr, grav_old, grav_new, grav_source_type, rot, nullptr, nullptr };
+    // without either array the call is still the FAB form, with that form's checks: refused unless the level is empty
+    static const castro_amd_fab none = { nullptr, { 0, 0, 0 }, { 0, 0, 0 }, 0 };
+    if (!grav_old && !grav_new) {
+        if (nboxes > 0) return CASTRO_AMD_ERR_ARG;
+        o.grav_old = &none;
+    }
+    return sources_mf_impl(c, stage, nboxes, boxes, o, geom, params, dt, clean_ntimes, stream);
 }
 
 int castro_amd_sources_mf_opts(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
@@ -795,65 +809,7 @@ int castro_amd_sources_mf_opts(castro_amd_ctx* c, int stage, int nboxes, const c
                                double dt, int clean_ntimes, void* stream)
 {
     if (!o) return CASTRO_AMD_ERR_ARG;
-    if (o->grav_old || o->grav_new) {
-        if (o->grav) return CASTRO_AMD_ERR_ARG;
-        if (o->diff) return CASTRO_AMD_ERR_UNSUPPORTED;
-        return sources_mf_gfab(c, stage, nboxes, boxes, o->grav_old, o->grav_new, o->grav_source_type, o->rot, o->sponge, geom, params, dt,
-                               clean_ntimes, stream);
-    }
-    return sources_mf_vec(c, stage, nboxes, boxes, o->grav, o->grav_source_type, o->rot, o->diff, o->sponge, geom, params, dt, clean_ntimes,
-                          stream);
-}
-
-static int sources_mf_gfab(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes,
-                           const castro_amd_fab* grav_old, const castro_amd_fab* grav_new, int grav_source_type,
-                           const castro_amd_rotation* rot, const castro_amd_sponge* sponge, const castro_amd_geom* geom,
-                           const castro_amd_params* params, double dt, int clean_ntimes, void* stream)
-{
-    if (!c || (stage != 0 && stage != 1) || nboxes < 0 || (nboxes > 0 && !boxes) || !geom || !params || clean_ntimes < 0) return CASTRO_AMD_ERR_ARG;
-    if (!sponge_ok(sponge, geom, dt)) return CASTRO_AMD_ERR_ARG;
-    if (nboxes > 0 && (!grav_old || (stage == 1 && !grav_new))) return CASTRO_AMD_ERR_ARG;
-    if (grav_source_type < 1 || grav_source_type > 4) return CASTRO_AMD_ERR_ARG;
-    if (rot && (rot->rot_source_type < 1 || rot->rot_source_type > 4)) return CASTRO_AMD_ERR_ARG;
-    if ((rot || stage == 1) && geom->coord != 0) return CASTRO_AMD_ERR_ARG;
-    if (rot && stage == 1 && !(dt > 0.0)) return CASTRO_AMD_ERR_ARG;
-    if (nboxes == 0) return CASTRO_AMD_OK;
-    std::vector<SrcBoxGDev> tab((size_t)nboxes);
-    for (int i = 0; i < nboxes; ++i) {
-        const castro_amd_source_box& b = boxes[i];
-        if (!b.S_old.p || !b.S_new.p || !b.source.p || b.S_old.ncomp != NUM_STATE || b.S_new.ncomp != NUM_STATE || b.source.ncomp < 7)
-            return CASTRO_AMD_ERR_ARG;
-        if (!fab_contains(&b.S_old, b.lo, b.hi) || !fab_contains(&b.S_new, b.lo, b.hi) || !fab_contains(&b.source, b.lo, b.hi)) return CASTRO_AMD_ERR_ARG;
-        // stage 0 reads the zone itself, stage 1 with grav_source_type 4 its six neighbours as well
-        if (!grav_fab_ok(&grav_old[i], b.lo, b.hi, stage == 1 ? grav_source_type : 1)) return CASTRO_AMD_ERR_ARG;
-        if (stage == 1 && !grav_fab_ok(&grav_new[i], b.lo, b.hi, grav_source_type)) return CASTRO_AMD_ERR_ARG;
-        SrcBoxGDev& TG = tab[(size_t)i];
-        SrcBoxDev& T = TG.box;
-        T.So = to_dfab(&b.S_old); T.Sn = to_dfab(&b.S_new); T.Src = to_dfab(&b.source);
-        T.M0 = T.M1 = T.M2 = to_dfab(nullptr);
-        if (stage == 1) {
-            DFab M[3];
-            for (int d = 0; d < 3; ++d) {
-                int fhi[3] = { b.hi[0], b.hi[1], b.hi[2] };
-                fhi[d] += 1;
-                if (!b.mass_flux[d].p || b.mass_flux[d].ncomp != 1 || !fab_contains(&b.mass_flux[d], b.lo, fhi)) return CASTRO_AMD_ERR_ARG;
-                M[d] = to_dfab(&b.mass_flux[d]);
-            }
-            T.M0 = M[0]; T.M1 = M[1]; T.M2 = M[2];
-        }
-        for (int d = 0; d < 3; ++d) {
-            if (b.source.hi[d] < b.source.lo[d]) return CASTRO_AMD_ERR_ARG;
-            T.lo[d] = b.source.lo[d]; T.n[d] = b.source.hi[d] - b.source.lo[d] + 1;
-            T.vlo[d] = b.lo[d]; T.vhi[d] = b.hi[d];
-        }
-        T.nsc = b.source.ncomp;
-        TG.GO = to_dfab(&grav_old[i]);
-        TG.GN = to_dfab(stage == 1 ? &grav_new[i] : &grav_old[i]);
-    }
-    hipSetDevice(c->device);
-    const int rc = launch_sources_apply_gfab(stage, nboxes, tab.data(), grav_source_type, rot, geom, to_devparams(params), dt, clean_ntimes,
-                                             &c->ops_arena, (hipStream_t)stream, &c->prof, 0, sponge);
-    return rc == 0 ? CASTRO_AMD_OK : (rc < 0 ? CASTRO_AMD_ERR_HIP : rc);
+    return sources_mf_impl(c, stage, nboxes, boxes, *o, geom, params, dt, clean_ntimes, stream);
 }
 
 int castro_amd_clean_state_reduce_mf(castro_amd_ctx* c, int nboxes, const castro_amd_state_box* boxes, const castro_amd_geom* geom,
@@ -1064,12 +1020,7 @@ int castro_amd_new_gravity_source_gfab(castro_amd_ctx* c, const castro_amd_fab* 
     if (!fab_contains(state_old, lo, hi) || !fab_contains(state_new, lo, hi) || !fab_contains(source, lo, hi)) return CASTRO_AMD_ERR_ARG;
     if (!grav_fab_ok(grav_old, lo, hi, grav_source_type) || !grav_fab_ok(grav_new, lo, hi, grav_source_type)) return CASTRO_AMD_ERR_ARG;
     DFab M[3];
-    for (int d = 0; d < 3; ++d) {
-        int fhi[3] = { hi[0], hi[1], hi[2] };
-        fhi[d] += 1;
-        if (!mass_fluxes[d].p || mass_fluxes[d].ncomp != 1 || !fab_contains(&mass_fluxes[d], lo, fhi)) return CASTRO_AMD_ERR_ARG;
-        M[d] = to_dfab(&mass_fluxes[d]);
-    }
+    if (!mass_flux_dfabs(mass_fluxes, lo, hi, M)) return CASTRO_AMD_ERR_ARG;
     hipSetDevice(c->device);
     return launch_new_grav_source_gfab(to_dfab(state_old), to_dfab(state_new), to_dfab(source), M, lo, hi, to_dfab(grav_old),
                                        to_dfab(grav_new), grav_source_type, dt, geom->dx, (hipStream_t)stream, &c->prof);
@@ -1110,7 +1061,7 @@ int castro_amd_add_pointmass_mf(castro_amd_ctx* c, int nfabs, const castro_amd_f
         }
     }
     hipSetDevice(c->device);
-    return launch_add_pointmass(nfabs, tab.data(), G, d_point_mass, &c->pm_ws, (hipStream_t)stream, &c->prof);
+    return launch_add_pointmass(nfabs, tab.data(), G, d_point_mass, &c->pm_tables, (hipStream_t)stream, &c->prof);
 }
 
 int castro_amd_add_pointmass_fab(castro_amd_ctx* c, const castro_amd_fab* grav_fab, const castro_amd_pointmass_params* pm,
@@ -1158,7 +1109,7 @@ int castro_amd_pointmass_delta_mf(castro_amd_ctx* c, int nboxes, const castro_am
     const int rt = pm_boxes(nboxes, boxes, pm, geom, tab, clo);
     if (rt != CASTRO_AMD_OK) return rt;
     hipSetDevice(c->device);
-    return launch_pointmass_delta(nboxes, tab.data(), clo, geom->dx[0] * geom->dx[1] * geom->dx[2], d_delta, &c->pm_ws,
+    return launch_pointmass_delta(nboxes, tab.data(), clo, geom->dx[0] * geom->dx[1] * geom->dx[2], d_delta, &c->pm_tables,
                                   (hipStream_t)stream, &c->prof);
 }
 
@@ -1172,7 +1123,7 @@ int castro_amd_pointmass_apply_mf(castro_amd_ctx* c, int nboxes, const castro_am
     const int rt = pm_boxes(nboxes, boxes, pm, geom, tab, clo);
     if (rt != CASTRO_AMD_OK) return rt;
     hipSetDevice(c->device);
-    return launch_pointmass_apply(nboxes, tab.data(), clo, d_delta, d_point_mass, &c->pm_ws, (hipStream_t)stream, &c->prof);
+    return launch_pointmass_apply(nboxes, tab.data(), clo, d_delta, d_point_mass, &c->pm_tables, (hipStream_t)stream, &c->prof);
 }
 
 int castro_amd_saxpy_fab(castro_amd_ctx* c, const castro_amd_fab* dst, double a, const castro_amd_fab* src, int ncomp,

@@ -4,6 +4,7 @@
 #include <string>
 #include <vector>
 #include "hydro_device.h"
+#include "dev_table.h"
 
 struct castro_amd_rotation;      // include/castro_hydro_amd.h
 struct castro_amd_sponge;
@@ -117,9 +118,6 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
                      int* d_status, hipStream_t stream, Profiler* prof, int clean_ntimes, double* red, const DFab& SrcCorr,
                      const LaunchAux& aux);
 
-// device buffer for operation tables longer than a kernel argument holds (owned by the context)
-struct FabOpsArena { void* p = nullptr; size_t bytes = 0; };
-
 // One box of a level-wide launch (castro_amd_ctu_hydro_mf): its tile, its own scratch, the caller's arrays
 struct LevelBoxDesc {
     Tile t;
@@ -131,7 +129,7 @@ struct LevelBoxDesc {
 // default options only (PPM, CGF solver, no staging, the default kernel forms; traced source terms without a predictor): else box by box
 // K: the knobs of the context whose prepare_box laid out the boxes' scratch
 bool level_launch_supported(const LaunchKnobs& K, const DevParams& P, int flags, bool with_src = false);
-int launch_ctu_hydro_level(const LaunchKnobs& K, int nbox, const LevelBoxDesc* boxes, FabOpsArena* table, const DevGeom& g, const DevParams& P,
+int launch_ctu_hydro_level(const LaunchKnobs& K, int nbox, const LevelBoxDesc* boxes, StagedTable* table, const DevGeom& g, const DevParams& P,
                            double dt, int flags, int* d_status, hipStream_t stream, Profiler* prof, int clean_ntimes, double* red, int sb_clean);
 
 // auxiliary per-FAB kernels (aux_kernels.hip)
@@ -160,10 +158,10 @@ struct SrcBoxDev { DFab So, Sn, Src, M0, M1, M2; int lo[3], n[3]; int vlo[3], vh
 // one box of castro_amd_sources_mf_g: the same, and its Gravity_Type FABs (3 components, one ghost zone around [vlo, vhi])
 struct SrcBoxGDev { SrcBoxDev box; DFab GO, GN; };
 int launch_sources_apply_gfab(int stage, int nbox, const SrcBoxGDev* boxes, int grav_type, const ::castro_amd_rotation* rot,
-                              const ::castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
+                              const ::castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, StagedTable* arena,
                               hipStream_t stream, Profiler* prof, int diff_on = 0, const ::castro_amd_sponge* sponge = nullptr);
 int launch_sources_apply(int stage, int nbox, const SrcBoxDev* boxes, const double* grav, int grav_type, const ::castro_amd_rotation* rot,
-                         const ::castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, FabOpsArena* arena,
+                         const ::castro_amd_geom* geom, const DevParams& P, double dt, int ntimes, StagedTable* arena,
                          hipStream_t stream, Profiler* prof, int diff_on = 0, const ::castro_amd_sponge* sponge = nullptr);
 // thermal diffusion (diffusion_kernels.hip).  One box of a castro_amd_temp_diffusion_* launch: U (and U2, the old state of the
 // time-centred corrector) with at least one ghost zone around [lo, hi]; Src: the Source_Type FAB (p == nullptr: none);
@@ -172,7 +170,7 @@ struct DiffBoxDev { DFab U, U2, Src, Out; int lo[3], hi[3], nt[3]; };
 // phys_lo / phys_hi: the domain face of that direction is a physical boundary (zero flux) rather than periodic
 struct DiffDev { double cond, cutoff, cutoff_hi, scale; double dh[3]; int domlo[3], domhi[3]; int phys_lo[3], phys_hi[3]; };
 int launch_temp_diffusion(int nbox, DiffBoxDev* boxes, bool two, const DiffDev& D, double m1, double m2, int init,
-                          FabOpsArena* arena, hipStream_t stream, Profiler* prof);
+                          StagedTable* arena, hipStream_t stream, Profiler* prof);
 int launch_estdt_temp_diffusion(const DFab& U, const int lo[3], const int hi[3], const double dx[3], const DevParams& P,
                                 double cond, double cutoff, double below, double* d_out, hipStream_t stream, Profiler* prof);
 // integrated quantities (diag_kernels.hip).  One box of a castro_amd_integrated_quantities_mf launch: the valid zones
@@ -184,7 +182,7 @@ struct DiagGeom { double dx[3], problo[3], center[3], vol; };
 struct DiagWorkspace { double* p = nullptr; size_t rows = 0; };
 // start[r]: first workgroup of box r (start[nbox]: all of them); iters: pairs a thread takes.  Returns 0 or CASTRO_AMD_ERR_ARG
 int diag_layout(int nbox, DiagBoxDev* boxes, std::vector<int>& start, int& iters);
-int launch_integrated_quantities(int nbox, DiagBoxDev* boxes, const DiagGeom& G, FabOpsArena* arena, DiagWorkspace* ws,
+int launch_integrated_quantities(int nbox, DiagBoxDev* boxes, const DiagGeom& G, StagedTable* arena, DiagWorkspace* ws,
                                  double* d_out, hipStream_t stream, Profiler* prof);
 // monopole gravity (monopole_kernels.hip).  One box of a castro_amd_radial_mass_mf launch: the valid zones [lo, lo + n) of U, the
 // byte mask of those zones (nullptr: every zone counts); nb: bricks per direction, set by the launcher.  A table is compared
@@ -199,13 +197,12 @@ struct MonoCombine { const double* mv[MONO_MAX_LEVELS]; int n1d[MONO_MAX_LEVELS]
 // octant_factor: 8 when the centre sits on problo (Gravity.cpp:1439-1447), else 1; max_radius: max_radius_all_in_domain
 struct MonoGeom { double dx[3], problo[3], center[3]; double octant_factor, max_radius, Gconst; int n1d, drdxfac; };
 // what a context keeps for the binning: one row of 64 bins and its first bin per workgroup, the integer counts per bin, and the
-// box tables it has copied to the device (by content).  Reserved at first use; grown only by a call with more workgroups,
+// box tables it has copied to the device (dev_table.h).  Reserved at first use; grown only by a call with more workgroups,
 // more bins or a table not seen before -- any other call neither allocates nor synchronises
 struct MonoWorkspace {
     double* rows = nullptr; int* rbase = nullptr; size_t nrows = 0;
     unsigned long long* count = nullptr; size_t ncount = 0;
-    struct Table { std::vector<char> host; void* dev = nullptr; };
-    std::vector<Table> tables;
+    TableCache tables{8};
 };
 bool radial_window_ok(const MonoGeom& G);
 void mono_workspace_free(MonoWorkspace* ws);
@@ -227,13 +224,13 @@ int launch_monopole_grav(const double* d_radial_grav, const MonoGeom& G, const D
 struct PmFabDev { DFab F; int lo[3], n[3]; long start; };
 struct PmBoxDev { DFab So, Sn; int lo[3], hi[3]; };
 struct PmGeom { double dx[3], problo[3], center[3]; double Gconst; };
-int launch_add_pointmass(int nfab, PmFabDev* fabs, const PmGeom& G, const double* d_mass, MonoWorkspace* ws, hipStream_t stream,
+int launch_add_pointmass(int nfab, PmFabDev* fabs, const PmGeom& G, const double* d_mass, TableCache* tables, hipStream_t stream,
                          Profiler* prof);
 // clo: the low corner of the 4 x 4 x 4 cube (icen - 2 of Castro_pointmass.cpp:43-65)
-int launch_pointmass_delta(int nbox, const PmBoxDev* boxes, const int clo[3], double vol, double* d_delta, MonoWorkspace* ws,
+int launch_pointmass_delta(int nbox, const PmBoxDev* boxes, const int clo[3], double vol, double* d_delta, TableCache* tables,
                            hipStream_t stream, Profiler* prof);
 int launch_pointmass_apply(int nbox, const PmBoxDev* boxes, const int clo[3], const double* d_delta, double* d_mass,
-                           MonoWorkspace* ws, hipStream_t stream, Profiler* prof);
+                           TableCache* tables, hipStream_t stream, Profiler* prof);
 // the gravity sources with a per-zone vector: GO / GN are 3-component FABs with one ghost zone around [lo, hi] (type 4)
 int launch_old_grav_source_gfab(const DFab& U, const DFab& SRC, const int lo[3], const int hi[3], const DFab& GO,
                                 int type, double dt, hipStream_t stream, Profiler* prof);
@@ -244,7 +241,7 @@ int launch_saxpy(const DFab& D, const DFab& S, const int lo[3], const int hi[3],
                  hipStream_t stream, Profiler* prof);
 int launch_fab_ops(int nops, const DFab* D, const DFab* X, const DFab* Y, const int* lo, const int* hi, const int* kind,
                    const int* dir, const int* side, const int* ncomp, const double* a, const double* b, hipStream_t stream, Profiler* prof,
-                   const DevParams* P = nullptr, FabOpsArena* arena = nullptr);
+                   const DevParams* P = nullptr, StagedTable* arena = nullptr);
 int launch_apply_source(const DFab& D, const DFab& B, const DFab& S, const int lo[3], const int hi[3], double a, int nsrc,
                         const DevParams& P, int ntimes, hipStream_t stream, Profiler* prof);
 int launch_cc_interp(const DFab& C, const DFab& F, const int lo[3], const int hi[3], int ncomp, hipStream_t stream, Profiler* prof);

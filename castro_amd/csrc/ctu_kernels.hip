@@ -3569,15 +3569,15 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
             KL("k_ctoprim", k_ctoprim<false>, plain, t.lo, t.hi, Sborder, S.Q, P, d_status, none, 0, nolv, lean_q, 0, ShellBoxes{}, BcKinds{});
             if (inner_ok) trace_with_xriemann(inner_box.lo, inner_box.hi);
         }
-        return hipGetLastError() == hipSuccess ? 0 : -4;
+        return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
     }
     // The light split (round 6: CASTRO_AMD_STAGE_VALID / _REST): ctoprim -- with the pending clean_states -- on the valid zones
     // is all that runs beside the halo exchange; the ghost shell follows as ONE launch, everything downstream is un-split.
     // CASTRO_AMD_BC_FILL: the zones of grow(bx, 4) outside the problem domain in a non-periodic direction are filled here
     // (k_ctoprim in its boundary-zone mode) from in-domain zones that the launches in front of it have cleaned, instead of by a k_bc_fill before the call.
     const bool light_a = (flags & 16) != 0, light_b = (flags & 32) != 0, fill_bc = (flags & 64) != 0;
-    if ((light_a || light_b || fill_bc) && staged) return -1;
-    if (light_a && light_b) return -1;
+    if ((light_a || light_b || fill_bc) && staged) return CASTRO_AMD_ERR_ARG;
+    if (light_a && light_b) return CASTRO_AMD_ERR_ARG;
     int ilo[3], ihi[3];                                  // the zones of grow(bx, 4) that hold data when the call starts
     BcKinds M;
     const ShellBoxes no_shell = {};
@@ -3591,9 +3591,9 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
         if (M.kind_lo[d] != 0 && qb.lo[d] < g.domlo[d]) { ilo[d] = g.domlo[d]; have_bc = true; }
         if (M.kind_hi[d] != 0 && qb.hi[d] > g.domhi[d]) { ihi[d] = g.domhi[d]; have_bc = true; }
         // the tile lies inside the domain, and a mirrored ghost layer finds its image among the in-domain zones of this FAB
-        if (t.lo[d] < ilo[d] || t.hi[d] > ihi[d]) return -1;
-        if (M.kind_lo[d] == 2 && 2 * g.domlo[d] - qb.lo[d] - 1 > ihi[d]) return -2;
-        if (M.kind_hi[d] == 2 && 2 * g.domhi[d] - qb.hi[d] + 1 < ilo[d]) return -2;
+        if (t.lo[d] < ilo[d] || t.hi[d] > ihi[d]) return CASTRO_AMD_ERR_ARG;
+        if (M.kind_lo[d] == 2 && 2 * g.domlo[d] - qb.lo[d] - 1 > ihi[d]) return CASTRO_AMD_ERR_UNSUPPORTED;
+        if (M.kind_hi[d] == 2 && 2 * g.domhi[d] - qb.hi[d] + 1 < ilo[d]) return CASTRO_AMD_ERR_UNSUPPORTED;
     }
     auto shell_launch_boxes = [&](const int olo_[3], const int ohi_[3], const int nlo_[3], const int nhi_[3], ShellBoxes& sb) {
         int lo6[6][3], hi6[6][3];
@@ -3614,7 +3614,7 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
     if (light_a) {
         if (aux.sb_clean > 0) KL("k_ctoprim_clean", k_ctoprim<true>, plain, t.lo, t.hi, Sborder, S.Q, P, d_status, none, aux.sb_clean, nolv, lean_q, 0, no_shell, M);
         else KL("k_ctoprim", k_ctoprim<false>, plain, t.lo, t.hi, Sborder, S.Q, P, d_status, none, 0, nolv, lean_q, 0, no_shell, M);
-        return hipGetLastError() == hipSuccess ? 0 : -4;
+        return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
     }
     const bool second_half = stage_b && splittable;     // stage A has run on this tile
     int slo[6][3], shi[6][3];
@@ -3779,7 +3779,7 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
                 hipLaunchKernelGGL((k_final_tile<false, 0, ry, rz>), dim3(tr.nb), dim3(64 * ry * rz), 0, stream, t, tr, S.Q, S, g, Sborder, fo, Snew, dt,
                                    area0, area1, area2, vol, assign_yz, (flags & 1) ? 1 : 0, P, 0, (double*)nullptr);
             prof_end(prof, stream);
-            return hipGetLastError() == hipSuccess ? 0 : -4;
+            return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
         }
 #endif
         if (lim) {
@@ -3808,7 +3808,7 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
         }
 #undef FXC
         prof_end(prof, stream);
-        return hipGetLastError() == hipSuccess ? 0 : -4;
+        return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
     }
     else { if (lim) TRANSVERSE_STAGES(false, true); else TRANSVERSE_STAGES(false, false); }
 #undef TRANSVERSE_STAGES
@@ -3821,7 +3821,7 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
            P, 0, 0.0, 0.0, 0.0, (double*)nullptr);
     }
 
-    return hipGetLastError() == hipSuccess ? 0 : -4;
+    return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3838,16 +3838,16 @@ bool level_launch_supported(const LaunchKnobs& K, const DevParams& P, int flags,
            K.fuse_consup == 1 && K.fold_r1 != 0 && (flags & (4 | 8 | 16 | 32 | 64)) == 0;
 }
 
-int launch_ctu_hydro_level(const LaunchKnobs& K, int nbox, const LevelBoxDesc* boxes, FabOpsArena* table, const DevGeom& g, const DevParams& P,
+int launch_ctu_hydro_level(const LaunchKnobs& K, int nbox, const LevelBoxDesc* boxes, StagedTable* table, const DevGeom& g, const DevParams& P,
                            double dt, int flags, int* d_status, hipStream_t stream, Profiler* prof, int clean_ntimes, double* red, int sb_clean)
 {
-    if (nbox < 1 || !boxes || !table) return -1;
+    if (nbox < 1 || !boxes || !table) return CASTRO_AMD_ERR_ARG;
     // Traced source terms: every box of the launch has its old-time source FAB or none has.  The sequence is launch_ctu_hydro's
     // for Src.p != nullptr -- k_divu_pair, k_src_to_prim, the one-zone trace with sources, the first x solves as a launch of
     // their own -- through the table forms of those kernels; the transverse and final stages are the same either way.
     const bool with_src = boxes[0].Src.p != nullptr;
-    for (int i = 1; i < nbox; ++i) if ((boxes[i].Src.p != nullptr) != with_src) return -1;
-    if (with_src && sb_clean > 0) return -1;
+    for (int i = 1; i < nbox; ++i) if ((boxes[i].Src.p != nullptr) != with_src) return CASTRO_AMD_ERR_ARG;
+    if (with_src && sb_clean > 0) return CASTRO_AMD_ERR_ARG;
     const Shape plain = plain_shape(K);
     std::vector<LevelBox> hb((size_t)nbox);
     std::vector<unsigned> start((size_t)NLB * (size_t)(nbox + 1), 0u);
@@ -3888,17 +3888,11 @@ int launch_ctu_hydro_level(const LaunchKnobs& K, int nbox, const LevelBoxDesc* b
             st(kind, i + 1) = st(kind, i) + nb;
         }
     }
-    // the table: boxes, then the prefix arrays; hipMemcpyAsync from pageable memory stages the bytes before it returns
-    const size_t box_bytes = sizeof(LevelBox) * (size_t)nbox, bytes = box_bytes + sizeof(unsigned) * start.size();
-    if (table->bytes < bytes) {
-        if (table->p) { hipStreamSynchronize(stream); hipFree(table->p); table->p = nullptr; table->bytes = 0; }
-        if (hipMalloc(&table->p, bytes + 4096) != hipSuccess) return -3;
-        table->bytes = bytes + 4096;
-    }
-    hipMemcpyAsync(table->p, hb.data(), box_bytes, hipMemcpyHostToDevice, stream);
-    hipMemcpyAsync((char*)table->p + box_bytes, start.data(), sizeof(unsigned) * start.size(), hipMemcpyHostToDevice, stream);
-    const LevelBox* dbox = (const LevelBox*)table->p;
-    const unsigned* dstart = (const unsigned*)((const char*)table->p + box_bytes);
+    // the table: boxes, then the prefix arrays
+    const LevelBox* dbox;
+    const unsigned* dstart;
+    const int rt = table->stage(hb.data(), hb.size(), start.data(), start.size(), stream, dbox, dstart);
+    if (rt != 0) return rt;
     auto lv = [&](int kind) { return LevelTab{ dbox, dstart + (size_t)kind * (size_t)(nbox + 1), nbox }; };
     auto total = [&](int kind) { return st(kind, nbox); };
 
@@ -3964,7 +3958,7 @@ int launch_ctu_hydro_level(const LaunchKnobs& K, int nbox, const LevelBoxDesc* b
                            hb[0].fl[0], hb[0].mass[0], hb[0].qe[0], hb[0].Unew, hdtdy, hdtdz, dt, area0, area1, area2, vol, hb[0].acc_hi[0],
                            assign, (flags & 1) ? 1 : 0, P, 0, (double*)nullptr, lv(LB_FX));
     prof_end(prof, stream);
-    return hipGetLastError() == hipSuccess ? 0 : -4;
+    return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
 }
 
 } // namespace cad

@@ -175,7 +175,7 @@ int diag_layout(int nbox, DiagBoxDev* boxes, std::vector<int>& start, int& iters
     return 0;
 }
 
-int launch_integrated_quantities(int nbox, DiagBoxDev* boxes, const DiagGeom& G, FabOpsArena* arena, DiagWorkspace* ws,
+int launch_integrated_quantities(int nbox, DiagBoxDev* boxes, const DiagGeom& G, StagedTable* arena, DiagWorkspace* ws,
                                  double* d_out, hipStream_t stream, Profiler* prof)
 {
     std::vector<int> start;
@@ -192,20 +192,12 @@ int launch_integrated_quantities(int nbox, DiagBoxDev* boxes, const DiagGeom& G,
             if (hipMalloc(&ws->p, rows * DIAG_N * sizeof(double)) != hipSuccess) return CASTRO_AMD_ERR_NOMEM;
             ws->rows = rows;
         }
-        const size_t bo = (size_t)nbox * sizeof(DiagBoxDev), bs = start.size() * sizeof(int);
-        const size_t need = ((bo + 255) & ~(size_t)255) + bs;
-        if (need > arena->bytes) {
-            if (arena->p) { (void)hipStreamSynchronize(stream); (void)hipFree(arena->p); arena->p = nullptr; arena->bytes = 0; }
-            if (hipMalloc(&arena->p, 2 * need) != hipSuccess) return CASTRO_AMD_ERR_NOMEM;
-            arena->bytes = 2 * need;
-        }
-        char* base = (char*)arena->p;
-        int* dstart = (int*)(base + ((bo + 255) & ~(size_t)255));
-        if (hipMemcpyAsync(base, boxes, bo, hipMemcpyHostToDevice, stream) != hipSuccess) return CASTRO_AMD_ERR_HIP;
-        if (hipMemcpyAsync(dstart, start.data(), bs, hipMemcpyHostToDevice, stream) != hipSuccess) return CASTRO_AMD_ERR_HIP;
+        const DiagBoxDev* dbox;
+        const int* dstart;
+        const int rt = arena->stage(boxes, (size_t)nbox, start.data(), start.size(), stream, dbox, dstart);
+        if (rt != 0) return rt;
         prof_begin(prof, "k_diag_partial", stream);
-        hipLaunchKernelGGL(k_diag_partial, dim3((unsigned)nb), dim3(DIAG_WG), 0, stream, (const DiagBoxDev*)base, (const int*)dstart,
-                           nbox, iters, G, ws->p);
+        hipLaunchKernelGGL(k_diag_partial, dim3((unsigned)nb), dim3(DIAG_WG), 0, stream, dbox, dstart, nbox, iters, G, ws->p);
         prof_end(prof, stream);
         if (hipGetLastError() != hipSuccess) return CASTRO_AMD_ERR_HIP;
     }

@@ -147,7 +147,7 @@ __global__ void __launch_bounds__(64 * DIFF_TJ) k_temp_diffusion(const DiffBoxDe
 }
 
 int launch_temp_diffusion(int nbox, DiffBoxDev* boxes, bool two, const DiffDev& D, double m1, double m2, int init,
-                          FabOpsArena* arena, hipStream_t stream, Profiler* prof)
+                          StagedTable* arena, hipStream_t stream, Profiler* prof)
 {
     if (nbox < 1 || !boxes || !arena) return 0;
     std::vector<int> start((size_t)nbox + 1, 0);
@@ -164,23 +164,14 @@ int launch_temp_diffusion(int nbox, DiffBoxDev* boxes, bool two, const DiffDev& 
         start[(size_t)r + 1] = start[(size_t)r] + (int)n;
     }
     if (start.back() <= 0) return 0;
-    const size_t bo = (size_t)nbox * sizeof(DiffBoxDev), bs = start.size() * sizeof(int);
-    const size_t need = ((bo + 255) & ~(size_t)255) + bs;
-    if (need > arena->bytes) {
-        if (arena->p) { (void)hipStreamSynchronize(stream); (void)hipFree(arena->p); arena->p = nullptr; arena->bytes = 0; }
-        if (hipMalloc(&arena->p, 2 * need) != hipSuccess) return CASTRO_AMD_ERR_NOMEM;
-        arena->bytes = 2 * need;
-    }
-    char* base = (char*)arena->p;
-    int* dstart = (int*)(base + ((bo + 255) & ~(size_t)255));
-    if (hipMemcpyAsync(base, boxes, bo, hipMemcpyHostToDevice, stream) != hipSuccess) return CASTRO_AMD_ERR_HIP;
-    if (hipMemcpyAsync(dstart, start.data(), bs, hipMemcpyHostToDevice, stream) != hipSuccess) return CASTRO_AMD_ERR_HIP;
+    const DiffBoxDev* dbox;
+    const int* dstart;
+    const int rt = arena->stage(boxes, (size_t)nbox, start.data(), start.size(), stream, dbox, dstart);
+    if (rt != 0) return rt;
     const unsigned nb = (unsigned)start.back();
     prof_begin(prof, two ? "k_temp_diffusion_corr" : "k_temp_diffusion", stream);
-    if (two) hipLaunchKernelGGL(k_temp_diffusion<true>, dim3(nb), dim3(64 * DIFF_TJ), 0, stream, (const DiffBoxDev*)base, (const int*)dstart,
-                                nbox, nb, D, m1, m2, init);
-    else hipLaunchKernelGGL(k_temp_diffusion<false>, dim3(nb), dim3(64 * DIFF_TJ), 0, stream, (const DiffBoxDev*)base, (const int*)dstart,
-                            nbox, nb, D, m1, m2, init);
+    if (two) hipLaunchKernelGGL(k_temp_diffusion<true>, dim3(nb), dim3(64 * DIFF_TJ), 0, stream, dbox, dstart, nbox, nb, D, m1, m2, init);
+    else hipLaunchKernelGGL(k_temp_diffusion<false>, dim3(nb), dim3(64 * DIFF_TJ), 0, stream, dbox, dstart, nbox, nb, D, m1, m2, init);
     prof_end(prof, stream);
     return diff_launch_status();
 }

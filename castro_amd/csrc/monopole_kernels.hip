@@ -309,9 +309,8 @@ void mono_workspace_free(MonoWorkspace* ws)
     if (ws->rows) (void)hipFree(ws->rows);
     if (ws->rbase) (void)hipFree(ws->rbase);
     if (ws->count) (void)hipFree(ws->count);
-    for (auto& t : ws->tables) if (t.dev) (void)hipFree(t.dev);
+    ws->tables.release();
     ws->rows = nullptr; ws->rbase = nullptr; ws->count = nullptr; ws->nrows = 0; ws->ncount = 0;
-    ws->tables.clear();
 }
 
 static void radial_partial_launch(const MonoBoxDev* tab, const int* start, int nbox, const MonoGeom& G, MonoWorkspace* ws, int nb,
@@ -353,35 +352,12 @@ static int launch_radial_mass_t(int nbox, BOX* boxes, const MonoGeom& G, MonoWor
         if (hipMalloc(&ws->count, (size_t)G.n1d * sizeof(unsigned long long)) != hipSuccess) return CASTRO_AMD_ERR_NOMEM;
         ws->ncount = (size_t)G.n1d;
     }
-    // the box table on the device: kept per content (a driver alternates between the tables of its two state buffers), so a
-    // table that has been seen before costs no copy -- an asynchronous copy from this call's host vector could not be
-    // captured into a graph
+    // the box table on the device: kept per content (a driver alternates between the tables of its two state buffers)
     const BOX* dtab = nullptr;
     const int* dstart = nullptr;
     if (nb > 0) {
-        const size_t bo = (size_t)nbox * sizeof(BOX), bs = start.size() * sizeof(int);
-        const size_t off = (bo + 255) & ~(size_t)255;
-        std::vector<char> key(off + bs, 0);
-        std::memcpy(key.data(), boxes, bo);
-        std::memcpy(key.data() + off, start.data(), bs);
-        MonoWorkspace::Table* hit = nullptr;
-        for (auto& t : ws->tables) if (t.host == key) { hit = &t; break; }
-        if (!hit) {
-            if (ws->tables.size() >= 8) {
-                (void)hipStreamSynchronize(stream);
-                (void)hipFree(ws->tables.front().dev);
-                ws->tables.erase(ws->tables.begin());
-            }
-            void* d = nullptr;
-            if (hipMalloc(&d, key.size()) != hipSuccess) return CASTRO_AMD_ERR_NOMEM;
-            if (hipMemcpy(d, key.data(), key.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return CASTRO_AMD_ERR_HIP; }
-            ws->tables.push_back(MonoWorkspace::Table());
-            ws->tables.back().host.swap(key);
-            ws->tables.back().dev = d;
-            hit = &ws->tables.back();
-        }
-        dtab = (const BOX*)hit->dev;
-        dstart = (const int*)((const char*)hit->dev + off);
+        const int rt = ws->tables.find(boxes, (size_t)nbox, start.data(), start.size(), stream, dtab, dstart);
+        if (rt != 0) return rt;
     }
     if (hipMemsetAsync(ws->count, 0, (size_t)G.n1d * sizeof(unsigned long long), stream) != hipSuccess) return CASTRO_AMD_ERR_HIP;
     if (nb > 0) {

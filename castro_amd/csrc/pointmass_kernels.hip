@@ -114,28 +114,9 @@ __global__ void __launch_bounds__(64) k_pointmass_apply(const PmBoxDev* __restri
     if (l == 0) *d_mass = *d_mass + delta;
 }
 
-// A table on the device, kept per content like the box tables of the binning (monopole_kernels.hip): a table the context has
-// seen costs neither a copy nor a synchronisation, so the call can be captured into a graph.  host: fully initialised bytes
-static int pm_table(MonoWorkspace* ws, const void* host, size_t bytes, hipStream_t stream, const void** dev)
-{
-    std::vector<char> key((const char*)host, (const char*)host + bytes);
-    for (auto& t : ws->tables) if (t.host == key) { *dev = t.dev; return 0; }
-    if (ws->tables.size() >= 32) {
-        (void)hipStreamSynchronize(stream);
-        (void)hipFree(ws->tables.front().dev);
-        ws->tables.erase(ws->tables.begin());
-    }
-    void* d = nullptr;
-    if (hipMalloc(&d, bytes) != hipSuccess) return CASTRO_AMD_ERR_NOMEM;
-    if (hipMemcpy(d, host, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return CASTRO_AMD_ERR_HIP; }
-    ws->tables.push_back(MonoWorkspace::Table());
-    ws->tables.back().host.swap(key);
-    ws->tables.back().dev = d;
-    *dev = d;
-    return 0;
-}
+// The tables are kept on the device per content (TableCache, dev_table.h): fully initialised bytes
 
-int launch_add_pointmass(int nfab, PmFabDev* fabs, const PmGeom& G, const double* d_mass, MonoWorkspace* ws, hipStream_t stream,
+int launch_add_pointmass(int nfab, PmFabDev* fabs, const PmGeom& G, const double* d_mass, TableCache* tables, hipStream_t stream,
                          Profiler* prof)
 {
     long tot = 0;
@@ -147,40 +128,40 @@ int launch_add_pointmass(int nfab, PmFabDev* fabs, const PmGeom& G, const double
     }
     if (nfab == 0 || tot == 0) return 0;
     if ((tot + 255) / 256 >= 0x7fffffffL) return CASTRO_AMD_ERR_ARG;
-    const void* dtab = nullptr;
-    const int rt = pm_table(ws, fabs, (size_t)nfab * sizeof(PmFabDev), stream, &dtab);
+    const PmFabDev* dtab = nullptr;
+    const int rt = tables->find(fabs, (size_t)nfab, stream, dtab);
     if (rt != 0) return rt;
     prof_begin(prof, "k_add_pointmass", stream);
-    hipLaunchKernelGGL(k_add_pointmass, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, (const PmFabDev*)dtab, nfab, tot, G, d_mass);
+    hipLaunchKernelGGL(k_add_pointmass, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, dtab, nfab, tot, G, d_mass);
     prof_end(prof, stream);
     return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
 }
 
 // nbox == 0 (a rank without a box of the level): the delta is 0, the apply only adds the summed change to the point mass
-int launch_pointmass_delta(int nbox, const PmBoxDev* boxes, const int clo[3], double vol, double* d_delta, MonoWorkspace* ws,
+int launch_pointmass_delta(int nbox, const PmBoxDev* boxes, const int clo[3], double vol, double* d_delta, TableCache* tables,
                            hipStream_t stream, Profiler* prof)
 {
-    const void* dtab = nullptr;
+    const PmBoxDev* dtab = nullptr;
     if (nbox > 0) {
-        const int rt = pm_table(ws, boxes, (size_t)nbox * sizeof(PmBoxDev), stream, &dtab);
+        const int rt = tables->find(boxes, (size_t)nbox, stream, dtab);
         if (rt != 0) return rt;
     }
     prof_begin(prof, "k_pointmass_delta", stream);
-    hipLaunchKernelGGL(k_pointmass_delta, dim3(1), dim3(64), 0, stream, (const PmBoxDev*)dtab, nbox, clo[0], clo[1], clo[2], vol, d_delta);
+    hipLaunchKernelGGL(k_pointmass_delta, dim3(1), dim3(64), 0, stream, dtab, nbox, clo[0], clo[1], clo[2], vol, d_delta);
     prof_end(prof, stream);
     return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
 }
 
 int launch_pointmass_apply(int nbox, const PmBoxDev* boxes, const int clo[3], const double* d_delta, double* d_mass,
-                           MonoWorkspace* ws, hipStream_t stream, Profiler* prof)
+                           TableCache* tables, hipStream_t stream, Profiler* prof)
 {
-    const void* dtab = nullptr;
+    const PmBoxDev* dtab = nullptr;
     if (nbox > 0) {
-        const int rt = pm_table(ws, boxes, (size_t)nbox * sizeof(PmBoxDev), stream, &dtab);
+        const int rt = tables->find(boxes, (size_t)nbox, stream, dtab);
         if (rt != 0) return rt;
     }
     prof_begin(prof, "k_pointmass_apply", stream);
-    hipLaunchKernelGGL(k_pointmass_apply, dim3(1), dim3(64), 0, stream, (const PmBoxDev*)dtab, nbox, clo[0], clo[1], clo[2], d_delta, d_mass);
+    hipLaunchKernelGGL(k_pointmass_apply, dim3(1), dim3(64), 0, stream, dtab, nbox, clo[0], clo[1], clo[2], d_delta, d_mass);
     prof_end(prof, stream);
     return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
 }
