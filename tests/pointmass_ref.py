@@ -57,9 +57,29 @@ def delta_terms(boxes, geom, center):
     return np.concatenate(out) if out else np.zeros(0)
 
 
+def delta_parts(boxes, geom, center):
+    """the sum of every box on its own, one accumulator over the box's cube zones in the order of the reference's loop nest (k
+    outermost, i innermost; Castro_pointmass.cpp:35-79) -- a numpy sum adds in another order.  Within ONE box this is the
+    reference's order; a box that misses the cube gives 0"""
+    parts = []
+    for b in boxes:
+        s = 0.0
+        for t in delta_terms([b], geom, center):
+            s += float(t)
+        parts.append(s)
+    return parts
+
+
 def delta(boxes, geom, center):
-    """mass_change_at_center of this rank's boxes (any summation order is within n 2^-52 sum |terms| of any other)"""
-    return float(np.sum(delta_terms(boxes, geom, center)))
+    """mass_change_at_center of this rank's boxes: the parts of delta_parts added in box order.  For one box that is the
+    reference's order.  For several it is ONE of the orders the reference may take, not THE order: AMReX on one rank carries a
+    single accumulator across the MFIter loop (another association), threads, ranks and a GPU reduction others again.  Any
+    order is within n 2^-52 sum |terms| of any other; bit equality across several boxes can be asked only where the sum is
+    exact (the multi-box cases of tests/golden/stub_probe/source_vectors.npz)"""
+    s = 0.0
+    for p in delta_parts(boxes, geom, center):
+        s += p
+    return s
 
 
 def apply(boxes, geom, center, d, M):

@@ -13,6 +13,11 @@ namespace castro {
     int mol_order = 2, do_ctu = 1, sdc_order = 2, domain_is_plane_parallel = 0;
     Real rotational_period = -1.e200, rotational_dPdt = 0.0;
     int rot_axis = 3, rot_source_type = 4, implicit_rotation_update = 1, rotation_include_centrifugal = 1, rotation_include_coriolis = 1;
+    int sponge_implicit = 1, grav_source_type = 4, use_point_mass = 0, point_mass_fix_solution = 0;
+    Real sponge_lower_radius = -1.0, sponge_upper_radius = -1.0, sponge_lower_density = -1.0, sponge_upper_density = -1.0,
+         sponge_lower_pressure = -1.0, sponge_upper_pressure = -1.0, sponge_lower_factor = 0.0, sponge_upper_factor = 1.0,
+         sponge_target_x_velocity = 0.0, sponge_target_y_velocity = 0.0, sponge_target_z_velocity = 0.0, sponge_timescale = -1.0,
+         point_mass = 0.0;
 }
 Geometry Castro::geom;
 BCRec Castro::phys_bc;
