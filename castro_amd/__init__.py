@@ -10,12 +10,12 @@ Layout:
   plotfile.py      Castro plotfile writer / reader
 """
 from ._lib import (NUM_STATE, NGDNV, NUM_GROW, URHO, UMX, UMY, UMZ, UEDEN, UEINT, UTEMP, UFS,
-                   default_params, make_geom, make_rotation, make_diffusion, make_sponge, LIB_PATH)
+                   default_params, make_geom, make_rotation, make_diffusion, make_sponge, make_ext_bc, LIB_PATH)
 from .castro import Castro, DistComm, SingleComm, AdvanceFailure, default_grid
 from .amr import CastroAmr
 from .gravity import MonopoleGravity, PointMass
 
-__all__ = ["Castro", "CastroAmr", "MonopoleGravity", "PointMass", "DistComm", "SingleComm", "AdvanceFailure", "default_grid", "default_params", "make_geom", "make_rotation", "make_diffusion", "make_sponge",
+__all__ = ["Castro", "CastroAmr", "MonopoleGravity", "PointMass", "DistComm", "SingleComm", "AdvanceFailure", "default_grid", "default_params", "make_geom", "make_rotation", "make_diffusion", "make_sponge", "make_ext_bc",
            "NUM_STATE", "NGDNV", "NUM_GROW", "LIB_PATH"]
 
 

@@ -74,6 +74,7 @@ EXPORTED_SYMBOLS = (
     "castro_amd_radial_mass_mf_ex", "castro_amd_radial_combine", "castro_amd_grav_bc_fill_fab", "castro_amd_sources_mf_g",
     "castro_amd_new_sponge_source_fab", "castro_amd_sources_mf_opts",
     "castro_amd_add_pointmass_fab", "castro_amd_add_pointmass_mf", "castro_amd_pointmass_delta_mf", "castro_amd_pointmass_apply_mf",
+    "castro_amd_ext_bc_fill_fab",
 )
 
 
@@ -229,6 +230,88 @@ def make_sponge(timescale, lower_radius=-1.0, upper_radius=-1.0, lower_density=-
     S.timescale, S.implicit = float(timescale), int(implicit)
     S.center_given = center is not None
     return S
+
+
+class ExtBc(C.Structure):
+    """castro_amd_ext_bc, and beside it the three runtime parameters the ambient state is built from (castro.ambient_density,
+    ambient_temp, ambient_energy): they are no part of the C struct, which carries the finished ambient_state.  They default to
+    the reference's -1e200 ("not set": the small_* quantities) on every instance, however it was made; copy() keeps them, a
+    from_buffer_copy is a copy of the C struct alone and has the defaults again."""
+    _fields_ = [("lo_type", C.c_int * 3), ("hi_type", C.c_int * 3), ("hse_zero_vels", C.c_int), ("hse_interp_temp", C.c_int),
+                ("hse_reflect_vels", C.c_int), ("fill_ambient_bc", C.c_int), ("ambient_fill_dir", C.c_int),
+                ("ambient_outflow_vel", C.c_int), ("const_grav", C.c_double), ("ambient_state", C.c_double * 8)]
+    ambient_density = ambient_temp = ambient_energy = -1.e200
+
+    def copy(self):
+        E = ExtBc.from_buffer_copy(self)
+        E.ambient_density, E.ambient_temp, E.ambient_energy = self.ambient_density, self.ambient_temp, self.ambient_energy
+        return E
+
+
+EXT_BC_TYPES = {"none": -1, "hse": 1, -1: -1, 1: 1}       # Source/problems/ext_bc_types.H: EXT_UNDEFINED, EXT_HSE
+BC_INFLOW, BC_OUTFLOW = 1, 2
+
+
+def ambient_state(params, ambient_density=-1.e200, ambient_temp=-1.e200, ambient_energy=-1.e200):
+    """ambient::ambient_state (Castro_setup.cpp:339-350): the parameters where they were set, else the "small" quantities;
+    UEDEN = UEINT, one species, momenta zero"""
+    rho = max(float(ambient_density), params.small_dens)
+    rhoe = rho * max(float(ambient_energy), params.small_ener)
+    return (rho, 0.0, 0.0, 0.0, rhoe, rhoe, max(float(ambient_temp), params.small_temp), rho * (1.0 / 1))
+
+
+def make_ext_bc(xl=-1, xr=-1, yl=-1, yr=-1, zl=-1, zr=-1, hse_zero_vels=0, hse_interp_temp=0, hse_reflect_vels=0,
+                fill_ambient_bc=0, ambient_fill_dir=-1, ambient_outflow_vel=0, ambient_density=-1.e200, ambient_temp=-1.e200,
+                ambient_energy=-1.e200):
+    """castro.{xl,xr,yl,yr,zl,zr}_ext_bc_type ("hse" / 1, "none" / -1), castro.hse_*, castro.fill_ambient_bc and castro.ambient_*
+    with the defaults of Source/driver/_cpp_parameters:193-253.  const_grav and ambient_state are completed by the driver
+    (complete_ext_bc); a direct caller of HipHydro.ext_bc_fill sets them.  Raises ValueError for what
+    castro_amd_ext_bc_fill_fab refuses whatever the geometry: HSE on +z, HSE faces that meet at an edge."""
+    E = ExtBc()
+    for d, (l, h) in enumerate(((xl, xr), (yl, yr), (zl, zr))):
+        for v in (l, h):
+            if isinstance(v, bool) or v not in EXT_BC_TYPES:
+                raise ValueError("ext_bc_type %r: \"hse\" (1) or \"none\" (-1)" % (v,))
+        E.lo_type[d], E.hi_type[d] = EXT_BC_TYPES[l], EXT_BC_TYPES[h]
+    if E.hi_type[2] == 1:
+        raise ValueError("HSE boundaries not implemented for +Z")
+    if sum(E.lo_type[d] == 1 or E.hi_type[d] == 1 for d in range(3)) > 1:
+        raise ValueError("external boundaries meeting at a corner not supported")
+    if int(ambient_fill_dir) not in (-1, 0, 1, 2):
+        raise ValueError("ambient_fill_dir: -1 (all), 0, 1 or 2")
+    E.hse_zero_vels, E.hse_interp_temp, E.hse_reflect_vels = int(hse_zero_vels), int(hse_interp_temp), int(hse_reflect_vels)
+    E.fill_ambient_bc, E.ambient_fill_dir, E.ambient_outflow_vel = int(fill_ambient_bc), int(ambient_fill_dir), int(ambient_outflow_vel)
+    E.ambient_density, E.ambient_temp, E.ambient_energy = float(ambient_density), float(ambient_temp), float(ambient_energy)
+    return E
+
+
+def complete_ext_bc(ext, params, const_grav):
+    """a copy of `ext` with gravity.const_grav and the ambient state of `params` (what a driver hands to the fill)"""
+    E = ext.copy()
+    E.const_grav = float(const_grav)
+    for n, v in enumerate(ambient_state(params, ext.ambient_density, ext.ambient_temp, ext.ambient_energy)):
+        E.ambient_state[n] = v
+    return E
+
+
+def ext_bc_hse_faces(ext, geom):
+    """(direction, side) of the faces with a hydrostatic fill: of type HSE and Inflow (the reference's EXT_DIR)"""
+    return [(d, s) for d in range(3) for s, (t, bc) in enumerate(((ext.lo_type[d], geom.lo_bc[d]), (ext.hi_type[d], geom.hi_bc[d])))
+            if t == 1 and bc == BC_INFLOW]
+
+
+def check_ext_bc(ext, geom):
+    """ValueError for what castro_amd_ext_bc_fill_fab refuses with this geometry (its CASTRO_AMD_ERR_UNSUPPORTED and the
+    domain-size part of CASTRO_AMD_ERR_ARG)"""
+    if geom.coord != 0:
+        raise ValueError("ext_bc: Cartesian geometry only")
+    if sum(geom.lo_bc[d] == BC_INFLOW or geom.hi_bc[d] == BC_INFLOW for d in range(3)) > 1:
+        raise ValueError("external boundaries meeting at a corner not supported")
+    if geom.hi_bc[2] == BC_INFLOW and ext.hi_type[2] == 1:
+        raise ValueError("HSE boundaries not implemented for +Z")
+    for d, _ in ext_bc_hse_faces(ext, geom):
+        if ext.hse_interp_temp == 1 and geom.domhi[d] - geom.domlo[d] + 1 < 2:
+            raise ValueError("hse_interp_temp needs two zones of the domain in direction %d" % d)
 
 
 class PointMassParams(C.Structure):
@@ -455,6 +538,9 @@ def load(numerics=None):
     L.castro_amd_fluxreg_fine_add_fab.argtypes = [C.c_void_p, PF, PF, I3, I3, C.c_int, C.c_int, C.c_double, C.c_void_p]
     L.castro_amd_reflux_fab.argtypes = [C.c_void_p, PF, PF, I3, I3, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]
     L.castro_amd_bc_fill_fab.argtypes = [C.c_void_p, PF, C.POINTER(Geom), C.c_void_p]
+    if hasattr(L, "castro_amd_ext_bc_fill_fab"):            # absent from A/B builds of revisions before the boundary overrides
+        L.castro_amd_ext_bc_fill_fab.argtypes = [C.c_void_p, PF, C.POINTER(Geom), C.POINTER(Params), C.POINTER(ExtBc), C.c_void_p,
+                                                 C.c_void_p]
     L.castro_amd_copy_fab.argtypes = [C.c_void_p, PF, PF, I3, I3, C.c_void_p]
     L.castro_amd_pack_fab.argtypes = [C.c_void_p, PF, I3, I3, C.c_void_p, C.c_void_p]
     L.castro_amd_unpack_fab.argtypes = [C.c_void_p, PF, I3, I3, C.c_void_p, C.c_void_p]

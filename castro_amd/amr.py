@@ -125,6 +125,8 @@ class _Level:
         self.red = self.mine[0].red if self.mine else self.hydro.alloc(1, (0, 0, 0), (2, 0, 0)).reshape(3)
         for b in self.mine:
             b.red = self.red      # one [min dt, min rho] pair for the level: every box reduces into it
+            if b.ext_bc is not None:       # and one count of unconverged HSE columns behind it
+                b._red_all, b._unconverged = self.mine[0]._red_all, self.mine[0]._unconverged
             b.fuse_post_clean = False      # post_timestep's clean_state comes after reflux and avgDown (_time_step)
         self._pending_cleans, self._post_clean_done, self._whole_step = 2, False, False
         for k in ("use_retry", "retry_subcycle_factor", "max_subcycles", "dt_cutoff", "max_dt", "fixed_dt", "have_sources"):
@@ -252,7 +254,20 @@ class _Level:
         h = self.hydro
         for s, (lo, hi), sh in b.sib:
             h.copy(S, b.gbox, getattr(s, which), _shift(s.gbox, sh), lo, hi)
-        h.bc_fill(S, b.gbox, b.geom)                           # fine zones outside the domain
+        self._bc_fill_state(b, S)                              # fine zones outside the domain
+
+    def _bc_fill_state(self, b, S):
+        """the physical-boundary fill of a state array of box b: the generic fill, then -- with ext_bc -- the ambient and
+        hydrostatic overrides (Castro._bc_fill_state on the level's context)"""
+        self.hydro.bc_fill(S, b.gbox, b.geom)
+        if b.ext_bc is not None:
+            self.hydro.ext_bc_fill(S, b.gbox, b.geom, b.params, b.ext_bc, unconverged=b._unconverged)
+
+    def _read_red(self):
+        """self.red on the host; with ext_bc the same copy carries the count of unconverged HSE columns (Castro._read_red)"""
+        if self.mine and self.mine[0].ext_bc is not None:
+            return self.mine[0]._read_red()
+        return self.red.tolist()
 
     def _cached_ops(self, key, ptrs, build):
         """Operation tables hold raw pointers: S_old_b / S_new_b swap at every advance, so a table is kept per
@@ -312,7 +327,7 @@ class _Level:
         # 4. physical boundaries
         for b in self.boxes:
             if b.at_domain_edge:
-                h.bc_fill(getattr(b, which), b.gbox, b.geom)
+                self._bc_fill_state(b, getattr(b, which))
 
     def _fill_ranks(self, which):
         """fill() with the boxes of this level and of the parent level spread over ranks: the same four passes, every
@@ -325,7 +340,7 @@ class _Level:
                 if hasattr(h, "fillpatch_shell") else self._interp_shell(b, getattr(b, which))
         X([("copy", b, sb, lo, hi, (which, sh)) for b in self.boxes for sb, (lo, hi), sh in b.sib])
         for b in self.mine:
-            h.bc_fill(getattr(b, which), b.gbox, b.geom)
+            self._bc_fill_state(b, getattr(b, which))
 
     def _interp_shell(self, b, S):
         for lo, hi in b.shell:
@@ -524,7 +539,7 @@ class _Level:
             self._hydro_calls(hydro)
         self._clean_reduce_new()
         self.amr.comm.allreduce_min(self.red)
-        bad = density_failure(self.red.tolist()[1], self.params)
+        bad = density_failure(self._read_red()[1], self.params)
         if bad:
             return bad
         sources(1)
@@ -644,7 +659,7 @@ class _Level:
         if not self.fuse_clean:
             self._clean_reduce_new()
         self.amr.comm.allreduce_min(self.red)                 # the level's minima over the ranks that hold its boxes
-        est_last, rho_min, est = self.red.tolist()    # [2]: the estimate after the first clean_state (the only one here
+        est_last, rho_min, est = self._read_red()    # [2]: the estimate after the first clean_state (the only one here
                                                       # unless post_timestep's rode along: then [0] is the one after it)
         if self._post_clean_done:
             # the state leaves this advance as post_timestep will leave it (finest level, whole-step attempt): its CFL
@@ -674,7 +689,7 @@ class _Level:
             for b in self.mine:
                 self.hydro.estdt_cfl(b.S_new_b, b.gbox, b.lo, b.hi, b.geom, b.params, self.red)
         self.amr.comm.allreduce_min(self.red)
-        return min(self.max_dt, checked_estimate(self.red.tolist()[0], empty_ok=not self.boxes) * self.params.cfl)
+        return min(self.max_dt, checked_estimate(self._read_red()[0], empty_ok=not self.boxes) * self.params.cfl)
 
     def clean_new(self):
         self._clean_boxes("S_new_b", 1)
@@ -747,8 +762,11 @@ class CastroAmr:
                  blocking_factor=8, patches=None, max_level=1, cluster=False, grid_eff=0.7, max_grid_size=128,
                  do_grav=False, const_grav=0.0, grav_source_type=4, rotation=None, comm=None, base_grid=None, box_streams=4,
                  diffusion=None, sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", gravity=None,
-                 sponge=None, use_point_mass=False, point_mass=0.0, point_mass_fix_solution=False):
-        """use_point_mass, point_mass, point_mass_fix_solution: as in castro_amd.Castro, with gravity=MonopoleGravity(...) -- ONE
+                 sponge=None, use_point_mass=False, point_mass=0.0, point_mass_fix_solution=False, ext_bc=None):
+        """ext_bc: _lib.make_ext_bc(...) -- the boundary overrides of the state fill (hydrostatic Inflow faces, the ambient state
+        beyond Outflow faces) on every box of every level that reaches the boundary, as in castro_amd.Castro; the hydrostatic
+        fill assumes constant gravity (not with gravity=MonopoleGravity(...)).
+        use_point_mass, point_mass, point_mass_fix_solution: as in castro_amd.Castro, with gravity=MonopoleGravity(...) -- ONE
         point mass per hierarchy (self.point_mass reads the device value), its field added after the Gravity_Type FillPatch of
         every level, Castro::pointmass_update after every advance of the finest existing level.  Constant gravity plus a point
         mass is not built for AMR levels (the Gravity_Type FillPatch tables exist for monopole gravity only).
@@ -816,6 +834,8 @@ class CastroAmr:
             self._kw["gravity"] = gravity
         if sponge is not None:
             self._kw["sponge"] = sponge
+        if ext_bc is not None:
+            self._kw["ext_bc"] = ext_bc
         self.n_cell = tuple(n_cell)
         self.periodic = tuple(lo_bc[d] == 0 and hi_bc[d] == 0 for d in range(3))
         # boxes of a level whose hydro updates may be in flight at once (device backend); CASTRO_AMD_BOX_STREAMS overrides

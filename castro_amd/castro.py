@@ -17,6 +17,7 @@ sub-box, which needs no remote data, on the compute stream.
 """
 import itertools
 import os
+import struct
 
 import time
 
@@ -260,8 +261,14 @@ class Castro:
                  do_grav=False, const_grav=0.0, grav_source_type=4, box=None, rotation=None, fixed_dt=-1.0, initial_dt=-1.0, max_dt=1.e200,
                  alloc=True, numerics=None, proxy_ranks=1, diffusion=None, do_hydro=True,
                  sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", drdxfac=1, Gconst=L.GCONST,
-                 gravity=None, sponge=None, use_point_mass=False, point_mass=0.0, point_mass_fix_solution=False):
-        """use_point_mass, point_mass, point_mass_fix_solution (castro.use_point_mass / point_mass / point_mass_fix_solution): a
+                 gravity=None, sponge=None, use_point_mass=False, point_mass=0.0, point_mass_fix_solution=False, ext_bc=None):
+        """ext_bc: _lib.make_ext_bc(zl="hse", ...) turns on the boundary overrides of the state fill (ca_statefill's second half:
+        castro.*_ext_bc_type = HSE on Inflow faces, castro.fill_ambient_bc beyond Outflow faces); const_grav and the ambient state
+        are completed from this object's gravity and params, and every physical-boundary fill of a state array is followed by
+        castro_amd_ext_bc_fill_fab (_bc_fill_state).  The hydro call then never fills boundary zones itself, so the light overlap
+        falls back to overlap=False.  A column whose Newton iteration does not converge raises RuntimeError where the step reads
+        its reduction back.
+        use_point_mass, point_mass, point_mass_fix_solution (castro.use_point_mass / point_mass / point_mass_fix_solution): a
         mass M at problem::center -- the `center` attribute, else the middle of the domain -- whose field is added to the gravity
         vector of either gravity_type (Gravity::add_pointmass_to_gravity); needs do_grav.  M lives in one device double
         (self.point_mass reads it).  With "constant" the gravity is then no longer one vector: the box gets grav_old / grav_new
@@ -344,6 +351,17 @@ class Castro:
             self.mass_fluxes.append(hydro_alloc(1, self.lo, fhi))
         # [CFL estimate after the last clean_state, min rho, CFL estimate after the first clean_state]
         self.red = hydro.alloc(1, (0, 0, 0), (2, 0, 0)).reshape(3) if alloc else None
+        self.ext_bc, self._unconverged = None, None         # no counter without buffers of its own (alloc=False): a null pointer
+        if ext_bc is not None:
+            if do_grav and (gravity_type == "monopole" or gravity is not None) and L.ext_bc_hse_faces(ext_bc, self.geom):
+                raise ValueError("HSE boundaries assume constant gravity: not with gravity_type=\"monopole\"")
+            L.check_ext_bc(ext_bc, self.geom)
+            self.ext_bc = L.complete_ext_bc(ext_bc, self.params, const_grav if do_grav else 0.0)
+            if alloc:
+                # the reduction with a fourth word behind it: the count of unconverged HSE columns (an int32 in the low half),
+                # so that one copy brings both to the host
+                self._red_all = hydro.alloc(1, (0, 0, 0), (3, 0, 0)).reshape(4)
+                self.red, self._unconverged = self._red_all[:3], self._red_all[3:].view(torch.int32)[:1]
 
         self._plans = {}
         self.neighbors = self._build_neighbors() if box is None else []
@@ -359,6 +377,8 @@ class Castro:
         # True: the light split of round 6 (ctoprim + the pending cleans on the valid zones beside the exchange, then the ghost
         # shell in one launch and the un-split update); "staged": the round-2 split (ctoprim + tracing of the inner zones beside
         # the exchange, split trace launches after it); "tiles": interior tile + six slabs
+        if self.ext_bc is not None and overlap is True:
+            overlap = False                     # the light split needs the boundary fill inside the hydro call
         self.overlap = overlap                                                   # True | "staged" | "tiles" | False
         # the hydro call can fill the physical-boundary zones of Sborder itself (CASTRO_AMD_BC_FILL: the boundary-zone mode of
         # k_ctoprim instead of k_bc_fill + the k_ctoprim pass over those zones); needs the image of a mirrored ghost layer inside
@@ -366,14 +386,16 @@ class Castro:
         # cleans); the plain path keeps k_bc_fill + ONE k_ctoprim over the whole grown box, which is 0.05 ms faster per 256^3 step
         # (a launch over (n+8)^3 zones of an (n+8)-wide FAB is one contiguous stream, the valid rows alone are not:
         # profiles/r06h_*).  CASTRO_AMD_BC_IN_HYDRO=0: never; =2: in the plain path as well (A/B, tests).
+        # Not with ext_bc: the boundary-zone mode of k_ctoprim cannot do an HSE walk.
         self.bc_in_hydro = (hasattr(self.hydro, "lib") and box is None and alloc and min(self.n) >= NUM_GROW
-                            and os.environ.get("CASTRO_AMD_BC_IN_HYDRO", "1") != "0")
+                            and self.ext_bc is None and os.environ.get("CASTRO_AMD_BC_IN_HYDRO", "1") != "0")
         self.bc_in_hydro_plain = self.bc_in_hydro and os.environ.get("CASTRO_AMD_BC_IN_HYDRO", "1") == "2"
         self.fuse_clean = bool(fuse_clean)
         self.fuse_post_clean = True        # post_timestep's clean_state may ride in the fused pass (a level of CastroAmr: no)
         # the clean_state sweeps in front of the hydro update ride inside k_ctoprim (castro_amd_ctu_hydro_fab_ex) when the
         # rank's box is updated by one un-staged call; CASTRO_AMD_FUSE_SBORDER_CLEAN=0 keeps the separate sweep
-        self.fuse_sborder_clean = (self.fuse_clean and hasattr(self.hydro, "lib") and box is None
+        # (not with ext_bc: its fill reads the state it starts from, which the reference has cleaned by then)
+        self.fuse_sborder_clean = (self.fuse_clean and hasattr(self.hydro, "lib") and box is None and self.ext_bc is None
                                    and os.environ.get("CASTRO_AMD_FUSE_SBORDER_CLEAN", "1") != "0")
         self._pending_cleans, self._post_clean_done, self._whole_step = 2, False, False
         # one hydro call per step: "zero fluxes, then +=" (Castro_advance.cpp:391-394) is an assignment
@@ -579,6 +601,8 @@ class Castro:
                 self._packed = ("c", plan["cplan"])
             else:
                 h.fill_boundary(plan["cplan"], S, box, self.geom if bc else None)
+            if bc:
+                self._ext_bc_fill(S, box)
             return
 
         def packed():
@@ -598,7 +622,7 @@ class Castro:
             if plan["unpack_remote"] is not None:
                 h.unpack_regions(S, box, plan["unpack_remote"], plan["rall"])
             if bc:
-                h.bc_fill(S, box, self.geom)
+                self._bc_fill_state(S, box)
             return
         sends, recvs, local = [], [], []
         for nb in neighbors:
@@ -618,7 +642,32 @@ class Castro:
         for nb in neighbors:
             h.unpack(S, box, nb["rbox"][0], nb["rbox"][1], nb["rbuf"])
         if bc:
-            h.bc_fill(S, box, self.geom)
+            self._bc_fill_state(S, box)
+
+    def _bc_fill_state(self, S, box):
+        """the physical-boundary fill of a FAB: the generic fill, then -- with ext_bc, on a NUM_STATE array -- the ambient and
+        hydrostatic overrides (ca_statefill)"""
+        self.hydro.bc_fill(S, box, self.geom)
+        self._ext_bc_fill(S, box)
+
+    def _ext_bc_fill(self, S, box):
+        if self.ext_bc is not None and S.shape[0] == NUM_STATE:
+            self.hydro.ext_bc_fill(S, box, self.geom, self.params, self.ext_bc, unconverged=self._unconverged)
+
+    def _read_red(self):
+        """self.red on the host (the step's one read-back); with ext_bc the same copy carries the count of HSE columns whose
+        Newton iteration did not converge since the last read.  The count is this rank's own and is not reduced: of several ranks
+        only those that own such a column raise, the others go on to their next collective -- like any exception of one rank, it
+        ends the run through the launcher, not through an exception on every rank."""
+        if self.ext_bc is None or self._unconverged is None:
+            return self.red.tolist()
+        v = self._red_all.tolist()
+        bad = struct.unpack("<ii", struct.pack("<d", v[3]))[0]
+        if bad:
+            self._unconverged.zero_()
+            faces = ", ".join("xyz"[d] + ("-high" if s else "-low") for d, s in L.ext_bc_hse_faces(self.ext_bc, self.geom))
+            raise RuntimeError("HSE boundary (%s): %d ghost columns failed to converge" % (faces, bad))
+        return v[:3]
 
     def _wait_packed(self):
         """the current stream waits for the pack of the last expand_state(mark_packed=True)"""
@@ -867,7 +916,7 @@ class Castro:
         self.red.fill_(1.e200)
         self.hydro.estdt_cfl(self.S_new_b, self.gbox, self.lo, self.hi, self.geom, self.params, self.red)
         self.comm.allreduce_min(self.red)
-        v = self.red.tolist()
+        v = self._read_red()
         return v[0], v[1]
 
     def estTimeStep(self):
@@ -1017,7 +1066,7 @@ class Castro:
         if not fuse:
             h.clean_state_reduce(self.S_new_b, self.gbox, self.lo, self.hi, self.geom, self.params, self.red, ntimes=1)
         self.comm.allreduce_min(self.red)
-        est, rho_min, est1 = self.red.tolist()
+        est, rho_min, est1 = self._read_red()
         bad = density_failure(rho_min, self.params)
         if bad:
             return bad
@@ -1159,7 +1208,7 @@ class Castro:
             # S_new.min(URHO) (:168-216), clean_state(S_new) (:221-225)
             h.clean_state_reduce(self.S_new_b, self.gbox, lo, hi, self.geom, self.params, self.red, ntimes=1)
             self.comm.allreduce_min(self.red)
-            bad = density_failure(self.red.tolist()[1], self.params)
+            bad = density_failure(self._read_red()[1], self.params)
             if bad:
                 return bad
         else:
@@ -1364,7 +1413,8 @@ class Castro:
         # dt limits and the flags of the driver -- a run that changes one of them between two batches gets a new graph
         # instead of a replay of the old values
         baked = (bytes(self.params), bytes(self.geom), self.max_dt, self.fixed_dt, bool(self.use_retry), bool(self.flux_assign),
-                 bool(self.fuse_clean), bool(self.fuse_post_clean), bool(self.fuse_sborder_clean), str(self.overlap))
+                 bool(self.fuse_clean), bool(self.fuse_post_clean), bool(self.fuse_sborder_clean), str(self.overlap),
+                 b"" if self.ext_bc is None else bytes(self.ext_bc))
         key = (float(stop_time), self.S_old_b.data_ptr(), self.S_new_b.data_ptr(), hash(baked))
         if key not in self._graphs:
             # No finaliser may run while the stream is capturing: a collected context, graph or event would call hipFree /
@@ -1513,6 +1563,8 @@ class Castro:
             k = min(done, L.CTL_NHIST)
             self.dt_history = [v[L.CTL_HIST + (self.nstep - k + m) % L.CTL_NHIST] for m in range(k)]
         self._next_est, self._device_next_dt = None, v[L.CTL_DT]
+        if self.ext_bc is not None:
+            self._read_red()                        # the count of unconverged HSE columns of the batch: the stream has drained
         if status:
             # The launches after the rejected step wrote nothing (they check the latched status): its old state is intact
             # in whichever buffer held it.  `nsteps - done` steps were issued from the rejected one on, each swapping roles.

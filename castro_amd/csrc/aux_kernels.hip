@@ -1068,8 +1068,6 @@ __global__ void __launch_bounds__(256) k_cc_interp(DFab C, DFab F, Box3 b, int n
 // The coarse-level part of a fine box's FillPatch in one launch: every zone of grow(valid, ng) \ valid gets the
 // cell-conservative interpolation of the coarse state and then clean_state x ntimes (Castro_advance.cpp:186 cleans
 // the ghost zones of Sborder too).  The shell is six slabs (z slabs over the full x-y extent, then y, then x).
-struct Slabs { int lo[6][3], nn[6][3]; long start[7]; };
-
 __global__ void __launch_bounds__(256) k_fillpatch_shell(DFab C, DFab F, Slabs S, DevParams P, int ntimes)
 {
     const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1616,18 +1614,7 @@ static int launch_bc_fill_map(const DFab& U, const int flo[3], const int fhi[3],
         bhi[d] = (M.kind_hi[d] != 0 && fhi[d] > M.hi[d]) ? M.hi[d] : fhi[d];
         if (blo[d] > bhi[d]) return 0;                                      // FAB entirely outside the domain: nothing to copy from
     }
-    // FAB box minus [blo, bhi] as six slabs (z slabs over the full x-y extent, then y, then x)
-    const int lo[6][3] = { { flo[0], flo[1], flo[2] }, { flo[0], flo[1], bhi[2] + 1 }, { flo[0], flo[1], blo[2] },
-                           { flo[0], bhi[1] + 1, blo[2] }, { flo[0], blo[1], blo[2] }, { bhi[0] + 1, blo[1], blo[2] } };
-    const int hi[6][3] = { { fhi[0], fhi[1], blo[2] - 1 }, { fhi[0], fhi[1], fhi[2] }, { fhi[0], blo[1] - 1, bhi[2] },
-                           { fhi[0], fhi[1], bhi[2] }, { blo[0] - 1, bhi[1], bhi[2] }, { fhi[0], bhi[1], bhi[2] } };
-    Slabs S;
-    S.start[0] = 0;
-    for (int r = 0; r < 6; ++r) {
-        long n = 1;
-        for (int d = 0; d < 3; ++d) { S.lo[r][d] = lo[r][d]; S.nn[r][d] = hi[r][d] - lo[r][d] + 1; n *= S.nn[r][d] > 0 ? S.nn[r][d] : 0; }
-        S.start[r + 1] = S.start[r] + n;
-    }
+    const Slabs S = shell_slabs(flo, fhi, blo, bhi);      // the FAB box minus [blo, bhi]
     if (S.start[6] <= 0) return 0;
     prof_begin(prof, "k_bc_fill", stream);
     hipLaunchKernelGGL(k_bc_fill, dim3((unsigned)((S.start[6] + 255) / 256)), dim3(256), 0, stream, U, S, ncomp, M);

@@ -1477,6 +1477,16 @@ int castro_amd_bc_fill_fab(castro_amd_ctx* c, const castro_amd_fab* state, const
                           geom->lo_bc, geom->hi_bc, (hipStream_t)stream, &c->prof);
 }
 
+int castro_amd_ext_bc_fill_fab(castro_amd_ctx* c, const castro_amd_fab* state, const castro_amd_geom* geom,
+                               const castro_amd_params* params, const castro_amd_ext_bc* ext, int* d_unconverged, void* stream)
+{
+    if (!c || !state || !state->p || !geom || !params || !ext) return CASTRO_AMD_ERR_ARG;
+    if (state->ncomp != NUM_STATE) return CASTRO_AMD_OK;          // not the state: a derive's fill ends after the generic part
+    hipSetDevice(c->device);
+    return launch_ext_bc_fill(to_dfab(state), state->lo, state->hi, geom, to_devparams(params), ext, d_unconverged,
+                              (hipStream_t)stream, &c->prof);
+}
+
 int castro_amd_copy_fab(castro_amd_ctx* c, const castro_amd_fab* dst, const castro_amd_fab* src,
                         const int lo[3], const int hi[3], void* stream)
 {

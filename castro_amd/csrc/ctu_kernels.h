@@ -8,6 +8,7 @@
 
 struct castro_amd_rotation;      // include/castro_hydro_amd.h
 struct castro_amd_sponge;
+struct castro_amd_ext_bc;
 struct castro_amd_geom;
 
 namespace cad {
@@ -261,6 +262,28 @@ int launch_derive(int which, const DFab& U, const DFab& D, int dcomp, const int 
                   hipStream_t stream, Profiler* prof);
 int launch_bc_fill(const DFab& U, const int flo[3], const int fhi[3], int ncomp, const DevGeom& g,
                    const int lo_bc[3], const int hi_bc[3], hipStream_t stream, Profiler* prof);
+// A box minus a box inside it as six slabs (z slabs over the full x-y extent, then y, then x): slab r holds the threads
+// [start[r], start[r + 1]) of a launch, nn[r] zones from lo[r]
+struct Slabs { int lo[6][3], nn[6][3]; long start[7]; };
+// [flo, fhi] minus [blo, bhi]; flo <= blo <= bhi <= fhi in every direction
+inline Slabs shell_slabs(const int flo[3], const int fhi[3], const int blo[3], const int bhi[3])
+{
+    const int lo[6][3] = { { flo[0], flo[1], flo[2] }, { flo[0], flo[1], bhi[2] + 1 }, { flo[0], flo[1], blo[2] },
+                           { flo[0], bhi[1] + 1, blo[2] }, { flo[0], blo[1], blo[2] }, { bhi[0] + 1, blo[1], blo[2] } };
+    const int hi[6][3] = { { fhi[0], fhi[1], blo[2] - 1 }, { fhi[0], fhi[1], fhi[2] }, { fhi[0], blo[1] - 1, bhi[2] },
+                           { fhi[0], fhi[1], bhi[2] }, { blo[0] - 1, bhi[1], bhi[2] }, { fhi[0], bhi[1], bhi[2] } };
+    Slabs S;
+    S.start[0] = 0;
+    for (int r = 0; r < 6; ++r) {
+        long n = 1;
+        for (int d = 0; d < 3; ++d) { S.lo[r][d] = lo[r][d]; S.nn[r][d] = hi[r][d] - lo[r][d] + 1; n *= S.nn[r][d] > 0 ? S.nn[r][d] : 0; }
+        S.start[r + 1] = S.start[r] + n;
+    }
+    return S;
+}
+// the second half of the physical-boundary fill of a state FAB (extbc_kernels.hip): ambient_fill, then hse_fill
+int launch_ext_bc_fill(const DFab& U, const int flo[3], const int fhi[3], const ::castro_amd_geom* geom, const DevParams& P,
+                       const ::castro_amd_ext_bc* ext, int* d_unconverged, hipStream_t stream, Profiler* prof);
 int launch_copy(const DFab& dst, const DFab& src, const int lo[3], const int hi[3], int ncomp,
                 hipStream_t stream, Profiler* prof);
 int launch_pack(const DFab& f, const int lo[3], const int hi[3], int ncomp, double* buf, int unpack,

@@ -656,6 +656,18 @@ class HipHydro:
         L.check(self.lib.castro_amd_bc_fill_fab(self.h, C.byref(L.fab_of(state, *box)), C.byref(geom),
                                                 _stream_ptr(stream)), "bc_fill_fab")
 
+    def ext_bc_fill(self, state, box, geom, params, ext, unconverged=None, stream=None):
+        """castro_amd_ext_bc_fill_fab: the ambient fill and the hydrostatic fill of the zones of `state` outside the domain, after
+        the generic fill (bc_fill, or a fill_boundary with a geometry).  unconverged: an int32 tensor of one element on the
+        device to which every column that leaves its Newton loop unconverged adds 1"""
+        if unconverged is not None and (unconverged.dtype != torch.int32 or unconverged.numel() != 1 or not unconverged.is_cuda):
+            raise ValueError("ext_bc_fill: unconverged must be one int32 on the device")
+        rc = self.lib.castro_amd_ext_bc_fill_fab(self.h, C.byref(L.fab_of(state, *box)), C.byref(geom), C.byref(params), C.byref(ext),
+                                                 None if unconverged is None else unconverged.data_ptr(), _stream_ptr(stream))
+        if rc in (-1, -2):                # CASTRO_AMD_ERR_ARG, CASTRO_AMD_ERR_UNSUPPORTED
+            L.check_ext_bc(ext, geom)
+        L.check(rc, "ext_bc_fill_fab")
+
     def copy(self, dst, dst_box, src, src_box, lo, hi, stream=None):
         L.check(self.lib.castro_amd_copy_fab(self.h, C.byref(L.fab_of(dst, *dst_box)), C.byref(L.fab_of(src, *src_box)),
                                              L.i3(lo), L.i3(hi), _stream_ptr(stream)), "copy_fab")

@@ -855,6 +855,38 @@ int castro_amd_estdt_fab(castro_amd_ctx *ctx, const castro_amd_fab *state,
 int castro_amd_bc_fill_fab(castro_amd_ctx *ctx, const castro_amd_fab *state,
                            const castro_amd_geom *geom, void *stream);
 
+/* The second half of ca_statefill (Source/problems/Castro_bc_fill_nd.cpp:41-105): the ambient fill
+ * (Source/problems/ambient_fill.cpp:61-154), then the hydrostatic fill (Source/problems/hse_fill.cpp), in place, on a state
+ * FAB whose zones outside the domain hold the generic fill already -- call it after castro_amd_bc_fill_fab, or after a
+ * castro_amd_fill_boundary* that was given a geometry.  3-D Cartesian, gamma-law EOS.
+ *   lo_type / hi_type      castro.{xl,yl,zl}_ext_bc_type / {xr,yr,zr}_ext_bc_type: -1 none, 1 HSE.  The hydrostatic fill runs on
+ *                          a face only where its type is 1 AND its boundary is Inflow (the reference's EXT_DIR): every ghost
+ *                          column of that face, ghost rows included, is integrated outward from the first zone inside the
+ *                          domain with Newton's method on the density (at most 250 iterations, tolerance 1e-8 rho, every update
+ *                          clamped to [0.9 rho, 1.1 rho]) under gravity.const_grav.
+ *   hse_zero_vels, hse_interp_temp, hse_reflect_vels      the reference's parameters of those names
+ *   fill_ambient_bc, ambient_fill_dir, ambient_outflow_vel: a zone beyond an Outflow face of direction ambient_fill_dir (-1:
+ *                          any direction) takes ambient_state; with ambient_outflow_vel its normal momentum is the outgoing part
+ *                          of the momentum of the first zone inside the domain, and UEDEN is made consistent.
+ *   ambient_state          ambient::ambient_state (Castro_setup.cpp:339-350)
+ * d_unconverged: NULL, or a device int to which every column that leaves a Newton loop unconverged adds 1 (the reference
+ * aborts on the CPU and is silent on the GPU); the zone is written with the last iterate all the same.
+ * Neither allocates nor synchronises.  Returns CASTRO_AMD_OK with nothing touched when state->ncomp != CASTRO_AMD_NUM_STATE
+ * (a derive's fill, Castro_bc_fill_nd.cpp:47-49) or when the FAB holds no zone of the domain.  CASTRO_AMD_ERR_UNSUPPORTED:
+ * geom->coord != 0; hi_type[2] == 1 on an Inflow +z face (hse_fill.cpp:988-991); two Inflow faces that meet at an edge
+ * (Castro_bc_fill_nd.cpp:74-100).  CASTRO_AMD_ERR_ARG: hse_interp_temp or hse_reflect_vels on a face where the FAB holds
+ * fewer zones of the domain than they read (two; as many as it has ghost layers). */
+typedef struct castro_amd_ext_bc {
+    int lo_type[3], hi_type[3];          /* -1 none, 1 HSE */
+    int hse_zero_vels, hse_interp_temp, hse_reflect_vels;
+    int fill_ambient_bc, ambient_fill_dir, ambient_outflow_vel;
+    double const_grav;
+    double ambient_state[8];
+} castro_amd_ext_bc;
+int castro_amd_ext_bc_fill_fab(castro_amd_ctx *ctx, const castro_amd_fab *state, const castro_amd_geom *geom,
+                               const castro_amd_params *params, const castro_amd_ext_bc *ext, int *d_unconverged,
+                               void *stream);
+
 /* dst(lo:hi, 0:ncomp) = src(lo:hi, 0:ncomp) between two FABs (MultiFab::Copy /
  * the same-level copy part of FillPatch). */
 int castro_amd_copy_fab(castro_amd_ctx *ctx, const castro_amd_fab *dst, const castro_amd_fab *src,

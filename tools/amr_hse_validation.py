@@ -2,7 +2,9 @@
 """An isothermal atmosphere at rest under constant gravity (rho = rho0 exp(-z/H), p = rho cT^2, H = cT^2/|g|) on a
 single level and with a refined box in the middle: the sources on the refined level, their ghost zones and the reflux must
 not disturb the balance more than the discretisation does.  Prints the largest Mach number after a fraction of a sound
-crossing time.  usage: tools/amr_hse_validation.py [oracle]   (oracle: run on the CPU with the oracle backend)"""
+crossing time.  The lids here are reflecting, and the measurement keeps away from them; a hydrostatic lower boundary is
+`lo_bc` z = Inflow with `ext_bc=castro_amd.make_ext_bc(zl="hse")` (tests/test_ext_bc_cpu.py runs a patch on such a boundary).
+usage: tools/amr_hse_validation.py [oracle]   (oracle: run on the CPU with the oracle backend)"""
 import math
 import sys
 

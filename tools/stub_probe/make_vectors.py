@@ -99,6 +99,19 @@ def build(tmp):
                                                        "-I" + os.path.join(src, "gravity"), "-c", path, "-o", o])
         osrc.append(o)
     subprocess.check_call(["g++", "-o", exe + "_sources"] + osrc)
+    # the boundary overrides of the state fill (Source/problems/ambient_fill.cpp, hse_fill.cpp, unmodified); the stand-ins grow by
+    # what they touch only under PROBE_BC
+    obc = []
+    for path in (os.path.join(src, "problems", "ambient_fill.cpp"), os.path.join(src, "problems", "hse_fill.cpp"),
+                 os.path.join(HERE, "probe_bc.cpp"), os.path.join(HERE, "probe_params.cpp")):
+        o = os.path.join(tmp, "bc_" + os.path.basename(path)[:-4] + ".o")
+        subprocess.check_call(["g++"] + flags + inc + ["-DPROBE_BC", "-DGRAVITY", "-c", path, "-o", o])
+        obc.append(o)
+    subprocess.check_call(["g++", "-o", exe + "_bc"] + obc)
+    o = os.path.join(tmp, "bc_hse_fill_silent.o")
+    subprocess.check_call(["g++"] + flags + inc + ["-DPROBE_BC", "-DGRAVITY", "-DAMREX_USE_GPU", "-c",
+                                                   os.path.join(src, "problems", "hse_fill.cpp"), "-o", o])
+    subprocess.check_call(["g++", "-o", exe + "_bc_silent"] + [o if x.endswith("bc_hse_fill.o") else x for x in obc])
     return exe
 
 
@@ -313,6 +326,135 @@ def source_vectors(exe, tmp, dst):
         print("  %-8s %8d recorded values" % (fam, sum(v.size for k, v in shaped.items() if k.startswith("out:" + fam))))
 
 
+# ---- the boundary overrides: bc<c>.* of tests/golden/stub_probe/bc_vectors.npz -------------------------------------------------
+# FAB boxes: the two of the source-term fixture.  cut: {(direction, side): n} -- that face of the domain cuts the FAB n zones in;
+# every other face lies 10 zones outside the FAB.  bc: {(direction, side): physical boundary}, Outflow where not named
+INTERIOR, INFLOW, OUTFLOW, SYMMETRY, SLIPWALL = 0, 1, 2, 3, 4
+_BOX_A, _BOX_B = (SRC_BOXES[0]["lo"], SRC_BOXES[0]["hi"]), (SRC_BOXES[1]["lo"], SRC_BOXES[1]["hi"])
+_XL, _XR, _YL, _YR, _ZL, _ZR = (0, 0), (0, 1), (1, 0), (1, 1), (2, 0), (2, 1)
+_ALL6 = {_XL: 2, _XR: 2, _YL: 2, _YR: 2, _ZL: 1, _ZR: 1}
+_ZLOW = dict(box=_BOX_B, cut={_ZL: 4, _XL: 1}, bc={_ZL: INFLOW, _XL: SLIPWALL}, hse=[_ZL])      # with a ghost row beyond an x wall
+_XLOW = dict(box=_BOX_A, cut={_XL: 4, _YR: 1}, bc={_XL: INFLOW, _YR: SYMMETRY}, hse=[_XL])
+BC_CASES = [
+    dict(_XLOW),                                                                        # 0-4: each of the five HSE faces alone
+    dict(box=_BOX_A, cut={_XR: 4}, bc={_XR: INFLOW}, hse=[_XR]),
+    dict(box=_BOX_A, cut={_YL: 4}, bc={_YL: INFLOW}, hse=[_YL]),
+    dict(box=_BOX_A, cut={_YR: 4, _ZL: 1}, bc={_YR: INFLOW, _ZL: SLIPWALL}, hse=[_YR]),
+    dict(_ZLOW),
+    dict(box=_BOX_A, cut={_XL: 4, _XR: 4}, bc={_XL: INFLOW, _XR: INFLOW}, hse=[_XL, _XR]),     # 5: x low and x high together
+    dict(_ZLOW, hse_zero_vels=1), dict(_ZLOW, hse_reflect_vels=1), dict(_ZLOW, hse_interp_temp=1, temp=1.7e-8),      # 6-8
+    dict(_XLOW, hse_zero_vels=1), dict(_XLOW, hse_reflect_vels=1), dict(_XLOW, hse_interp_temp=1, temp=0.9e-8),      # 9-11
+    dict(_ZLOW, const_grav=-21.3, temp=1.2e-8),             # 12: a scale height of 3/4 dx: a density ratio of 5 per zone under the 10 % clamp
+    dict(_ZLOW, const_grav=0.0),                            # 13
+    dict(box=_BOX_A, cut={}, bc={_ZL: INFLOW}, hse=[_ZL]),                              # 14: the FAB does not reach the boundary
+    dict(box=_BOX_B, cut={_ZL: 1}, bc={_ZL: INFLOW}, hse=[_ZL]),                        # 15: one ghost layer (four: case 4)
+    dict(box=_BOX_A, cut=_ALL6, bc={}, fill_ambient_bc=1, ambient_fill_dir=-1),         # 16-19: ambient alone; edges beyond two faces
+    dict(box=_BOX_A, cut=_ALL6, bc={}, fill_ambient_bc=1, ambient_fill_dir=0),
+    dict(box=_BOX_A, cut=_ALL6, bc={}, fill_ambient_bc=1, ambient_fill_dir=1),
+    dict(box=_BOX_A, cut=_ALL6, bc={}, fill_ambient_bc=1, ambient_fill_dir=2),
+    dict(box=_BOX_A, cut=_ALL6, bc={_XL: INFLOW, _XR: SLIPWALL}, fill_ambient_bc=1),    # 20: a wall and an Inflow face stay as they are
+    dict(box=_BOX_A, cut=_ALL6, bc={}, fill_ambient_bc=1, ambient_outflow_vel=1),       # 21: both signs on low and high faces, edges
+    dict(box=_BOX_A, cut=_ALL6, bc={_XL: SLIPWALL, _XR: SYMMETRY, _ZL: INTERIOR, _ZR: INTERIOR}, fill_ambient_bc=1,
+         ambient_outflow_vel=1),                                                        # 22: edge zones beyond an ambient face and a wall
+    dict(box=_BOX_B, cut={_ZL: 4, _ZR: 2, _XL: 1}, bc={_ZL: INFLOW, _XL: SLIPWALL}, hse=[_ZL], fill_ambient_bc=1, ambient_fill_dir=2,
+         ambient_outflow_vel=1),                                                        # 23: ambient on +z, HSE on z low
+    dict(box=_BOX_B, cut={_ZL: 4, _XL: 1}, bc={_ZL: INFLOW}, hse=[_ZL], fill_ambient_bc=1),     # 24: an HSE column that starts from an ambient zone
+    dict(box=_BOX_B, cut={_ZL: 4, _YR: 1}, bc={_ZL: INFLOW}, hse=[_ZL], hse_reflect_vels=1, fill_ambient_bc=1, ambient_outflow_vel=1),
+    # 26: temperatures a decade apart from zone to zone, extrapolated below zero in some columns: their Newton loops run out.  The
+    # reference's CPU build aborts there, its GPU build says nothing: this case runs in the executable whose hse_fill.cpp saw
+    # -DAMREX_USE_GPU (the abort is the only thing the macro touches in the two files and the headers they include)
+    dict(_ZLOW, hse_interp_temp=1, silent=True),
+]
+BC_AMBIENT = dict(ambient_density=0.01372918, ambient_temp=3.1871e-9, ambient_energy=0.6172839)
+BC_SMALL = dict(small_dens=1.e-6, small_temp=1.e-12, small_ener=1.e-9)
+
+
+def generic_fill(U, lo, hi, domlo, domhi, lo_bc, hi_bc):
+    """the generic physical-boundary fill (first-order extrapolation, Inflow included; mirrors with the normal momentum negated
+    at the walls): every zone outside the domain from the zone inside it that the three sweeps compose to"""
+    idx, flip = [], []
+    for d in range(3):
+        i = np.arange(lo[d], hi[d] + 1)
+        s, f = i.copy(), np.zeros(i.size, dtype=bool)
+        for side, bc in ((0, lo_bc[d]), (1, hi_bc[d])):
+            out = i < domlo[d] if side == 0 else i > domhi[d]
+            edge = domlo[d] if side == 0 else domhi[d]
+            if bc in (INFLOW, OUTFLOW):
+                s[out] = edge
+            elif bc >= SYMMETRY:
+                s[out] = 2 * edge - i[out] + (-1 if side == 0 else 1)
+                f |= out
+        idx.append(s - lo[d]), flip.append(f)
+    V = U[:, idx[2][:, None, None], idx[1][None, :, None], idx[0][None, None, :]].copy()
+    for d, ax in enumerate((2, 1, 0)):
+        shape = [1, 1, 1]
+        shape[ax] = -1
+        V[1 + d] = np.where(flip[d].reshape(shape), -V[1 + d], V[1 + d])
+    return V
+
+
+def bc_inputs(rng, A):
+    for c, case in enumerate(BC_CASES):
+        P = "bc%d." % c
+        lo, hi = case["box"]
+        shp = _shape(lo, hi)
+        domlo, domhi = [x - 10 for x in lo], [x + 10 for x in hi]
+        for (d, side), n in case["cut"].items():
+            if side == 0:
+                domlo[d] = lo[d] + n
+            else:
+                domhi[d] = hi[d] - n
+        lo_bc, hi_bc = [OUTFLOW] * 3, [OUTFLOW] * 3
+        for (d, side), bc in case["bc"].items():
+            (lo_bc if side == 0 else hi_bc)[d] = bc
+        types = [-1.0] * 6
+        for d, side in case.get("hse", []):
+            types[2 * d + side] = 1.0
+        rho = 10.0 ** rng.uniform(-1.0, 1.0, shp)
+        T = 10.0 ** rng.uniform(-8.5, -7.5, shp) if "temp" not in case else case["temp"] * rng.uniform(0.95, 1.05, shp)
+        U = np.zeros((8,) + shp)
+        U[0], U[6], U[7] = rho, T, rho * rng.uniform(0.9, 1.0, shp)
+        for k in range(3):
+            U[1 + k] = rho * rng.normal(size=shp)
+        U[5] = rho * (K_B * T / ((GAMMA - 1.0) * M_U))
+        U[4] = U[5] + 0.5 * (U[1] ** 2 + U[2] ** 2 + U[3] ** 2) / rho
+        A[P + "U"] = generic_fill(U, lo, hi, domlo, domhi, lo_bc, hi_bc)
+        A[P + "box"], A[P + "dx"] = np.array(lo + hi, dtype=np.float64), SRC_DX
+        A[P + "domlo"], A[P + "domhi"], A[P + "lo_bc"], A[P + "hi_bc"] = domlo, domhi, lo_bc, hi_bc
+        A[P + "types"] = types
+        A[P + "flags"] = [case.get(k, v) for k, v in (("hse_zero_vels", 0), ("hse_interp_temp", 0), ("hse_reflect_vels", 0),
+                                                      ("fill_ambient_bc", 0), ("ambient_fill_dir", -1), ("ambient_outflow_vel", 0))]
+        A[P + "const_grav"], A[P + "eos_gamma"], A[P + "silent"] = case.get("const_grav", -1.0), GAMMA, float(bool(case.get("silent")))
+        # ambient::ambient_state (Castro_setup.cpp:339-350)
+        dens = max(BC_AMBIENT["ambient_density"], BC_SMALL["small_dens"])
+        rhoe = dens * max(BC_AMBIENT["ambient_energy"], BC_SMALL["small_ener"])
+        A[P + "ambient"] = [dens, 0.0, 0.0, 0.0, rhoe, rhoe, max(BC_AMBIENT["ambient_temp"], BC_SMALL["small_temp"]), dens * (1.0 / 1)]
+        for k, v in dict(BC_AMBIENT, **BC_SMALL).items():
+            A[P + k] = v
+
+
+def bc_vectors(exe, tmp, dst):
+    rng = np.random.default_rng(20261019)
+    A = {}
+    bc_inputs(rng, A)
+    A = {k: np.atleast_1d(np.asarray(v, dtype=np.float64)) for k, v in A.items()}
+    silent = tuple("bc%d." % c for c, case in enumerate(BC_CASES) if case.get("silent"))
+    O = {}
+    for tag, suffix, keep in (("in6", "_bc", lambda k: not k.startswith(silent)), ("in7", "_bc_silent", lambda k: k.startswith(silent))):
+        write_blob(os.path.join(tmp, tag + ".bin"), {k: v for k, v in A.items() if keep(k)})
+        subprocess.check_call([exe + suffix, os.path.join(tmp, tag + ".bin"), os.path.join(tmp, tag + ".out")])
+        O.update(read_blob(os.path.join(tmp, tag + ".out")))
+    allv = {"in:" + k: v for k, v in A.items()}
+    for k, v in O.items():
+        allv["out:" + k] = v.reshape(A[k].shape)
+    path = os.path.join(dst, "bc_vectors.npz")
+    save_npz(path, allv)
+    print("wrote %s: %d input arrays, %d output arrays, %.1f KB" % (path, len(A), len(O), os.path.getsize(path) / 1024.0))
+    for k in sorted(O, key=lambda s: int(s[2:].split(".")[0])):
+        changed = int((allv["out:" + k].view(np.int64) != A[k].view(np.int64)).any(axis=0).sum())
+        print("  %-8s %6d zones, %5d changed, %d NaN" % (k, A[k][0].size, changed, int(np.isnan(O[k]).sum())))
+
+
 def edge_states(rng, n, gam=1.4, cold=0.15):
     """(7, n) edge states (rho,u,v,w,p,rhoe,X): jumps of many decades, supersonic flows, some with rho e <= 0 or a tiny
     pressure (the EOS clean-up of load_input_states)"""
@@ -515,6 +657,7 @@ def main():
         O.update(read_blob(os.path.join(tmp, "out4.bin")))
         B.update(R)
         source_vectors(exe, tmp, dst)
+        bc_vectors(exe, tmp, dst)
     A.update(B)
     # whole-tile outputs: keep the zones and faces the call defines (everything lives on the box grown by 4 in the probe)
     m = nb + 8

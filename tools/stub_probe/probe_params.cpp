@@ -18,7 +18,15 @@ namespace castro {
          sponge_lower_pressure = -1.0, sponge_upper_pressure = -1.0, sponge_lower_factor = 0.0, sponge_upper_factor = 1.0,
          sponge_target_x_velocity = 0.0, sponge_target_y_velocity = 0.0, sponge_target_z_velocity = 0.0, sponge_timescale = -1.0,
          point_mass = 0.0;
+#ifdef PROBE_BC
+    int xl_ext_bc_type = -1, xr_ext_bc_type = -1, yl_ext_bc_type = -1, yr_ext_bc_type = -1, zl_ext_bc_type = -1, zr_ext_bc_type = -1;
+    int hse_zero_vels = 0, hse_interp_temp = 0, hse_reflect_vels = 0, fill_ambient_bc = 0, ambient_fill_dir = -1, ambient_outflow_vel = 0;
+    Real ambient_density = -1.e200, ambient_temp = -1.e200, ambient_energy = -1.e200;
+#endif
 }
+#ifdef PROBE_BC
+namespace gravity { Real const_grav = 0.0; }
+#endif
 Geometry Castro::geom;
 BCRec Castro::phys_bc;
 int Castro::verbose = 0;
