@@ -100,6 +100,10 @@ struct LaunchKnobs {
                                 // occupancy A/B, slower
     int side_stream = 0;        // CASTRO_AMD_SIDE_STREAM: 1 = k_divu runs on the context's side stream beside the trace kernel; measured: no
                                 // gain, two independent pipelines on two streams take as long as one after the other (tools/concurrency_probe.py)
+    int lazy_loads = 1;         // CASTRO_AMD_LAZY_LOADS: the final kernels load what the update discards in almost every zone only where it is
+                                // kept: the old state of apply_av on compressive faces (`contract` build), the operands of the evolved (rho e)
+                                // where reset_internal_energy keeps it.  0 = every zone loads them (A/B in one binary; same bits in S_new);
+                                // 2 / 3 = the first / the second of the two alone
 };
 // the variables above as the environment has them now; one that is not set gives the default
 LaunchKnobs launch_knobs_from_env();

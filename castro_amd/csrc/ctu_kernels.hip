@@ -1576,12 +1576,42 @@ __global__ void __launch_bounds__(256) k_riemann1(Tile t, LinBox b, const double
 // viscosity, species normalisation, record for consup, scaling and accumulation
 //   (Castro_ctu_hydro.cpp:1192-1243, 1322-1433; apply_av advection_util.cpp:482-528;
 //    normalize_species_fluxes :577-613; scale_flux :616-641)
+// apply_av's coefficient for a pair of x-adjacent faces: difmag * min(0, div(u) averaged to the face)
+__device__ __forceinline__ void av_div1(const DevScratch& S, unsigned c, unsigned s1, unsigned s2, const DevParams& P, double div1[2])
+{
+    const double* DIV = S.DIV;
+    const D2 d00 = ldg2(DIV, c), d10 = ldg2(DIV, c + s1), d01 = ldg2(DIV, c + s2), d11 = ldg2(DIV, c + s1 + s2);
+    div1[0] = 0.25 * (d00.a + d10.a + d01.a + d11.a);
+    div1[1] = 0.25 * (d00.b + d10.b + d01.b + d11.b);
+    div1[0] = P.difmag * (kAsmMinMax ? amin_hw(0.0, div1[0]) : amin(0.0, div1[0]));
+    div1[1] = P.difmag * (kAsmMinMax ? amin_hw(0.0, div1[1]) : amin(0.0, div1[1]));
+}
+
+// The `assign` argument of the final kernels: bit 0 = assign (else accumulate) the fluxes; bit 1 = the old state of apply_av only
+// on compressive faces; bit 2 = the operands of the evolved (rho e) only where clean_zone keeps it.  LaunchKnobs::lazy_loads:
+// 0 = neither, 1 = both, 2 = the first alone, 3 = the second alone (the last two for timing them apart).
+__host__ __device__ constexpr bool lazy_av_on(int assign) { return (assign & 2) != 0; }
+__host__ __device__ constexpr bool lazy_eint_on(int assign) { return (assign & 4) != 0; }
+static int assign_word(int flags, const LaunchKnobs& K)
+{
+    const int l = K.lazy_loads;
+    return ((flags & 2) ? 1 : 0) | ((l == 1 || l == 2) ? 2 : 0) | ((l == 1 || l == 3) ? 4 : 0);
+}
+
+// the old state of apply_av is loaded only where a face of the pair is compressive (LaunchKnobs::lazy_loads): `contract` build,
+// kernels without the flux limiters (they need uR / uL anyway).  Not in the `exact` build: a skipped F + (+-0) can differ from
+// the reference in the sign of a zero.
+template <bool LIM> constexpr bool lazy_av() { return kContract && !LIM; }
+
+//   div1: av_div1 of the pair, formed by the caller (early, where lazy_av: the old-state loads depend on it)
+//   lazy: LaunchKnobs::lazy_loads asks for this part (lazy_av_on)
 template <int N, bool LIM, bool NOX = false>      // NOX: the species flux is the mass flux (gamma_law_edges)
 __device__ __forceinline__ void final_flux_tail(const Tile& t, const DevScratch& S, const IFlux f[2], unsigned c,
                                                 unsigned s1, unsigned s2, const DFab& U, unsigned cu, unsigned un_,
                                                 const DFab& fluxes, const DFab& mass, const DFab& qe,
                                                 int i, int j, int k, double dt, double area, double dxn, double vol,
-                                                int acc_hi, bool assign, bool v0, bool v1, const DevParams& P, double R[2][NFIN])
+                                                int acc_hi, bool assign, bool lazy, const double div1[2], bool v0, bool v1,
+                                                const DevParams& P, double R[2][NFIN])
 {
     double F[2][NUM_STATE];
 #pragma unroll
@@ -1597,14 +1627,15 @@ __device__ __forceinline__ void final_flux_tail(const Tile& t, const DevScratch&
     }
 
     {
-        const double* DIV = S.DIV;
-        const D2 d00 = ldg2(DIV, c), d10 = ldg2(DIV, c + s1), d01 = ldg2(DIV, c + s2), d11 = ldg2(DIV, c + s1 + s2);
-        double div1[2];
-        div1[0] = 0.25 * (d00.a + d10.a + d01.a + d11.a);
-        div1[1] = 0.25 * (d00.b + d10.b + d01.b + d11.b);
-        div1[0] = P.difmag * (kAsmMinMax ? amin_hw(0.0, div1[0]) : amin(0.0, div1[0]));
-        div1[1] = P.difmag * (kAsmMinMax ? amin_hw(0.0, div1[1]) : amin(0.0, div1[1]));
         double uR[2][NUM_STATE], uL[2][NUM_STATE];            // kept only by the flux limiters
+        // Where neither face is compressive div1 is zero and the term below is +-0: the six planes of U at the zone and its low
+        // neighbour are not loaded (a wave without a compressive face jumps over the block).  An Inf or NaN in U on a skipped face
+        // does not go unseen: the reference's term would be NaN there, and here the same zone still enters the update through u0
+        // and gave the edge states of the face, so the NaN reaches S_new and nan_guard all the same.  A NaN in div(u) is dropped by
+        // the hardware minimum (amin_hw(0, NaN) = 0): div1 is 0 and the block is skipped, where the term was 0 * dU before -- no
+        // result changes; such a div(u) comes from NaN velocities in Q, which reach the fluxes through the edge states.
+        const bool av = !lazy_av<LIM>() || !lazy || div1[0] != 0.0 || div1[1] != 0.0;
+        if (av) {
 #pragma unroll
         for (int m = 0; m < NUM_STATE; ++m) {
             if (m == UTEMP) { if (LIM) { uR[0][m] = uR[1][m] = uL[0][m] = uL[1][m] = 0.0; } continue; }
@@ -1614,6 +1645,7 @@ __device__ __forceinline__ void final_flux_tail(const Tile& t, const DevScratch&
             d1 = div1[1] * (uc.b - ul.b);
             F[1][m] += dxn * d1;
             if (LIM) { uR[0][m] = uc.a; uR[1][m] = uc.b; uL[0][m] = ul.a; uL[1][m] = ul.b; }
+        }
         }
         if (LIM) {
             // limit_fluxes_on_small_dens / _large_vel (Castro_ctu_hydro.cpp:1219-1239), between apply_av and the
@@ -2855,6 +2887,10 @@ __device__ __forceinline__ void final_body(const Tile& t, const int ijk[3], bool
         for (int w = 0; w < 2; ++w) trans_final(q[w], f1r[w], f1l[w], f2r[w], f2l[w], P.gamma, hdtdx_t1, hdtdx_t2, P, qr[w]);
     }
 
+    // lazy_av: requested here and reduced to two values before the Riemann solves, so that the chain div(u) -> predicate -> old
+    // state does not lengthen the tail on a compressive flow
+    double div1[2];
+    if (lazy_av<LIM>()) av_div1(S, c, s1, s2, P, div1);
     const D2 cl = ldg2(Q + PC * NC, c - sn);
     const D2 cr = ldg2(Q + PC * NC, c);
     const unsigned usn = 8u * (N == 0 ? 1u : N == 1 ? (unsigned)U.sy : (unsigned)U.sz);
@@ -2874,8 +2910,11 @@ __device__ __forceinline__ void final_body(const Tile& t, const int ijk[3], bool
         interface_flux<N, GEN>(rl, rr, Xl, Xr, w ? cl.b : cl.a, w ? cr.b : cr.a, wall_fac<N>(g, idxN),
                           face_shock(S, P, c + 8u * w, sn), P, f[w]);
     }
+    if (!lazy_av<LIM>()) av_div1(S, c, s1, s2, P, div1);
+    // assign: bit 0 = assign (else accumulate) the fluxes, bits 1 and 2 = the two lazy loads (assign_word)
     final_flux_tail<N, LIM, (gamma_law_edges(GEN) && !LIM)>(t, S, f, c, s1, s2, U, foff(U, ijk[0], ijk[1], ijk[2]), usn, fluxes, mass, qe,
-                            ijk[0], ijk[1], ijk[2], dt, area, dxn, g.dx[0] * g.dx[1] * g.dx[2], acc_hi, assign != 0, v0, v1, P, R);
+                            ijk[0], ijk[1], ijk[2], dt, area, dxn, g.dx[0] * g.dx[1] * g.dx[2], acc_hi, (assign & 1) != 0, lazy_av_on(assign),
+                            div1, v0, v1, P, R);
     if (!STORE_FL) return;
     double* FL = S.FL[N];
     constexpr bool NOX = gamma_law_edges(GEN) && !LIM;      // record GX == record GRHO: not stored, consup reads GRHO
@@ -3080,10 +3119,38 @@ __global__ void __launch_bounds__(256) CG_TWO_WAVES k_finalx_consup(Tile t, XRow
         // one species, gamma-law gas, clean_state fused in (gamma_law_edges): the temperature and the species of the old state are
         // dead -- computeTemp overwrites the one, normalize_species makes rho X = rho of the other -- and are not read
         constexpr bool DEAD_TX = gamma_law_edges(GEN) && !LIM && CLEAN;
+        // The evolved (rho e).  With clean_state fused in it is wanted only where reset_internal_energy keeps it (clean_zone: cold
+        // hypersonic gas, e/E <= eta2); everywhere else clean_zone overwrites it unseen.  So its operands that nothing else reads
+        // -- the old UEINT, the GEI records of FL[y], FL[z] and their eight GPG / GUG values -- are loaded zone by zone (`load_e`)
+        // and combined (`eint_new`: the expression and order of consup_hydro below, the x faces from R / Rn) when clean_zone asks
+        // for the value.  Switched off (lazy_eint_on): loaded for every zone as before.  The arithmetic has one site per zone of the pair
+        // either way, so the switch cannot change a bit.
+        double eu0, ey0, ey1, ez0, ez1, py0, py1, uy0, uy1, pz0, pz1, uz0, uz1;
+        auto load_e = [&](int w) {
+            const unsigned o = 8u * (unsigned)w;
+            eu0 = from_sborder ? ldg(U.p + UEINT * U.sn, ci + o) : ldg(Unew.p + UEINT * Unew.sn, cn + o);
+            ey0 = ldg(F1 + (long)GEI * NC, c + o); ey1 = ldg(F1 + (long)GEI * NC, c + sy + o);
+            ez0 = ldg(F2 + (long)GEI * NC, c + o); ez1 = ldg(F2 + (long)GEI * NC, c + sz + o);
+            py0 = ldg(F1 + GPG * NC, c + o); py1 = ldg(F1 + GPG * NC, c + sy + o);
+            uy0 = ldg(F1 + GUG * NC, c + o); uy1 = ldg(F1 + GUG * NC, c + sy + o);
+            pz0 = ldg(F2 + GPG * NC, c + o); pz1 = ldg(F2 + GPG * NC, c + sz + o);
+            uz0 = ldg(F2 + GUG * NC, c + o); uz1 = ldg(F2 + GUG * NC, c + sz + o);
+        };
+        auto eint_new = [&](int w) -> double {
+            const double* Rl = w ? R[1] : R[0];       // low and high x face of zone w
+            const double* Rh = w ? Rn : R[1];
+            double e = eu0 + dt * (Rl[GEI] * area0 - Rh[GEI] * area0 + ey0 * area1 - ey1 * area1 + ez0 * area2 - ez1 * area2) * volinv;
+            double pdu = (Rh[GPG] + Rl[GPG]) * (Rh[GUG] * area0 - Rl[GUG] * area0);
+            pdu += (py1 + py0) * (uy1 * area1 - uy0 * area1);
+            pdu += (pz1 + pz0) * (uz1 * area2 - uz0 * area2);
+            pdu = 0.5 * pdu * volinv;
+            return e - dt * pdu;
+        };
 #pragma unroll
         for (int m = 0; m < NUM_STATE; ++m) {
             if (DEAD_TX && m == UTEMP) { un[0][m] = un[1][m] = 0.0; continue; }
             if (DEAD_TX && m == UFS) { un[0][m] = un[0][URHO]; un[1][m] = un[1][URHO]; continue; }
+            if (CLEAN && m == UEINT) { un[0][m] = un[1][m] = 0.0; continue; }     // clean_zone asks for it, or overwrites it
             const D2 u0 = from_sborder ? ldg2(U.p + m * U.sn, ci) : ldg2(Unew.p + m * Unew.sn, cn);
             if (m == UTEMP) { un[0][m] = u0.a; un[1][m] = u0.b; continue; }       // zero flux
             const int r = rec[m];
@@ -3114,7 +3181,10 @@ __global__ void __launch_bounds__(256) CG_TWO_WAVES k_finalx_consup(Tile t, XRow
                 if (w == 1 && !zB) continue;
                 rmin_raw = fmin(rmin_raw, nan_guard(un[w][URHO]));
                 double d1, d2;
-                clean_zone_dt(P, ntimes, g.dx[0], g.dx[1], g.dx[2], un[w][URHO], un[w][UMX], un[w][UMY], un[w][UMZ], un[w][UEDEN], un[w][UEINT], un[w][UTEMP], un[w][UFS], d1, d2);
+                bool e_loaded = false;
+                if (!lazy_eint_on(assign)) { load_e(w); e_loaded = true; }
+                clean_zone_dt(P, ntimes, g.dx[0], g.dx[1], g.dx[2], un[w][URHO], un[w][UMX], un[w][UMY], un[w][UMZ], un[w][UEDEN], un[w][UEINT], un[w][UTEMP], un[w][UFS], d1, d2,
+                              [&]() { if (!e_loaded) load_e(w); return eint_new(w); }, false);
                 dtmin1 = fmin(dtmin1, d1);
                 dtmin = fmin(dtmin, d2);
             }
@@ -3350,6 +3420,7 @@ LaunchKnobs launch_knobs_from_env()
     K.divu_in_trace = knob("CASTRO_AMD_DIVU_IN_TRACE", d.divu_in_trace);
     K.trace_one_zone = knob("CASTRO_AMD_TRACE_ONE_ZONE", d.trace_one_zone);
     K.side_stream = knob("CASTRO_AMD_SIDE_STREAM", d.side_stream);
+    K.lazy_loads = knob("CASTRO_AMD_LAZY_LOADS", d.lazy_loads);
     return K;
 }
 
@@ -3764,7 +3835,7 @@ int launch_ctu_hydro(const Tile& t, const DevScratch& S, const DFab& Sborder, co
             }
         } else
         KL2_SOLV("k_trans1", K_T1, plain, ob.lo, ob.hi, S.Q, S, g, cdtdx, cdtdy, cdtdz, P);
-        const int assign_yz = (flags & 2) ? 1 : 0;
+        const int assign_yz = assign_word(flags, K);
 #ifdef CAD_NUMERICS_CONTRACT
         if (K.final_tile && solv == 0 && !lim) {
             constexpr int ry = 4, rz = 2;
@@ -3899,7 +3970,7 @@ int launch_ctu_hydro_level(const LaunchKnobs& K, int nbox, const LevelBoxDesc* b
     const Tile t0 = hb[0].t;
     const DevScratch S0 = hb[0].S;
     const SkipBox none = { { 0, 0, 0 }, { -1, -1, -1 } };
-    const int assign = (flags & 2) ? 1 : 0;
+    const int assign = assign_word(flags, K);
     const auto [cdtdx, cdtdy, cdtdz, hdtdx, hdtdy, hdtdz, area0, area1, area2, vol] = step_consts(g, dt);
 
     prof_begin(prof, sb_clean > 0 ? "k_ctoprim_clean" : "k_ctoprim", stream);

@@ -323,8 +323,13 @@ __device__ __forceinline__ void ppm_int_wave(double sm, double sp, double s6, do
 //   reset_internal_energy       Source/driver/Castro.cpp:3353-3414
 //   computeTemp (EOS re -> T)   Source/driver/Castro.cpp:3682-3707
 // ---------------------------------------------------------------------------------------
+//   The incoming (rho e) is taken lazily: `eint_in` is invoked only where reset_internal_energy keeps the evolved value, that
+//   is where !(eden - rho ke > eta2 eden) in a zone above the density floor.  Everywhere else eint is overwritten without being
+//   looked at, so a caller whose incoming value costs loads (k_finalx_consup) pays for them in those zones only.  `have`: eint
+//   already holds a value (always from the second application on).  There is ONE copy of the predicate: the branch itself.
+template <class EintIn>
 __device__ __forceinline__ void clean_zone(const DevParams& P, int ntimes, double& rho, double& mx, double& my, double& mz,
-                                           double& eden, double& eint, double& temp, double& rX)
+                                           double& eden, double& eint, double& temp, double& rX, EintIn&& eint_in, bool have)
 {
     for (int it = 0; it < ntimes; ++it) {
         // enforce_min_density
@@ -335,6 +340,7 @@ __device__ __forceinline__ void clean_zone(const DevParams& P, int ntimes, doubl
             temp = P.small_temp;
             mx = 0.0; my = 0.0; mz = 0.0;
             eint = rho * e;
+            have = true;
             eden = eint;
         }
 
@@ -375,14 +381,18 @@ __device__ __forceinline__ void clean_zone(const DevParams& P, int ntimes, doubl
 
             double small_e = eos_e_of_T(P, P.small_temp, rX * rhoInv);       // Castro.cpp:3376
 
-            eint = amax(eint, rho * small_e);
             eden = amax(eden, rho * (small_e + ke) + 0.0);
 
             double rho_eint = eden - rho * ke - 0.0;
 
+            // the reference floors eint first and then resets it; the floored value survives only on the second branch
             if (rho_eint > P.eta2 * eden) {
                 eint = rho_eint;
+            } else {
+                if (!have) eint = eint_in();
+                eint = amax(eint, rho * small_e);
             }
+            have = true;
         }
 
         // computeTemp
@@ -393,6 +403,13 @@ __device__ __forceinline__ void clean_zone(const DevParams& P, int ntimes, doubl
         }
     }
 
+}
+
+// the incoming (rho e) in a register: every caller but k_finalx_consup
+__device__ __forceinline__ void clean_zone(const DevParams& P, int ntimes, double& rho, double& mx, double& my, double& mz,
+                                           double& eden, double& eint, double& temp, double& rX)
+{
+    clean_zone(P, ntimes, rho, mx, my, mz, eden, eint, temp, rX, [&]() { return eint; }, true);
 }
 
 // zone term of Castro::estdt_cfl (Source/driver/timestep.cpp:31-140)
@@ -484,17 +501,25 @@ __device__ __forceinline__ void wave_min3_atomic(double a, double b, double c3, 
 // and after the LAST, the state estTimeStep of the next coarse step sees (post_timestep has cleaned once more by then,
 // Castro.cpp:1909-1916).  A second clean_state is not always the identity (the dual-energy reset can flip its branch once
 // eden has been floored), so the two are reduced separately.
+template <class EintIn>
 __device__ __forceinline__ void clean_zone_dt(const DevParams& P, int ntimes, double dx0, double dx1, double dx2,
                                               double& rho, double& mx, double& my, double& mz, double& eden, double& eint,
-                                              double& temp, double& rX, double& dt_first, double& dt_last)
+                                              double& temp, double& rX, double& dt_first, double& dt_last, EintIn&& eint_in, bool have)
 {
-    clean_zone(P, 1, rho, mx, my, mz, eden, eint, temp, rX);
+    clean_zone(P, 1, rho, mx, my, mz, eden, eint, temp, rX, eint_in, have);
     dt_first = nan_guard(zone_dt_cfl(P, dx0, dx1, dx2, rho, mx, my, mz, eint));
     dt_last = dt_first;
     if (ntimes > 1) {
         clean_zone(P, ntimes - 1, rho, mx, my, mz, eden, eint, temp, rX);
         dt_last = nan_guard(zone_dt_cfl(P, dx0, dx1, dx2, rho, mx, my, mz, eint));
     }
+}
+
+__device__ __forceinline__ void clean_zone_dt(const DevParams& P, int ntimes, double dx0, double dx1, double dx2,
+                                              double& rho, double& mx, double& my, double& mz, double& eden, double& eint,
+                                              double& temp, double& rX, double& dt_first, double& dt_last)
+{
+    clean_zone_dt(P, ntimes, dx0, dx1, dx2, rho, mx, my, mz, eden, eint, temp, rX, dt_first, dt_last, [&]() { return eint; }, true);
 }
 
 // PLM slopes (Source/hydro/slope.H); q[0..4] = zones i-2..i+2
