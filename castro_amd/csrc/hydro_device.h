@@ -1319,8 +1319,11 @@ __device__ __forceinline__ void hllc_flux(const RState& ql, const RState& qr, do
     double S_c = (pr - pl + rl * ul * (S_l - ul) - rr * ur * (S_r - ur)) /
         (rl * (S_l - ul) - rr * (S_r - ur));
     // `contract`: the two states of a wall face are mirror images in the reference's arithmetic and its S_c is an exact zero there; traced
-    // with contracted FMAs they are mirror images up to a rounding, and the sign of that rounding would pick the star state (see above)
-    if (kContract && bnd_fac == 0.0) S_c = 0.0;
+    // with contracted FMAs they are mirror images up to a rounding, and the sign of that rounding would pick the star state (see above).
+    // Only there: a caller's Sborder whose zones behind the wall are no mirror images (the C ABI takes any) has a contact speed of its
+    // own, which the reference follows.  1e-6 of the wave fan is far above what rounding leaves of an exact zero -- cold flow included,
+    // where the pressures of the two sides agree to E / e roundings only -- and far below the speed of a contact that is really there.
+    if (kContract && bnd_fac == 0.0 && fabs(S_c) <= 1.e-6 * (S_r - S_l)) S_c = 0.0;
 
     // cons_state / HLLC_state (riemann.H:379-440) of the RAW state q with passive X
     auto cons = [&](const RState& q, double X, CState& U) {

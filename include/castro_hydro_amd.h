@@ -255,7 +255,9 @@ int castro_amd_ctu_hydro_clean_fab(castro_amd_ctx *ctx,
  *                         the ghost zones of a single level are copies (or mirror images) of valid zones, so
  *                         "FillPatch the uncleaned state, then clean everything" equals the reference's "clean, FillPatch,
  *                         clean".  Only for whole-box calls (bx == vbx, one tile per FAB: overlapping tiles would clean
- *                         shared ghost zones twice) without CASTRO_AMD_STAGE_A/B; Sborder is written.  With
+ *                         shared ghost zones twice) without CASTRO_AMD_STAGE_A/B; Sborder is written (in the `contract`
+ *                         build's default path, which reads neither afterwards, its temperature and species planes may
+ *                         stay as they came).  With
  *                         CASTRO_AMD_STAGE_VALID the zones of bx are cleaned, with CASTRO_AMD_STAGE_REST the ghost shell
  *                         (pass the same count to both calls).
  *                         In the `contract` build (castro_amd_numerics()), on the default-solver path and together with
