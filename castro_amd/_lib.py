@@ -75,6 +75,7 @@ EXPORTED_SYMBOLS = (
     "castro_amd_new_sponge_source_fab", "castro_amd_sources_mf_opts",
     "castro_amd_add_pointmass_fab", "castro_amd_add_pointmass_mf", "castro_amd_pointmass_delta_mf", "castro_amd_pointmass_apply_mf",
     "castro_amd_ext_bc_fill_fab",
+    "castro_amd_fluxreg_to_flux_fab",
 )
 
 
@@ -402,6 +403,8 @@ class FabOp(C.Structure):
 
 
 OP_COPY, OP_LINCOMB, OP_FLUXREG_CRSE_INIT, OP_FLUXREG_FINE_ADD, OP_REFLUX, OP_CLEAN, OP_INTERP_CLEAN, OP_AVGDOWN, OP_INTERP = 0, 1, 2, 3, 4, 5, 6, 7, 8
+OP_FLUXREG_TO_FLUX = 9
+SOURCES_AFTER_REFLUX = 16      # CASTRO_AMD_SOURCES_AFTER_REFLUX: OR-ed to stage 1 of the one-pass source stages
 
 _libs = {}
 ABI_VERSION = 5          # CASTRO_AMD_ABI_VERSION of include/castro_hydro_amd.h this binding was written against
@@ -537,6 +540,9 @@ def load(numerics=None):
     L.castro_amd_fluxreg_crse_init_fab.argtypes = [C.c_void_p, PF, PF, I3, I3, C.c_int, C.c_double, C.c_void_p]
     L.castro_amd_fluxreg_fine_add_fab.argtypes = [C.c_void_p, PF, PF, I3, I3, C.c_int, C.c_int, C.c_double, C.c_void_p]
     L.castro_amd_reflux_fab.argtypes = [C.c_void_p, PF, PF, I3, I3, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]
+    if hasattr(L, "castro_amd_fluxreg_to_flux_fab"):        # absent from A/B builds of revisions before update_sources_after_reflux
+        L.castro_amd_fluxreg_to_flux_fab.restype = C.c_int
+        L.castro_amd_fluxreg_to_flux_fab.argtypes = [C.c_void_p, PF, PF, PF, I3, I3, C.c_int, C.c_void_p]
     L.castro_amd_bc_fill_fab.argtypes = [C.c_void_p, PF, C.POINTER(Geom), C.c_void_p]
     if hasattr(L, "castro_amd_ext_bc_fill_fab"):            # absent from A/B builds of revisions before the boundary overrides
         L.castro_amd_ext_bc_fill_fab.argtypes = [C.c_void_p, PF, C.POINTER(Geom), C.POINTER(Params), C.POINTER(ExtBc), C.c_void_p,

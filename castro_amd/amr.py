@@ -57,6 +57,14 @@ def _shift(box, sh):
     return tuple(box[0][d] + sh[d] for d in range(3)), tuple(box[1][d] + sh[d] for d in range(3))
 
 
+def _box_minus(box, cut):
+    """The box minus the box `cut` as a list of boxes (shell_slabs around the part of `cut` that lies inside it)."""
+    it = CL.intersect(box, cut)
+    if not it:
+        return [box]
+    return [sl for sl in shell_slabs(box, it) if all(sl[1][d] >= sl[0][d] for d in range(3))]
+
+
 def _is_box(x):
     return len(x) == 2 and len(x[0]) == 3 and not hasattr(x[0][0], "__len__")
 
@@ -180,7 +188,7 @@ class _Level:
                     assert cov.all(), "box %s of level %d not properly nested: the coarse zones under its gravity ghost zones " \
                         "reach beyond the gravity data of level %d" % (b.bx, self.l, self.l - 1)
             if self.l == 0:                    # no coarser level: no coarse data, no flux registers, nothing to average onto
-                b.csrc, b.csrc_valid, b.crse_init, b.reflux_to, b.avg_to = [], [], {}, {}, []
+                b.csrc, b.csrc_valid, b.crse_init, b.reflux_to, b.flux_to, b.avg_to = [], [], {}, {}, {}, []
                 if self.have_sources:
                     b.ssrc, b.ssrc_valid, b.sshell = [], [], []
                 continue
@@ -197,7 +205,7 @@ class _Level:
                     cov[lo[2] - o[2]:hi[2] - o[2] + 1, lo[1] - o[1]:hi[1] - o[1] + 1, lo[0] - o[0]:hi[0] - o[0] + 1] = True
                 assert cov.all(), "box not properly nested in the union of its parents"
             # FluxRegCrseInit sources and reflux targets per register
-            b.crse_init, b.reflux_to = {}, {}
+            b.crse_init, b.reflux_to, b.flux_to = {}, {}, {}
             for (d, side), (reg, rbox) in b.regs.items():
                 b.crse_init[(d, side)] = [(p, it) for p in parents for it in [CL.intersect(rbox, p.flux_boxes[d])] if it]
                 sh = -1 if side == 0 else 0           # the coarse zone outside the fine box: face - 1 (low side) or face
@@ -212,6 +220,17 @@ class _Level:
                             flo[d] -= sh; fhi[d] -= sh
                             tg.append((p, (tuple(flo), tuple(fhi)), csh))
                 b.reflux_to[(d, side)] = tg
+                # the faces of this register on the coarse-fine boundary (FluxRegister::ClearInternalBorders [3P]: a face that is
+                # also a face of the opposite side of a box of this level, or of a periodic image of one, lies between two fine
+                # boxes) and the parents' flux FABs that hold them -- a face on the seam of two parents is in both, a face beyond
+                # a periodic boundary is its image inside: castro.update_sources_after_reflux (Castro.cpp:2617-2644)
+                faces = [rbox]
+                for s2 in self.boxes:
+                    for csh in cshifts:
+                        cut = _shift(s2.regs[(d, 1 - side)][1], csh)
+                        faces = [x for f in faces for x in _box_minus(f, cut)]
+                b.flux_to[(d, side)] = [(p, it, csh) for f in faces for p in parents for csh in cshifts
+                                        for it in [CL.intersect(f, _shift(p.flux_boxes[d], csh))] if it]
                 # proper nesting (AMReX's Amr::grid_places guarantees it): every parent-level zone next to a face of
                 # this box is a valid zone of the parent level (or lies outside a non-periodic domain); a face that
                 # touched a still coarser level directly would lose its flux correction
@@ -592,10 +611,54 @@ class _Level:
         return [b.S_old_b.clone() for b in self.mine]
 
     def _restore_old_state(self, prev):
+        if self.amr.update_sources_after_reflux and self.have_sources:
+            # keep_prev_state (Castro_advance_ctu.cpp:722-755): the advance ended with more than one subcycle and a reflux may
+            # re-evaluate the new-time sources, which belong to the LAST subcycle.  Of the state types only State_Type differs
+            # here: old_source and grav_old are rebuilt by every subcycle and are the last one's as they stand.
+            self._last_old = [b.S_old_b.clone() for b in self.mine]
         for b, p in zip(self.mine, prev):
             b.S_old_b.copy_(p)
 
-    advance = Castro.advance
+    # ---- Castro::reflux with castro.update_sources_after_reflux (Castro.cpp:2773-2868) ----------------------------------
+    def renew_sources(self):
+        """The new-time sources of this level again, after a reflux has changed S_new and the mass fluxes: S_new += -dt x
+        new_source, clean_state, do_new_sources(apply = true) -- with dt and the old data of the level's last advance, of its
+        last subcycle if a retry split it.  The gravity field is the one that advance constructed (construct_new_gravity belongs
+        to do_advance_ctu).  One call of stage 1 | SOURCES_AFTER_REFLUX for the level where the source stages go out level-wide, else box by box."""
+        if not self.have_sources or not self.mine:
+            return
+        h, dt = self.hydro, self.lastDt
+        keep = None
+        if getattr(self, "_last_old", None) is not None:
+            keep = [b.S_old_b.clone() for b in self.mine]
+            for b, p in zip(self.mine, self._last_old):
+                b.S_old_b.copy_(p)
+        lvl = self._source_level_calls()
+        if lvl is not None:
+            sp = tuple(t.data_ptr() for b in self.mine for t in (b.S_old_b, b.S_new_b))
+            gf = None
+            if self.amr.gravity is not None:
+                gf = self._cached_ops(("grav_fabs",), (), lambda: (h.make_grav_fabs([(b.grav_old, b.gravbox) for b in self.mine]),
+                                                                   h.make_grav_fabs([(b.grav_new, b.gravbox) for b in self.mine])))
+            lvl._sources_one_pass(1 | L.SOURCES_AFTER_REFLUX, dt, self._cached_ops(("src_new",), sp, lambda: h.make_source_boxes(
+                [b._source_spec(1) for b in self.mine])), **({} if gf is None else {"grav_fabs": gf}))
+        else:
+            for b in self.mine:
+                if hasattr(h, "apply_source"):
+                    h.apply_source(b.S_new_b, b.gbox, b.S_new_b, b.gbox, -dt, b.new_source, b.bx, NSRC, b.lo, b.hi, b.params, ntimes=1)
+                else:
+                    h.saxpy(b.S_new_b, b.gbox, -dt, b.new_source, b.bx, NSRC, b.lo, b.hi)
+                    h.clean_state(b.S_new_b, b.gbox, b.lo, b.hi, b.params, ntimes=1)
+                b._source_stage(1, dt)
+        if keep is not None:
+            for b, p in zip(self.mine, keep):
+                b.S_old_b.copy_(p)
+        self.invalidate_estimate()              # S_new has been written outside the level's advance
+
+    def advance(self, time, dt):
+        self._last_old = None                   # the old data of the last retry subcycle of this advance (_restore_old_state)
+        return Castro.advance(self, time, dt)
+
     subcycle_advance_ctu = Castro.subcycle_advance_ctu
 
     def _pointmass_update(self):
@@ -762,8 +825,14 @@ class CastroAmr:
                  blocking_factor=8, patches=None, max_level=1, cluster=False, grid_eff=0.7, max_grid_size=128,
                  do_grav=False, const_grav=0.0, grav_source_type=4, rotation=None, comm=None, base_grid=None, box_streams=4,
                  diffusion=None, sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", gravity=None,
-                 sponge=None, use_point_mass=False, point_mass=0.0, point_mass_fix_solution=False, ext_bc=None):
-        """ext_bc: _lib.make_ext_bc(...) -- the boundary overrides of the state fill (hydrostatic Inflow faces, the ambient state
+                 sponge=None, use_point_mass=False, point_mass=0.0, point_mass_fix_solution=False, ext_bc=None,
+                 update_sources_after_reflux=False):
+        """update_sources_after_reflux: castro.update_sources_after_reflux.  True is the reference's default (1) and the setting
+        that follows it: after the reflux of post_timestep the flux registers are added to the coarse level's fluxes (mass
+        fluxes = their density component) and both levels take their new-time sources out of S_new, clean it, and evaluate and
+        apply them again from the refluxed state and the corrected mass fluxes (Castro.cpp:2612-2644, 2762-2868).  False (the
+        default here): the reflux ends with the flux correction of the state.
+        ext_bc: _lib.make_ext_bc(...) -- the boundary overrides of the state fill (hydrostatic Inflow faces, the ambient state
         beyond Outflow faces) on every box of every level that reaches the boundary, as in castro_amd.Castro; the hydrostatic
         fill assumes constant gravity (not with gravity=MonopoleGravity(...)).
         use_point_mass, point_mass, point_mass_fix_solution: as in castro_amd.Castro, with gravity=MonopoleGravity(...) -- ONE
@@ -812,6 +881,7 @@ class CastroAmr:
             gravity.bind(self, lo_bc, hi_bc)
         self.gravity = gravity
         self.pm = None
+        self.update_sources_after_reflux = bool(update_sources_after_reflux)
         if use_point_mass:
             if not do_grav:
                 raise ValueError("use_point_mass needs do_grav=True: the point mass is a term of the gravity vector")
@@ -1017,6 +1087,10 @@ class CastroAmr:
             d, side, vol, csh = extra
             reg, rbox = S.regs[(d, side)]
             h.copy(t, box, reg, rbox, lo, hi)
+        elif kind == "reg_to_flux":
+            d, side, csh = extra
+            reg, rbox = S.regs[(d, side)]
+            h.copy(t, box, reg, rbox, lo, hi)
         elif kind == "avgdown":
             h.avgdown(S.S_new_b, S.gbox, t, box, lo, hi, NUM_STATE)
         else:
@@ -1074,6 +1148,11 @@ class CastroAmr:
             d, side, vol, csh = extra
             reg, rbox = S.regs[(d, side)] if buf is None else (buf, box)
             h.reflux(D.S_new_b, _shift(D.gbox, csh), reg, rbox, lo, hi, d, side, NUM_STATE, vol)
+        elif kind == "reg_to_flux":
+            d, side, csh = extra
+            reg, rbox = S.regs[(d, side)] if buf is None else (buf, box)
+            fbox = _shift(D.flux_boxes[d], csh)
+            h.fluxreg_to_flux(D.fluxes[d], fbox, reg, rbox, D.mass_fluxes[d], fbox, lo, hi, NUM_STATE)
         elif kind == "avgdown":
             if buf is None:
                 h.avgdown(S.S_new_b, S.gbox, D.S_new_b, D.gbox, lo, hi, NUM_STATE)
@@ -1503,11 +1582,44 @@ class CastroAmr:
                             for p, (lo, hi), csh in b.reflux_to[(d, side)]:
                                 h.reflux(p.S_new_b, _shift(p.gbox, csh), reg, rbox, lo, hi, d, side, NUM_STATE, vol)
             lev.invalidate_estimate()                   # reflux has corrected this level's S_new
+            if self.update_sources_after_reflux:
+                self._fluxes_after_reflux(l)
+                for k in (l + 1, l):                    # the finer level first (Castro.cpp:2777)
+                    self.lev[k].renew_sources()
             self.avgDown(l + 1)
         # Castro::post_timestep ends with clean_state(S_new) on EVERY level (Castro.cpp:1909-1916), the finest included
         # (there it may have ridden in the fused pass of the update: _hydro_level)
         if not (l == finest and lev._post_clean_done):
             lev.clean_new()
+
+    def _fluxes_after_reflux(self, l):
+        """Castro::reflux with castro.update_sources_after_reflux, the flux half (Castro.cpp:2617-2644): the registers of level
+        l + 1 are added to the fluxes of level l on the faces of the coarse-fine boundary, the mass fluxes take the density
+        component there -- and on the whole level where fluxes and mass fluxes differ (after retry subcycles the fluxes are sums
+        over the subcycles, the mass fluxes those of the last one).  Whether or not the level has sources."""
+        lev, fine = self.lev[l], self.lev[l + 1]
+        h = lev.hydro
+        if self.nranks > 1:
+            self._xrun([("reg_to_flux", p, b, lo, hi, (d, side, csh)) for d in range(3) for side in (0, 1)
+                        for b in fine.boxes for p, (lo, hi), csh in b.flux_to[(d, side)]])
+        for d in (range(3) if self.nranks == 1 else ()):
+            for side in (0, 1):                         # the faces of one orientation are disjoint: one launch
+                if fine.batched:
+                    h.fab_ops(fine._cached_ops(("reg_to_flux", d, side), (), lambda d=d, side=side: h.make_ops(
+                        [(L.OP_FLUXREG_TO_FLUX, d, NUM_STATE, lo, hi, 0.0, 0.0, (p.fluxes[d], _shift(p.flux_boxes[d], csh)),
+                          b.regs[(d, side)], (p.mass_fluxes[d], _shift(p.flux_boxes[d], csh)))
+                         for b in fine.boxes for p, (lo, hi), csh in b.flux_to[(d, side)]])))
+                else:
+                    for b in fine.boxes:
+                        reg, rbox = b.regs[(d, side)]
+                        for p, (lo, hi), csh in b.flux_to[(d, side)]:
+                            fbox = _shift(p.flux_boxes[d], csh)
+                            h.fluxreg_to_flux(p.fluxes[d], fbox, reg, rbox, p.mass_fluxes[d], fbox, lo, hi, NUM_STATE)
+        if lev.nsubcycles > 1:
+            for p in lev.mine:
+                for d in range(3):
+                    fb = p.flux_boxes[d]
+                    h.copy(p.mass_fluxes[d], fb, p.fluxes[d][0:1], fb, fb[0], fb[1])
 
     # ---- Amr::coarseTimeStep ---------------------------------------------------------------------
     def step(self, stop_time=-1.0):

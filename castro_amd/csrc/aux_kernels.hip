@@ -866,8 +866,12 @@ __device__ __forceinline__ const SrcBoxDev& src_box_of(const SrcBoxGDev& b) { re
 // GFAB = false (BOX = SrcBoxDev): the one vector of the call through GravConst.  GFAB = true (BOX = SrcBoxGDev,
 // castro_amd_sources_mf_g): the gravity of a zone through GravFab from the box's grav_old / grav_new FABs, the zone functions
 // of k_old_grav_source_gfab / k_new_grav_source_gfab
-// SP: nothing, or one SpongeDev (STAGE 1 only) -- the sponge after rotation, sponge_zone on the S_new values this thread loads for
+// SP: nothing, or one SpongeDev (STAGE 1 and 2) -- the sponge after rotation, sponge_zone on the S_new values this thread loads for
 // the apply anyway.  Without it the kernel has the arguments and the code it had before there was a sponge.
+// STAGE 2 (the source re-evaluation after a reflux, Castro.cpp:2773-2868): in front of stage 1 the zone's stored new-time source
+// is taken out of S_new and the zone cleaned (k_apply_source with a = -dt), in the same thread.  The new-time zone functions read
+// S_new in their own zone only -- the value this thread has just stored -- and neighbours enter through the gravity FABs and the
+// face mass fluxes, which this kernel does not write: the three sweeps of the separate calls become one.
 __device__ __forceinline__ const SpongeDev& sponge_arg(const SpongeDev& s) { return s; }
 
 template <int STAGE, bool GFAB, class BOX, class... SP>
@@ -876,7 +880,8 @@ __global__ void __launch_bounds__(256) k_sources_apply(const BOX* __restrict__ t
                                                        DevParams P, int ntimes, int diff_on, SP... sp)
 {
     constexpr bool SPONGE = sizeof...(SP) == 1;
-    static_assert(sizeof...(SP) <= 1 && (!SPONGE || STAGE == 1), "the sponge is one argument of the new-time stage");
+    static_assert(STAGE >= 0 && STAGE <= 2, "stage 0: old time, 1: new time, 2: new time again after a reflux");
+    static_assert(sizeof...(SP) <= 1 && (!SPONGE || STAGE >= 1), "the sponge is one argument of the new-time stages");
     long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= start[nbox]) return;
     int lo_ = 0, hi_ = nbox - 1;
@@ -894,6 +899,20 @@ __global__ void __launch_bounds__(256) k_sources_apply(const BOX* __restrict__ t
     if (i < B.vlo[0] || i > B.vhi[0] || j < B.vlo[1] || j > B.vhi[1] || k < B.vlo[2] || k > B.vhi[2]) {
         for (int n = 0; n < B.nsc; ++n) B.Src.p[cs + B.Src.sn * n] = 0.0;         // the memset of the ghost zones
         return;
+    }
+    if constexpr (STAGE == 2) {
+        // apply_source_to_state(S_new, source, -dt) and clean_state (Castro.cpp:2794-2799): k_apply_source with base == dst
+        const long cn = fidx(B.Sn, i, j, k, 0);
+        const double a = -dt;
+        double v[NUM_STATE];
+#pragma unroll
+        for (int n = 0; n < NUM_STATE; ++n) {
+            v[n] = B.Sn.p[cn + B.Sn.sn * n];
+            if (n < NSRC) v[n] += a * B.Src.p[cs + B.Src.sn * n];
+        }
+        if (ntimes > 0) clean_zone(P, ntimes, v[URHO], v[UMX], v[UMY], v[UMZ], v[UEDEN], v[UEINT], v[UTEMP], v[UFS]);
+#pragma unroll
+        for (int n = 0; n < NUM_STATE; ++n) B.Sn.p[cn + B.Sn.sn * n] = v[n];
     }
     double acc[NSRC], src[NSRC];
     for (int n = 0; n < NSRC; ++n) acc[n] = 0.0;
@@ -976,13 +995,16 @@ static int launch_sources_apply_t(int stage, int nbox, const BOX* boxes, const d
     if (rot) R = make_rotdev(rot, geom, dt);
     const unsigned nb = (unsigned)((start.back() + 255) / 256);
     // the sponge has no old-time source: stage 0 with a sponge is the launch without one
-    const bool sp = sponge && stage == 1;
-    prof_begin(prof, sp ? "k_sources_new_sponge" : stage == 0 ? "k_sources_old" : "k_sources_new", stream);
+    const bool sp = sponge && stage >= 1;
+    prof_begin(prof, stage == 2 ? (sp ? "k_sources_renew_sponge" : "k_sources_renew")
+                                : sp ? "k_sources_new_sponge" : stage == 0 ? "k_sources_old" : "k_sources_new", stream);
     auto launch = [&](auto kernel, auto... tail) {
         hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, stream, dbox, dstart, nbox, G, R, rot ? 1 : 0, dt, geom->dx[0], geom->dx[1],
                            geom->dx[2], P, ntimes, diff_on, tail...);
     };
-    if (sp) launch(k_sources_apply<1, GFAB, BOX, SpongeDev>, make_spongedev(sponge, geom, dt));
+    if (stage == 2 && sp) launch(k_sources_apply<2, GFAB, BOX, SpongeDev>, make_spongedev(sponge, geom, dt));
+    else if (stage == 2) launch(k_sources_apply<2, GFAB, BOX>);
+    else if (sp) launch(k_sources_apply<1, GFAB, BOX, SpongeDev>, make_spongedev(sponge, geom, dt));
     else if (stage == 0) launch(k_sources_apply<0, GFAB, BOX>);
     else launch(k_sources_apply<1, GFAB, BOX>);
     prof_end(prof, stream);
@@ -1146,6 +1168,20 @@ __global__ void __launch_bounds__(256) k_fluxreg(DFab R, DFab X, Box3 b, int dir
     }
 }
 
+// flux += reg on the faces of the region, and mass_flux = flux(URHO) there where a mass-flux FAB is given: the coarse fluxes
+// after a reflux (Castro.cpp:2617-2644)
+__global__ void __launch_bounds__(256) k_fluxreg_to_flux(DFab F, DFab R, DFab M, Box3 b, int ncomp)
+{
+    int i, j, k;
+    if (!box_thread3(b.lo, b.n, i, j, k)) return;
+    for (int n = 0; n < ncomp; ++n) {
+        const long cf = fidx(F, i, j, k, n);
+        const double f = F.p[cf] + R.p[fidx(R, i, j, k, n)];
+        F.p[cf] = f;
+        if (n == URHO && M.p) M.p[fidx(M, i, j, k, 0)] = f;
+    }
+}
+
 __global__ void __launch_bounds__(256) k_reflux(DFab U, DFab R, Box3 b, int dir, int side, int ncomp, double vol)
 {
     int c[3];
@@ -1276,6 +1312,15 @@ __device__ __forceinline__ void fab_op_thread(const FabOp& o, long t, const DevP
             o.D.p[fidx(o.D, z[0], z[1], z[2], n)] += mult * o.X.p[fidx(o.X, c[0], c[1], c[2], n)] / o.a;
         return;
     }
+    if (o.kind == CASTRO_AMD_OP_FLUXREG_TO_FLUX) {      // k_fluxreg_to_flux's arithmetic; Y: the mass-flux FAB or none
+        for (int n = 0; n < o.ncomp; ++n) {
+            const long cf = fidx(o.D, c[0], c[1], c[2], n);
+            const double f = o.D.p[cf] + o.X.p[fidx(o.X, c[0], c[1], c[2], n)];
+            o.D.p[cf] = f;
+            if (n == URHO && o.Y.p) o.Y.p[fidx(o.Y, c[0], c[1], c[2], 0)] = f;
+        }
+        return;
+    }
     for (int n = 0; n < o.ncomp; ++n) {
         const long cd = fidx(o.D, c[0], c[1], c[2], n);
         if (o.kind == CASTRO_AMD_OP_COPY) {
@@ -1343,10 +1388,10 @@ int launch_fab_ops(int nops, const DFab* D, const DFab* X, const DFab* Y, const 
         const long* dstart;
         const int rt = arena->stage(ops.data(), ops.size(), start.data(), start.size(), stream, dops, dstart);
         if (rt != 0) return rt;
-        static const char* const kind_name[9] = { "k_fab_ops_copy", "k_fab_ops_lincomb", "k_fab_ops_crse_init", "k_fab_ops_fine_add",
-                                                  "k_fab_ops_reflux", "k_fab_ops_clean", "k_fab_ops_interp_clean", "k_fab_ops_avgdown",
-                                                  "k_fab_ops_interp" };
-        prof_begin(prof, kind_name[ops[0].kind >= 0 && ops[0].kind < 9 ? ops[0].kind : 0], stream);     // tables are built per purpose: one kind each
+        static const char* const kind_name[10] = { "k_fab_ops_copy", "k_fab_ops_lincomb", "k_fab_ops_crse_init", "k_fab_ops_fine_add",
+                                                   "k_fab_ops_reflux", "k_fab_ops_clean", "k_fab_ops_interp_clean", "k_fab_ops_avgdown",
+                                                   "k_fab_ops_interp", "k_fab_ops_reg_to_flux" };
+        prof_begin(prof, kind_name[ops[0].kind >= 0 && ops[0].kind < 10 ? ops[0].kind : 0], stream);     // tables are built per purpose: one kind each
         hipLaunchKernelGGL(k_fab_ops_mem, dim3((unsigned)((start.back() + 255) / 256)), dim3(256), 0, stream,
                            dops, dstart, (int)ops.size(), P);
         prof_end(prof, stream);
@@ -1406,6 +1451,9 @@ int launch_avgdown(const DFab& F, const DFab& C, const int lo[3], const int hi[3
 int launch_fluxreg(const DFab& R, const DFab& X, const int lo[3], const int hi[3], int dir, int ncomp, double mult, int mode,
                    hipStream_t stream, Profiler* prof)
 { AMR_LAUNCH("k_fluxreg", k_fluxreg, R, X, b, dir, ncomp, mult, mode); }
+int launch_fluxreg_to_flux(const DFab& F, const DFab& R, const DFab& M, const int lo[3], const int hi[3], int ncomp,
+                           hipStream_t stream, Profiler* prof)
+{ AMR_LAUNCH("k_fluxreg_to_flux", k_fluxreg_to_flux, F, R, M, b, ncomp); }
 int launch_reflux(const DFab& U, const DFab& R, const int lo[3], const int hi[3], int dir, int side, int ncomp, double vol,
                   hipStream_t stream, Profiler* prof)
 { AMR_LAUNCH("k_reflux", k_reflux, U, R, b, dir, side, ncomp, vol); }

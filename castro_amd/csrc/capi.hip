@@ -717,20 +717,27 @@ static int src_box(SrcBoxDev& T, const castro_amd_source_box& b, bool mass_fluxe
 
 // The one-pass sources behind their four entry points.  Gravity is a vector for the level (o.grav) or one FAB per box
 // (o.grav_old / o.grav_new), not both; the FABs do not go together with diffusion.
-static int sources_mf_impl(castro_amd_ctx* c, int stage, int nboxes, const castro_amd_source_box* boxes, const castro_amd_source_opts& o,
+static int sources_mf_impl(castro_amd_ctx* c, int stage_arg, int nboxes, const castro_amd_source_box* boxes, const castro_amd_source_opts& o,
                            const castro_amd_geom* geom, const castro_amd_params* params, double dt, int clean_ntimes, void* stream)
 {
+    // the kernel's stage: 0, 1, or 2 for stage 1 with CASTRO_AMD_SOURCES_AFTER_REFLUX; any other value of the argument
+    // (the bare 2 included) is refused below
+    const int stage = stage_arg == (1 | CASTRO_AMD_SOURCES_AFTER_REFLUX) ? 2 : (stage_arg == 0 || stage_arg == 1) ? stage_arg : -1;
     const bool gfab = o.grav_old || o.grav_new, grav_on = gfab || o.grav;
     if (gfab && o.grav) return CASTRO_AMD_ERR_ARG;
     if (gfab && o.diff) return CASTRO_AMD_ERR_UNSUPPORTED;
-    if (!c || (stage != 0 && stage != 1) || nboxes < 0 || (nboxes > 0 && !boxes) || !geom || !params || clean_ntimes < 0) return CASTRO_AMD_ERR_ARG;
+    if (!c || stage < 0 || nboxes < 0 || (nboxes > 0 && !boxes) || !geom || !params || clean_ntimes < 0) return CASTRO_AMD_ERR_ARG;
+    // after a reflux: stage 1 behind the removal of the stored source; the stencil of the diffusion term would read neighbours that
+    // other threads of the one pass are rewriting
+    if (stage == 2 && o.diff) return CASTRO_AMD_ERR_UNSUPPORTED;
+    const bool newt = stage >= 1;          // the new-time source functions
     if (!sponge_ok(o.sponge, geom, dt)) return CASTRO_AMD_ERR_ARG;
-    if (gfab && nboxes > 0 && (!o.grav_old || (stage == 1 && !o.grav_new))) return CASTRO_AMD_ERR_ARG;
+    if (gfab && nboxes > 0 && (!o.grav_old || (newt && !o.grav_new))) return CASTRO_AMD_ERR_ARG;
     // the checks of the single-box entry points (castro_amd_old/new_gravity_source_fab, _rotation_source_fab, _apply_source_fab)
     if (grav_on && (o.grav_source_type < 1 || o.grav_source_type > 4)) return CASTRO_AMD_ERR_ARG;
     if (o.rot && (o.rot->rot_source_type < 1 || o.rot->rot_source_type > 4)) return CASTRO_AMD_ERR_ARG;
-    if ((o.rot || (grav_on && stage == 1)) && geom->coord != 0) return CASTRO_AMD_ERR_ARG;
-    if (o.rot && stage == 1 && !(dt > 0.0)) return CASTRO_AMD_ERR_ARG;
+    if ((o.rot || (grav_on && newt)) && geom->coord != 0) return CASTRO_AMD_ERR_ARG;
+    if (o.rot && newt && !(dt > 0.0)) return CASTRO_AMD_ERR_ARG;
     if (o.diff) {
         const int rc = diff_check(o.diff, geom);
         if (rc != CASTRO_AMD_OK) return rc;
@@ -741,14 +748,14 @@ static int sources_mf_impl(castro_amd_ctx* c, int stage, int nboxes, const castr
     std::vector<DiffBoxDev> dtab(o.diff ? (size_t)nboxes : 0);
     for (int i = 0; i < nboxes; ++i) {
         const castro_amd_source_box& b = boxes[i];
-        const int rb = src_box(gfab ? gtab[(size_t)i].box : tab[(size_t)i], b, stage == 1 && (grav_on || o.rot));
+        const int rb = src_box(gfab ? gtab[(size_t)i].box : tab[(size_t)i], b, newt && (grav_on || o.rot));
         if (rb != CASTRO_AMD_OK) return rb;
         if (gfab) {
             // stage 0 reads the zone itself, stage 1 with grav_source_type 4 its six neighbours as well
-            if (!grav_fab_ok(&o.grav_old[i], b.lo, b.hi, stage == 1 ? o.grav_source_type : 1)) return CASTRO_AMD_ERR_ARG;
-            if (stage == 1 && !grav_fab_ok(&o.grav_new[i], b.lo, b.hi, o.grav_source_type)) return CASTRO_AMD_ERR_ARG;
+            if (!grav_fab_ok(&o.grav_old[i], b.lo, b.hi, newt ? o.grav_source_type : 1)) return CASTRO_AMD_ERR_ARG;
+            if (newt && !grav_fab_ok(&o.grav_new[i], b.lo, b.hi, o.grav_source_type)) return CASTRO_AMD_ERR_ARG;
             gtab[(size_t)i].GO = to_dfab(&o.grav_old[i]);
-            gtab[(size_t)i].GN = to_dfab(stage == 1 ? &o.grav_new[i] : &o.grav_old[i]);
+            gtab[(size_t)i].GN = to_dfab(newt ? &o.grav_new[i] : &o.grav_old[i]);
         }
         // diff_src: stage 0 the term of S_old, stage 1 the corrector 0.5 DiffTerm(S_new) - 0.5 DiffTerm(S_old)
         if (o.diff) {
@@ -1215,6 +1222,10 @@ static int fab_ops_impl(castro_amd_ctx* c, int nops, const castro_amd_fab_op* op
             if (o.side == 0) { zlo[o.dir] -= 1; zhi[o.dir] -= 1; }
             if (!fab_contains(&o.dst, zlo, zhi)) return CASTRO_AMD_ERR_ARG;
             break; }
+        case CASTRO_AMD_OP_FLUXREG_TO_FLUX:
+            // src2: the mass-flux FAB (one component) or none (p == NULL)
+            if (!fab_contains(&o.src, o.lo, o.hi) || (o.src2.p && (o.src2.ncomp < 1 || !fab_contains(&o.src2, o.lo, o.hi)))) return CASTRO_AMD_ERR_ARG;
+            break;
         case CASTRO_AMD_OP_LINCOMB:
             if (!fab_ok(&o.src2, o.ncomp) || !fab_contains(&o.src2, o.lo, o.hi)) return CASTRO_AMD_ERR_ARG;
             /* fall through */
@@ -1232,7 +1243,7 @@ static int fab_ops_impl(castro_amd_ctx* c, int nops, const castro_amd_fab_op* op
             return CASTRO_AMD_ERR_ARG;
         }
         D[r] = to_dfab(&o.dst); X[r] = to_dfab(&o.src);
-        Y[r] = (o.kind == CASTRO_AMD_OP_LINCOMB) ? to_dfab(&o.src2) : X[r];
+        Y[r] = (o.kind == CASTRO_AMD_OP_LINCOMB || o.kind == CASTRO_AMD_OP_FLUXREG_TO_FLUX) ? to_dfab(&o.src2) : X[r];
         for (int d = 0; d < 3; ++d) { lo[3 * r + d] = o.lo[d]; hi[3 * r + d] = o.hi[d]; }
         kind[r] = o.kind; dir[r] = o.dir; side[r] = o.side; ncomp[r] = o.ncomp; a[r] = o.a; b[r] = o.b;
     }
@@ -1417,6 +1428,18 @@ int castro_amd_fluxreg_fine_add_fab(castro_amd_ctx* c, const castro_amd_fab* reg
     if (!fab_contains(fine_flux, flo, fhi)) return CASTRO_AMD_ERR_ARG;
     hipSetDevice(c->device);
     return launch_fluxreg(to_dfab(reg), to_dfab(fine_flux), lo, hi, dir, ncomp, mult, 1, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_fluxreg_to_flux_fab(castro_amd_ctx* c, const castro_amd_fab* flux, const castro_amd_fab* reg,
+                                   const castro_amd_fab* mass_flux, const int lo[3], const int hi[3], int ncomp, void* stream)
+{
+    if (!c || !lo || !hi || ncomp < 1 || !fab_ok(flux, ncomp) || !fab_ok(reg, ncomp)) return CASTRO_AMD_ERR_ARG;
+    if (!fab_contains(flux, lo, hi) || !fab_contains(reg, lo, hi)) return CASTRO_AMD_ERR_ARG;
+    const bool mass = mass_flux && mass_flux->p;
+    if (mass && (mass_flux->ncomp < 1 || !fab_contains(mass_flux, lo, hi))) return CASTRO_AMD_ERR_ARG;
+    hipSetDevice(c->device);
+    return launch_fluxreg_to_flux(to_dfab(flux), to_dfab(reg), to_dfab(mass ? mass_flux : nullptr), lo, hi, ncomp,
+                                  (hipStream_t)stream, &c->prof);
 }
 
 int castro_amd_reflux_fab(castro_amd_ctx* c, const castro_amd_fab* state, const castro_amd_fab* reg,

@@ -253,6 +253,8 @@ int launch_cc_interp(const DFab& C, const DFab& F, const int lo[3], const int hi
 int launch_fillpatch_shell(const DFab& C, const DFab& F, const int vlo[3], const int vhi[3], int ng, const DevParams& P, int ntimes,
                            hipStream_t stream, Profiler* prof);
 int launch_avgdown(const DFab& F, const DFab& C, const int lo[3], const int hi[3], int ncomp, hipStream_t stream, Profiler* prof);
+int launch_fluxreg_to_flux(const DFab& F, const DFab& R, const DFab& M, const int lo[3], const int hi[3], int ncomp,
+                           hipStream_t stream, Profiler* prof);
 int launch_fluxreg(const DFab& R, const DFab& X, const int lo[3], const int hi[3], int dir, int ncomp, double mult, int mode,
                    hipStream_t stream, Profiler* prof);
 int launch_reflux(const DFab& U, const DFab& R, const int lo[3], const int hi[3], int dir, int side, int ncomp, double vol,

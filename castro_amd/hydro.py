@@ -403,6 +403,9 @@ class HipHydro:
             for d in range(3):
                 o.lo[d], o.hi[d] = lo[d], hi[d]
             o.dst, o.src = L.fab_of(dst[0], *dst[1]), L.fab_of(src[0], *src[1])
+            if kind == L.OP_FLUXREG_TO_FLUX:        # src2 is written: the mass-flux FAB, or none
+                o.src2 = L.fab_of(src2[0], *src2[1]) if src2 is not None else L.fab_desc(None, lo, hi, 0)
+                continue
             o.src2 = L.fab_of(src2[0], *src2[1]) if src2 is not None else o.src
         return arr, len(specs)
 
@@ -469,7 +472,8 @@ class HipHydro:
     def sources_mf(self, stage, boxes, grav, grav_source_type, rot, geom, params, dt, ntimes=1, stream=None, diffusion=None,
                    sponge=None):
         """castro_amd_sources_mf: stage 0 = old-time sources + S_new = S_old + dt * source + clean_state, stage 1 = new-time
-        sources + S_new += dt * source + clean_state, for every box of `boxes` (make_source_boxes).  diffusion
+        sources + S_new += dt * source + clean_state, stage 1 | _lib.SOURCES_AFTER_REFLUX = S_new -= dt * (stored new-time source) + clean_state, then stage 1
+        (the re-evaluation after a reflux), for every box of `boxes` (make_source_boxes).  diffusion
         (_lib.make_diffusion): castro_amd_sources_mf_ex, the thermal-diffusion term in front of gravity and rotation.
         sponge (_lib.make_sponge with a center): castro_amd_sources_mf_opts, the sponge after rotation in stage 1."""
         arr, n = boxes
@@ -615,6 +619,13 @@ class HipHydro:
         L.check(self.lib.castro_amd_reflux_fab(self.h, C.byref(L.fab_of(state, *state_box)), C.byref(L.fab_of(reg, *reg_box)),
                                                L.i3(lo), L.i3(hi), int(dir), int(side), int(ncomp), float(vol), _stream_ptr(stream)),
                 "reflux_fab")
+
+    def fluxreg_to_flux(self, flux, flux_box, reg, reg_box, mass_flux, mass_box, lo, hi, ncomp, stream=None):
+        """castro_amd_fluxreg_to_flux_fab: flux += reg on the faces [lo, hi]; mass_flux (or None) = component URHO of the sum"""
+        mf = C.byref(L.fab_of(mass_flux, *mass_box)) if mass_flux is not None else None
+        L.check(self.lib.castro_amd_fluxreg_to_flux_fab(self.h, C.byref(L.fab_of(flux, *flux_box)), C.byref(L.fab_of(reg, *reg_box)),
+                                                        mf, L.i3(lo), L.i3(hi), int(ncomp), _stream_ptr(stream)),
+                "fluxreg_to_flux_fab")
 
     # ---- derived plotfile fields (Source/driver/Derive.cpp) ---------------------------------
     def derive(self, name, state, box, der, der_box, dcomp, lo, hi, geom, params, center, stream=None):

@@ -61,7 +61,9 @@ extern "C" {
  *      castro_amd_old_gravity_source_gfab, castro_amd_new_gravity_source_gfab;
  *      castro_amd_new_sponge_source_fab (struct castro_amd_sponge), castro_amd_sources_mf_opts (struct castro_amd_source_opts);
  *      castro_amd_add_pointmass_fab / _mf, castro_amd_pointmass_delta_mf, castro_amd_pointmass_apply_mf (structs
- *      castro_amd_pointmass_params, castro_amd_pointmass_box).
+ *      castro_amd_pointmass_params, castro_amd_pointmass_box);
+ *      castro_amd_fluxreg_to_flux_fab, CASTRO_AMD_OP_FLUXREG_TO_FLUX, CASTRO_AMD_SOURCES_AFTER_REFLUX (stage 1 | that flag of
+ *      castro_amd_sources_mf / _ex / _g / _opts).
  * A caller checks `castro_amd_abi_version() == CASTRO_AMD_ABI_VERSION` once after loading the library; a mismatch means
  * the library was built from another revision of this header (a 0.2 caller with 2-double vectors would be written 8 bytes
  * out of bounds by a 0.3 library). */
@@ -390,12 +392,19 @@ int castro_amd_new_rotation_source_fab(castro_amd_ctx *ctx, const castro_amd_fab
  *   stage 1 (new time, :262-268):  source = 0; += new gravity source; += new rotation source (both read S_old, S_new and
  *            mass_flux[d]);  S_new += dt * source on [lo, hi], then clean_state x clean_ntimes
  * with the arithmetic -- and the kernels -- of the single-box entry points above: the same bits.  stage 0: `source` is the
- * old-time Source_Type FAB with its ghost zones; stage 1: the new-time one (valid zones); mass_flux is read by stage 1 only. */
+ * old-time Source_Type FAB with its ghost zones; stage 1: the new-time one (valid zones); mass_flux is read by stage 1 only.
+ *   stage 1 | CASTRO_AMD_SOURCES_AFTER_REFLUX (the re-evaluation of the new-time sources after a reflux, Castro.cpp:2773-2868
+ *             with update_sources_after_reflux; any other stage value, the bare 2 included, is CASTRO_AMD_ERR_ARG as before):
+ *             S_new += -dt * source (the stored new-time source), clean_state x clean_ntimes, then stage 1 -- one launch, the
+ *             bits of castro_amd_apply_source_fab(S_new, S_new, -dt, source) followed by stage 1.  `source` and mass_flux as
+ *             in stage 1; dt is the dt of the advance that stored the source.  With a diffusion term (_ex, _opts):
+ *             CASTRO_AMD_ERR_UNSUPPORTED -- its stencil reads the neighbours' S_new, which the one pass rewrites. */
 typedef struct castro_amd_source_box {
     int lo[3], hi[3];
     castro_amd_fab S_old, S_new, source;
     castro_amd_fab mass_flux[3];
 } castro_amd_source_box;
+#define CASTRO_AMD_SOURCES_AFTER_REFLUX 16   /* OR-ed to stage 1 of castro_amd_sources_mf / _ex / _g / _opts */
 int castro_amd_sources_mf(castro_amd_ctx *ctx, int stage, int nboxes, const castro_amd_source_box *boxes,
                           const double *grav /* [3] or NULL */, int grav_source_type, const castro_amd_rotation *rot /* or NULL */,
                           const castro_amd_geom *geom, const castro_amd_params *params, double dt, int clean_ntimes, void *stream);
@@ -723,6 +732,9 @@ int castro_amd_pointmass_apply_mf(castro_amd_ctx *ctx, int nboxes, const castro_
  *   castro_amd_fluxreg_fine_add_fab   FluxRegister::FineAdd of FluxRegFineAdd (:2516-2545): reg += mult * sum of 4 fine faces
  *   castro_amd_reflux_fab             FluxRegister::Reflux of Castro::reflux (:2549-2700): zones outside the faces [lo,hi]
  *                                     get -reg/vol (side 0, low face of the fine region) or +reg/vol (side 1)
+ *   castro_amd_fluxreg_to_flux_fab    the coarse fluxes after the reflux (:2617-2644, castro.update_sources_after_reflux):
+ *                                     flux += reg on the faces [lo,hi], ncomp components, and mass_flux = flux(URHO) there
+ *                                     (mass_flux NULL or with p == NULL: the fluxes alone)
  *   castro_amd_error_tag_fab          amrex::AMRErrorTag of Castro::errorEst (Castro.cpp:3131-3164): kind 0 value_greater,
  *                                     1 value_less, 2 gradient, 3 relative_gradient on component `comp` of `field`
  *                                     (one ghost zone for the gradient kinds); tags (1 comp, 1.0 = tagged) are OR-ed
@@ -739,6 +751,7 @@ int castro_amd_pointmass_apply_mf(castro_amd_ctx *ctx, int nboxes, const castro_
  *   CASTRO_AMD_OP_FLUXREG_FINE_ADD   castro_amd_fluxreg_fine_add_fab  dst += a (sum of the 4 fine faces of src), dir
  *   CASTRO_AMD_OP_REFLUX             castro_amd_reflux_fab            dst zones outside the faces [lo,hi] -= / += src / a
  *   CASTRO_AMD_OP_AVGDOWN            castro_amd_avgdown_fab           dst = mean of the 8 fine zones of src (region in dst's index space)
+ *   CASTRO_AMD_OP_FLUXREG_TO_FLUX    castro_amd_fluxreg_to_flux_fab   dst += src, and src2 = dst(URHO) where src2.p != NULL
  *                                                                      (side 0 / 1), a = zone volume */
 #define CASTRO_AMD_OP_COPY 0
 #define CASTRO_AMD_OP_LINCOMB 1
@@ -753,6 +766,8 @@ int castro_amd_pointmass_apply_mf(castro_amd_ctx *ctx, int nboxes, const castro_
                                          * Castro::avgDown of a whole level in one call */
 #define CASTRO_AMD_OP_INTERP 8          /* dst (fine) = cell_cons_interp of src on the region, the first ncomp (<= 8) components, nothing else
                                          * (castro_amd_cc_interp_fab): the ghost shells of the Source_Type FillPatch of a level in one call */
+#define CASTRO_AMD_OP_FLUXREG_TO_FLUX 9 /* dst (coarse flux) += src (register) on the faces of the region; src2: the mass-flux FAB that takes
+                                         * component URHO of the sum, or p == NULL.  The registers of one orientation of a level in one call */
 typedef struct castro_amd_fab_op {
     int kind;
     int dir;                     /* FLUXREG_FINE_ADD, REFLUX */
@@ -760,7 +775,7 @@ typedef struct castro_amd_fab_op {
     int lo[3], hi[3];            /* region, in the index space of dst (REFLUX: the faces, in the index space of src) */
     int side;                    /* REFLUX only */
     double a, b;
-    castro_amd_fab dst, src, src2;   /* src2: LINCOMB only */
+    castro_amd_fab dst, src, src2;   /* src2: LINCOMB; FLUXREG_TO_FLUX (written, or p == NULL) */
 } castro_amd_fab_op;
 int castro_amd_fab_ops(castro_amd_ctx *ctx, int nops, const castro_amd_fab_op *ops, void *stream);
 /* The same with the runtime parameters the CLEAN kinds need.  Any number of operations: up to sixteen travel as a kernel
@@ -803,6 +818,8 @@ int castro_amd_fluxreg_fine_add_fab(castro_amd_ctx *ctx, const castro_amd_fab *r
                                     const int lo[3], const int hi[3], int dir, int ncomp, double mult, void *stream);
 int castro_amd_reflux_fab(castro_amd_ctx *ctx, const castro_amd_fab *state, const castro_amd_fab *reg,
                           const int lo[3], const int hi[3], int dir, int side, int ncomp, double vol, void *stream);
+int castro_amd_fluxreg_to_flux_fab(castro_amd_ctx *ctx, const castro_amd_fab *flux, const castro_amd_fab *reg,
+                                   const castro_amd_fab *mass_flux, const int lo[3], const int hi[3], int ncomp, void *stream);
 
 /* Derived plotfile fields (Source/driver/Derive.cpp, registered in Castro_setup.cpp:756-960) for the
  * 3-D Cartesian gamma-law build.  Not provided: entropy (needs the Microphysics entropy formula),
