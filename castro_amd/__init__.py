@@ -7,6 +7,7 @@ Layout:
   castro.py        Castro: single-level driver (FillPatch halo exchange over RCCL, dt control, retry, gravity, rotation, thermal diffusion, sponge)
   amr.py           CastroAmr: coarse level + one refined patch with subcycling, reflux, avgDown
   gravity.py       MonopoleGravity: monopole self-gravity over the levels of CastroAmr (radial arrays, level combination); PointMass: the central point mass
+  particles.py     TracerParticles: tracer particles over the levels of Castro / CastroAmr (advect, redistribute, timestamp, particle_count)
   plotfile.py      Castro plotfile writer / reader
 """
 from ._lib import (NUM_STATE, NGDNV, NUM_GROW, URHO, UMX, UMY, UMZ, UEDEN, UEINT, UTEMP, UFS,
@@ -14,8 +15,9 @@ from ._lib import (NUM_STATE, NGDNV, NUM_GROW, URHO, UMX, UMY, UMZ, UEDEN, UEINT
 from .castro import Castro, DistComm, SingleComm, AdvanceFailure, default_grid
 from .amr import CastroAmr
 from .gravity import MonopoleGravity, PointMass
+from .particles import TracerParticles
 
-__all__ = ["Castro", "CastroAmr", "MonopoleGravity", "PointMass", "DistComm", "SingleComm", "AdvanceFailure", "default_grid", "default_params", "make_geom", "make_rotation", "make_diffusion", "make_sponge", "make_ext_bc",
+__all__ = ["Castro", "CastroAmr", "MonopoleGravity", "PointMass", "TracerParticles", "DistComm", "SingleComm", "AdvanceFailure", "default_grid", "default_params", "make_geom", "make_rotation", "make_diffusion", "make_sponge", "make_ext_bc",
            "NUM_STATE", "NGDNV", "NUM_GROW", "LIB_PATH"]
 
 

@@ -76,6 +76,7 @@ EXPORTED_SYMBOLS = (
     "castro_amd_add_pointmass_fab", "castro_amd_add_pointmass_mf", "castro_amd_pointmass_delta_mf", "castro_amd_pointmass_apply_mf",
     "castro_amd_ext_bc_fill_fab",
     "castro_amd_fluxreg_to_flux_fab",
+    "castro_amd_tracer_advect_mf", "castro_amd_tracer_locate", "castro_amd_tracer_sample_mf", "castro_amd_tracer_count_mf",
 )
 
 
@@ -342,6 +343,34 @@ def pointmass_cube(center, geom):
     return tuple(i - 2 for i in icen), tuple(i + 1 for i in icen)
 
 
+class Tracers(C.Structure):
+    """castro_amd_tracers: the particle arrays on the device, one entry per particle"""
+    _fields_ = [("n", C.c_longlong), ("x", C.c_void_p), ("y", C.c_void_p), ("z", C.c_void_p), ("r0", C.c_void_p),
+                ("r1", C.c_void_p), ("r2", C.c_void_p), ("id", C.c_void_p), ("cpu", C.c_void_p), ("level", C.c_void_p),
+                ("grid", C.c_void_p)]
+
+
+def make_tracers(pos, r, ints):
+    """castro_amd_tracers of device tensors: pos and r float64 (3, N) (rows x, y, z / r0, r1, r2), ints int32 (4, N) (rows id,
+    cpu, level, grid); the tensors must outlive the struct"""
+    import torch
+    n = pos.shape[1]
+    assert pos.dtype == torch.float64 and r.dtype == torch.float64 and ints.dtype == torch.int32
+    assert pos.is_contiguous() and r.is_contiguous() and ints.is_contiguous()
+    assert tuple(pos.shape) == (3, n) and tuple(r.shape) == (3, n) and tuple(ints.shape) == (4, n)
+    t = Tracers()
+    t.n = n
+    t.x, t.y, t.z = (pos.data_ptr() + 8 * n * k for k in range(3))
+    t.r0, t.r1, t.r2 = (r.data_ptr() + 8 * n * k for k in range(3))
+    t.id, t.cpu, t.level, t.grid = (ints.data_ptr() + 4 * n * k for k in range(4))
+    return t
+
+
+class TracerBox(C.Structure):
+    """castro_amd_tracer_box: a FAB of a box of a level and the valid box inside it"""
+    _fields_ = [("fab", Fab), ("vlo", C.c_int * 3), ("vhi", C.c_int * 3)]
+
+
 class Diffusion(C.Structure):
     """castro_amd_diffusion"""
     _fields_ = [("const_conductivity", C.c_double), ("diffuse_cutoff_density", C.c_double),
@@ -512,6 +541,15 @@ def load(numerics=None):
                                                     C.c_void_p]
         L.castro_amd_pointmass_apply_mf.argtypes = [C.c_void_p, C.c_int, C.POINTER(PointMassBox), PP, C.POINTER(Geom), C.c_void_p,
                                                     C.c_void_p, C.c_void_p]
+    if hasattr(L, "castro_amd_tracer_locate"):              # absent from A/B builds of revisions before the tracer particles
+        PT, PB = C.POINTER(Tracers), C.POINTER(TracerBox)
+        L.castro_amd_tracer_advect_mf.argtypes = [C.c_void_p, C.c_int, C.c_int, PB, C.POINTER(Geom), C.c_double, C.c_int, PT,
+                                                  C.c_void_p, C.c_void_p]
+        L.castro_amd_tracer_locate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), PB,
+                                               C.POINTER(Geom), PT, C.c_void_p, C.c_void_p]
+        L.castro_amd_tracer_sample_mf.argtypes = [C.c_void_p, C.c_int, C.c_int, PB, C.POINTER(Geom), C.c_int, C.POINTER(C.c_int), PT,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]
+        L.castro_amd_tracer_count_mf.argtypes = [C.c_void_p, C.c_int, C.c_int, PB, C.POINTER(Geom), PT, C.c_void_p]
     L.castro_amd_step_control.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_double, C.c_double,
                                           C.c_double, C.c_int, C.c_void_p]
     L.castro_amd_clean_state_fab.argtypes = [C.c_void_p, PF, I3, I3, C.POINTER(Params), C.c_int, C.c_void_p]

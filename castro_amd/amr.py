@@ -30,7 +30,9 @@ the level below.  Level 0 is one box (per rank; this driver is single-rank).
 Periodic domains: the periodic images of the boxes of a level enter the same-level copies and the reflux as boxes shifted
 by the domain extent.  Constant gravity and rotation sources on every level (the Source_Type FillPatch of a refined level
 interpolates the coarse sources like the state); monopole self-gravity with gravity=MonopoleGravity(...) (castro_amd/gravity.py:
-the radial arrays span the levels, _Level.fill_grav is the Gravity_Type FillPatch).  Not provided: multi-rank AMR.  The interpolation,
+the radial arrays span the levels, _Level.fill_grav is the Gravity_Type FillPatch); tracer particles with
+tracers=TracerParticles(...) (castro_amd/particles.py: advected at the end of every level's advance, redistributed and
+timestamped at the end of its post_timestep and after every regrid).  Not provided: multi-rank AMR.  The interpolation,
 flux-register and clustering arithmetic is AMReX's, restated from its published description
 (include/castro_hydro_amd.h, castro_amd/cluster.py): parity with an AMReX build is unpinned.
 """
@@ -145,6 +147,10 @@ class _Level:
         # castro.source_term_predictor: Castro::lastDt of this level (1e200 in every constructor, Castro.cpp:906 -- a level made
         # by a regrid starts with it again) and the in_retry flag of subcycle_advance_ctu
         self.lastDt, self._in_retry = 1.e200, False
+        self._iteration = 1       # Amr::timeStep's iteration of the advance in progress (1 on level 0, 1 or 2 above)
+        if getattr(amr, "tracers", None) is not None:
+            for b in self.mine:   # the half-time state the tracer velocity is gathered from
+                b.S_half_b = b.hydro.alloc(NUM_STATE, b.glo, b.ghi)
 
     def __getattr__(self, name):
         # a level of one box answers for its box (S_new(), lo, hi, n, gbox, S_new_b, ...)
@@ -674,6 +680,35 @@ class _Level:
         self.invalidate_estimate()              # S_new has been written outside the update pass
         return True
 
+    # ---- tracer particles (castro_amd/particles.py) -----------------------------------------------------------------------
+    def _tracer_boxes(self, which):
+        """the make_tracer_boxes table of S_half_b / S_new_b of the boxes of the level, in box order (a particle's `grid`)"""
+        key = (which,) + tuple(getattr(b, which).data_ptr() for b in self.boxes)
+        tabs = self.__dict__.setdefault("_tracer_tabs", {})
+        if key not in tabs:
+            if len(tabs) > 8:
+                tabs.clear()
+            tabs[key] = self.hydro.make_tracer_boxes([(b.lo, b.hi, (getattr(b, which), b.gbox)) for b in self.boxes])
+        return tabs[key]
+
+    def _advance_particles(self, time, dt):
+        """Castro::advance_particles of this level (CastroParticles.cpp:252-281), at the end of its advance: the FillPatch of the
+        state at time + dt / 2 into S_half_b of every box -- the valid zones 0.5 old + 0.5 new, the ghost zones through the
+        level's fill with the coarse data interpolated in time first (a quarter of the parent's step past this level's old
+        time), then in space -- and AdvectWithUcc.  time, dt: those of the whole advance."""
+        tr = self.amr.tracers
+        if tr is None:
+            return
+        h = self.hydro
+        for b in self.mine:
+            h.lincomb(b.S_half_b, b.gbox, 0.5, b.S_old_b, b.gbox, 0.5, b.S_new_b, b.gbox, NUM_STATE, b.lo, b.hi)
+        keep = self.alpha
+        if self.l > 0:
+            self.alpha = self._alpha0 + 0.25
+        self.fill("S_half_b")
+        self.alpha = keep
+        tr.advect(self.l, self._tracer_boxes("S_half_b"), self.geom, dt, ng=self._iteration)
+
     def _hydro_calls(self, fn):
         """fn(b) -- the hydro update of one box -- for every box of this rank.  The boxes of a level are independent
         there, and one small box fills a fraction of the chip (a 32^3 box is 64 workgroups of 256 CUs' worth), so with
@@ -826,8 +861,11 @@ class CastroAmr:
                  do_grav=False, const_grav=0.0, grav_source_type=4, rotation=None, comm=None, base_grid=None, box_streams=4,
                  diffusion=None, sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", gravity=None,
                  sponge=None, use_point_mass=False, point_mass=0.0, point_mass_fix_solution=False, ext_bc=None,
-                 update_sources_after_reflux=False):
-        """update_sources_after_reflux: castro.update_sources_after_reflux.  True is the reference's default (1) and the setting
+                 update_sources_after_reflux=False, tracers=None):
+        """tracers: a castro_amd.TracerParticles (castro.do_tracer_particles = 1) spanning the levels: advected at the end of
+        every level's advance, redistributed and timestamped at the end of its post_timestep and after every regrid, as in
+        castro_amd.Castro; one rank only.
+        update_sources_after_reflux: castro.update_sources_after_reflux.  True is the reference's default (1) and the setting
         that follows it: after the reflux of post_timestep the flux registers are added to the coarse level's fluxes (mass
         fluxes = their density component) and both levels take their new-time sources out of S_new, clean it, and evaluate and
         apply them again from the refluxed state and the corrected mass fluxes (Castro.cpp:2612-2644, 2762-2868).  False (the
@@ -896,6 +934,9 @@ class CastroAmr:
         from .castro import SingleComm
         self.comm = comm if comm is not None else SingleComm()
         self.rank, self.nranks = self.comm.rank, self.comm.size
+        if tracers is not None and self.nranks > 1:
+            raise NotImplementedError("tracer particles on more than one rank need the migration between ranks, which is not built")
+        self.tracers = tracers
         self._mk = (lambda: None) if make_hydro is None else make_hydro
         self.params = params if params is not None else (make_params() if make_params else L.default_params())
         self._kw = dict(prob_lo=prob_lo, prob_hi=prob_hi, lo_bc=lo_bc, hi_bc=hi_bc, params=self.params, overlap=False,
@@ -941,6 +982,8 @@ class CastroAmr:
             lev0.bind()
             if gravity is not None:
                 gravity.check_level(0, lev0.geom)
+        if tracers is not None:
+            tracers.bind(self._hydro_for(0), self.lev[0].geom, self.comm)
         if use_point_mass:
             from .gravity import PointMass
             self.pm = gravity.point_mass = PointMass(self._hydro_for(0), point_mass, point_mass_fix_solution, gravity.Gconst)
@@ -1376,6 +1419,14 @@ class CastroAmr:
     # ---- Amr::regrid(lbase): new grids above level lbase, data from the old boxes of a level where they exist,
     #      else interpolated ---------------------------------------------------------------------------------
     def regrid(self, lbase=0, alpha=1.0):
+        """Amr::regrid(lbase), then the particle part of Castro::post_regrid (Castro.cpp:2114-2117): Redistribute(lbase).
+        True if the grids changed."""
+        changed = self._regrid(lbase, alpha)
+        if self.tracers is not None and self.tracers.pos is not None:
+            self._particles_redistribute(lbase)
+        return changed
+
+    def _regrid(self, lbase=0, alpha=1.0):
         new = self._grid_places(lbase, alpha)
         if new == self.boxes[1:]:
             return False
@@ -1463,9 +1514,42 @@ class CastroAmr:
             self.avgDown(l)
         self.time, self.nstep = 0.0, 0
         self.level_count = [0] * 16
+        if self.tracers is not None:                    # Castro::init_particles on level 0, Redistribute(0) over the built levels
+            self.tracers.init_particles(self.lev[0].geom)
+            self._particles_redistribute(0)
+            self.tracers.check_flags()
         self.diag.reset()
         if self.diag.sum_interval > 0:                  # Castro::post_init: the entry of time 0, dt reported as 0
             self.diag.record(self.sum_integrated_quantities(), 0, 0.0, finest_level=len(self.lev) - 1)
+
+    # ---- tracer particles over the hierarchy (castro_amd/particles.py) ---------------------------------------------------
+    def _tracer_levels(self):
+        return [lev.box_list() for lev in self.lev], [lev.geom for lev in self.lev]
+
+    def _particles_redistribute(self, lev_min, ngrow=0):
+        boxes, geoms = self._tracer_levels()
+        self.tracers.redistribute(boxes, geoms, lev_min, len(self.lev) - 1, ngrow)
+
+    def _particles_post_timestep(self, l, iteration, t_new, alpha_new):
+        """the particle part of Castro::post_timestep of level l (Castro.cpp:1982-1997), under the reference's condition
+        `iteration < ncycle || level == 0` -- not after the last of a refined level's two subcycles, whose particles the coarser
+        level's call covers: Redistribute(l, finest, ngrow = 0 on level 0, else the iteration) and TimestampParticles(ngrow + 1)
+        over the levels from l up, whose new-time ghost zones are filled for it (level l sits at alpha_new inside its parent's
+        step)."""
+        tr = self.tracers
+        if tr is None or (l > 0 and iteration >= 2):
+            return
+        self._particles_redistribute(l, 0 if l == 0 else iteration)
+        if tr.timestamp_dir is not None:
+            keep = [lev.alpha for lev in self.lev]
+            self._fill_ghosts_new(len(self.lev) - 1, l, alpha_new)      # ghost zones only: the run does not change
+            for lev, a in zip(self.lev, keep):
+                lev.alpha = a
+            tr.timestamp(l, t_new, lambda k: self.lev[k]._tracer_boxes("S_new_b"), self._tracer_levels()[1])
+
+    def writePlotFile(self, dirname, derive=None):
+        from .plotfile import write_plotfile_amr
+        return write_plotfile_amr(dirname, self, derive=derive)
 
     # ---- Castro::avgDown (Castro.cpp:3096-3113): level l onto level l-1 ------------------------------
     def invalidate_estimates(self):
@@ -1513,8 +1597,9 @@ class CastroAmr:
         return dt_0
 
     # ---- Amr::timeStep: advance level l, then recursively twice the next finer level, then post_timestep -----
-    def _time_step(self, l, t, dt, alpha):
-        """alpha: position of this level's old time inside the parent's [old, new] interval (0 or 1/2)."""
+    def _time_step(self, l, t, dt, alpha, iteration=1):
+        """alpha: position of this level's old time inside the parent's [old, new] interval (0 or 1/2); iteration: which of the
+        parent's subcycles this is (1 on level 0, 1 or 2 above)."""
         # Amr::timeStep: every level i >= l that has taken regrid_int steps since its last regrid gets new grids above
         # it (all those levels are synchronised at time t here)
         if self.refine is not None and self.regrid_int > 0:
@@ -1531,6 +1616,7 @@ class CastroAmr:
         lev._t0, lev._alpha0, lev._dt_parent = t, alpha, 2.0 * dt
         lev.t_old, lev.t_new = t, t + dt        # StateData::prevTime / curTime of the level (Gravity::make_radial_gravity)
         lev.fuse_post_level = l == finest and os.environ.get("CASTRO_AMD_FUSE_POST_FINEST", "1") != "0"
+        lev._iteration = iteration
         lev.advance(t, dt)
         self.level_count[l] += 1
         if l > 0:
@@ -1560,7 +1646,7 @@ class CastroAmr:
                         for p, (lo, hi) in b.crse_init[(d, side)]:
                             h.fluxreg_crse_init(reg, rbox, p.fluxes[d], p.flux_boxes[d], lo, hi, NUM_STATE, -1.0)
             for it in range(2):
-                self._time_step(l + 1, t + it * (dt / 2), dt / 2, 0.5 * it)
+                self._time_step(l + 1, t + it * (dt / 2), dt / 2, 0.5 * it, iteration=it + 1)
             # post_timestep: reflux, avgDown, clean_state
             vol = lev.geom.dx[0] * lev.geom.dx[1] * lev.geom.dx[2]
             # face orientation by face orientation, like FluxRegister::Reflux's OrientationIter [3P]: the registers of one
@@ -1591,6 +1677,7 @@ class CastroAmr:
         # (there it may have ridden in the fused pass of the update: _hydro_level)
         if not (l == finest and lev._post_clean_done):
             lev.clean_new()
+        self._particles_post_timestep(l, iteration, t + dt, alpha + 0.5)
 
     def _fluxes_after_reflux(self, l):
         """Castro::reflux with castro.update_sources_after_reflux, the flux half (Castro.cpp:2617-2644): the registers of level
@@ -1633,6 +1720,8 @@ class CastroAmr:
         self.nstep += 1
         for lev in self.lev:
             lev.time, lev.nstep = self.time, self.nstep
+        if self.tracers is not None:
+            self.tracers.check_flags()                  # the step's one look at the clamp and lost counts
         if self.diag.due(self.nstep):                   # Castro::post_timestep of level 0
             self.diag.record(self.sum_integrated_quantities(), self.nstep, dt0, finest_level=len(self.lev) - 1)
         return dt0

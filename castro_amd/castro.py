@@ -261,8 +261,13 @@ class Castro:
                  do_grav=False, const_grav=0.0, grav_source_type=4, box=None, rotation=None, fixed_dt=-1.0, initial_dt=-1.0, max_dt=1.e200,
                  alloc=True, numerics=None, proxy_ranks=1, diffusion=None, do_hydro=True,
                  sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", drdxfac=1, Gconst=L.GCONST,
-                 gravity=None, sponge=None, use_point_mass=False, point_mass=0.0, point_mass_fix_solution=False, ext_bc=None):
-        """ext_bc: _lib.make_ext_bc(zl="hse", ...) turns on the boundary overrides of the state fill (ca_statefill's second half:
+                 gravity=None, sponge=None, use_point_mass=False, point_mass=0.0, point_mass_fix_solution=False, ext_bc=None,
+                 tracers=None):
+        """tracers: a castro_amd.TracerParticles (castro.do_tracer_particles = 1): passive particles advected with the fluid
+        velocity at the end of every advance (Castro::advance_particles), redistributed and -- with a timestamp_dir -- sampled
+        after every step; one rank only.  The object owns the particle arrays; this box gets one more state array for the
+        half-time state.  Steps then go through step(): host_free_ok() is False.
+        ext_bc: _lib.make_ext_bc(zl="hse", ...) turns on the boundary overrides of the state fill (ca_statefill's second half:
         castro.*_ext_bc_type = HSE on Inflow faces, castro.fill_ambient_bc beyond Outflow faces); const_grav and the ambient state
         are completed from this object's gravity and params, and every physical-boundary fill of a state array is followed by
         castro_amd_ext_bc_fill_fab (_bc_fill_state).  The hydro call then never fills boundary zones itself, so the light overlap
@@ -293,6 +298,8 @@ class Castro:
         self.n_cell = tuple(int(x) for x in n_cell)
         self.owned = bool(alloc)
         self.comm = comm if comm is not None else SingleComm()
+        if tracers is not None and self.comm.size > 1:
+            raise NotImplementedError("tracer particles on more than one rank need the migration between ranks, which is not built")
         try:
             import weakref
             if getattr(self.comm, "_users", None) is None:
@@ -363,6 +370,11 @@ class Castro:
                 self._red_all = hydro.alloc(1, (0, 0, 0), (3, 0, 0)).reshape(4)
                 self.red, self._unconverged = self._red_all[:3], self._red_all[3:].view(torch.int32)[:1]
 
+        # tracer particles: the half-time state the velocity is gathered from (FillPatch at time + dt / 2)
+        self.tracers, self.S_half_b = tracers, None
+        if tracers is not None:
+            tracers.bind(hydro, self.geom, self.comm)
+            self.S_half_b = hydro_alloc(NUM_STATE, self.glo, self.ghi)
         self._plans = {}
         self.neighbors = self._build_neighbors() if box is None else []
         # Overlap of the halo exchange with compute (the forms are listed where self.overlap is set below): True = the light
@@ -722,6 +734,7 @@ class Castro:
         self.clean_state(self.S_new_b, 1)      # Castro.cpp:1100-1160
         self.time, self.nstep, self.dt = 0.0, 0, 0.0
         self._diag_post_init()
+        self._init_particles()
 
     def diffusion_test_analytic(self, time, diff_coeff=1.0, T1=1.0, T2=2.0, t_0=1.e-3):
         """The temperature of Exec/unit_tests/diffusion_test at `time` on the whole domain, (nz, ny, nx): a Gaussian pulse about
@@ -760,6 +773,7 @@ class Castro:
         self.clean_state(self.S_new_b, 1)
         self.time, self.nstep, self.dt = 0.0, 0, 0.0
         self._diag_post_init()
+        self._init_particles()
 
     def dust_collapse_state(self, rho_0=1.e9, r_0=6.5e8, p_0=1.e10, rho_ambient=1.0, smooth_delta=1.e-5, nsub=5):
         """problem_initialize_state_data of Exec/gravity_tests/DustCollapse (no r_offset) on the whole domain: the density of a
@@ -869,6 +883,53 @@ class Castro:
             tabs[key] = self.hydro.make_pointmass_boxes([(self.lo, self.hi, (self.S_old_b, self.gbox), (self.S_new_b, self.gbox))])
         pm.update(self.hydro, self.comm, tabs[key], diag.domain_center(self), self.geom)
         return True
+
+    # ---- tracer particles (Source/particles/CastroParticles.cpp; castro_amd/particles.py) -------------------------------------
+    def _tracer_levels(self):
+        """([boxes of level l], [geometry of level l]) as Redistribute takes them: one level, this box"""
+        return [[(self.lo, self.hi)]], [self.geom]
+
+    def _tracer_boxes(self, which):
+        """the make_tracer_boxes table of S_half_b / S_new_b (the two state buffers swap roles: a table per buffer)"""
+        S = getattr(self, which)
+        tabs = self.__dict__.setdefault("_tracer_tabs", {})
+        if S.data_ptr() not in tabs:
+            tabs[S.data_ptr()] = self.hydro.make_tracer_boxes([(self.lo, self.hi, (S, self.gbox))])
+        return tabs[S.data_ptr()]
+
+    def _init_particles(self):
+        """Castro::init_particles (Castro.cpp:1399), then Redistribute(0)"""
+        tr = self.tracers
+        if tr is None:
+            return
+        tr.init_particles(self.geom)
+        tr.redistribute(*self._tracer_levels(), 0)
+        tr.check_flags()
+
+    def _advance_particles(self, time, dt):
+        """Castro::advance_particles (CastroParticles.cpp:252-281) after the whole advance: the FillPatch of the state at
+        time + dt / 2 -- StateData's 0.5 old + 0.5 new on the conserved components, S_old_b being the step's original old state --
+        with its ghost zones, then AdvectWithUcc; the kernel forms u = mom * (1 / rho) at every stencil corner."""
+        tr = self.tracers
+        if tr is None:
+            return
+        self.hydro.lincomb(self.S_half_b, self.gbox, 0.5, self.S_old_b, self.gbox, 0.5, self.S_new_b, self.gbox, NUM_STATE,
+                           self.lo, self.hi)
+        self.expand_state(self.S_half_b)
+        tr.advect(0, self._tracer_boxes("S_half_b"), self.geom, dt, ng=1)
+
+    def _particles_post_timestep(self):
+        """the particle part of Castro::post_timestep (Castro.cpp:1982-1997) on a single level: Redistribute(0), then
+        TimestampParticles(1) from the ghost-filled new state; the step's one look at the particle flags"""
+        tr = self.tracers
+        if tr is None:
+            return
+        boxes, geoms = self._tracer_levels()
+        tr.redistribute(boxes, geoms, 0)
+        if tr.timestamp_dir is not None:
+            self.expand_state(self.S_new_b)         # ghost zones only: the next advance fills them again from the same zones
+            tr.timestamp(0, self.time, lambda l: self._tracer_boxes("S_new_b"), geoms)
+        tr.check_flags()
 
     def radial_gravity(self):
         """(radial_mass, radial_vol, radial_grav) of the last gravity construction, as numpy arrays of n1d entries"""
@@ -1281,6 +1342,7 @@ class Castro:
         # the next time step afresh (step(): computeNewDt without `est`)
         if self._pointmass_update():
             new_dt = None
+        self._advance_particles(time, dt)       # advance_particles (Castro_advance.cpp:115): passive, after everything else
         return new_dt
 
     # ---- Castro::subcycle_advance_ctu + retry_advance_ctu (Castro_advance_ctu.cpp:403-768) ------
@@ -1351,6 +1413,7 @@ class Castro:
             self._next_est = None                   # computeNewDt estimates from the state post_timestep leaves
         self.time += self.dt
         self.nstep += 1
+        self._particles_post_timestep()
         self._diag_post_timestep()
         return self.dt
 
@@ -1363,7 +1426,7 @@ class Castro:
         # with castro.use_retry a rejected step is redone by the host from its old state (run_steps): every write to the
         # caller's arrays must then sit in a kernel that checks the latched status, i.e. the cleans ride in k_ctoprim
         retry_ok = (not self.use_retry) or (self.fuse_sborder_clean and (not use_overlap or self._light_overlap()))
-        return (self.fuse_clean and self.fuse_post_clean and not self.have_sources and retry_ok
+        return (self.fuse_clean and self.fuse_post_clean and not self.have_sources and retry_ok and self.tracers is None
                 and hasattr(self.hydro, "step_control") and getattr(self.comm, "device_side", False)
                 and self.overlap != "tiles")
 

@@ -34,6 +34,7 @@ struct castro_amd_ctx {
     DiagWorkspace diag_ws;                          // its rows of partial sums, one per workgroup
     MonoWorkspace mono_ws;                          // castro_amd_radial_mass_mf: rows, counts and device box tables
     TableCache pm_tables{32};                       // castro_amd_add_pointmass_mf / castro_amd_pointmass_*_mf
+    TableCache tr_tables{32};                       // castro_amd_tracer_*
 };
 
 namespace cad {
@@ -248,6 +249,7 @@ void castro_amd_ctx_destroy(castro_amd_ctx* c)
     if (c->diag_ws.p) hipFree(c->diag_ws.p);
     mono_workspace_free(&c->mono_ws);
     c->pm_tables.release();
+    c->tr_tables.release();
     prof_collect(&c->prof);
     for (auto e : c->prof.pool) hipEventDestroy(e);
     if (c->arena) hipFree(c->arena);
@@ -1131,6 +1133,153 @@ int castro_amd_pointmass_apply_mf(castro_amd_ctx* c, int nboxes, const castro_am
     if (rt != CASTRO_AMD_OK) return rt;
     hipSetDevice(c->device);
     return launch_pointmass_apply(nboxes, tab.data(), clo, d_delta, d_point_mass, &c->pm_tables, (hipStream_t)stream, &c->prof);
+}
+
+// ---- tracer particles (tracer_kernels.hip) ---------------------------------------------------------------------------------------
+static bool tr_particles_ok(const castro_amd_tracers* t)
+{
+    if (!t || t->n < 0) return false;
+    if (t->n == 0) return true;
+    return t->x && t->y && t->z && t->r0 && t->r1 && t->r2 && t->id && t->level && t->grid;
+}
+
+// the geometry every tracer kernel reads: problo / probhi, the periodic directions, 1 / dx of the level into dxi[slot]
+static int tr_geom(const castro_amd_geom* geom, int slot, TrGeom& G)
+{
+    if (!geom) return CASTRO_AMD_ERR_ARG;
+    if (geom->coord != 0) return CASTRO_AMD_ERR_UNSUPPORTED;
+    for (int d = 0; d < 3; ++d) {
+        if (!(geom->dx[d] > 0.0) || !(geom->probhi[d] > geom->problo[d])) return CASTRO_AMD_ERR_ARG;
+        G.plo[d] = geom->problo[d]; G.phi[d] = geom->probhi[d];
+        G.periodic[d] = (geom->lo_bc[d] == 0 && geom->hi_bc[d] == 0) ? 1 : 0;
+        G.dxi[slot][d] = 1.0 / geom->dx[d];
+    }
+    return CASTRO_AMD_OK;
+}
+
+// table entries [at, at + nboxes) from the caller's boxes; need_fab: a FAB of at least min_ncomp components that holds the valid box
+static int tr_boxes(int nboxes, const castro_amd_tracer_box* boxes, bool need_fab, int min_ncomp, std::vector<TrBoxDev>& tab, size_t at)
+{
+    for (int i = 0; i < nboxes; ++i) {
+        const castro_amd_tracer_box& b = boxes[i];
+        TrBoxDev& T = tab[at + (size_t)i];
+        for (int d = 0; d < 3; ++d) {
+            if (b.vhi[d] < b.vlo[d]) return CASTRO_AMD_ERR_ARG;
+            T.vlo[d] = b.vlo[d]; T.vhi[d] = b.vhi[d];
+        }
+        if (need_fab) {
+            if (!b.fab.p || b.fab.ncomp < min_ncomp || !fab_contains(&b.fab, b.vlo, b.vhi)) return CASTRO_AMD_ERR_ARG;
+            const DFab F = to_dfab(&b.fab);
+            T.F.p = F.p; T.F.sy = F.sy; T.F.sz = F.sz; T.F.sn = F.sn;
+            for (int d = 0; d < 3; ++d) { T.F.lo[d] = F.lo[d]; T.alo[d] = b.fab.lo[d]; T.ahi[d] = b.fab.hi[d]; }
+        }
+    }
+    return CASTRO_AMD_OK;
+}
+
+static void tr_zero(std::vector<TrBoxDev>& tab, TrGeom& G)
+{
+    if (!tab.empty()) std::memset((void*)tab.data(), 0, tab.size() * sizeof(TrBoxDev));
+    std::memset((void*)&G, 0, sizeof(TrGeom));
+}
+
+int castro_amd_tracer_advect_mf(castro_amd_ctx* c, int level, int nboxes, const castro_amd_tracer_box* boxes,
+                                const castro_amd_geom* geom, double dt, int ipass, const castro_amd_tracers* tracers, int* d_flags,
+                                void* stream)
+{
+    if (!c || level < 0 || nboxes < 0 || (nboxes > 0 && !boxes) || !tr_particles_ok(tracers) || !d_flags || (ipass != 0 && ipass != 1))
+        return CASTRO_AMD_ERR_ARG;
+    std::vector<TrBoxDev> tab((size_t)nboxes);
+    TrGeom G;
+    tr_zero(tab, G);
+    int rt = tr_geom(geom, 0, G);
+    if (rt != CASTRO_AMD_OK) return rt;
+    rt = tr_boxes(nboxes, boxes, true, UMZ + 1, tab, 0);
+    if (rt != CASTRO_AMD_OK) return rt;
+    hipSetDevice(c->device);
+    return launch_tracer_advect(nboxes, tab.data(), level, G, dt, ipass, *tracers, d_flags, &c->tr_tables, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_tracer_sample_mf(castro_amd_ctx* c, int level, int nboxes, const castro_amd_tracer_box* boxes,
+                                const castro_amd_geom* geom, int ncomps, const int* comps, const castro_amd_tracers* tracers,
+                                double* d_out, int* d_flags, void* stream)
+{
+    if (!c || level < 0 || nboxes < 0 || (nboxes > 0 && !boxes) || !tr_particles_ok(tracers) || !d_flags || !comps || ncomps < 1
+        || ncomps > CASTRO_AMD_NUM_STATE || (tracers->n > 0 && !d_out))
+        return CASTRO_AMD_ERR_ARG;
+    std::vector<TrBoxDev> tab((size_t)nboxes);
+    TrGeom G;
+    tr_zero(tab, G);
+    int rt = tr_geom(geom, 0, G);
+    if (rt != CASTRO_AMD_OK) return rt;
+    TrComps C;
+    std::memset((void*)&C, 0, sizeof(C));
+    C.n = ncomps;
+    int maxc = 0;
+    for (int q = 0; q < ncomps; ++q) {
+        if (comps[q] < 0) return CASTRO_AMD_ERR_ARG;
+        C.comp[q] = comps[q];
+        if (comps[q] > maxc) maxc = comps[q];
+    }
+    rt = tr_boxes(nboxes, boxes, true, maxc + 1, tab, 0);
+    if (rt != CASTRO_AMD_OK) return rt;
+    hipSetDevice(c->device);
+    return launch_tracer_sample(nboxes, tab.data(), level, G, C, *tracers, d_out, d_flags, &c->tr_tables, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_tracer_locate(castro_amd_ctx* c, int lev_min, int lev_max, int ngrow, int nlev, const int* nboxes_per_level,
+                             const castro_amd_tracer_box* boxes, const castro_amd_geom* geoms, const castro_amd_tracers* tracers,
+                             int* d_flags, void* stream)
+{
+    if (!c || nlev < 1 || nlev > CAD_TRACER_MAX_LEVELS || lev_min < 0 || lev_max < lev_min || lev_max >= nlev || ngrow < 0
+        || !nboxes_per_level || !geoms || !tr_particles_ok(tracers) || !d_flags)
+        return CASTRO_AMD_ERR_ARG;
+    long tot = 0;
+    for (int l = 0; l < nlev; ++l) {
+        if (nboxes_per_level[l] < 0) return CASTRO_AMD_ERR_ARG;
+        tot += nboxes_per_level[l];
+    }
+    if (tot > 0x7fffffffL || (tot > 0 && !boxes)) return CASTRO_AMD_ERR_ARG;
+    std::vector<TrBoxDev> tab((size_t)tot);
+    TrGeom G;
+    tr_zero(tab, G);
+    G.nlev = nlev;
+    size_t at = 0;
+    for (int l = 0; l < nlev; ++l) {
+        TrGeom Gl;
+        std::memset((void*)&Gl, 0, sizeof(Gl));
+        const int rg = tr_geom(&geoms[l], 0, Gl);
+        if (rg != CASTRO_AMD_OK) return rg;
+        for (int d = 0; d < 3; ++d) {
+            if (l == 0) { G.plo[d] = Gl.plo[d]; G.phi[d] = Gl.phi[d]; G.periodic[d] = Gl.periodic[d]; }
+            else if (G.plo[d] != Gl.plo[d] || G.phi[d] != Gl.phi[d] || G.periodic[d] != Gl.periodic[d]) return CASTRO_AMD_ERR_ARG;
+            G.dxi[l][d] = Gl.dxi[0][d];
+        }
+        G.start[l] = (int)at;
+        const int rt = tr_boxes(nboxes_per_level[l], boxes + at, false, 0, tab, at);
+        if (rt != CASTRO_AMD_OK) return rt;
+        at += (size_t)nboxes_per_level[l];
+    }
+    for (int l = nlev; l <= CAD_TRACER_MAX_LEVELS; ++l) G.start[l] = (int)at;
+    hipSetDevice(c->device);
+    return launch_tracer_locate((int)tot, tab.data(), G, lev_min, lev_max, ngrow, *tracers, d_flags, &c->tr_tables, (hipStream_t)stream,
+                                &c->prof);
+}
+
+int castro_amd_tracer_count_mf(castro_amd_ctx* c, int level, int nboxes, const castro_amd_tracer_box* count_boxes,
+                               const castro_amd_geom* geom, const castro_amd_tracers* tracers, void* stream)
+{
+    if (!c || level < 0 || nboxes < 0 || (nboxes > 0 && !count_boxes) || !tr_particles_ok(tracers)) return CASTRO_AMD_ERR_ARG;
+    std::vector<TrBoxDev> tab((size_t)nboxes);
+    TrGeom G;
+    tr_zero(tab, G);
+    int rt = tr_geom(geom, 0, G);
+    if (rt != CASTRO_AMD_OK) return rt;
+    for (int i = 0; i < nboxes; ++i) if (count_boxes[i].fab.ncomp != 1) return CASTRO_AMD_ERR_ARG;
+    rt = tr_boxes(nboxes, count_boxes, true, 1, tab, 0);
+    if (rt != CASTRO_AMD_OK) return rt;
+    hipSetDevice(c->device);
+    return launch_tracer_count(nboxes, tab.data(), level, G, *tracers, &c->tr_tables, (hipStream_t)stream, &c->prof);
 }
 
 int castro_amd_saxpy_fab(castro_amd_ctx* c, const castro_amd_fab* dst, double a, const castro_amd_fab* src, int ncomp,

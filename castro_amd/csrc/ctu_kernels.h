@@ -236,6 +236,21 @@ int launch_pointmass_delta(int nbox, const PmBoxDev* boxes, const int clo[3], do
                            hipStream_t stream, Profiler* prof);
 int launch_pointmass_apply(int nbox, const PmBoxDev* boxes, const int clo[3], const double* d_delta, double* d_mass,
                            TableCache* tables, hipStream_t stream, Profiler* prof);
+// tracer particles (tracer_kernels.hip).  One box of a level: the FAB (count: its int32 zones behind F.p), the box of the array
+// [alo, ahi] and the valid box [vlo, vhi].  Compared byte by byte like the tables above: fill over zeroed storage.
+// TrGeom: advect / sample / count read dxi[0] (the level's own), locate dxi[l] and the boxes tab[start[l], start[l + 1]) of level l
+#define CAD_TRACER_MAX_LEVELS 16
+struct TrBoxDev { DFab F; int alo[3], ahi[3], vlo[3], vhi[3]; };
+struct TrGeom { double plo[3], phi[3]; int periodic[3]; int nlev; int start[CAD_TRACER_MAX_LEVELS + 1]; double dxi[CAD_TRACER_MAX_LEVELS][3]; };
+struct TrComps { int n; int comp[CASTRO_AMD_NUM_STATE]; };
+int launch_tracer_advect(int nbox, const TrBoxDev* boxes, int level, const TrGeom& G, double dt, int ipass, const castro_amd_tracers& T,
+                         int* d_flags, TableCache* tables, hipStream_t stream, Profiler* prof);
+int launch_tracer_sample(int nbox, const TrBoxDev* boxes, int level, const TrGeom& G, const TrComps& C, const castro_amd_tracers& T,
+                         double* d_out, int* d_flags, TableCache* tables, hipStream_t stream, Profiler* prof);
+int launch_tracer_locate(int nbox, const TrBoxDev* boxes, const TrGeom& G, int lev_min, int lev_max, int ngrow,
+                         const castro_amd_tracers& T, int* d_flags, TableCache* tables, hipStream_t stream, Profiler* prof);
+int launch_tracer_count(int nbox, const TrBoxDev* boxes, int level, const TrGeom& G, const castro_amd_tracers& T, TableCache* tables,
+                        hipStream_t stream, Profiler* prof);
 // the gravity sources with a per-zone vector: GO / GN are 3-component FABs with one ghost zone around [lo, hi] (type 4)
 int launch_old_grav_source_gfab(const DFab& U, const DFab& SRC, const int lo[3], const int hi[3], const DFab& GO,
                                 int type, double dt, hipStream_t stream, Profiler* prof);

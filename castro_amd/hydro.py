@@ -298,6 +298,63 @@ class HipHydro:
         L.check(self.lib.castro_amd_pointmass_apply_mf(self.h, n, arr, C.byref(pm), C.byref(geom), C.c_void_p(delta.data_ptr()),
                                                        C.c_void_p(mass.data_ptr()), _stream_ptr(stream)), "pointmass_apply_mf")
 
+    # ---- tracer particles (castro.do_tracer_particles; castro_amd/particles.py) ------------------------------------------
+    @staticmethod
+    def make_tracer_boxes(specs):
+        """ctypes array of castro_amd_tracer_box from (vlo, vhi, (fab, box) or None): the FAB of a box of a level (None: the
+        valid box alone, for tracer_locate; an int32 tensor: a count FAB) and the valid box inside it."""
+        arr = (L.TracerBox * max(len(specs), 1))()
+        for i, (vlo, vhi, fab) in enumerate(specs):
+            if fab is None:
+                arr[i].fab = L.fab_desc(None, vlo, vhi, 0)
+            elif fab[0].dtype == torch.int32:
+                t, (lo, hi) = fab
+                assert t.is_contiguous() and tuple(t.shape[-3:]) == tuple(hi[d] - lo[d] + 1 for d in (2, 1, 0))
+                arr[i].fab = L.fab_desc(t.data_ptr(), lo, hi, 1)
+            else:
+                arr[i].fab = L.fab_of(fab[0], *fab[1])
+            arr[i].vlo, arr[i].vhi = L.i3(vlo), L.i3(vhi)
+        return arr, len(specs), [s[2][0] for s in specs if s[2] is not None]      # the tensors stay alive with the table
+
+    @staticmethod
+    def _tracers(tracers):
+        return tracers if isinstance(tracers, L.Tracers) else tracers.struct()
+
+    def tracer_advect(self, level, boxes, geom, dt, ipass, tracers, flags, stream=None, ng=None):
+        """castro_amd_tracer_advect_mf: pass `ipass` of AdvectWithUcc over the particles of `level`; boxes: make_tracer_boxes of
+        the half-time state; tracers: an _lib.Tracers (or a TracerParticles); flags: two device int32 (clamped, lost).  ng: the
+        ghost zones the reference's FillPatch asks for -- not needed here, the stencil is clamped to the whole array"""
+        tracers = self._tracers(tracers)
+        L.check(self.lib.castro_amd_tracer_advect_mf(self.h, int(level), boxes[1], boxes[0], C.byref(geom), float(dt), int(ipass),
+                                                     C.byref(tracers), C.c_void_p(flags.data_ptr()), _stream_ptr(stream)),
+                "tracer_advect_mf")
+
+    def tracer_locate(self, lev_min, lev_max, ngrow, level_boxes, geoms, tracers, flags, stream=None):
+        """castro_amd_tracer_locate: Redistribute(lev_min, lev_max, ngrow); level_boxes[l]: [(vlo, vhi)] of level l, geoms[l] its
+        geometry"""
+        nlev, tracers = len(level_boxes), self._tracers(tracers)
+        arr, _, _ = self.make_tracer_boxes([(lo, hi, None) for bl in level_boxes for lo, hi in bl])
+        cnt = (C.c_int * nlev)(*[len(bl) for bl in level_boxes])
+        garr = (L.Geom * nlev)(*geoms)
+        L.check(self.lib.castro_amd_tracer_locate(self.h, int(lev_min), int(lev_max), int(ngrow), nlev, cnt, arr, garr,
+                                                  C.byref(tracers), C.c_void_p(flags.data_ptr()), _stream_ptr(stream)),
+                "tracer_locate")
+
+    def tracer_sample(self, level, boxes, geom, comps, tracers, out, flags, stream=None):
+        """castro_amd_tracer_sample_mf: components `comps` of the FABs of `boxes` at the particles of `level` into
+        out[c, particle] (a device tensor (len(comps), n))"""
+        carr, tracers = (C.c_int * len(comps))(*[int(x) for x in comps]), self._tracers(tracers)
+        assert out.is_contiguous() and tuple(out.shape) == (len(comps), int(tracers.n))
+        L.check(self.lib.castro_amd_tracer_sample_mf(self.h, int(level), boxes[1], boxes[0], C.byref(geom), len(comps), carr,
+                                                     C.byref(tracers), C.c_void_p(out.data_ptr()), C.c_void_p(flags.data_ptr()),
+                                                     _stream_ptr(stream)), "tracer_sample_mf")
+
+    def tracer_count(self, level, boxes, geom, tracers, stream=None):
+        """castro_amd_tracer_count_mf: += 1 per particle of `level` in its zone of the int32 FABs of `boxes` (make_tracer_boxes)"""
+        tracers = self._tracers(tracers)
+        L.check(self.lib.castro_amd_tracer_count_mf(self.h, int(level), boxes[1], boxes[0], C.byref(geom), C.byref(tracers),
+                                                    _stream_ptr(stream)), "tracer_count_mf")
+
     def sources_mf_g(self, stage, boxes, grav_old, grav_new, grav_source_type, rot, geom, params, dt, ntimes=1, stream=None,
                      sponge=None):
         """castro_amd_sources_mf_g: sources_mf with the gravity of box i read from grav_old[i] / grav_new[i] (make_grav_fabs).

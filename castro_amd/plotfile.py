@@ -12,6 +12,10 @@ Reference behaviour restated:
 With castro.use_point_mass the plotfile directory also holds the file `point_mass`: the value as one line, %.17g
 (Castro_io.cpp:1137-1150); the readers return it as "point_mass" (None when the file is absent).
 
+With tracer particles the derived field `particle_count` (ParticleDerive, Source/particles/CastroParticles.cpp:125-133: the
+number of valid particles of a level in each zone of that level) is written when it is asked for by name; it is not part of
+the default field list.
+
 The field data are produced on the device (state copy + castro_amd_derive_fab); this module only does the
 host-side file layout.  One rank = one box = one Cell_D file; rank 0 writes Header and Cell_H.
 """
@@ -55,9 +59,22 @@ def read_point_mass(dirname):
         return float(f.read().split()[0])
 
 
-def plot_data(castro, derive=None):
+PARTICLE_COUNT = "particle_count"
+
+
+def particle_counts(tracers, derive, level, box_list, geom):
+    """the particle_count field of the boxes of a level (a list of (nz, ny, nx) tensors), or None when `derive` does not ask
+    for it; asking for it without tracer particles is an error, as an unknown derive name is"""
+    if derive is None or PARTICLE_COUNT not in derive:
+        return None
+    if tracers is None:
+        raise ValueError("particle_count needs tracer particles (tracers=castro_amd.TracerParticles(...))")
+    return tracers.count_level(level, box_list, geom)
+
+
+def plot_data(castro, derive=None, particle_count=None):
     """(names, tensor (ncomp, nz, ny, nx)) of this rank's box: the plotMF of Castro_io.cpp:1099-1126
-    (state components first, then derived fields, nGrow = 0)."""
+    (state components first, then derived fields, nGrow = 0).  particle_count: that field of this box (particle_counts)."""
     import torch
     derive = list(DERIVE_NAMES if derive is None else derive)
     names = STATE_NAMES + derive
@@ -72,13 +89,17 @@ def plot_data(castro, derive=None):
     center = [0.5 * (castro.geom.problo[d] + castro.geom.probhi[d]) for d in range(3)] \
         if getattr(castro, "center", None) is None else castro.center
     for m, name in enumerate(derive):
+        if name == PARTICLE_COUNT:
+            out[8 + m] = particle_count
+            continue
         castro.hydro.derive(name, S, castro.gbox, out, (lo, hi), 8 + m, lo, hi, castro.geom, castro.params, center)
     return names, out
 
 
 def write_plotfile(dirname, castro, derive=None, job_info=None):
     """Write `dirname`/{Header, job_info, Level_0/Cell_H, Level_0/Cell_D_nnnnn}."""
-    names, data = plot_data(castro, derive)
+    cnt = particle_counts(getattr(castro, "tracers", None), derive, 0, [castro.bx], castro.geom)
+    names, data = plot_data(castro, derive, particle_count=None if cnt is None else cnt[0])
     comm = castro.comm
     rank, size = comm.rank, comm.size
     arr = data.cpu().numpy() if hasattr(data, "cpu") else np.asarray(data)
@@ -173,8 +194,9 @@ def write_plotfile_amr(dirname, amr, derive=None):
     for l, lev in enumerate(levels):
         lev.alpha = 1.0              # ghost zones for the stencil derives: parent data at the current (new) time
         fabs = []
-        for b in lev.boxes:
-            names, data = plot_data(b, derive)
+        cnt = particle_counts(getattr(amr, "tracers", None), derive, l, lev.box_list(), lev.geom)
+        for g, b in enumerate(lev.boxes):
+            names, data = plot_data(b, derive, particle_count=None if cnt is None else cnt[g])
             fabs.append(data.cpu().numpy() if hasattr(data, "cpu") else np.asarray(data))
         per.append(fabs)
     ncomp = per[0][0].shape[0]

@@ -63,7 +63,9 @@ extern "C" {
  *      castro_amd_add_pointmass_fab / _mf, castro_amd_pointmass_delta_mf, castro_amd_pointmass_apply_mf (structs
  *      castro_amd_pointmass_params, castro_amd_pointmass_box);
  *      castro_amd_fluxreg_to_flux_fab, CASTRO_AMD_OP_FLUXREG_TO_FLUX, CASTRO_AMD_SOURCES_AFTER_REFLUX (stage 1 | that flag of
- *      castro_amd_sources_mf / _ex / _g / _opts).
+ *      castro_amd_sources_mf / _ex / _g / _opts);
+ *      castro_amd_tracer_advect_mf, castro_amd_tracer_locate, castro_amd_tracer_sample_mf, castro_amd_tracer_count_mf (structs
+ *      castro_amd_tracers, castro_amd_tracer_box).
  * A caller checks `castro_amd_abi_version() == CASTRO_AMD_ABI_VERSION` once after loading the library; a mismatch means
  * the library was built from another revision of this header (a 0.2 caller with 2-double vectors would be written 8 bytes
  * out of bounds by a 0.3 library). */
@@ -719,6 +721,62 @@ int castro_amd_pointmass_delta_mf(castro_amd_ctx *ctx, int nboxes, const castro_
 int castro_amd_pointmass_apply_mf(castro_amd_ctx *ctx, int nboxes, const castro_amd_pointmass_box *boxes,
                                   const castro_amd_pointmass_params *pm, const castro_amd_geom *geom, const double *d_delta,
                                   double *d_point_mass, void *stream);
+
+/* Tracer particles (castro.do_tracer_particles; Source/particles/CastroParticles.cpp).  The container is AMReX's
+ * AmrTracerParticleContainer [3P, not in the reference tree]: AdvectWithUcc, Redistribute and the cloud-in-cell interpolation
+ * are restated from the published algorithm and are NOT pinned against an AMReX build.  3-D Cartesian
+ * (CASTRO_AMD_ERR_UNSUPPORTED unless geom->coord == 0).  The particles are the caller's device arrays, one entry per particle, in
+ * an order that never changes; none of the four calls allocates particle memory or synchronises.  The box tables are kept on the
+ * device by content like those of the point mass.  n == 0 launches nothing and returns CASTRO_AMD_OK.
+ *   id <= 0: an invalid particle -- never moved, sampled, counted or located again.
+ *   level, grid: the level and the index of the box (in the level's table) where the particle lives, set by
+ *                castro_amd_tracer_locate.
+ *   r0..r2: the saved position between the two advection passes, the velocity of the corrector afterwards.
+ *   cpu is not read (may be NULL).
+ * d_flags: two device int32.  [0] += 1 for every particle and pass whose stencil had to be clamped to the array it reads (or
+ * whose grid is no box of the table: that particle is skipped); [1] += 1 for every particle castro_amd_tracer_locate finds in no
+ * box.  No input makes a call read or write outside a FAB; the caller reads the flags when it reads particle data. */
+typedef struct castro_amd_tracers {
+    long long n;
+    double *x, *y, *z;
+    double *r0, *r1, *r2;
+    int *id, *cpu, *level, *grid;
+} castro_amd_tracers;
+/* One box of a level: a FAB with its ghost zones and the valid box inside it.  castro_amd_tracer_locate reads the valid box
+ * only (fab.p may be NULL); castro_amd_tracer_count_mf takes fab.p as the address of int32 zones, one component. */
+typedef struct castro_amd_tracer_box {
+    castro_amd_fab fab;
+    int vlo[3], vhi[3];
+} castro_amd_tracer_box;
+/* One pass (ipass = 0, 1) of AdvectWithUcc over the valid particles with level == `level`; boxes[b].fab is the state at
+ * time + dt / 2 of box b (at least 4 components: URHO, UMX..UMZ), ghost zones filled.  The velocity of a stencil corner is
+ * mom * (1.0 / rho) of that zone (CastroParticles.cpp:271-274), interpolated cell-centred cloud-in-cell in the index space of
+ * the level:  l = (pos - problo) * (1 / dx) - 0.5, i = floor(l), f = l - i, s = {1 - f, f},
+ *             val = sum over kk, jj, ii (in that nesting) of sx[ii] * sy[jj] * sz[kk] * data(i + ii, j + jj, k + kk).
+ *   pass 0: r = pos; pos += 0.5 * dt * v          pass 1: pos = r + dt * v; r = v
+ * Both numerics builds give the same bits (the file is compiled without contraction). */
+int castro_amd_tracer_advect_mf(castro_amd_ctx *ctx, int level, int nboxes, const castro_amd_tracer_box *boxes,
+                                const castro_amd_geom *geom, double dt, int ipass, const castro_amd_tracers *tracers,
+                                int *d_flags, void *stream);
+/* Redistribute(lev_min, lev_max, ngrow) over the valid particles with level >= lev_min.  boxes: the tables of levels
+ * 0 .. nlev - 1 one after the other (nboxes_per_level[l] entries each), geoms[l] the geometry of level l (one problo / probhi and
+ * boundary types for all).  Per particle: wrap into [problo, probhi) in every periodic direction (a result equal to probhi
+ * becomes problo); outside the domain in any other direction: id = -id; else the first level from lev_max down to lev_min with
+ * a valid box over the cell floor((pos - problo) * (1 / dx)) -- the lowest box index -- takes it; else, with ngrow > 0, the
+ * lowest-index box of lev_min whose valid box grown by ngrow holds the cell; else flags[1] += 1 and level / grid stay. */
+int castro_amd_tracer_locate(castro_amd_ctx *ctx, int lev_min, int lev_max, int ngrow, int nlev, const int *nboxes_per_level,
+                             const castro_amd_tracer_box *boxes, const castro_amd_geom *geoms, const castro_amd_tracers *tracers,
+                             int *d_flags, void *stream);
+/* The cloud-in-cell interpolation above of components comps[0 .. ncomps) of boxes[b].fab at the positions of the valid
+ * particles with level == `level`: d_out[c * n + particle].  Entries of other particles are not written. */
+int castro_amd_tracer_sample_mf(castro_amd_ctx *ctx, int level, int nboxes, const castro_amd_tracer_box *boxes,
+                                const castro_amd_geom *geom, int ncomps, const int *comps, const castro_amd_tracers *tracers,
+                                double *d_out, int *d_flags, void *stream);
+/* ParticleDerive: += 1 (32-bit integer atomics: the sums do not depend on the order) in the zone
+ * floor((pos - problo) * (1 / dx)) of the int32 FAB count_boxes[grid] for every valid particle with level == `level`; a zone
+ * outside that FAB is dropped.  The caller zeroes the FABs and converts them afterwards. */
+int castro_amd_tracer_count_mf(castro_amd_ctx *ctx, int level, int nboxes, const castro_amd_tracer_box *count_boxes,
+                               const castro_amd_geom *geom, const castro_amd_tracers *tracers, void *stream);
 
 /* Two-level AMR building blocks, refinement ratio 2 (first slice).  The reference calls AMReX for
  * all of these [3P, not in the reference tree]; the arithmetic is restated from the published descriptions and is
