@@ -77,6 +77,7 @@ EXPORTED_SYMBOLS = (
     "castro_amd_ext_bc_fill_fab",
     "castro_amd_fluxreg_to_flux_fab",
     "castro_amd_tracer_advect_mf", "castro_amd_tracer_locate", "castro_amd_tracer_sample_mf", "castro_amd_tracer_count_mf",
+    "castro_amd_tracer_migrate_count", "castro_amd_tracer_migrate_pack", "castro_amd_tracer_unpack",
 )
 
 
@@ -343,6 +344,9 @@ def pointmass_cube(center, geom):
     return tuple(i - 2 for i in icen), tuple(i + 1 for i in icen)
 
 
+TRACER_MAX_RANKS = 256          # CASTRO_AMD_TRACER_MAX_RANKS
+
+
 class Tracers(C.Structure):
     """castro_amd_tracers: the particle arrays on the device, one entry per particle"""
     _fields_ = [("n", C.c_longlong), ("x", C.c_void_p), ("y", C.c_void_p), ("z", C.c_void_p), ("r0", C.c_void_p),
@@ -550,6 +554,13 @@ def load(numerics=None):
         L.castro_amd_tracer_sample_mf.argtypes = [C.c_void_p, C.c_int, C.c_int, PB, C.POINTER(Geom), C.c_int, C.POINTER(C.c_int), PT,
                                                   C.c_void_p, C.c_void_p, C.c_void_p]
         L.castro_amd_tracer_count_mf.argtypes = [C.c_void_p, C.c_int, C.c_int, PB, C.POINTER(Geom), PT, C.c_void_p]
+    if hasattr(L, "castro_amd_tracer_unpack"):              # absent from A/B builds of revisions before the migration
+        PT = C.POINTER(Tracers)
+        L.castro_amd_tracer_migrate_count.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int,
+                                                      PT, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.castro_amd_tracer_migrate_pack.argtypes = [C.c_void_p, C.c_int, C.c_int, PT, C.c_void_p, PT, C.c_void_p, C.c_longlong,
+                                                     C.c_void_p]
+        L.castro_amd_tracer_unpack.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, PT, C.c_longlong, C.c_void_p]
     L.castro_amd_step_control.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_double, C.c_double,
                                           C.c_double, C.c_int, C.c_void_p]
     L.castro_amd_clean_state_fab.argtypes = [C.c_void_p, PF, I3, I3, C.POINTER(Params), C.c_int, C.c_void_p]

@@ -683,12 +683,13 @@ class _Level:
     # ---- tracer particles (castro_amd/particles.py) -----------------------------------------------------------------------
     def _tracer_boxes(self, which):
         """the make_tracer_boxes table of S_half_b / S_new_b of the boxes of the level, in box order (a particle's `grid`)"""
-        key = (which,) + tuple(getattr(b, which).data_ptr() for b in self.boxes)
+        key = (which,) + tuple(getattr(b, which).data_ptr() if b.owned else 0 for b in self.boxes)     # no FAB on another rank's box
         tabs = self.__dict__.setdefault("_tracer_tabs", {})
         if key not in tabs:
             if len(tabs) > 8:
                 tabs.clear()
-            tabs[key] = self.hydro.make_tracer_boxes([(b.lo, b.hi, (getattr(b, which), b.gbox)) for b in self.boxes])
+            tabs[key] = self.hydro.make_tracer_boxes([(b.lo, b.hi, (getattr(b, which), b.gbox) if b.owned else None)
+                                                      for b in self.boxes])
         return tabs[key]
 
     def _advance_particles(self, time, dt):
@@ -864,7 +865,7 @@ class CastroAmr:
                  update_sources_after_reflux=False, tracers=None):
         """tracers: a castro_amd.TracerParticles (castro.do_tracer_particles = 1) spanning the levels: advected at the end of
         every level's advance, redistributed and timestamped at the end of its post_timestep and after every regrid, as in
-        castro_amd.Castro; one rank only.
+        castro_amd.Castro; with the boxes dealt over ranks every rank holds the particles of its boxes (castro_amd/particles.py).
         update_sources_after_reflux: castro.update_sources_after_reflux.  True is the reference's default (1) and the setting
         that follows it: after the reflux of post_timestep the flux registers are added to the coarse level's fluxes (mass
         fluxes = their density component) and both levels take their new-time sources out of S_new, clean it, and evaluate and
@@ -934,8 +935,6 @@ class CastroAmr:
         from .castro import SingleComm
         self.comm = comm if comm is not None else SingleComm()
         self.rank, self.nranks = self.comm.rank, self.comm.size
-        if tracers is not None and self.nranks > 1:
-            raise NotImplementedError("tracer particles on more than one rank need the migration between ranks, which is not built")
         self.tracers = tracers
         self._mk = (lambda: None) if make_hydro is None else make_hydro
         self.params = params if params is not None else (make_params() if make_params else L.default_params())
@@ -952,6 +951,9 @@ class CastroAmr:
         # boxes of a level whose hydro updates may be in flight at once (device backend); CASTRO_AMD_BOX_STREAMS overrides
         self.box_streams = int(os.environ.get("CASTRO_AMD_BOX_STREAMS", box_streams))
         self._hydros = []
+        if tracers is not None:
+            from .particles import need_migration
+            need_migration(self._hydro_for(0), self.comm)   # NotImplementedError on more than one rank without the migration
         if base_grid is None or tuple(base_grid) == (1, 1, 1):
             base = Castro(n_cell, hydro=self._hydro_for(0), alloc=(self.rank == 0), **self._kw)
             base.owner = 0
@@ -1528,7 +1530,8 @@ class CastroAmr:
 
     def _particles_redistribute(self, lev_min, ngrow=0):
         boxes, geoms = self._tracer_levels()
-        self.tracers.redistribute(boxes, geoms, lev_min, len(self.lev) - 1, ngrow)
+        owners = [[b.owner for b in lev.boxes] for lev in self.lev] if self.nranks > 1 else None
+        self.tracers.redistribute(boxes, geoms, lev_min, len(self.lev) - 1, ngrow, owners=owners)
 
     def _particles_post_timestep(self, l, iteration, t_new, alpha_new):
         """the particle part of Castro::post_timestep of level l (Castro.cpp:1982-1997), under the reference's condition

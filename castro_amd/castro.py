@@ -265,7 +265,7 @@ class Castro:
                  tracers=None):
         """tracers: a castro_amd.TracerParticles (castro.do_tracer_particles = 1): passive particles advected with the fluid
         velocity at the end of every advance (Castro::advance_particles), redistributed and -- with a timestamp_dir -- sampled
-        after every step; one rank only.  The object owns the particle arrays; this box gets one more state array for the
+        after every step; on more than one rank every rank holds the particles of its box (castro_amd/particles.py).  The object owns the particle arrays; this box gets one more state array for the
         half-time state.  Steps then go through step(): host_free_ok() is False.
         ext_bc: _lib.make_ext_bc(zl="hse", ...) turns on the boundary overrides of the state fill (ca_statefill's second half:
         castro.*_ext_bc_type = HSE on Inflow faces, castro.fill_ambient_bc beyond Outflow faces); const_grav and the ambient state
@@ -298,8 +298,6 @@ class Castro:
         self.n_cell = tuple(int(x) for x in n_cell)
         self.owned = bool(alloc)
         self.comm = comm if comm is not None else SingleComm()
-        if tracers is not None and self.comm.size > 1:
-            raise NotImplementedError("tracer particles on more than one rank need the migration between ranks, which is not built")
         try:
             import weakref
             if getattr(self.comm, "_users", None) is None:
@@ -312,6 +310,9 @@ class Castro:
             dev = torch.cuda.current_device() if torch.cuda.is_available() else 0
             hydro = HipHydro(dev, numerics=numerics)          # raises without a GPU: no CPU fallback
         self.hydro = hydro
+        if tracers is not None:
+            from .particles import need_migration
+            need_migration(hydro, self.comm)        # NotImplementedError on more than one rank without the migration operations
         self.params = params if params is not None else (make_params() if make_params else L.default_params())
         self.geom = (hydro.make_geom if hasattr(hydro, "make_geom") else L.make_geom)(
             self.n_cell, prob_lo, prob_hi, lo_bc, hi_bc)
@@ -885,16 +886,33 @@ class Castro:
         return True
 
     # ---- tracer particles (Source/particles/CastroParticles.cpp; castro_amd/particles.py) -------------------------------------
+    def _rank_boxes(self):
+        """the boxes of all ranks in rank order (the decomposition of the constructor): a particle's `grid` is its owner's rank"""
+        if self.comm.size == 1:
+            return [(self.lo, self.hi)]
+        out = []
+        for r in range(self.comm.size):
+            co = (r % self.grid[0], (r // self.grid[0]) % self.grid[1], r // (self.grid[0] * self.grid[1]))
+            nloc = [self.n_cell[d] // self.grid[d] for d in range(3)]
+            out.append((tuple(co[d] * nloc[d] for d in range(3)), tuple((co[d] + 1) * nloc[d] - 1 for d in range(3))))
+        return out
+
     def _tracer_levels(self):
-        """([boxes of level l], [geometry of level l]) as Redistribute takes them: one level, this box"""
-        return [[(self.lo, self.hi)]], [self.geom]
+        """([boxes of level l], [geometry of level l]) as Redistribute takes them: one level, the boxes of all ranks"""
+        return [self._rank_boxes()], [self.geom]
+
+    def _tracer_owners(self):
+        """the owners Redistribute takes on more than one rank: box r is rank r's"""
+        return [list(range(self.comm.size))] if self.comm.size > 1 else None
 
     def _tracer_boxes(self, which):
-        """the make_tracer_boxes table of S_half_b / S_new_b (the two state buffers swap roles: a table per buffer)"""
+        """the make_tracer_boxes table of S_half_b / S_new_b (the two state buffers swap roles: a table per buffer); the boxes of
+        the other ranks carry no FAB"""
         S = getattr(self, which)
         tabs = self.__dict__.setdefault("_tracer_tabs", {})
         if S.data_ptr() not in tabs:
-            tabs[S.data_ptr()] = self.hydro.make_tracer_boxes([(self.lo, self.hi, (S, self.gbox))])
+            tabs[S.data_ptr()] = self.hydro.make_tracer_boxes([(lo, hi, (S, self.gbox) if r == self.comm.rank else None)
+                                                               for r, (lo, hi) in enumerate(self._rank_boxes())])
         return tabs[S.data_ptr()]
 
     def _init_particles(self):
@@ -903,7 +921,7 @@ class Castro:
         if tr is None:
             return
         tr.init_particles(self.geom)
-        tr.redistribute(*self._tracer_levels(), 0)
+        tr.redistribute(*self._tracer_levels(), 0, owners=self._tracer_owners())
         tr.check_flags()
 
     def _advance_particles(self, time, dt):
@@ -925,7 +943,7 @@ class Castro:
         if tr is None:
             return
         boxes, geoms = self._tracer_levels()
-        tr.redistribute(boxes, geoms, 0)
+        tr.redistribute(boxes, geoms, 0, owners=self._tracer_owners())
         if tr.timestamp_dir is not None:
             self.expand_state(self.S_new_b)         # ghost zones only: the next advance fills them again from the same zones
             tr.timestamp(0, self.time, lambda l: self._tracer_boxes("S_new_b"), geoms)

@@ -42,12 +42,86 @@ struct Box3 { int lo[3]; int n[3]; };
 // Every stage is zone-local, so running the whole chain per zone is identical to the
 // reference's stage-by-stage sweeps.
 // ---------------------------------------------------------------------------------------
-// REDUCE: also return [min dx/(c+|u|) of the CLEANED state, min density of the RAW state]
+// Up to CLEAN_BOXES_MAX regions in one launch; region r owns threads [start[r], start[r+1]).  The ONE compiled copy of the plain
+// clean sweep: castro_amd_clean_state_fab is a table of one region, CASTRO_AMD_OP_CLEAN of castro_amd_fab_ops_p a table of many,
+// so a level cleaned box by box and one cleaned through an operation table get the same bits in the `contract` build too
+// (two compiled copies of clean_zone may contract differently).
+#define CLEAN_BOXES_MAX 32
+struct CleanBoxes { int n; int ntimes[CLEAN_BOXES_MAX]; long start[CLEAN_BOXES_MAX + 1]; DFab U[CLEAN_BOXES_MAX]; Box3 b[CLEAN_BOXES_MAX]; };
+static_assert(sizeof(CleanBoxes) + sizeof(DevParams) <= 4096, "k_clean_state: the by-value table must fit the 4 KB of kernel arguments");
+
+__global__ void __launch_bounds__(256) k_clean_state(CleanBoxes T, DevParams P)
+{
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= T.start[T.n]) return;
+    int r = 0;
+    while (tid >= T.start[r + 1]) ++r;
+    const DFab U = T.U[r];
+    const Box3 b = T.b[r];
+    const long t = tid - T.start[r];
+    const int i = b.lo[0] + (int)(t % b.n[0]);
+    const long rr = t / b.n[0];
+    const int j = b.lo[1] + (int)(rr % b.n[1]);
+    const int k = b.lo[2] + (int)(rr / b.n[1]);
+    const long c = fidx(U, i, j, k, 0);
+    double rho = U.p[c + U.sn * URHO];
+    double mx = U.p[c + U.sn * UMX];
+    double my = U.p[c + U.sn * UMY];
+    double mz = U.p[c + U.sn * UMZ];
+    double eden = U.p[c + U.sn * UEDEN];
+    double eint = U.p[c + U.sn * UEINT];
+    double temp = U.p[c + U.sn * UTEMP];
+    double rX = U.p[c + U.sn * UFS];
+
+    clean_zone(P, T.ntimes[r], rho, mx, my, mz, eden, eint, temp, rX);
+
+    U.p[c + U.sn * URHO] = rho;
+    U.p[c + U.sn * UMX] = mx;
+    U.p[c + U.sn * UMY] = my;
+    U.p[c + U.sn * UMZ] = mz;
+    U.p[c + U.sn * UEDEN] = eden;
+    U.p[c + U.sn * UEINT] = eint;
+    U.p[c + U.sn * UTEMP] = temp;
+    U.p[c + U.sn * UFS] = rX;
+}
+
+// clean_state x ntimes[r] on [lo + 3 r, hi + 3 r] of U[r], r < nbox: one launch per CLEAN_BOXES_MAX non-empty regions
+int launch_clean_state_boxes(int nbox, const DFab* U, const int* lo, const int* hi, const int* ntimes, const DevParams& P,
+                             hipStream_t stream, Profiler* prof)
+{
+    int done = 0;
+    while (done < nbox) {
+        CleanBoxes T;
+        T.n = 0;
+        T.start[0] = 0;
+        for (; done < nbox && T.n < CLEAN_BOXES_MAX; ++done) {
+            Box3 b;
+            long n = 1;
+            for (int d = 0; d < 3; ++d) { b.lo[d] = lo[3 * done + d]; b.n[d] = hi[3 * done + d] - lo[3 * done + d] + 1; n *= b.n[d] > 0 ? b.n[d] : 0; }
+            if (n <= 0 || ntimes[done] <= 0) continue;          // nothing to clean
+            T.U[T.n] = U[done]; T.b[T.n] = b; T.ntimes[T.n] = ntimes[done];
+            T.start[T.n + 1] = T.start[T.n] + n;
+            ++T.n;
+        }
+        if (T.n == 0) continue;
+        prof_begin(prof, "k_clean_state", stream);
+        hipLaunchKernelGGL(k_clean_state, dim3((unsigned)((T.start[T.n] + 255) / 256)), dim3(256), 0, stream, T, P);
+        prof_end(prof, stream);
+    }
+    return launch_status();
+}
+
+int launch_clean_state(const DFab& U, const int lo[3], const int hi[3], const DevParams& P, int ntimes,
+                       hipStream_t stream, Profiler* prof)
+{
+    return launch_clean_state_boxes(1, &U, lo, hi, &ntimes, P, stream, prof);
+}
+
+// The same sweep with the reductions of the advance: [min dx/(c+|u|) of the CLEANED state, min density of the RAW state]
 // (Castro::estdt_cfl, timestep.cpp:31-140, and S_new.min(URHO), Castro_advance_ctu.cpp:168)
 // through one atomic pair per block.  Grid-stride so the number of atomics stays small.
-template <bool REDUCE>
-__global__ void __launch_bounds__(256) k_clean_state(DFab U, Box3 b, DevParams P, int ntimes,
-                                                     double dx0, double dx1, double dx2, double* red)
+__global__ void __launch_bounds__(256) k_clean_state_reduce(DFab U, Box3 b, DevParams P, int ntimes,
+                                                            double dx0, double dx1, double dx2, double* red)
 {
     double dtmin = 1.e200, rmin_raw = 1.e300, dtmin1 = 1.e200;
     const long total = (long)b.n[0] * b.n[1] * b.n[2];
@@ -65,16 +139,12 @@ __global__ void __launch_bounds__(256) k_clean_state(DFab U, Box3 b, DevParams P
     double eint = U.p[c + U.sn * UEINT];
     double temp = U.p[c + U.sn * UTEMP];
     double rX = U.p[c + U.sn * UFS];
-    if (REDUCE) rmin_raw = fmin(rmin_raw, nan_guard(rho));
+    rmin_raw = fmin(rmin_raw, nan_guard(rho));
 
-    if (REDUCE) {
-        double d1, d2;
-        clean_zone_dt(P, ntimes, dx0, dx1, dx2, rho, mx, my, mz, eden, eint, temp, rX, d1, d2);
-        dtmin1 = fmin(dtmin1, d1);
-        dtmin = fmin(dtmin, d2);
-    } else {
-        clean_zone(P, ntimes, rho, mx, my, mz, eden, eint, temp, rX);
-    }
+    double d1, d2;
+    clean_zone_dt(P, ntimes, dx0, dx1, dx2, rho, mx, my, mz, eden, eint, temp, rX, d1, d2);
+    dtmin1 = fmin(dtmin1, d1);
+    dtmin = fmin(dtmin, d2);
 
     U.p[c + U.sn * URHO] = rho;
     U.p[c + U.sn * UMX] = mx;
@@ -86,21 +156,7 @@ __global__ void __launch_bounds__(256) k_clean_state(DFab U, Box3 b, DevParams P
     U.p[c + U.sn * UFS] = rX;
 
     }
-    if (REDUCE) block_min3_atomic(dtmin, rmin_raw, dtmin1, red);
-}
-
-int launch_clean_state(const DFab& U, const int lo[3], const int hi[3], const DevParams& P, int ntimes,
-                       hipStream_t stream, Profiler* prof)
-{
-    Box3 b;
-    long n = 1;
-    for (int d = 0; d < 3; ++d) { b.lo[d] = lo[d]; b.n[d] = hi[d] - lo[d] + 1; n *= b.n[d]; }
-    if (n <= 0) return 0;
-    prof_begin(prof, "k_clean_state", stream);
-    hipLaunchKernelGGL(k_clean_state<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, U, b, P, ntimes,
-                       0.0, 0.0, 0.0, (double*)nullptr);
-    prof_end(prof, stream);
-    return launch_status();
+    block_min3_atomic(dtmin, rmin_raw, dtmin1, red);
 }
 
 int launch_clean_state_reduce(const DFab& U, const int lo[3], const int hi[3], const DevGeom& g, const DevParams& P,
@@ -113,7 +169,7 @@ int launch_clean_state_reduce(const DFab& U, const int lo[3], const int hi[3], c
     long nb = (n + 255) / 256;
     if (nb > 2048) nb = 2048;            // 256 CUs x 8 blocks; grid-stride the rest
     prof_begin(prof, "k_clean_state_reduce", stream);
-    hipLaunchKernelGGL(k_clean_state<true>, dim3((unsigned)nb), dim3(256), 0, stream, U, b, P, ntimes,
+    hipLaunchKernelGGL(k_clean_state_reduce, dim3((unsigned)nb), dim3(256), 0, stream, U, b, P, ntimes,
                        g.dx[0], g.dx[1], g.dx[2], d_out);
     prof_end(prof, stream);
     return launch_status();
@@ -1286,14 +1342,7 @@ __device__ __forceinline__ void fab_op_thread(const FabOp& o, long t, const DevP
         }
         return;
     }
-    if (o.kind == CASTRO_AMD_OP_CLEAN) {
-        double u[NUM_STATE];
-        for (int n = 0; n < NUM_STATE; ++n) u[n] = o.D.p[fidx(o.D, c[0], c[1], c[2], n)];
-        const int ntimes = (int)o.a;
-        if (ntimes > 0) clean_zone(P, ntimes, u[URHO], u[UMX], u[UMY], u[UMZ], u[UEDEN], u[UEINT], u[UTEMP], u[UFS]);
-        for (int n = 0; n < NUM_STATE; ++n) o.D.p[fidx(o.D, c[0], c[1], c[2], n)] = u[n];
-        return;
-    }
+    // CASTRO_AMD_OP_CLEAN never gets here: launch_fab_ops hands it to k_clean_state (launch_clean_state_boxes)
     if (o.kind == CASTRO_AMD_OP_AVGDOWN) {             // k_avgdown's arithmetic
         for (int n = 0; n < o.ncomp; ++n) {
             double s = 0.0;
@@ -1351,8 +1400,26 @@ int launch_fab_ops(int nops, const DFab* D, const DFab* X, const DFab* Y, const 
 {
     DevParams P;
     if (Pp) P = *Pp; else std::memset(&P, 0, sizeof(P));
+    // CASTRO_AMD_OP_CLEAN operations go to k_clean_state, the one compiled copy of the plain clean sweep (see there), as tables
+    // of their own, issued in front of the launches of the other kinds (the operations of a call are independent)
+    {
+        std::vector<DFab> cu;
+        std::vector<int> clo, chi, cn;
+        for (int r = 0; r < nops; ++r) {
+            if (kind[r] != CASTRO_AMD_OP_CLEAN) continue;
+            cu.push_back(D[r]);
+            clo.insert(clo.end(), lo + 3 * r, lo + 3 * r + 3);
+            chi.insert(chi.end(), hi + 3 * r, hi + 3 * r + 3);
+            cn.push_back((int)a[r]);
+        }
+        if (!cu.empty()) {
+            const int rc = launch_clean_state_boxes((int)cu.size(), cu.data(), clo.data(), chi.data(), cn.data(), P, stream, prof);
+            if (rc != 0) return rc;
+        }
+    }
     auto fill = [&](FabOp& o, int r, long& n) {
         n = 1;
+        if (kind[r] == CASTRO_AMD_OP_CLEAN) return false;
         int nn[3];
         for (int d = 0; d < 3; ++d) { nn[d] = hi[3 * r + d] - lo[3 * r + d] + 1; n *= nn[d] > 0 ? nn[d] : 0; }
         if (n <= 0) return false;

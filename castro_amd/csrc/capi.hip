@@ -35,6 +35,7 @@ struct castro_amd_ctx {
     MonoWorkspace mono_ws;                          // castro_amd_radial_mass_mf: rows, counts and device box tables
     TableCache pm_tables{32};                       // castro_amd_add_pointmass_mf / castro_amd_pointmass_*_mf
     TableCache tr_tables{32};                       // castro_amd_tracer_*
+    TrMigrateWorkspace tr_migrate;                  // castro_amd_tracer_migrate_count -> _pack: per-block counts per rank
 };
 
 namespace cad {
@@ -250,6 +251,7 @@ void castro_amd_ctx_destroy(castro_amd_ctx* c)
     mono_workspace_free(&c->mono_ws);
     c->pm_tables.release();
     c->tr_tables.release();
+    if (c->tr_migrate.hist) hipFree(c->tr_migrate.hist);
     prof_collect(&c->prof);
     for (auto e : c->prof.pool) hipEventDestroy(e);
     if (c->arena) hipFree(c->arena);
@@ -1157,7 +1159,8 @@ static int tr_geom(const castro_amd_geom* geom, int slot, TrGeom& G)
     return CASTRO_AMD_OK;
 }
 
-// table entries [at, at + nboxes) from the caller's boxes; need_fab: a FAB of at least min_ncomp components that holds the valid box
+// table entries [at, at + nboxes) from the caller's boxes; need_fab: a FAB of at least min_ncomp components that holds the valid
+// box -- or none at all (fab.p == NULL: a box of another rank, whose entry keeps a null FAB the kernels skip)
 static int tr_boxes(int nboxes, const castro_amd_tracer_box* boxes, bool need_fab, int min_ncomp, std::vector<TrBoxDev>& tab, size_t at)
 {
     for (int i = 0; i < nboxes; ++i) {
@@ -1167,8 +1170,8 @@ static int tr_boxes(int nboxes, const castro_amd_tracer_box* boxes, bool need_fa
             if (b.vhi[d] < b.vlo[d]) return CASTRO_AMD_ERR_ARG;
             T.vlo[d] = b.vlo[d]; T.vhi[d] = b.vhi[d];
         }
-        if (need_fab) {
-            if (!b.fab.p || b.fab.ncomp < min_ncomp || !fab_contains(&b.fab, b.vlo, b.vhi)) return CASTRO_AMD_ERR_ARG;
+        if (need_fab && b.fab.p) {
+            if (b.fab.ncomp < min_ncomp || !fab_contains(&b.fab, b.vlo, b.vhi)) return CASTRO_AMD_ERR_ARG;
             const DFab F = to_dfab(&b.fab);
             T.F.p = F.p; T.F.sy = F.sy; T.F.sz = F.sz; T.F.sn = F.sn;
             for (int d = 0; d < 3; ++d) { T.F.lo[d] = F.lo[d]; T.alo[d] = b.fab.lo[d]; T.ahi[d] = b.fab.hi[d]; }
@@ -1275,11 +1278,66 @@ int castro_amd_tracer_count_mf(castro_amd_ctx* c, int level, int nboxes, const c
     tr_zero(tab, G);
     int rt = tr_geom(geom, 0, G);
     if (rt != CASTRO_AMD_OK) return rt;
-    for (int i = 0; i < nboxes; ++i) if (count_boxes[i].fab.ncomp != 1) return CASTRO_AMD_ERR_ARG;
+    for (int i = 0; i < nboxes; ++i) if (count_boxes[i].fab.p && count_boxes[i].fab.ncomp != 1) return CASTRO_AMD_ERR_ARG;
     rt = tr_boxes(nboxes, count_boxes, true, 1, tab, 0);
     if (rt != CASTRO_AMD_OK) return rt;
     hipSetDevice(c->device);
     return launch_tracer_count(nboxes, tab.data(), level, G, *tracers, &c->tr_tables, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_tracer_migrate_count(castro_amd_ctx* c, int nlev, const int* nboxes_per_level, const int* owners, int nranks,
+                                    int myrank, const castro_amd_tracers* tracers, int* d_dest, int* d_counts, void* stream)
+{
+    if (!c || nlev < 1 || nlev > CAD_TRACER_MAX_LEVELS || !nboxes_per_level || nranks < 1 || myrank < 0 || myrank >= nranks
+        || !tr_particles_ok(tracers) || !d_counts || (tracers->n > 0 && !d_dest) || tracers->n > 0x7fffffffLL)
+        return CASTRO_AMD_ERR_ARG;
+    if (nranks > CASTRO_AMD_TRACER_MAX_RANKS) return CASTRO_AMD_ERR_UNSUPPORTED;
+    TrOwners O;
+    std::memset((void*)&O, 0, sizeof(O));
+    O.nlev = nlev;
+    long tot = 0;
+    for (int l = 0; l < nlev; ++l) {
+        if (nboxes_per_level[l] < 0) return CASTRO_AMD_ERR_ARG;
+        O.start[l] = (int)tot;
+        tot += nboxes_per_level[l];
+        if (tot > 0x7fffffffL) return CASTRO_AMD_ERR_ARG;
+    }
+    for (int l = nlev; l <= CAD_TRACER_MAX_LEVELS; ++l) O.start[l] = (int)tot;
+    if (tot > 0 && !owners) return CASTRO_AMD_ERR_ARG;
+    for (long i = 0; i < tot; ++i) if (owners[i] < 0 || owners[i] >= nranks) return CASTRO_AMD_ERR_ARG;
+    hipSetDevice(c->device);
+    return launch_tracer_migrate_count(owners, (int)tot, O, nranks, myrank, *tracers, d_dest, d_counts, &c->tr_migrate, &c->tr_tables,
+                                       (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_tracer_migrate_pack(castro_amd_ctx* c, int nranks, int myrank, const castro_amd_tracers* tracers_in, const int* d_dest,
+                                   const castro_amd_tracers* tracers_out, long long* d_wire, long long nwire, void* stream)
+{
+    if (!c || nranks < 1 || myrank < 0 || myrank >= nranks || !tr_particles_ok(tracers_in) || !tr_particles_ok(tracers_out) || nwire < 0
+        || (nwire > 0 && !d_wire) || ((size_t)d_wire & 15) || (tracers_in->n > 0 && !d_dest))
+        return CASTRO_AMD_ERR_ARG;
+    if (nranks > CASTRO_AMD_TRACER_MAX_RANKS) return CASTRO_AMD_ERR_UNSUPPORTED;
+    if (tracers_in->n > 0 && tracers_out->n > 0) {
+        // cpu may be NULL (all zero): a NULL never aliases
+        const void* in[10] = { tracers_in->x, tracers_in->y, tracers_in->z, tracers_in->r0, tracers_in->r1, tracers_in->r2,
+                               tracers_in->id, tracers_in->cpu, tracers_in->level, tracers_in->grid };
+        const void* out[10] = { tracers_out->x, tracers_out->y, tracers_out->z, tracers_out->r0, tracers_out->r1, tracers_out->r2,
+                                tracers_out->id, tracers_out->cpu, tracers_out->level, tracers_out->grid };
+        for (int i = 0; i < 10; ++i) for (int j = 0; j < 10; ++j) if (in[i] && in[i] == out[j]) return CASTRO_AMD_ERR_ARG;
+    }
+    hipSetDevice(c->device);
+    return launch_tracer_migrate_pack(nranks, myrank, *tracers_in, d_dest, *tracers_out, d_wire, nwire, &c->tr_migrate,
+                                      (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_tracer_unpack(castro_amd_ctx* c, const long long* d_wire, long long nrecv, const castro_amd_tracers* tracers_out,
+                             long long at, void* stream)
+{
+    if (!c || nrecv < 0 || at < 0 || !tr_particles_ok(tracers_out) || (nrecv > 0 && !d_wire) || ((size_t)d_wire & 15)
+        || at > tracers_out->n || nrecv > tracers_out->n - at)
+        return CASTRO_AMD_ERR_ARG;
+    hipSetDevice(c->device);
+    return launch_tracer_unpack(d_wire, nrecv, *tracers_out, at, (hipStream_t)stream, &c->prof);
 }
 
 int castro_amd_saxpy_fab(castro_amd_ctx* c, const castro_amd_fab* dst, double a, const castro_amd_fab* src, int ncomp,

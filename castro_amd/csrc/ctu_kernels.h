@@ -251,6 +251,19 @@ int launch_tracer_locate(int nbox, const TrBoxDev* boxes, const TrGeom& G, int l
                          const castro_amd_tracers& T, int* d_flags, TableCache* tables, hipStream_t stream, Profiler* prof);
 int launch_tracer_count(int nbox, const TrBoxDev* boxes, int level, const TrGeom& G, const castro_amd_tracers& T, TableCache* tables,
                         hipStream_t stream, Profiler* prof);
+// migration between ranks.  TrOwners: owners[start[l] + grid] is the rank of box `grid` of level l (nlev levels).  The workspace
+// is the context's: hist[block][rank] -- the per-block counts of launch_tracer_migrate_count, turned into exclusive prefixes over
+// the blocks by its scan launch -- which launch_tracer_migrate_pack reads for the same n and nranks.
+#define CAD_TRACER_MAX_RANKS CASTRO_AMD_TRACER_MAX_RANKS
+struct TrOwners { int nlev; int start[CAD_TRACER_MAX_LEVELS + 1]; };
+struct TrMigrateWorkspace { int* hist = nullptr; size_t ints = 0; long long n = -1; int nranks = 0; };
+int launch_tracer_migrate_count(const int* owners, int nown, const TrOwners& O, int nranks, int myrank, const castro_amd_tracers& T,
+                                int* d_dest, int* d_counts, TrMigrateWorkspace* ws, TableCache* tables, hipStream_t stream,
+                                Profiler* prof);
+int launch_tracer_migrate_pack(int nranks, int myrank, const castro_amd_tracers& T, const int* d_dest, const castro_amd_tracers& out, long long* d_wire, long long nwire, TrMigrateWorkspace* ws,
+                               hipStream_t stream, Profiler* prof);
+int launch_tracer_unpack(const long long* d_wire, long long nrecv, const castro_amd_tracers& out, long long at, hipStream_t stream,
+                         Profiler* prof);
 // the gravity sources with a per-zone vector: GO / GN are 3-component FABs with one ghost zone around [lo, hi] (type 4)
 int launch_old_grav_source_gfab(const DFab& U, const DFab& SRC, const int lo[3], const int hi[3], const DFab& GO,
                                 int type, double dt, hipStream_t stream, Profiler* prof);

@@ -9,10 +9,12 @@
 //   k_tracer_sample        the cloud-in-cell gather of state components at the particle positions (TimestampParticles, :195-247)
 //   k_tracer_count         particles per zone (ParticleDerive, :125-133): 32-bit integer atomics -- the sums do not depend on
 //                          the arrival order
-// One thread per particle over SoA arrays, 256-thread blocks, 64-bit offsets.  Particle order never changes, so the accesses of a
-// wave are a gather by nature: eight corners x four components through L2; whether sorting by box would pay is unmeasured.
+// and the migration between ranks (k_tracer_dest, k_tracer_scan, k_tracer_pack, k_tracer_unpack, further down).
+// One thread per particle over SoA arrays, 256-thread blocks, 64-bit offsets.  These four never change the particle order (only a
+// migration does, into new arrays), so the accesses of a wave are a gather by nature: eight corners x four components through L2; whether sorting by box would pay is unmeasured.
 //
-// Bounds.  Every stencil index is clamped to the array it reads, a particle whose `grid` is no box of the table is skipped, and a
+// Bounds.  Every stencil index is clamped to the array it reads, a particle whose `grid` is no box of the table (or a box of
+// another rank: an entry without a FAB) is skipped, and a
 // count outside its FAB is dropped: no input makes a kernel touch memory outside a FAB.  Each particle and pass that had to
 // clamp (or was skipped) adds 1 to flags[0], each lost particle 1 to flags[1]; the driver turns either into an error.
 //
@@ -87,12 +89,14 @@ __device__ __forceinline__ double tr_gather(const TrBoxDev& B, const TrStencil& 
     return val;
 }
 
-// the particle is one this launch acts on; its box into b.  A `grid` outside the table counts as a clamp and skips the particle
-__device__ __forceinline__ bool tr_mine(const castro_amd_tracers& T, long t, int level, int nbox, int* __restrict__ flags, int& b)
+// the particle is one this launch acts on; its box into b.  A `grid` outside the table, or one that names an entry without a FAB
+// (a box of another rank), counts as a clamp and skips the particle
+__device__ __forceinline__ bool tr_mine(const TrBoxDev* __restrict__ tab, const castro_amd_tracers& T, long t, int level, int nbox,
+                                        int* __restrict__ flags, int& b)
 {
     if (T.id[t] <= 0 || T.level[t] != level) return false;
     b = T.grid[t];
-    if (b < 0 || b >= nbox) { atomicAdd(&flags[0], 1); return false; }
+    if (b < 0 || b >= nbox || tab[b].F.p == nullptr) { atomicAdd(&flags[0], 1); return false; }
     return true;
 }
 
@@ -103,7 +107,7 @@ __global__ void __launch_bounds__(256) k_tracer_advect(const TrBoxDev* __restric
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= T.n) return;
     int b;
-    if (!tr_mine(T, t, level, nbox, flags, b)) return;
+    if (!tr_mine(tab, T, t, level, nbox, flags, b)) return;
     const TrBoxDev B = tab[b];
     const double x = T.x[t], y = T.y[t], z = T.z[t];
     const TrStencil S = tr_stencil(B, G, G.dxi[0], x, y, z);
@@ -128,7 +132,7 @@ __global__ void __launch_bounds__(256) k_tracer_sample(const TrBoxDev* __restric
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= T.n) return;
     int b;
-    if (!tr_mine(T, t, level, nbox, flags, b)) return;
+    if (!tr_mine(tab, T, t, level, nbox, flags, b)) return;
     const TrBoxDev B = tab[b];
     const TrStencil S = tr_stencil(B, G, G.dxi[0], T.x[t], T.y[t], T.z[t]);
     if (S.clamped) atomicAdd(&flags[0], 1);
@@ -190,6 +194,7 @@ __global__ void __launch_bounds__(256) k_tracer_count(const TrBoxDev* __restrict
     const int b = T.grid[t];
     if (b < 0 || b >= nbox) return;
     const TrBoxDev& B = tab[b];
+    if (B.F.p == nullptr) return;               // a box of another rank: no FAB here
     const int i = tr_floor((T.x[t] - G.plo[0]) * G.dxi[0][0]), j = tr_floor((T.y[t] - G.plo[1]) * G.dxi[0][1]),
               k = tr_floor((T.z[t] - G.plo[2]) * G.dxi[0][2]);
     if (i < B.alo[0] || i > B.ahi[0] || j < B.alo[1] || j > B.ahi[1] || k < B.alo[2] || k > B.ahi[2]) return;
@@ -265,6 +270,205 @@ int launch_tracer_count(int nbox, const TrBoxDev* boxes, int level, const TrGeom
     if (rt != 0) return rt;
     prof_begin(prof, "k_tracer_count", stream);
     hipLaunchKernelGGL(k_tracer_count, dim3(blocks), dim3(256), 0, stream, dtab, nbox, level, G, T);
+    prof_end(prof, stream);
+    return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
+}
+
+// ---- migration between ranks ------------------------------------------------------------------------------------------------------
+// A stable partition of the particle arrays by destination rank in three launches, none of which waits on another workgroup:
+//   k_tracer_dest   dest[t] and the counts of every block per destination, hist[block][rank] (LDS integer atomics: sums)
+//   k_tracer_scan   one workgroup per rank: the exclusive prefix of its column of hist over the blocks, in place, and the total
+//                   (to counts[rank] and to the row behind the last block, where the pack reads it)
+//   k_tracer_pack   the rank of a particle among those of its block with the same destination -- the waves peel the keys they
+//                   hold with ballots (most particles stay: very few keys per wave), per-wave totals in LDS -- then the copy:
+//                   stayers to the `out` arrays, leavers to 64-byte wire records, contiguous per destination in rank order
+// The order is the input order within every destination; integer work and bit copies only.
+// Wire record (eight 8-byte slots): the bits of x y z r0 r1 r2, then id | cpu << 32, then level | grid << 32 (unsigned halves).
+
+__global__ void __launch_bounds__(256) k_tracer_dest(const int* __restrict__ owners, TrOwners O, int nranks, int myrank,
+                                                     castro_amd_tracers T, int* __restrict__ dest, int* __restrict__ hist)
+{
+    __shared__ int s_cnt[CAD_TRACER_MAX_RANKS];
+    for (int r = threadIdx.x; r < nranks; r += 256) s_cnt[r] = 0;
+    __syncthreads();
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < T.n) {
+        int d = myrank;
+        const int l = T.level[t], g = T.grid[t];
+        if (T.id[t] > 0 && l >= 0 && l < O.nlev && g >= 0 && g < O.start[l + 1] - O.start[l]) d = owners[O.start[l] + g];
+        dest[t] = d;
+        atomicAdd(&s_cnt[d], 1);
+    }
+    __syncthreads();
+    for (int r = threadIdx.x; r < nranks; r += 256) hist[(long)blockIdx.x * nranks + r] = s_cnt[r];
+}
+
+// inclusive sum over the 256 threads of a block through s (every thread calls it)
+__device__ __forceinline__ int tr_block_scan(int* s, int tid, int v)
+{
+    s[tid] = v;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int add = tid >= off ? s[tid - off] : 0;
+        __syncthreads();
+        s[tid] += add;
+        __syncthreads();
+    }
+    return s[tid];
+}
+
+__global__ void __launch_bounds__(256) k_tracer_scan(int* __restrict__ hist, long nblocks, int nranks, int* __restrict__ counts)
+{
+    __shared__ int s[256];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    int carry = 0;
+    for (long base = 0; base < nblocks; base += 256) {          // the same trip count in every thread
+        const long b = base + tid;
+        const int v = b < nblocks ? hist[b * nranks + r] : 0;
+        const int incl = tr_block_scan(s, tid, v);
+        if (b < nblocks) hist[b * nranks + r] = carry + incl - v;
+        carry += s[255];
+        __syncthreads();
+    }
+    if (tid == 0) { counts[r] = carry; hist[nblocks * nranks + r] = carry; }
+}
+
+__device__ __forceinline__ unsigned long long tr_pair(int lo, int hi)
+{
+    return (unsigned long long)(unsigned)lo | ((unsigned long long)(unsigned)hi << 32);
+}
+
+__global__ void __launch_bounds__(256) k_tracer_pack(const int* __restrict__ hist, long nblocks, int nranks, int myrank,
+                                                     castro_amd_tracers T, const int* __restrict__ dest, castro_amd_tracers out,
+                                                     long long* __restrict__ wire, long nwire)
+{
+    __shared__ int s_wave[4][CAD_TRACER_MAX_RANKS];             // per wave and key: the count, then the offset of the wave's first
+    __shared__ int s_scan[256];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int r = tid; r < 4 * CAD_TRACER_MAX_RANKS; r += 256) (&s_wave[0][0])[r] = 0;
+    // first record of every destination in the wire buffer: the leavers to lower ranks come first (thread r: rank r)
+    const int tot = (tid < nranks && tid != myrank) ? hist[nblocks * nranks + tid] : 0;
+    const int wirebase = tr_block_scan(s_scan, tid, tot) - tot;
+
+    const long t = (long)blockIdx.x * blockDim.x + tid;
+    int key = t < T.n ? dest[t] : -1;
+    if (key >= nranks) key = -1;                                // not a value k_tracer_dest writes: nothing is indexed with it
+    int below = 0;
+    unsigned long long todo = __ballot(key >= 0);               // wave-uniform: every lane runs the loop
+    while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const int k = __shfl(key, leader);
+        const unsigned long long same = __ballot(key == k);
+        if (key == k) below = __popcll(same & ((1ull << lane) - 1ull));
+        if (lane == leader) s_wave[w][k] = __popcll(same);
+        todo &= ~same;
+    }
+    __syncthreads();
+    if (tid < nranks) {
+        int acc = (tid == myrank ? 0 : wirebase) + hist[(long)blockIdx.x * nranks + tid];
+        for (int q = 0; q < 4; ++q) { const int c = s_wave[q][tid]; s_wave[q][tid] = acc; acc += c; }
+    }
+    __syncthreads();
+    if (key < 0) return;
+    const long at = (long)s_wave[w][key] + below;
+    const int cpu = T.cpu ? T.cpu[t] : 0;
+    if (key == myrank) {
+        if (at >= out.n) return;
+        out.x[at] = T.x[t]; out.y[at] = T.y[t]; out.z[at] = T.z[t];
+        out.r0[at] = T.r0[t]; out.r1[at] = T.r1[t]; out.r2[at] = T.r2[t];
+        out.id[at] = T.id[t]; out.level[at] = T.level[t]; out.grid[at] = T.grid[t];
+        if (out.cpu) out.cpu[at] = cpu;
+    } else {
+        if (at >= nwire) return;
+        ulonglong2* rec = reinterpret_cast<ulonglong2*>(wire + 8 * at);                 // four 16-byte stores
+        rec[0] = make_ulonglong2((unsigned long long)__double_as_longlong(T.x[t]), (unsigned long long)__double_as_longlong(T.y[t]));
+        rec[1] = make_ulonglong2((unsigned long long)__double_as_longlong(T.z[t]), (unsigned long long)__double_as_longlong(T.r0[t]));
+        rec[2] = make_ulonglong2((unsigned long long)__double_as_longlong(T.r1[t]), (unsigned long long)__double_as_longlong(T.r2[t]));
+        rec[3] = make_ulonglong2(tr_pair(T.id[t], cpu), tr_pair(T.level[t], T.grid[t]));
+    }
+}
+
+__global__ void __launch_bounds__(256) k_tracer_unpack(const long long* __restrict__ wire, long nrecv, castro_amd_tracers out, long at0)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nrecv) return;
+    const ulonglong2* rec = reinterpret_cast<const ulonglong2*>(wire + 8 * t);
+    const ulonglong2 a = rec[0], b = rec[1], c = rec[2], d = rec[3];
+    const long at = at0 + t;
+    out.x[at] = __longlong_as_double((long long)a.x); out.y[at] = __longlong_as_double((long long)a.y);
+    out.z[at] = __longlong_as_double((long long)b.x); out.r0[at] = __longlong_as_double((long long)b.y);
+    out.r1[at] = __longlong_as_double((long long)c.x); out.r2[at] = __longlong_as_double((long long)c.y);
+    out.id[at] = (int)(unsigned)(d.x & 0xffffffffull);
+    if (out.cpu) out.cpu[at] = (int)(unsigned)(d.x >> 32);
+    out.level[at] = (int)(unsigned)(d.y & 0xffffffffull);
+    out.grid[at] = (int)(unsigned)(d.y >> 32);
+}
+
+// hist[nblocks + 1][nranks] of the context, grown behind the work queued on `stream`
+static int tr_migrate_scratch(TrMigrateWorkspace* ws, long nblocks, int nranks, hipStream_t stream)
+{
+    const size_t need = (size_t)(nblocks + 1) * (size_t)nranks;
+    if (need > ws->ints) {
+        if (ws->hist) { (void)hipStreamSynchronize(stream); (void)hipFree(ws->hist); }
+        ws->hist = nullptr; ws->ints = 0;
+        if (hipMalloc((void**)&ws->hist, 2 * need * sizeof(int)) != hipSuccess) { ws->hist = nullptr; return CASTRO_AMD_ERR_NOMEM; }
+        ws->ints = 2 * need;
+    }
+    return 0;
+}
+
+int launch_tracer_migrate_count(const int* owners, int nown, const TrOwners& O, int nranks, int myrank, const castro_amd_tracers& T,
+                                int* d_dest, int* d_counts, TrMigrateWorkspace* ws, TableCache* tables, hipStream_t stream,
+                                Profiler* prof)
+{
+    ws->n = -1;
+    if (T.n == 0) {                                            // no launch: the counts are zero
+        if (hipMemsetAsync(d_counts, 0, (size_t)nranks * sizeof(int), stream) != hipSuccess) return CASTRO_AMD_ERR_HIP;
+        ws->n = 0; ws->nranks = nranks;
+        return 0;
+    }
+    unsigned blocks;
+    if (T.n > 0x7fffffffLL || !tr_grid(T.n, blocks)) return CASTRO_AMD_ERR_ARG;     // the counts are int32
+    const int* down = nullptr;
+    if (nown > 0) {
+        const int rt = tables->find(owners, (size_t)nown, stream, down);
+        if (rt != 0) return rt;
+    }
+    const int rs = tr_migrate_scratch(ws, (long)blocks, nranks, stream);
+    if (rs != 0) return rs;
+    prof_begin(prof, "k_tracer_dest", stream);
+    hipLaunchKernelGGL(k_tracer_dest, dim3(blocks), dim3(256), 0, stream, down, O, nranks, myrank, T, d_dest, ws->hist);
+    prof_end(prof, stream);
+    prof_begin(prof, "k_tracer_scan", stream);
+    hipLaunchKernelGGL(k_tracer_scan, dim3((unsigned)nranks), dim3(256), 0, stream, ws->hist, (long)blocks, nranks, d_counts);
+    prof_end(prof, stream);
+    if (hipGetLastError() != hipSuccess) return CASTRO_AMD_ERR_HIP;
+    ws->n = T.n; ws->nranks = nranks;
+    return 0;
+}
+
+int launch_tracer_migrate_pack(int nranks, int myrank, const castro_amd_tracers& T, const int* d_dest, const castro_amd_tracers& out,
+                               long long* d_wire, long long nwire, TrMigrateWorkspace* ws, hipStream_t stream, Profiler* prof)
+{
+    if (ws->n != T.n || ws->nranks != nranks) return CASTRO_AMD_ERR_ARG;           // not the particles of the preceding count call
+    unsigned blocks;
+    if (T.n == 0) return 0;
+    if (!tr_grid(T.n, blocks)) return CASTRO_AMD_ERR_ARG;
+    prof_begin(prof, "k_tracer_pack", stream);
+    hipLaunchKernelGGL(k_tracer_pack, dim3(blocks), dim3(256), 0, stream, ws->hist, (long)blocks, nranks, myrank, T, d_dest, out, d_wire,
+                       (long)nwire);
+    prof_end(prof, stream);
+    return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
+}
+
+int launch_tracer_unpack(const long long* d_wire, long long nrecv, const castro_amd_tracers& out, long long at, hipStream_t stream,
+                         Profiler* prof)
+{
+    unsigned blocks;
+    if (nrecv == 0) return 0;
+    if (!tr_grid(nrecv, blocks)) return CASTRO_AMD_ERR_ARG;
+    prof_begin(prof, "k_tracer_unpack", stream);
+    hipLaunchKernelGGL(k_tracer_unpack, dim3(blocks), dim3(256), 0, stream, d_wire, (long)nrecv, out, (long)at);
     prof_end(prof, stream);
     return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
 }

@@ -302,7 +302,8 @@ class HipHydro:
     @staticmethod
     def make_tracer_boxes(specs):
         """ctypes array of castro_amd_tracer_box from (vlo, vhi, (fab, box) or None): the FAB of a box of a level (None: the
-        valid box alone, for tracer_locate; an int32 tensor: a count FAB) and the valid box inside it."""
+        valid box alone -- for tracer_locate, and in the other tables a box another rank owns, whose particles are not here;
+        an int32 tensor: a count FAB) and the valid box inside it."""
         arr = (L.TracerBox * max(len(specs), 1))()
         for i, (vlo, vhi, fab) in enumerate(specs):
             if fab is None:
@@ -354,6 +355,34 @@ class HipHydro:
         tracers = self._tracers(tracers)
         L.check(self.lib.castro_amd_tracer_count_mf(self.h, int(level), boxes[1], boxes[0], C.byref(geom), C.byref(tracers),
                                                     _stream_ptr(stream)), "tracer_count_mf")
+
+    def tracer_migrate_count(self, level_owners, nranks, myrank, tracers, dest, counts, stream=None):
+        """castro_amd_tracer_migrate_count: level_owners[l]: the owner rank of every box of level l; dest: device int32 (n),
+        counts: device int32 (nranks) -- the destination of every particle and the number per destination"""
+        nlev, tracers = len(level_owners), self._tracers(tracers)
+        flat = [int(o) for ol in level_owners for o in ol]
+        cnt = (C.c_int * nlev)(*[len(ol) for ol in level_owners])
+        own = (C.c_int * max(len(flat), 1))(*flat)
+        assert dest.dtype == torch.int32 and dest.numel() >= int(tracers.n) and counts.dtype == torch.int32 and counts.numel() >= nranks
+        L.check(self.lib.castro_amd_tracer_migrate_count(self.h, nlev, cnt, own, int(nranks), int(myrank), C.byref(tracers),
+                                                         C.c_void_p(dest.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                                         _stream_ptr(stream)), "tracer_migrate_count")
+
+    def tracer_migrate_pack(self, nranks, myrank, tracers, dest, out, wire, stream=None):
+        """castro_amd_tracer_migrate_pack after tracer_migrate_count on the same particles: the stayers into `out` (an
+        _lib.Tracers of counts[myrank] entries), the leavers into wire, an int64 (nwire, 8) device tensor of 64-byte records"""
+        tracers, out = self._tracers(tracers), self._tracers(out)
+        assert wire.dtype == torch.int64 and wire.is_contiguous() and wire.dim() == 2 and wire.shape[1] == 8
+        L.check(self.lib.castro_amd_tracer_migrate_pack(self.h, int(nranks), int(myrank), C.byref(tracers), C.c_void_p(dest.data_ptr()),
+                                                        C.byref(out), C.c_void_p(wire.data_ptr()), int(wire.shape[0]),
+                                                        _stream_ptr(stream)), "tracer_migrate_pack")
+
+    def tracer_unpack(self, wire, out, at, stream=None):
+        """castro_amd_tracer_unpack: the records of wire (int64 (nrecv, 8)) into out[at, at + nrecv)"""
+        out = self._tracers(out)
+        assert wire.dtype == torch.int64 and wire.is_contiguous() and wire.dim() == 2 and wire.shape[1] == 8
+        L.check(self.lib.castro_amd_tracer_unpack(self.h, C.c_void_p(wire.data_ptr()), int(wire.shape[0]), C.byref(out), int(at),
+                                                  _stream_ptr(stream)), "tracer_unpack")
 
     def sources_mf_g(self, stage, boxes, grav_old, grav_new, grav_source_type, rot, geom, params, dt, ntimes=1, stream=None,
                      sponge=None):
@@ -468,7 +497,8 @@ class HipHydro:
 
     def fab_ops(self, ops, stream=None, params=None):
         """Independent FAB-to-FAB region operations (make_ops): one launch for up to sixteen, and with `params`
-        (castro_amd_fab_ops_p: needed by OP_CLEAN / OP_INTERP_CLEAN) one launch for any number."""
+        (castro_amd_fab_ops_p: needed by OP_CLEAN / OP_INTERP_CLEAN) one launch for any number.  OP_CLEAN operations run
+        clean_state's own kernel, 32 regions per launch, in front of the others."""
         arr, n = ops
         if n:
             if params is not None:

@@ -7,9 +7,22 @@ cloud-in-cell interpolation are restated from its published algorithm (DESIGN.md
 is unpinned.
 
 `TracerParticles` spans the levels of a run like `MonopoleGravity`: it owns the particle arrays on the device (structure of
-arrays, in id order, which never changes), two device flags and the timestamp file; `Castro(tracers=...)` and
+arrays; on one rank in id order, which never changes), two device flags and the timestamp file; `Castro(tracers=...)` and
 `CastroAmr(tracers=...)` call it at the reference's call sites.  The four device operations are the backend's tracer_advect /
 tracer_locate / tracer_sample / tracer_count (castro_amd/hydro.py over castro_amd/csrc/tracer_kernels.hip).
+
+More than one rank (DESIGN.md "Tracer particles", ownership).  Every rank holds the particles of the boxes it owns, in arrays
+sized exactly (n_local, possibly 0); `grid` stays the index in the level's global box list and every rank knows all boxes.
+init_particles puts all N on rank 0; every Redistribute then ends with a migration: the backend's tracer_migrate_count (the
+destination of every local particle and the counts per destination -- read on the host, the one synchronisation of a multi-rank
+Redistribute: the receive sizes cannot be known without it), the counts of all ranks through comm.gather_objects,
+tracer_migrate_pack (a stable partition: stayers into new arrays, leavers into 64-byte wire records), comm.exchange (one
+message per non-empty pair of ranks) and tracer_unpack per source.  The order afterwards is defined: the stayers in their
+previous order, then the arrivals by ascending source rank, each group in its order at the source -- two runs give identical
+arrays.  Invalid particles and particles no box took stay where they are.  Reading particles back (positions(), ids(), ...,
+write_ascii, the timestamp file) is collective: every rank gets all N in id order, rank 0 writes the files, line for line what
+one rank writes.  check_flags sums the counts over the ranks, so that all ranks raise together.  A backend without the three
+migration operations cannot run on more than one rank: bind() raises NotImplementedError.
 
 Flags.  A particle whose interpolation stencil left the array it reads (impossible with CFL <= 1) is clamped by the kernel and
 counted; a particle no box takes is counted too.  The counts are read once per step() of a run with tracers and wherever particle
@@ -19,13 +32,44 @@ Files.  `particle_init_file` is AMReX's ASCII form: N, then N lines `x y z`.  wr
 per valid particle.  With timestamp_dir every Timestamp call appends one line per valid particle to timestamp_dir/Timestamp_00:
 `id cpu x y z time [rho] [T]`, space separated, reals with 17 significant digits (file name and number format are this project's).
 
-Left out: total_particle_count, the binary particle directory of a plotfile, restart, more than one rank."""
+Left out: total_particle_count, the binary particle directory of a plotfile, restart, multi-rank AMR plotfiles."""
 import os
 
 import numpy as np
 import torch
 
 from . import _lib as L
+
+
+MIGRATE_OPS = ("tracer_migrate_count", "tracer_migrate_pack", "tracer_unpack")
+WIRE_TAG = 7001             # the tag of the particle records in comm.exchange
+
+
+def can_migrate(hydro):
+    """the backend has the three operations a run on more than one rank needs"""
+    return all(hasattr(hydro, k) for k in MIGRATE_OPS)
+
+
+def need_migration(hydro, comm):
+    """the capability check of the constructors: looks at comm.size only"""
+    if comm is not None and comm.size > 1 and not can_migrate(hydro):
+        raise NotImplementedError("tracer particles on more than one rank need the migration between ranks, which is not built "
+                                  "for this backend")
+
+
+class _Arrays:
+    """particle arrays a migration fills: what the backend's operations take in place of a TracerParticles"""
+
+    def __init__(self, n, device):
+        self.pos = torch.empty((3, n), dtype=torch.float64, device=device)
+        self.r = torch.empty((3, n), dtype=torch.float64, device=device)
+        self.ints = torch.empty((4, n), dtype=torch.int32, device=device)
+        self._struct = None
+
+    def struct(self):
+        if self._struct is None:
+            self._struct = L.make_tracers(self.pos, self.r, self.ints)
+        return self._struct
 
 
 def read_init_file(path):
@@ -59,12 +103,13 @@ class TracerParticles:
         self.timestamp_dir = timestamp_dir
         self.timestamp_comps = ([L.URHO] if timestamp_density else []) + ([L.UTEMP] if timestamp_temperature else [])
         self.hydro, self.pos, self.r, self.ints, self.flags, self._struct = None, None, None, None, None, None
+        self.comm = None            # the communicator of a run on more than one rank, else None
 
     # ---- set-up --------------------------------------------------------------------------------------------------------------------
     def bind(self, hydro, geom, comm):
         """called by the driver that takes this object: the context the particle kernels run in and the domain check"""
-        if comm is not None and comm.size > 1:
-            raise NotImplementedError("tracer particles on more than one rank need the migration between ranks, which is not built")
+        need_migration(hydro, comm)
+        self.comm = comm if comm is not None and comm.size > 1 else None
         if not all(hasattr(hydro, k) for k in ("tracer_advect", "tracer_locate", "tracer_sample", "tracer_count")):
             raise RuntimeError("castro_amd: this backend has no tracer kernels; there is no host fallback")
         self.hydro = hydro
@@ -82,16 +127,19 @@ class TracerParticles:
 
     def init_particles(self, geom):
         """Castro::init_particles: the particles of the input on level 0, ids 1..N in input order, cpu 0; the driver runs
-        Redistribute(0) once its levels exist"""
+        Redistribute(0) once its levels exist.  On more than one rank, rank 0 holds them all until then."""
         self.check_domain(geom)
         dev, n = self.hydro.device, self.n
-        self.pos = torch.from_numpy(np.ascontiguousarray(self.initial_positions.T)).to(dev).contiguous()       # x, y, z rows
+        p0 = self.initial_positions
+        if self.comm is not None and self.comm.rank != 0:
+            n, p0 = 0, p0[:0]
+        self.pos = torch.from_numpy(np.ascontiguousarray(p0.T)).to(dev).contiguous()                           # x, y, z rows
         self.r = torch.zeros((3, n), dtype=torch.float64, device=dev)
         self.ints = torch.zeros((4, n), dtype=torch.int32, device=dev)                                         # id, cpu, level, grid
         self.ints[0] = torch.arange(1, n + 1, dtype=torch.int32, device=dev)
         self.flags = torch.zeros(2, dtype=torch.int32, device=dev)
         self._struct = None
-        if self.timestamp_dir is not None:
+        if self.timestamp_dir is not None and (self.comm is None or self.comm.rank == 0):
             os.makedirs(self.timestamp_dir, exist_ok=True)
             open(self.timestamp_file, "w").close()
 
@@ -102,6 +150,11 @@ class TracerParticles:
         if self._struct is None:
             self._struct = L.make_tracers(self.pos, self.r, self.ints)
         return self._struct
+
+    @property
+    def n_local(self):
+        """the particles this rank holds (all N on one rank)"""
+        return self.n if self.pos is None else int(self.pos.shape[1])
 
     def _ready(self):
         if self.pos is None:
@@ -115,16 +168,54 @@ class TracerParticles:
         for ipass in (0, 1):
             self.hydro.tracer_advect(level, boxes, geom, dt, ipass, self, self.flags, ng=ng)
 
-    def redistribute(self, level_boxes, geoms, lev_min, lev_max=None, ngrow=0):
-        """Redistribute(lev_min, lev_max = finest, ngrow); level_boxes[l]: [(lo, hi)] of the valid boxes of level l"""
+    def redistribute(self, level_boxes, geoms, lev_min, lev_max=None, ngrow=0, owners=None):
+        """Redistribute(lev_min, lev_max = finest, ngrow); level_boxes[l]: [(lo, hi)] of the valid boxes of level l -- all of
+        them, whoever owns them; owners[l]: their ranks (a run on more than one rank: the particles then move to the rank that
+        owns their box)"""
         self._ready()
         lev_max = len(level_boxes) - 1 if lev_max is None else lev_max
         self.hydro.tracer_locate(lev_min, lev_max, ngrow, level_boxes, geoms, self, self.flags)
+        if self.comm is not None:
+            self._migrate(owners)
+
+    def _migrate(self, owners):
+        """the particles to the ranks that own their boxes (module docstring); collective"""
+        if owners is None or len(owners) == 0:
+            raise ValueError("tracer particles on more than one rank: Redistribute needs the owners of the boxes")
+        h, comm, dev = self.hydro, self.comm, self.pos.device
+        size, me, n = comm.size, comm.rank, self.n_local
+        dest = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        counts = torch.zeros(size, dtype=torch.int32, device=dev)
+        h.tracer_migrate_count(owners, size, me, self, dest, counts)
+        mine = counts.tolist()                                  # the one synchronisation: the sizes of what is sent
+        table = comm.gather_objects(mine)                       # table[source][destination]
+        if not any(table[s][d] for s in range(size) for d in range(size) if s != d):
+            return                                              # nobody moves: the arrays are the partition already
+        nkeep, nleave = mine[me], sum(mine) - mine[me]
+        arrive = [(s, table[s][me]) for s in range(size) if s != me and table[s][me] > 0]
+        new = _Arrays(nkeep + sum(c for _, c in arrive), dev)
+        wire = torch.empty((nleave, 8), dtype=torch.int64, device=dev)
+        h.tracer_migrate_pack(size, me, self, dest, new, wire)
+        sends, at = [], 0
+        for d in range(size):
+            if d != me and mine[d] > 0:
+                sends.append((d, WIRE_TAG, wire[at:at + mine[d]]))
+                at += mine[d]
+        bufs = [(s, torch.empty((c, 8), dtype=torch.int64, device=dev)) for s, c in arrive]
+        comm.exchange(sends, [(s, WIRE_TAG, b) for s, b in bufs])
+        at = nkeep
+        for s, b in bufs:                                       # ascending source rank
+            h.tracer_unpack(b, new, at)
+            at += int(b.shape[0])
+        self.pos, self.r, self.ints, self._struct = new.pos, new.r, new.ints, None
 
     def check_flags(self):
-        """the clamp and lost counts since the last look (one copy to the host); RuntimeError if either is set"""
+        """the clamp and lost counts since the last look (one copy to the host); RuntimeError if either is set.  On more than
+        one rank the counts are summed over the ranks first (collective): every rank raises, or none"""
         if self.flags is None:
             return
+        if self.comm is not None:
+            self.comm.allreduce_sum(self.flags)
         clamped, lost = self.flags.tolist()
         if clamped or lost:
             self.flags.zero_()
@@ -143,6 +234,8 @@ class TracerParticles:
         if self.timestamp_dir is None:
             return
         self._ready()
+        if self.comm is not None:
+            return self._timestamp_ranks(lev_min, time, sample_boxes, geoms)
         ints = self.ints.cpu().numpy()
         pos = self.pos.cpu().numpy()
         self.check_flags()
@@ -166,19 +259,56 @@ class TracerParticles:
             with open(self.timestamp_file, "a") as f:
                 f.writelines(lines)
 
-    def count_level(self, level, box_list, geom):
+    def _timestamp_ranks(self, lev_min, time, sample_boxes, geoms):
+        """timestamp() on more than one rank: every rank samples at its own particles, rank 0 writes the lines of all ranks in
+        the order of one rank (per level, ascending id).  Collective; the same calls on every rank whatever it holds."""
+        ints = self.ints.cpu().numpy()
+        pos = self.pos.cpu().numpy()
+        nc, n = len(self.timestamp_comps), self.n_local
+        rows = []                                               # (level, id, line)
+        for l in range(lev_min, len(geoms)):
+            sel = np.nonzero((ints[0] > 0) & (ints[2] == l))[0]
+            if sel.size == 0:
+                continue
+            vals = None
+            if nc:
+                out = torch.zeros((nc, n), dtype=torch.float64, device=self.pos.device)
+                self.hydro.tracer_sample(l, sample_boxes(l), geoms[l], self.timestamp_comps, self, out, self.flags)
+                vals = out.cpu().numpy()
+            for t in sel:
+                f = ["%d" % ints[0, t], "%d" % ints[1, t]] + ["%.17g" % v for v in (pos[0, t], pos[1, t], pos[2, t], time)]
+                f += ["%.17g" % vals[c, t] for c in range(nc)]
+                rows.append((l, int(ints[0, t]), " ".join(f) + "\n"))
+        self.check_flags()
+        rows = [r for part in self.comm.gather_objects(rows) for r in part]
+        if rows and self.comm.rank == 0:
+            rows.sort(key=lambda r: (r[0], r[1]))
+            with open(self.timestamp_file, "a") as f:
+                f.writelines(r[2] for r in rows)
+
+    def count_level(self, level, box_list, geom, mine=None):
         """ParticleDerive: the number of valid particles of `level` in every zone of its boxes [(lo, hi)], as float64 tensors
-        (nz, ny, nx) -- counted with integer atomics into int32 FABs, converted afterwards"""
+        (nz, ny, nx) -- counted with integer atomics into int32 FABs, converted afterwards.  mine[b]: this rank owns box b (all
+        of them by default); the others get no FAB and None in the result -- their particles are on their owners"""
         self._ready()
         h = self.hydro
-        cnt = [torch.zeros(tuple(hi[d] - lo[d] + 1 for d in (2, 1, 0)), dtype=torch.int32, device=h.device) for lo, hi in box_list]
-        h.tracer_count(level, h.make_tracer_boxes([(lo, hi, (c, (lo, hi))) for c, (lo, hi) in zip(cnt, box_list)]), geom, self)
-        return [c.to(torch.float64) for c in cnt]
+        mine = [True] * len(box_list) if mine is None else list(mine)
+        cnt = [torch.zeros(tuple(hi[d] - lo[d] + 1 for d in (2, 1, 0)), dtype=torch.int32, device=h.device) if m else None
+               for (lo, hi), m in zip(box_list, mine)]
+        h.tracer_count(level, h.make_tracer_boxes([(lo, hi, None if c is None else (c, (lo, hi))) for c, (lo, hi) in zip(cnt, box_list)]),
+                       geom, self)
+        return [None if c is None else c.to(torch.float64) for c in cnt]
 
     # ---- read-back ---------------------------------------------------------------------------------------------------------------
     def _host(self):
+        """(pos, r, ints) of all particles on the host, in id order; collective on more than one rank"""
         self._ready()
         out = self.pos.cpu().numpy(), self.r.cpu().numpy(), self.ints.cpu().numpy()
+        if self.comm is not None:
+            parts = self.comm.gather_objects(out)
+            out = tuple(np.concatenate([p[k] for p in parts], axis=1) for k in range(3))
+            order = np.argsort(np.abs(out[2][0]), kind="stable")            # an invalid particle carries -id
+            out = tuple(np.ascontiguousarray(a[:, order]) for a in out)
         self.check_flags()
         return out
 
@@ -205,8 +335,11 @@ class TracerParticles:
         return int((self._host()[2][0] > 0).sum())
 
     def write_ascii(self, path):
-        """N, then `x y z r0 r1 r2 id cpu` per valid particle (reals with 17 significant digits)"""
+        """N, then `x y z r0 r1 r2 id cpu` per valid particle (reals with 17 significant digits); on more than one rank
+        collective, written by rank 0"""
         pos, r, ints = self._host()
+        if self.comm is not None and self.comm.rank != 0:
+            return
         sel = np.nonzero(ints[0] > 0)[0]
         with open(path, "w") as f:
             f.write("%d\n" % sel.size)

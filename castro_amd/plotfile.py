@@ -98,9 +98,14 @@ def plot_data(castro, derive=None, particle_count=None):
 
 def write_plotfile(dirname, castro, derive=None, job_info=None):
     """Write `dirname`/{Header, job_info, Level_0/Cell_H, Level_0/Cell_D_nnnnn}."""
-    cnt = particle_counts(getattr(castro, "tracers", None), derive, 0, [castro.bx], castro.geom)
-    names, data = plot_data(castro, derive, particle_count=None if cnt is None else cnt[0])
     comm = castro.comm
+    if comm.size > 1 and derive is not None and PARTICLE_COUNT in derive and getattr(castro, "tracers", None) is not None:
+        # every rank counts its own particles into its own box: box r of the table is rank r's
+        mine = [r == comm.rank for r in range(comm.size)]
+        cnt = [castro.tracers.count_level(0, castro._rank_boxes(), castro.geom, mine=mine)[comm.rank]]
+    else:
+        cnt = particle_counts(getattr(castro, "tracers", None), derive, 0, [castro.bx], castro.geom)
+    names, data = plot_data(castro, derive, particle_count=None if cnt is None else cnt[0])
     rank, size = comm.rank, comm.size
     arr = data.cpu().numpy() if hasattr(data, "cpu") else np.asarray(data)
     ncomp = arr.shape[0]

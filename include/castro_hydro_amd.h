@@ -65,7 +65,10 @@ extern "C" {
  *      castro_amd_fluxreg_to_flux_fab, CASTRO_AMD_OP_FLUXREG_TO_FLUX, CASTRO_AMD_SOURCES_AFTER_REFLUX (stage 1 | that flag of
  *      castro_amd_sources_mf / _ex / _g / _opts);
  *      castro_amd_tracer_advect_mf, castro_amd_tracer_locate, castro_amd_tracer_sample_mf, castro_amd_tracer_count_mf (structs
- *      castro_amd_tracers, castro_amd_tracer_box).
+ *      castro_amd_tracers, castro_amd_tracer_box);
+ *      castro_amd_tracer_migrate_count, castro_amd_tracer_migrate_pack, castro_amd_tracer_unpack
+ *      (CASTRO_AMD_TRACER_MAX_RANKS); a castro_amd_tracer_box without a FAB (fab.p == NULL) is accepted by
+ *      castro_amd_tracer_advect_mf / _sample_mf / _count_mf, which refused it before.
  * A caller checks `castro_amd_abi_version() == CASTRO_AMD_ABI_VERSION` once after loading the library; a mismatch means
  * the library was built from another revision of this header (a 0.2 caller with 2-double vectors would be written 8 bytes
  * out of bounds by a 0.3 library). */
@@ -726,7 +729,8 @@ int castro_amd_pointmass_apply_mf(castro_amd_ctx *ctx, int nboxes, const castro_
  * AmrTracerParticleContainer [3P, not in the reference tree]: AdvectWithUcc, Redistribute and the cloud-in-cell interpolation
  * are restated from the published algorithm and are NOT pinned against an AMReX build.  3-D Cartesian
  * (CASTRO_AMD_ERR_UNSUPPORTED unless geom->coord == 0).  The particles are the caller's device arrays, one entry per particle, in
- * an order that never changes; none of the four calls allocates particle memory or synchronises.  The box tables are kept on the
+ * an order these four calls never change (the migration calls below write new arrays); none of the four calls allocates
+ * particle memory or synchronises.  The box tables are kept on the
  * device by content like those of the point mass.  n == 0 launches nothing and returns CASTRO_AMD_OK.
  *   id <= 0: an invalid particle -- never moved, sampled, counted or located again.
  *   level, grid: the level and the index of the box (in the level's table) where the particle lives, set by
@@ -734,7 +738,7 @@ int castro_amd_pointmass_apply_mf(castro_amd_ctx *ctx, int nboxes, const castro_
  *   r0..r2: the saved position between the two advection passes, the velocity of the corrector afterwards.
  *   cpu is not read (may be NULL).
  * d_flags: two device int32.  [0] += 1 for every particle and pass whose stencil had to be clamped to the array it reads (or
- * whose grid is no box of the table: that particle is skipped); [1] += 1 for every particle castro_amd_tracer_locate finds in no
+ * whose grid is no box of the table, or a box of the table without a FAB: that particle is skipped); [1] += 1 for every particle castro_amd_tracer_locate finds in no
  * box.  No input makes a call read or write outside a FAB; the caller reads the flags when it reads particle data. */
 typedef struct castro_amd_tracers {
     long long n;
@@ -743,7 +747,10 @@ typedef struct castro_amd_tracers {
     int *id, *cpu, *level, *grid;
 } castro_amd_tracers;
 /* One box of a level: a FAB with its ghost zones and the valid box inside it.  castro_amd_tracer_locate reads the valid box
- * only (fab.p may be NULL); castro_amd_tracer_count_mf takes fab.p as the address of int32 zones, one component. */
+ * only (fab.p may be NULL); castro_amd_tracer_count_mf takes fab.p as the address of int32 zones, one component.  In the tables
+ * of advect, sample and count, fab.p == NULL marks a box another rank owns (the rest of `fab` is not read): a particle whose
+ * grid names it is skipped -- advect and sample add 1 to flags[0] for it, count, which has no flags, drops it -- exactly as for
+ * a grid outside the table.  After a migration no local particle names one. */
 typedef struct castro_amd_tracer_box {
     castro_amd_fab fab;
     int vlo[3], vhi[3];
@@ -777,6 +784,37 @@ int castro_amd_tracer_sample_mf(castro_amd_ctx *ctx, int level, int nboxes, cons
  * outside that FAB is dropped.  The caller zeroes the FABs and converts them afterwards. */
 int castro_amd_tracer_count_mf(castro_amd_ctx *ctx, int level, int nboxes, const castro_amd_tracer_box *count_boxes,
                                const castro_amd_geom *geom, const castro_amd_tracers *tracers, void *stream);
+/* Migration of particles between ranks (the second half of Redistribute when the boxes are dealt over ranks): a stable
+ * partition of a rank's particle arrays by destination rank, in three calls around the caller's transport.  A rank holds the
+ * particles of the boxes it owns; `grid` stays the index in the level's global box list.  None of the calls synchronises or
+ * allocates particle memory; the first keeps a scratch table in the context (grown behind `stream` when n grows).
+ *   destination of a particle: owners[first box of its level + grid] if id > 0, 0 <= level < nlev and 0 <= grid <
+ *   nboxes_per_level[level]; else myrank -- invalid particles and particles with no such box stay where they are.
+ *   order: the particles that stay keep their order in tracers_out[0, nkeep); the leavers are wire records, contiguous per
+ *   destination in ascending rank order, each group in its order in tracers_in.
+ *   wire record: 64 bytes, eight 8-byte slots: the bits of x y z r0 r1 r2, then id | cpu << 32, then level | grid << 32 (the
+ *   halves as unsigned 32-bit values; cpu travels as 0 when tracers_in->cpu is NULL).  d_wire is 16-byte aligned.
+ * Errors: CASTRO_AMD_ERR_ARG for null pointers, myrank outside [0, nranks), an owner outside [0, nranks), n above 2^31 - 1 (the
+ * counts are int32), at + nrecv > n; CASTRO_AMD_ERR_UNSUPPORTED for nranks > CASTRO_AMD_TRACER_MAX_RANKS (per-rank counters of
+ * a workgroup live in LDS).  A refused call writes nothing.  Both numerics builds give the same bits (integer work and copies). */
+#define CASTRO_AMD_TRACER_MAX_RANKS 256
+/* d_dest[t] (n int32) and d_counts[r] (nranks int32): the destination of every particle and the number per destination
+ * (d_counts[myrank]: the stayers).  owners: host ints, one per box, the levels one after the other.  n == 0 launches nothing
+ * and zeroes d_counts. */
+int castro_amd_tracer_migrate_count(castro_amd_ctx *ctx, int nlev, const int *nboxes_per_level, const int *owners, int nranks,
+                                    int myrank, const castro_amd_tracers *tracers, int *d_dest, int *d_counts, void *stream);
+/* The partition itself.  It relies on the scratch of the preceding castro_amd_tracer_migrate_count on the same context and
+ * stream, with the same nranks, myrank, tracers_in and d_dest (CASTRO_AMD_ERR_ARG when n or nranks differ from that call's).
+ * tracers_out: arrays of at least d_counts[myrank] entries (room for the arrivals may follow), none of them an array of
+ * tracers_in; d_wire: nwire records,
+ * nwire = the sum of the other d_counts (d_wire may be NULL when nwire == 0).  A particle whose place lies beyond
+ * tracers_out->n or nwire -- sizes that do not belong to these counts -- is dropped, never written out of bounds. */
+int castro_amd_tracer_migrate_pack(castro_amd_ctx *ctx, int nranks, int myrank, const castro_amd_tracers *tracers_in,
+                                   const int *d_dest, const castro_amd_tracers *tracers_out, long long *d_wire, long long nwire,
+                                   void *stream);
+/* nrecv wire records into tracers_out[at, at + nrecv); nothing else is written.  nrecv == 0 launches nothing. */
+int castro_amd_tracer_unpack(castro_amd_ctx *ctx, const long long *d_wire, long long nrecv, const castro_amd_tracers *tracers_out,
+                             long long at, void *stream);
 
 /* Two-level AMR building blocks, refinement ratio 2 (first slice).  The reference calls AMReX for
  * all of these [3P, not in the reference tree]; the arithmetic is restated from the published descriptions and is
@@ -816,7 +854,11 @@ int castro_amd_tracer_count_mf(castro_amd_ctx *ctx, int level, int nboxes, const
 #define CASTRO_AMD_OP_FLUXREG_CRSE_INIT 2
 #define CASTRO_AMD_OP_FLUXREG_FINE_ADD 3
 #define CASTRO_AMD_OP_REFLUX 4
-#define CASTRO_AMD_OP_CLEAN 5           /* Castro::clean_state x (int)a on the region of dst (ncomp 8); needs castro_amd_fab_ops_p */
+#define CASTRO_AMD_OP_CLEAN 5           /* Castro::clean_state x (int)a on the region of dst (ncomp 8); needs castro_amd_fab_ops_p.  Runs
+                                         * the kernel of castro_amd_clean_state_fab (up to 32 regions per launch): the same bits as
+                                         * that call in both numerics builds.  The CLEAN operations of a call are issued in front of
+                                         * its other operations, whatever their place in the table; one with an empty region or
+                                         * a == 0 does nothing */
 #define CASTRO_AMD_OP_INTERP_CLEAN 6    /* dst (fine, ncomp 8) = cell_cons_interp of src (coarse data under it) on the region,
                                          * then clean_state x (int)a: one slab of a FillPatch ghost shell
                                          * (castro_amd_fillpatch_shell_fab does the six slabs of one box); castro_amd_fab_ops_p */
