@@ -9,6 +9,7 @@ Layout:
   gravity.py       MonopoleGravity: monopole self-gravity over the levels of CastroAmr (radial arrays, level combination); PointMass: the central point mass
   particles.py     TracerParticles: tracer particles over the levels of Castro / CastroAmr (advect, redistribute, timestamp, particle_count)
   plotfile.py      Castro plotfile writer / reader
+  checkpoint.py    checkpoint / restart of Castro and CastroAmr (write_checkpoint, restart_from, read_checkpoint)
 """
 from ._lib import (NUM_STATE, NGDNV, NUM_GROW, URHO, UMX, UMY, UMZ, UEDEN, UEINT, UTEMP, UFS,
                    default_params, make_geom, make_rotation, make_diffusion, make_sponge, make_ext_bc, LIB_PATH)
@@ -16,8 +17,9 @@ from .castro import Castro, DistComm, SingleComm, AdvanceFailure, default_grid
 from .amr import CastroAmr
 from .gravity import MonopoleGravity, PointMass
 from .particles import TracerParticles
+from .checkpoint import read_checkpoint
 
-__all__ = ["Castro", "CastroAmr", "MonopoleGravity", "PointMass", "TracerParticles", "DistComm", "SingleComm", "AdvanceFailure", "default_grid", "default_params", "make_geom", "make_rotation", "make_diffusion", "make_sponge", "make_ext_bc",
+__all__ = ["Castro", "CastroAmr", "read_checkpoint", "MonopoleGravity", "PointMass", "TracerParticles", "DistComm", "SingleComm", "AdvanceFailure", "default_grid", "default_params", "make_geom", "make_rotation", "make_diffusion", "make_sponge", "make_ext_bc",
            "NUM_STATE", "NGDNV", "NUM_GROW", "LIB_PATH"]
 
 

@@ -78,6 +78,7 @@ EXPORTED_SYMBOLS = (
     "castro_amd_fluxreg_to_flux_fab",
     "castro_amd_tracer_advect_mf", "castro_amd_tracer_locate", "castro_amd_tracer_sample_mf", "castro_amd_tracer_count_mf",
     "castro_amd_tracer_migrate_count", "castro_amd_tracer_migrate_pack", "castro_amd_tracer_unpack",
+    "castro_amd_fab_pack", "castro_amd_fab_unpack",
 )
 
 
@@ -375,6 +376,11 @@ class TracerBox(C.Structure):
     _fields_ = [("fab", Fab), ("vlo", C.c_int * 3), ("vhi", C.c_int * 3)]
 
 
+class PackEntry(C.Structure):
+    """castro_amd_pack_entry: one FAB of a castro_amd_fab_pack / castro_amd_fab_unpack call"""
+    _fields_ = [("fab", Fab), ("vlo", C.c_int * 3), ("vhi", C.c_int * 3), ("offset", C.c_longlong)]
+
+
 class Diffusion(C.Structure):
     """castro_amd_diffusion"""
     _fields_ = [("const_conductivity", C.c_double), ("diffuse_cutoff_density", C.c_double),
@@ -561,6 +567,9 @@ def load(numerics=None):
         L.castro_amd_tracer_migrate_pack.argtypes = [C.c_void_p, C.c_int, C.c_int, PT, C.c_void_p, PT, C.c_void_p, C.c_longlong,
                                                      C.c_void_p]
         L.castro_amd_tracer_unpack.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, PT, C.c_longlong, C.c_void_p]
+    if hasattr(L, "castro_amd_fab_pack"):                   # absent from A/B builds of revisions before checkpoints
+        L.castro_amd_fab_pack.argtypes = [C.c_void_p, C.c_int, C.POINTER(PackEntry), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.castro_amd_fab_unpack.argtypes = [C.c_void_p, C.c_int, C.POINTER(PackEntry), C.c_void_p, C.c_void_p]
     L.castro_amd_step_control.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_double, C.c_double,
                                           C.c_double, C.c_int, C.c_void_p]
     L.castro_amd_clean_state_fab.argtypes = [C.c_void_p, PF, I3, I3, C.POINTER(Params), C.c_int, C.c_void_p]

@@ -45,6 +45,7 @@ import torch
 from . import _lib as L
 from . import cluster as CL
 from .castro import Castro, NUM_GROW, NUM_STATE, checked_estimate, density_failure, shell_slabs
+from .checkpoint import CheckpointMixin
 
 NSRC = 7                     # components of Source_Type (Castro_setup.cpp:317-327)
 
@@ -855,15 +856,19 @@ _TAG_KINDS = {"value_greater": 0, "value_less": 1, "gradient": 2, "relative_grad
 _FIELDS = {"density": 0, "xmom": 1, "ymom": 2, "zmom": 3, "rho_E": 4, "rho_e": 5, "Temp": 6, "rho_X": 7}
 
 
-class CastroAmr:
+class CastroAmr(CheckpointMixin):
     def __init__(self, n_cell, patch_crse=None, prob_lo=(0., 0., 0.), prob_hi=(1., 1., 1.), lo_bc=(2, 2, 2), hi_bc=(2, 2, 2),
                  params=None, make_hydro=None, make_params=None, refine=None, regrid_int=2, n_error_buf=1,
                  blocking_factor=8, patches=None, max_level=1, cluster=False, grid_eff=0.7, max_grid_size=128,
                  do_grav=False, const_grav=0.0, grav_source_type=4, rotation=None, comm=None, base_grid=None, box_streams=4,
                  diffusion=None, sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", gravity=None,
                  sponge=None, use_point_mass=False, point_mass=0.0, point_mass_fix_solution=False, ext_bc=None,
-                 update_sources_after_reflux=False, tracers=None):
-        """tracers: a castro_amd.TracerParticles (castro.do_tracer_particles = 1) spanning the levels: advected at the end of
+                 update_sources_after_reflux=False, tracers=None, check_int=-1, check_file="chk"):
+        """check_int, check_file (amr.check_int, default -1: never / amr.check_file): evolve() writes the checkpoint
+        check_file + "%05d" % nstep after every coarse step with nstep % check_int == 0, in the background
+        (castro_amd/checkpoint.py: writeCheckpoint, restart -- the box lists of every level come from the file, nothing is
+        clustered again --, checkpoint_wait, close).
+        tracers: a castro_amd.TracerParticles (castro.do_tracer_particles = 1) spanning the levels: advected at the end of
         every level's advance, redistributed and timestamped at the end of its post_timestep and after every regrid, as in
         castro_amd.Castro; with the boxes dealt over ranks every rank holds the particles of its boxes (castro_amd/particles.py).
         update_sources_after_reflux: castro.update_sources_after_reflux.  True is the reference's default (1) and the setting
@@ -1001,6 +1006,7 @@ class CastroAmr:
         self.time, self.nstep = 0.0, 0
         self.dt_level = [0.0] * 16
         self.level_count = [0] * 16                                   # Amr::level_count: steps of a level since its last regrid
+        self.check_int, self.check_file = int(check_int), str(check_file)
         from .diag import DiagLog
         self.diag = DiagLog(sum_interval, show_center_of_mass, diag_dir, io_rank=self.rank == 0)
         self._diag_out = None
@@ -1733,7 +1739,18 @@ class CastroAmr:
         eps = 2.220446049250313e-16
         while self.nstep < max_step and self.time < stop_time - eps:
             self.step(stop_time)
+            self._checkpoint_post_timestep()    # amr.check_int: nstep % check_int == 0, written in the background
         return self.nstep
+
+    def close(self):
+        """join a checkpoint in flight and re-raise what its thread raised (collective on more than one rank)"""
+        self.checkpoint_wait()
+
+    def __del__(self):
+        try:
+            self._checkpoint_join_only()        # a finaliser issues no collective and raises nothing: the thread only
+        except Exception:
+            pass
 
     # ---- diagnostics -------------------------------------------------------------------------
     def composite_sum(self, comp):

@@ -24,6 +24,7 @@ import time
 import torch
 
 from . import _lib as L
+from .checkpoint import CheckpointMixin
 
 NUM_STATE, NUM_GROW = L.NUM_STATE, L.NUM_GROW
 
@@ -254,7 +255,7 @@ OVERLAP_MIN_ZONES = 0
 
 
 # --------------------------------------------------------------------------------------------
-class Castro:
+class Castro(CheckpointMixin):
     def __init__(self, n_cell, prob_lo=(0., 0., 0.), prob_hi=(1., 1., 1.), lo_bc=(2, 2, 2), hi_bc=(2, 2, 2),
                  params=None, hydro=None, comm=None, grid=None, overlap=None, make_params=None, fuse_clean=True, flux_assign=True,
                  use_retry=True, retry_subcycle_factor=0.5, max_subcycles=10, dt_cutoff=1.e-12,
@@ -262,8 +263,12 @@ class Castro:
                  alloc=True, numerics=None, proxy_ranks=1, diffusion=None, do_hydro=True,
                  sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", drdxfac=1, Gconst=L.GCONST,
                  gravity=None, sponge=None, use_point_mass=False, point_mass=0.0, point_mass_fix_solution=False, ext_bc=None,
-                 tracers=None):
-        """tracers: a castro_amd.TracerParticles (castro.do_tracer_particles = 1): passive particles advected with the fluid
+                 tracers=None, check_int=-1, check_file="chk"):
+        """check_int, check_file (amr.check_int, default -1: never / amr.check_file): evolve() writes the checkpoint
+        check_file + "%05d" % nstep after every coarse step with nstep % check_int == 0, in the background
+        (castro_amd/checkpoint.py: writeCheckpoint, restart, checkpoint_wait); its host-free batches end on multiples of
+        check_int.  A caller's own run_steps batch that runs past a multiple writes nothing for it, as for the diagnostics.
+        tracers: a castro_amd.TracerParticles (castro.do_tracer_particles = 1): passive particles advected with the fluid
         velocity at the end of every advance (Castro::advance_particles), redistributed and -- with a timestamp_dir -- sampled
         after every step; on more than one rank every rank holds the particles of its box (castro_amd/particles.py).  The object owns the particle arrays; this box gets one more state array for the
         half-time state.  Steps then go through step(): host_free_ok() is False.
@@ -483,6 +488,8 @@ class Castro:
         self.time = 0.0
         self.dt = 0.0
         self.nstep = 0
+        self._next_est = None
+        self.check_int, self.check_file = int(check_int), str(check_file)
         self.hydro_seconds = 0.0
         from .diag import DiagLog
         self.diag = DiagLog(sum_interval, show_center_of_mass, diag_dir, io_rank=self.comm.rank == 0)
@@ -494,7 +501,16 @@ class Castro:
     def close(self):
         """Give back what lives outside torch's allocator: the C-ABI halo plans of this object (two packed device buffers
         each).  The RCCL communicator of the C ABI belongs to the comm object (DistComm / SingleComm.close), which may serve
-        several Castro objects.  Idempotent; never called while a stream is capturing (a free inside a capture aborts)."""
+        several Castro objects.  Idempotent; never called while a stream is capturing (a free inside a capture aborts).
+        A checkpoint in flight is joined first (checkpoint_wait): on more than one rank the call is then collective -- every
+        rank calls it --, and what the writer thread raised is raised here, once, after the plans have been released all the same;
+        a second call finds nothing in flight and nothing to release."""
+        try:
+            self.checkpoint_wait()
+        finally:
+            self._release_plans()
+
+    def _release_plans(self):
         plans = getattr(self, "_plans", {})
         # a captured step graph holds the plans' buffers (and the communicator's collectives) by address: never replay one
         # after they are gone -- the next run_steps captures afresh (or runs stream-ordered)
@@ -519,6 +535,7 @@ class Castro:
         try:
             if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
                 return
+            self._checkpoint_join_only()        # a finaliser issues no collective and raises nothing: the thread only
             self.close()
         except Exception:
             pass
@@ -1692,9 +1709,10 @@ class Castro:
                     k = int(math.floor(math.log(x) / math.log(cm))) if x > 1.0 else 0
                 else:
                     k = int(0.99 * remaining / self.dt)
-                k = self.diag.cap(min(k, max_step - self.nstep, 4 * L.CTL_NHIST), self.nstep)
+                k = self._checkpoint_cap(self.diag.cap(min(k, max_step - self.nstep, 4 * L.CTL_NHIST), self.nstep))
             if k >= 2:
                 self.run_steps(k, stop_time)
             else:
                 self.step(stop_time)
+            self._checkpoint_post_timestep()    # amr.check_int: nstep % check_int == 0, written in the background
         return self.nstep

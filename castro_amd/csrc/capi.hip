@@ -8,6 +8,7 @@
 #include <new>
 #include "../../include/castro_hydro_amd.h"
 #include <cstdlib>
+#include <cstdint>
 #include "ctu_kernels.h"
 
 using namespace cad;
@@ -36,6 +37,8 @@ struct castro_amd_ctx {
     TableCache pm_tables{32};                       // castro_amd_add_pointmass_mf / castro_amd_pointmass_*_mf
     TableCache tr_tables{32};                       // castro_amd_tracer_*
     TrMigrateWorkspace tr_migrate;                  // castro_amd_tracer_migrate_count -> _pack: per-block counts per rank
+    StagedTable pack_arena;                         // castro_amd_fab_pack / castro_amd_fab_unpack
+    DiagWorkspace pack_ws;                          // castro_amd_fab_pack: one (min, max) pair per workgroup
 };
 
 namespace cad {
@@ -246,8 +249,9 @@ void castro_amd_ctx_destroy(castro_amd_ctx* c)
     if (c->ev_join) hipEventDestroy(c->ev_join);
     if (c->mf_fork) hipEventDestroy(c->mf_fork);
     if (c->mf_join) hipEventDestroy(c->mf_join);
-    for (StagedTable* t : { &c->ops_arena, &c->level_arena, &c->diff_arena, &c->diag_arena }) t->release();
+    for (StagedTable* t : { &c->ops_arena, &c->level_arena, &c->diff_arena, &c->diag_arena, &c->pack_arena }) t->release();
     if (c->diag_ws.p) hipFree(c->diag_ws.p);
+    if (c->pack_ws.p) hipFree(c->pack_ws.p);
     mono_workspace_free(&c->mono_ws);
     c->pm_tables.release();
     c->tr_tables.release();
@@ -875,6 +879,59 @@ int castro_amd_integrated_quantities_mf(castro_amd_ctx* c, int nboxes, const cas
     G.vol = geom->dx[0] * geom->dx[1] * geom->dx[2];
     hipSetDevice(c->device);
     return launch_integrated_quantities(nboxes, tab.data(), G, &c->diag_arena, &c->diag_ws, d_out, (hipStream_t)stream, &c->prof);
+}
+
+// the checks of castro_amd_fab_pack / castro_amd_fab_unpack on their table, and the table the kernels read
+static int pack_table(int n, const castro_amd_pack_entry* entries, const double* buf, std::vector<PackEntryDev>& tab)
+{
+    tab.resize((size_t)n);
+    const bool buf16 = (reinterpret_cast<uintptr_t>(buf) & 15u) == 0;
+    for (int i = 0; i < n; ++i) {
+        const castro_amd_pack_entry& e = entries[i];
+        if (!e.fab.p || e.fab.ncomp < 1 || e.offset < 0) return CASTRO_AMD_ERR_ARG;
+        for (int d = 0; d < 3; ++d) if (e.vhi[d] < e.vlo[d]) return CASTRO_AMD_ERR_ARG;
+        if (!fab_contains(&e.fab, e.vlo, e.vhi)) return CASTRO_AMD_ERR_ARG;
+        const DFab F = to_dfab(&e.fab);
+        PackEntryDev& T = tab[(size_t)i];
+        long zones = 1;
+        for (int d = 0; d < 3; ++d) { T.n[d] = e.vhi[d] - e.vlo[d] + 1; zones *= T.n[d]; }
+        if (zones > 0x7fffffffL) return CASTRO_AMD_ERR_ARG;      // the kernels divide 32-bit zone numbers
+        T.p = F.p + (long)(e.vlo[0] - F.lo[0]) + F.sy * (long)(e.vlo[1] - F.lo[1]) + F.sz * (long)(e.vlo[2] - F.lo[2]);
+        T.sy = F.sy; T.sz = F.sz; T.sn = F.sn;
+        T.offset = (long)e.offset;
+        T.zones = zones;
+        T.ncomp = e.fab.ncomp;
+        T.bpc = 0;
+        T.vec2 = (buf16 && (reinterpret_cast<uintptr_t>(T.p) & 15u) == 0 && T.n[0] % 2 == 0 && F.sy % 2 == 0 && F.sz % 2 == 0 &&
+                  F.sn % 2 == 0 && e.offset % 2 == 0) ? 1 : 0;
+        T.items = T.vec2 ? zones / 2 : zones;
+    }
+    return CASTRO_AMD_OK;
+}
+
+int castro_amd_fab_pack(castro_amd_ctx* c, int n, const castro_amd_pack_entry* entries, double* d_dst, double* d_minmax, void* stream)
+{
+    if (!c || n < 0) return CASTRO_AMD_ERR_ARG;
+    if (n == 0) return CASTRO_AMD_OK;
+    if (!entries || !d_dst) return CASTRO_AMD_ERR_ARG;
+    std::vector<PackEntryDev> tab;
+    const int rt = pack_table(n, entries, d_dst, tab);
+    if (rt != CASTRO_AMD_OK) return rt;
+    hipSetDevice(c->device);
+    return launch_fab_pack(0, n, tab.data(), &c->pack_arena, &c->pack_ws, d_dst, d_minmax, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_fab_unpack(castro_amd_ctx* c, int n, const castro_amd_pack_entry* entries, const double* d_src, void* stream)
+{
+    if (!c || n < 0) return CASTRO_AMD_ERR_ARG;
+    if (n == 0) return CASTRO_AMD_OK;
+    if (!entries || !d_src) return CASTRO_AMD_ERR_ARG;
+    std::vector<PackEntryDev> tab;
+    const int rt = pack_table(n, entries, d_src, tab);
+    if (rt != CASTRO_AMD_OK) return rt;
+    hipSetDevice(c->device);
+    return launch_fab_pack(1, n, tab.data(), &c->pack_arena, &c->pack_ws, const_cast<double*>(d_src), nullptr, (hipStream_t)stream,
+                           &c->prof);
 }
 
 int castro_amd_diag_workgroups(int nboxes, const castro_amd_diag_box* boxes)

@@ -189,6 +189,14 @@ struct DiagWorkspace { double* p = nullptr; size_t rows = 0; };
 int diag_layout(int nbox, DiagBoxDev* boxes, std::vector<int>& start, int& iters);
 int launch_integrated_quantities(int nbox, DiagBoxDev* boxes, const DiagGeom& G, StagedTable* arena, DiagWorkspace* ws,
                                  double* d_out, hipStream_t stream, Profiler* prof);
+// checkpoints (checkpoint_kernels.hip).  One entry of a castro_amd_fab_pack / _unpack launch: p -> the first valid zone of component
+// 0, the strides of the FAB in doubles, n: the extent of the valid region, zones = n[0] n[1] n[2], offset: where the region starts
+// in the buffer; vec2: a lane moves two zones per access (every row starts on a 16-byte boundary on both sides), items: zones or
+// pairs per component; bpc: workgroups per component, set by the launcher
+struct PackEntryDev { double* p; long sy, sz, sn, offset, zones, items; int n[3]; int ncomp, bpc, vec2; };
+// mode 0: pack (d_minmax or nullptr), 1: unpack; ws: one (min, max) pair per workgroup
+int launch_fab_pack(int mode, int n, PackEntryDev* tab, StagedTable* arena, DiagWorkspace* ws, double* buf, double* d_minmax,
+                    hipStream_t stream, Profiler* prof);
 // monopole gravity (monopole_kernels.hip).  One box of a castro_amd_radial_mass_mf launch: the valid zones [lo, lo + n) of U, the
 // byte mask of those zones (nullptr: every zone counts); nb: bricks per direction, set by the launcher.  A table is compared
 // byte by byte with the ones the context has on the device: fill it field by field over zeroed storage

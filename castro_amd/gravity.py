@@ -20,8 +20,7 @@
                                      update(): Castro::pointmass_update (Source/gravity/Castro_pointmass.cpp), two launches with
                                      the sum over the ranks between them and no host round trip.
 
-Levels finer than `level` do not enter.  Not provided: GR_GRAV, gravity.max_solve_level, a potential (phiGrav), checkpoint / restart
-of the point mass, domains with a periodic direction (the Gravity_Type FillPatch across a periodic boundary is not built), thermal
+Levels finer than `level` do not enter.  Not provided: GR_GRAV, gravity.max_solve_level, a potential (phiGrav), domains with a periodic direction (the Gravity_Type FillPatch across a periodic boundary is not built), thermal
 diffusion on AMR levels, constant gravity plus a point mass on AMR levels.
 """
 from . import _lib as L

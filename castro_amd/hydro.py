@@ -506,6 +506,48 @@ class HipHydro:
             else:
                 L.check(self.lib.castro_amd_fab_ops(self.h, n, arr, _stream_ptr(stream)), "fab_ops")
 
+    # ---- checkpoints: the valid zones of many FABs into one buffer and back (castro_amd/checkpoint.py) ----
+    @staticmethod
+    def make_pack_entries(specs):
+        """(ctypes array of castro_amd_pack_entry, n, doubles, pairs) from [(tensor, box, (lo, hi)), ...]: the region [lo, hi] of
+        every FAB tensor (ncomp, nz, ny, nx) on `box`, one after the other in the buffer (offsets 0, ncomp x zones, ...); doubles:
+        what the regions take together; pairs: the sum of ncomp (the min / max vector has 2 x pairs entries).  The tensors must
+        outlive the table."""
+        arr = (L.PackEntry * max(len(specs), 1))()
+        at, pairs = 0, 0
+        for e, (t, box, (lo, hi)) in zip(arr, specs):
+            e.fab = L.fab_of(t, *box)
+            for d in range(3):
+                e.vlo[d], e.vhi[d] = lo[d], hi[d]
+            e.offset = at
+            at += int(t.shape[0]) * max(hi[0] - lo[0] + 1, 0) * max(hi[1] - lo[1] + 1, 0) * max(hi[2] - lo[2] + 1, 0)
+            pairs += int(t.shape[0])
+        return arr, len(specs), at, pairs
+
+    def fab_pack(self, entries, dst, minmax=None, stream=None):
+        """castro_amd_fab_pack: the regions of `entries` (make_pack_entries) into the 1-D float64 device tensor dst, in the
+        on-disk FAB order; minmax: a float64 device tensor of 2 x pairs entries that receives the minimum of every (entry,
+        component), then the maxima -- one launch, plus a small one for the reduction."""
+        arr, n, doubles, pairs = entries
+        if n == 0:
+            return
+        if dst.dtype != torch.float64 or not dst.is_contiguous() or dst.numel() < doubles:
+            raise ValueError("fab_pack: dst must be a contiguous float64 tensor of at least %d entries" % doubles)
+        if minmax is not None and (minmax.dtype != torch.float64 or not minmax.is_contiguous() or minmax.numel() < 2 * pairs):
+            raise ValueError("fab_pack: minmax must be a contiguous float64 tensor of at least %d entries" % (2 * pairs))
+        L.check(self.lib.castro_amd_fab_pack(self.h, n, arr, C.c_void_p(dst.data_ptr()),
+                                             C.c_void_p(minmax.data_ptr()) if minmax is not None else None, _stream_ptr(stream)),
+                "fab_pack")
+
+    def fab_unpack(self, entries, src, stream=None):
+        """castro_amd_fab_unpack: the reverse copy, src into the regions; the zones of the FABs outside them are untouched"""
+        arr, n, doubles, _ = entries
+        if n == 0:
+            return
+        if src.dtype != torch.float64 or not src.is_contiguous() or src.numel() < doubles:
+            raise ValueError("fab_unpack: src must be a contiguous float64 tensor of at least %d entries" % doubles)
+        L.check(self.lib.castro_amd_fab_unpack(self.h, n, arr, C.c_void_p(src.data_ptr()), _stream_ptr(stream)), "fab_unpack")
+
     @staticmethod
     def make_hydro_boxes(specs):
         """ctypes array of castro_amd_hydro_box from (bx, vbx, (Sborder, box), (S_new, box), fluxes, flux_boxes, mass_fluxes

@@ -32,7 +32,10 @@ Files.  `particle_init_file` is AMReX's ASCII form: N, then N lines `x y z`.  wr
 per valid particle.  With timestamp_dir every Timestamp call appends one line per valid particle to timestamp_dir/Timestamp_00:
 `id cpu x y z time [rho] [T]`, space separated, reals with 17 significant digits (file name and number format are this project's).
 
-Left out: total_particle_count, the binary particle directory of a plotfile, restart, multi-rank AMR plotfiles."""
+Restart.  A checkpoint holds every rank's pos, r, ints and the two flag words (castro_amd/checkpoint.py, Particles/); restore()
+puts them back in place of init_particles.
+
+Left out: total_particle_count, the binary particle directory of a plotfile, particle_restart_file, multi-rank AMR plotfiles."""
 import os
 
 import numpy as np
@@ -142,6 +145,19 @@ class TracerParticles:
         if self.timestamp_dir is not None and (self.comm is None or self.comm.rank == 0):
             os.makedirs(self.timestamp_dir, exist_ok=True)
             open(self.timestamp_file, "w").close()
+
+    def restore(self, pos, r, ints, flags):
+        """restart (castro_amd/checkpoint.py): this rank's arrays as a checkpoint holds them -- pos, r float64 (3, n), ints int32
+        (4, n), the two flag words -- in place of init_particles.  Ids were handed out by init_particles of the run that wrote
+        the checkpoint; the timestamp file is appended to, not started again."""
+        dev = self.hydro.device
+        self.pos = torch.from_numpy(np.ascontiguousarray(pos, dtype=np.float64)).to(dev).contiguous()
+        self.r = torch.from_numpy(np.ascontiguousarray(r, dtype=np.float64)).to(dev).contiguous()
+        self.ints = torch.from_numpy(np.ascontiguousarray(ints, dtype=np.int32)).to(dev).contiguous()
+        self.flags = torch.from_numpy(np.ascontiguousarray(flags, dtype=np.int32)).to(dev).contiguous()
+        self._struct = None
+        if self.timestamp_dir is not None and (self.comm is None or self.comm.rank == 0):
+            os.makedirs(self.timestamp_dir, exist_ok=True)
 
     timestamp_file = property(lambda self: os.path.join(self.timestamp_dir, "Timestamp_00"))
 

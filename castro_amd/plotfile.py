@@ -44,6 +44,96 @@ def _box(lo, hi):
     return "((%d,%d,%d) (%d,%d,%d) (0,0,0))" % (lo[0], lo[1], lo[2], hi[0], hi[1], hi[2])
 
 
+def fab_minmax(arr):
+    """(min, max) per component of a FAB (ncomp, nz, ny, nx) as Python floats: what a VisMF header lists"""
+    ncomp = arr.shape[0]
+    return [float(arr[n].min()) for n in range(ncomp)], [float(arr[n].max()) for n in range(ncomp)]
+
+
+def write_fab_file(path, fabs):
+    """VisMF data file [3P]: the FABs [(lo, hi, array (ncomp, nz, ny, nx))] one after the other, each as the FAB header line
+    and little-endian doubles (i fastest, component slowest).  Returns the byte offset of every FAB."""
+    offsets = []
+    with open(path, "wb") as f:
+        for lo, hi, arr in fabs:
+            offsets.append(f.tell())
+            f.write(("FAB %s%s %d\n" % (FAB_REAL_DESCRIPTOR, _box(lo, hi), arr.shape[0])).encode("ascii"))
+            np.ascontiguousarray(arr, dtype="<f8").tofile(f)
+    return offsets
+
+
+def write_vismf_header(path, ncomp, boxes):
+    """VisMF header file [3P] (Version_v1, one file per rank, nGrow 0): boxes = [dict(lo, hi, file, offset, min, max)] in the
+    order of the box array."""
+    with open(path, "w") as f:
+        w = f.write
+        w("1\n")                                                # VisMF::Header::Version_v1
+        w("0\n")                                                # VisMF::OneFilePerCPU
+        w("%d\n" % ncomp)
+        w("0\n")                                                # nGrow
+        w("(%d 0\n" % len(boxes))
+        for b in boxes:
+            w(_box(b["lo"], b["hi"]) + "\n")
+        w(")\n")
+        w("%d\n" % len(boxes))
+        for b in boxes:
+            w("FabOnDisk: %s %d\n" % (b["file"], b["offset"]))
+        w("\n")
+        for key in ("min", "max"):
+            w("%d,%d\n" % (len(boxes), ncomp))
+            for b in boxes:
+                w("".join("%.16e," % v for v in b[key]) + "\n")
+            w("\n")
+
+
+def read_vismf_header(path):
+    """(ncomp, [dict(lo, hi, file, offset, min, max)]) of a VisMF header file written by write_vismf_header"""
+    with open(path) as f:
+        H = [ln.rstrip("\n") for ln in f]
+    ncomp = int(H[2])
+    nb = int(H[4].strip("(").split()[0])
+    boxes = []
+    for b in range(nb):
+        v = [int(x) for x in re.findall(r"-?\d+", H[5 + b])]
+        boxes.append(dict(lo=tuple(v[0:3]), hi=tuple(v[3:6])))
+    q = 5 + nb + 2
+    for b in range(nb):
+        _, fn, off = H[q + b].split()
+        boxes[b].update(file=fn, offset=int(off))
+    q += nb + 1
+    for key in ("min", "max"):
+        for b in range(nb):
+            boxes[b][key] = [float(x) for x in H[q + 1 + b].split(",") if x.strip()]
+        q += nb + 2
+    return ncomp, boxes
+
+
+def read_fab(path, offset, lo, hi):
+    """the FAB at byte `offset` of a VisMF data file, as an array (ncomp, nz, ny, nx)"""
+    with open(path, "rb") as f:
+        f.seek(offset)
+        head = f.readline().decode("ascii")
+        assert head.startswith("FAB "), head
+        nc = int(head.split()[-1])
+        m = [hi[d] - lo[d] + 1 for d in range(3)]
+        return np.fromfile(f, dtype="<f8", count=nc * m[0] * m[1] * m[2]).reshape(nc, m[2], m[1], m[0])
+
+
+def job_info_text(nranks, n_cell, nstep, time, geom, params, job_info=None):
+    """the free-form text of the `job_info` file (Castro::writeJobInfo restated for this code)"""
+    out = ["==============================================================================\n",
+           " Castro Job Information (castro_amd, MI355X hydro path)\n",
+           "==============================================================================\n",
+           "number of MPI processes: %d\n" % nranks,
+           "n_cell: %d %d %d\nnstep: %d\ntime: %s\n" % (n_cell[0], n_cell[1], n_cell[2], nstep, _g(time)),
+           "lo_bc: %s\nhi_bc: %s\n" % (list(geom.lo_bc), list(geom.hi_bc))]
+    for fld, _ in params._fields_:
+        out.append("castro.%s = %s\n" % (fld, getattr(params, fld)))
+    if job_info:
+        out.append(str(job_info) + "\n")
+    return "".join(out)
+
+
 def write_point_mass(dirname, driver):
     """the `point_mass` file of plotFileOutput (Castro_io.cpp:1137-1150), by the I/O rank, when castro.use_point_mass is set"""
     if getattr(driver, "use_point_mass", False):
@@ -114,12 +204,9 @@ def write_plotfile(dirname, castro, derive=None, job_info=None):
         os.makedirs(lev, exist_ok=True)
     comm.barrier()
     fname = "Cell_D_%05d" % rank
-    head = "FAB %s%s %d\n" % (FAB_REAL_DESCRIPTOR, _box(castro.lo, castro.hi), ncomp)
-    with open(os.path.join(lev, fname), "wb") as f:
-        f.write(head.encode("ascii"))
-        np.ascontiguousarray(arr, dtype="<f8").tofile(f)
-    mine = dict(lo=tuple(castro.lo), hi=tuple(castro.hi), file=fname, offset=0,
-                min=[float(arr[n].min()) for n in range(ncomp)], max=[float(arr[n].max()) for n in range(ncomp)])
+    write_fab_file(os.path.join(lev, fname), [(castro.lo, castro.hi, arr)])
+    mn, mx = fab_minmax(arr)
+    mine = dict(lo=tuple(castro.lo), hi=tuple(castro.hi), file=fname, offset=0, min=mn, max=mx)
     boxes = comm.gather_objects(mine)
     if rank == 0:
         geom = castro.geom
@@ -150,36 +237,9 @@ def write_plotfile(dirname, castro, derive=None, job_info=None):
                     w("%s %s\n" % (_g(geom.problo[d] + (b["lo"][d] - dom_lo[d]) * geom.dx[d]),
                                    _g(geom.problo[d] + (b["hi"][d] + 1 - dom_lo[d]) * geom.dx[d])))
             w("Level_0/Cell\n")
-        with open(os.path.join(lev, "Cell_H"), "w") as f:
-            w = f.write
-            w("1\n")                                                # VisMF::Header::Version_v1
-            w("0\n")                                                # VisMF::OneFilePerCPU
-            w("%d\n" % ncomp)
-            w("0\n")                                                # nGrow
-            w("(%d 0\n" % len(boxes))
-            for b in boxes:
-                w(_box(b["lo"], b["hi"]) + "\n")
-            w(")\n")
-            w("%d\n" % len(boxes))
-            for b in boxes:
-                w("FabOnDisk: %s %d\n" % (b["file"], b["offset"]))
-            w("\n")
-            for key in ("min", "max"):
-                w("%d,%d\n" % (len(boxes), ncomp))
-                for b in boxes:
-                    w("".join("%.16e," % v for v in b[key]) + "\n")
-                w("\n")
+        write_vismf_header(os.path.join(lev, "Cell_H"), ncomp, boxes)
         with open(os.path.join(dirname, "job_info"), "w") as f:     # free-form text in the reference
-            f.write("==============================================================================\n")
-            f.write(" Castro Job Information (castro_amd, MI355X hydro path)\n")
-            f.write("==============================================================================\n")
-            f.write("number of MPI processes: %d\n" % size)
-            f.write("n_cell: %d %d %d\nnstep: %d\ntime: %s\n" % (n_cell[0], n_cell[1], n_cell[2], castro.nstep, _g(castro.time)))
-            f.write("lo_bc: %s\nhi_bc: %s\n" % (list(geom.lo_bc), list(geom.hi_bc)))
-            for fld, _ in castro.params._fields_:
-                f.write("castro.%s = %s\n" % (fld, getattr(castro.params, fld)))
-            if job_info:
-                f.write(str(job_info) + "\n")
+            f.write(job_info_text(size, n_cell, castro.nstep, castro.time, geom, castro.params, job_info))
     if getattr(castro, "use_point_mass", False):
         pm = castro.point_mass                  # every rank reads its device copy; the I/O rank writes
         if rank == 0:
@@ -230,23 +290,12 @@ def write_plotfile_amr(dirname, amr, derive=None):
     for l, (lev, fabs) in enumerate(zip(levels, per)):
         ld = os.path.join(dirname, "Level_%d" % l)
         os.makedirs(ld, exist_ok=True)
-        offsets = []
-        with open(os.path.join(ld, "Cell_D_00000"), "wb") as f:
-            for b, arr in zip(lev.boxes, fabs):
-                offsets.append(f.tell())
-                f.write(("FAB %s%s %d\n" % (FAB_REAL_DESCRIPTOR, _box(b.lo, b.hi), ncomp)).encode("ascii"))
-                np.ascontiguousarray(arr, dtype="<f8").tofile(f)
-        ng = len(fabs)
-        with open(os.path.join(ld, "Cell_H"), "w") as f:
-            f.write("1\n0\n%d\n0\n(%d 0\n" % (ncomp, ng) + "".join(_box(b.lo, b.hi) + "\n" for b in lev.boxes) + ")\n%d\n" % ng)
-            for off in offsets:
-                f.write("FabOnDisk: Cell_D_00000 %d\n" % off)
-            f.write("\n")
-            for fn in (np.min, np.max):
-                f.write("%d,%d\n" % (ng, ncomp))
-                for arr in fabs:
-                    f.write("".join("%.16e," % fn(arr[n]) for n in range(ncomp)) + "\n")
-                f.write("\n")
+        offsets = write_fab_file(os.path.join(ld, "Cell_D_00000"), [(b.lo, b.hi, arr) for b, arr in zip(lev.boxes, fabs)])
+        entries = []
+        for b, arr, off in zip(lev.boxes, fabs, offsets):
+            mn, mx = fab_minmax(arr)
+            entries.append(dict(lo=b.lo, hi=b.hi, file="Cell_D_00000", offset=off, min=mn, max=mx))
+        write_vismf_header(os.path.join(ld, "Cell_H"), ncomp, entries)
     write_point_mass(dirname, amr)
     return names
 

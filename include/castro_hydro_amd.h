@@ -69,6 +69,8 @@ extern "C" {
  *      castro_amd_tracer_migrate_count, castro_amd_tracer_migrate_pack, castro_amd_tracer_unpack
  *      (CASTRO_AMD_TRACER_MAX_RANKS); a castro_amd_tracer_box without a FAB (fab.p == NULL) is accepted by
  *      castro_amd_tracer_advect_mf / _sample_mf / _count_mf, which refused it before.
+ *      castro_amd_fab_pack, castro_amd_fab_unpack (struct castro_amd_pack_entry): the valid zones of many FABs into one
+ *      contiguous buffer and back, for checkpoints.
  * A caller checks `castro_amd_abi_version() == CASTRO_AMD_ABI_VERSION` once after loading the library; a mismatch means
  * the library was built from another revision of this header (a 0.2 caller with 2-double vectors would be written 8 bytes
  * out of bounds by a 0.3 library). */
@@ -815,6 +817,30 @@ int castro_amd_tracer_migrate_pack(castro_amd_ctx *ctx, int nranks, int myrank, 
 /* nrecv wire records into tracers_out[at, at + nrecv); nothing else is written.  nrecv == 0 launches nothing. */
 int castro_amd_tracer_unpack(castro_amd_ctx *ctx, const long long *d_wire, long long nrecv, const castro_amd_tracers *tracers_out,
                              long long at, void *stream);
+
+/* Checkpoints (castro_amd/checkpoint.py; for hosts without AMReX's own checkpoint writer): the valid zones of many ghosted FABs
+ * into ONE contiguous buffer in the order of a FAB on disk -- x fastest, component slowest, entry after entry -- and back.
+ *   castro_amd_pack_entry   fab: the (ghosted) FAB, ncomp >= 1; [vlo, vhi]: the region that is copied, inside the FAB's box;
+ *                           offset: where the region's first double goes in the buffer (the region takes
+ *                           ncomp x nx x ny x nz doubles; the caller keeps the regions of one call apart)
+ *   castro_amd_fab_pack     copies every region to d_dst + offset.  d_minmax (or NULL): 2 x M doubles, M = the sum of ncomp over
+ *                           the entries: the minimum of every (entry, component) in the order of the table, then the M maxima,
+ *                           reduced from the values as they pass by two launches and no atomics.  A NaN in the region
+ *                           propagates: the minimum and the maximum of its (entry, component) are then NaN.
+ *   castro_amd_fab_unpack   the reverse copy: d_src + offset into the region; the zones of the FAB outside it are untouched.
+ * Both return CASTRO_AMD_ERR_ARG for n < 0, a null pointer with n > 0, a region outside its FAB's box or empty, ncomp < 1 or a
+ * negative offset; n == 0 returns 0 and launches nothing.
+ * Like every table-driven call the two keep their device table and the rows of partial minima / maxima in the context: the calls
+ * of ONE context must be ordered on ONE stream (a call that has to grow either buffer synchronises the stream it was given, not
+ * others); use a context per stream for calls that may overlap. */
+typedef struct {
+    castro_amd_fab fab;
+    int vlo[3], vhi[3];
+    long long offset;
+} castro_amd_pack_entry;
+int castro_amd_fab_pack(castro_amd_ctx *ctx, int n, const castro_amd_pack_entry *entries, double *d_dst, double *d_minmax,
+                        void *stream);
+int castro_amd_fab_unpack(castro_amd_ctx *ctx, int n, const castro_amd_pack_entry *entries, const double *d_src, void *stream);
 
 /* Two-level AMR building blocks, refinement ratio 2 (first slice).  The reference calls AMReX for
  * all of these [3P, not in the reference tree]; the arithmetic is restated from the published descriptions and is
