@@ -79,6 +79,8 @@ EXPORTED_SYMBOLS = (
     "castro_amd_tracer_advect_mf", "castro_amd_tracer_locate", "castro_amd_tracer_sample_mf", "castro_amd_tracer_count_mf",
     "castro_amd_tracer_migrate_count", "castro_amd_tracer_migrate_pack", "castro_amd_tracer_unpack",
     "castro_amd_fab_pack", "castro_amd_fab_unpack",
+    "castro_amd_multipole_moments_mf", "castro_amd_multipole_phi_bc_fab", "castro_amd_poisson_plan_create",
+    "castro_amd_poisson_plan_destroy", "castro_amd_poisson_solve", "castro_amd_poisson_level_op", "castro_amd_grad_phi_to_grav_fab",
 )
 
 
@@ -184,6 +186,50 @@ def make_monopole(n_cell, geom, center, drdxfac=1, Gconst=GCONST, n1d=None):
     m.max_radius_all_in_domain = min(geom.probhi[d] - float(center[d]) for d in range(3))
     m.Gconst = float(Gconst)
     return m
+
+
+class Multipole(C.Structure):
+    """castro_amd_multipole"""
+    _fields_ = [("lnum", C.c_int), ("rmax", C.c_double), ("center", C.c_double * 3), ("Gconst", C.c_double)]
+
+
+MAX_MULTIPOLE = 16             # CASTRO_AMD_MAX_MULTIPOLE
+POISSON_MAX_BOTTOM = 4096      # CASTRO_AMD_POISSON_MAX_BOTTOM
+MG_SMOOTH, MG_RESIDUAL, MG_RESTRICT, MG_PROLONG, MG_NORM = range(5)       # CASTRO_AMD_MG_*
+
+
+def multipole_rmax(geom):
+    """multipole::rmax (Gravity.cpp:1735-1739): 0.5 * the widest extent of the domain * sqrt(3)"""
+    import math
+    width = geom.probhi[0] - geom.problo[0]
+    width = max(width, geom.probhi[1] - geom.problo[1])
+    width = max(width, geom.probhi[2] - geom.problo[2])
+    return 0.5 * width * math.sqrt(float(3))
+
+
+def make_multipole(geom, center, lnum=0, Gconst=GCONST):
+    """castro_amd_multipole of a domain: gravity.max_multipole_order, rmax of the domain, problem::center, C::Gconst"""
+    if int(lnum) < 0:
+        raise ValueError("gravity.max_multipole_order must not be negative, not %r" % (lnum,))
+    if int(lnum) > MAX_MULTIPOLE:
+        raise ValueError("gravity.max_multipole_order = %d is above the %d this library is built for (CASTRO_AMD_MAX_MULTIPOLE)"
+                         % (int(lnum), MAX_MULTIPOLE))
+    m = Multipole()
+    m.lnum, m.rmax, m.Gconst = int(lnum), multipole_rmax(geom), float(Gconst)
+    for d in range(3):
+        m.center[d] = float(center[d])
+    return m
+
+
+def poisson_level_extents(n_cell):
+    """the extents of the multigrid levels of a domain of n_cell zones: coarsened by 2 while every extent is even and the
+    coarsened extent is at least 2 (castro_amd_poisson_plan_create)"""
+    n = tuple(int(x) for x in n_cell)
+    out = [n]
+    while all(x % 2 == 0 and x // 2 >= 2 for x in n) and len(out) < 32:
+        n = tuple(x // 2 for x in n)
+        out.append(n)
+    return out
 
 
 class Rotation(C.Structure):
@@ -570,6 +616,18 @@ def load(numerics=None):
     if hasattr(L, "castro_amd_fab_pack"):                   # absent from A/B builds of revisions before checkpoints
         L.castro_amd_fab_pack.argtypes = [C.c_void_p, C.c_int, C.POINTER(PackEntry), C.c_void_p, C.c_void_p, C.c_void_p]
         L.castro_amd_fab_unpack.argtypes = [C.c_void_p, C.c_int, C.POINTER(PackEntry), C.c_void_p, C.c_void_p]
+    if hasattr(L, "castro_amd_poisson_solve"):              # absent from A/B builds of revisions before Poisson gravity
+        PMP = C.POINTER(Multipole)
+        L.castro_amd_multipole_moments_mf.argtypes = [C.c_void_p, C.c_int, C.POINTER(DiagBox), C.POINTER(Geom), PMP, C.c_void_p,
+                                                      C.c_void_p]
+        L.castro_amd_multipole_phi_bc_fab.argtypes = [C.c_void_p, PF, C.POINTER(Geom), PMP, C.c_void_p, C.c_void_p]
+        L.castro_amd_poisson_plan_create.argtypes = [C.c_void_p, C.POINTER(Geom), C.POINTER(C.c_void_p)]
+        L.castro_amd_poisson_plan_destroy.argtypes = [C.c_void_p, C.c_void_p]
+        L.castro_amd_poisson_plan_destroy.restype = None
+        L.castro_amd_poisson_solve.argtypes = [C.c_void_p, C.c_void_p, PF, PF, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
+                                               C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
+        L.castro_amd_poisson_level_op.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, PF, PF, PF, C.c_void_p, C.c_void_p]
+        L.castro_amd_grad_phi_to_grav_fab.argtypes = [C.c_void_p, PF, PF, C.POINTER(Geom), C.c_void_p]
     L.castro_amd_step_control.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_double, C.c_double,
                                           C.c_double, C.c_int, C.c_void_p]
     L.castro_amd_clean_state_fab.argtypes = [C.c_void_p, PF, I3, I3, C.POINTER(Params), C.c_int, C.c_void_p]

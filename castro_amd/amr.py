@@ -863,8 +863,9 @@ class CastroAmr(CheckpointMixin):
                  do_grav=False, const_grav=0.0, grav_source_type=4, rotation=None, comm=None, base_grid=None, box_streams=4,
                  diffusion=None, sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", gravity=None,
                  sponge=None, use_point_mass=False, point_mass=0.0, point_mass_fix_solution=False, ext_bc=None,
-                 update_sources_after_reflux=False, tracers=None, check_int=-1, check_file="chk"):
-        """check_int, check_file (amr.check_int, default -1: never / amr.check_file): evolve() writes the checkpoint
+                 update_sources_after_reflux=False, tracers=None, check_int=-1, check_file="chk", poisson=None):
+        """poisson: refused -- castro_amd.PoissonGravity is the single-level form (castro_amd.Castro).
+        check_int, check_file (amr.check_int, default -1: never / amr.check_file): evolve() writes the checkpoint
         check_file + "%05d" % nstep after every coarse step with nstep % check_int == 0, in the background
         (castro_amd/checkpoint.py: writeCheckpoint, restart -- the box lists of every level come from the file, nothing is
         clustered again --, checkpoint_wait, close).
@@ -905,6 +906,10 @@ class CastroAmr(CheckpointMixin):
         value_greater | value_less | gradient | relative_gradient) for boxes that follow the tags up to
         amr.max_level = max_level: one bounding box per level, or with cluster=True the Berger-Rigoutsos boxes
         (amr.grid_eff, amr.blocking_factor and amr.max_grid_size in zones of the new level)."""
+        if poisson is not None:
+            raise NotImplementedError("CastroAmr: Poisson gravity (poisson=...) is built for a single level only -- the level "
+                                      "solves, gravity_sync and the composite correction of the hierarchy are a follow-up; use "
+                                      "castro_amd.Castro")
         if diffusion is not None:
             # the operator of a refined level needs AMReX's coarse-fine boundary stencil [3P], which is not restated
             raise NotImplementedError("CastroAmr: thermal diffusion (diffusion=...) is built for a single level only; "

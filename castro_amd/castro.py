@@ -263,8 +263,13 @@ class Castro(CheckpointMixin):
                  alloc=True, numerics=None, proxy_ranks=1, diffusion=None, do_hydro=True,
                  sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", drdxfac=1, Gconst=L.GCONST,
                  gravity=None, sponge=None, use_point_mass=False, point_mass=0.0, point_mass_fix_solution=False, ext_bc=None,
-                 tracers=None, check_int=-1, check_file="chk"):
-        """check_int, check_file (amr.check_int, default -1: never / amr.check_file): evolve() writes the checkpoint
+                 tracers=None, check_int=-1, check_file="chk", poisson=None):
+        """poisson: a castro_amd.PoissonGravity (gravity.gravity_type = PoissonGrav; the string gravity_type keeps its two
+        values): with do_grav the gravity of every zone is -grad(phi) of the Poisson solve of the state -- multipole boundary
+        values, a multigrid on the device (castro_amd/gravity.py) -- in the grav_old / grav_new FABs the per-zone gravity sources
+        read.  Single level, one rank, 3-D Cartesian, no periodic and no Symmetry face; everything else raises.  phi_grav() and
+        poisson_stats() read the potential and the cycle counts.
+        check_int, check_file (amr.check_int, default -1: never / amr.check_file): evolve() writes the checkpoint
         check_file + "%05d" % nstep after every coarse step with nstep % check_int == 0, in the background
         (castro_amd/checkpoint.py: writeCheckpoint, restart, checkpoint_wait); its host-free batches end on multiples of
         check_int.  A caller's own run_steps batch that runs past a multiple writes nothing for it, as for the diagnostics.
@@ -368,6 +373,8 @@ class Castro(CheckpointMixin):
         if ext_bc is not None:
             if do_grav and (gravity_type == "monopole" or gravity is not None) and L.ext_bc_hse_faces(ext_bc, self.geom):
                 raise ValueError("HSE boundaries assume constant gravity: not with gravity_type=\"monopole\"")
+            if do_grav and poisson is not None and L.ext_bc_hse_faces(ext_bc, self.geom):
+                raise ValueError("HSE boundaries assume constant gravity: not with poisson=PoissonGravity(...)")
             L.check_ext_bc(ext_bc, self.geom)
             self.ext_bc = L.complete_ext_bc(ext_bc, self.params, const_grav if do_grav else 0.0)
             if alloc:
@@ -447,6 +454,9 @@ class Castro(CheckpointMixin):
                 self.center = gravity.center
         elif self.monopole:
             self._init_monopole(hydro_alloc, box)
+        self.poisson = None
+        if poisson is not None:
+            self._init_poisson(poisson, hydro_alloc, box, gravity_type, gravity, check_int)
         if self.use_point_mass and self.level_gravity is None:
             if box is not None:
                 raise NotImplementedError("a point mass on a refined patch belongs to the hierarchy: CastroAmr(use_point_mass=True, "
@@ -460,7 +470,7 @@ class Castro(CheckpointMixin):
                 self.grav_old = hydro_alloc(3, *self.gravbox)
                 self.grav_new = hydro_alloc(3, *self.gravbox)
         # the gravity of a zone comes from grav_old / grav_new instead of the one vector self.grav
-        self.grav_fab = self.monopole or (self.use_point_mass and self.do_grav)
+        self.grav_fab = self.monopole or self.poisson is not None or (self.use_point_mass and self.do_grav)
         # castro.do_rotation: `rotation` = _lib.make_rotation(rotational_period, rot_axis, ...)
         self.rotation = rotation
         # castro.diffuse_temp = 1: `diffusion` = _lib.make_diffusion(const_conductivity, ...); castro.do_hydro
@@ -500,7 +510,8 @@ class Castro(CheckpointMixin):
     # ----------------------------------------------------------------------------------------
     def close(self):
         """Give back what lives outside torch's allocator: the C-ABI halo plans of this object (two packed device buffers
-        each).  The RCCL communicator of the C ABI belongs to the comm object (DistComm / SingleComm.close), which may serve
+        each) and, with Poisson gravity, the multigrid plan (the arrays of every level and a pinned word; a later step makes it
+        again).  The RCCL communicator of the C ABI belongs to the comm object (DistComm / SingleComm.close), which may serve
         several Castro objects.  Idempotent; never called while a stream is capturing (a free inside a capture aborts).
         A checkpoint in flight is joined first (checkpoint_wait): on more than one rank the call is then collective -- every
         rank calls it --, and what the writer thread raised is raised here, once, after the plans have been released all the same;
@@ -509,6 +520,8 @@ class Castro(CheckpointMixin):
             self.checkpoint_wait()
         finally:
             self._release_plans()
+            if getattr(self, "poisson", None) is not None:
+                self.poisson.close()
 
     def _release_plans(self):
         plans = getattr(self, "_plans", {})
@@ -851,6 +864,45 @@ class Castro(CheckpointMixin):
         self._radial_g = hydro_alloc(1, (0, 0, 0), (self.n1d - 1, 0, 0))
         self._mono_tables = {}
 
+    # ---- gravity.gravity_type = PoissonGrav on a single level (castro_amd/gravity.py: PoissonGravity) ---------------------
+    def _init_poisson(self, poisson, hydro_alloc, box, gravity_type, gravity, check_int):
+        if not self.do_grav:
+            raise ValueError("poisson=PoissonGravity(...) needs do_grav=True")
+        if gravity_type == "monopole" or gravity is not None:
+            raise ValueError("poisson=PoissonGravity(...) selects the gravity by itself: not together with gravity_type=\"monopole\" "
+                             "or gravity=MonopoleGravity(...)")
+        if box is not None:
+            raise NotImplementedError("Poisson gravity on a refined patch: the level solves, gravity_sync and the composite "
+                                      "correction of the AMR hierarchy are a follow-up")
+        if self.comm.size > 1:
+            raise NotImplementedError("Poisson gravity on more than one rank: the multigrid needs a halo exchange of phi on every "
+                                      "level and the moments a sum over the ranks -- a follow-up")
+        if self.use_point_mass:
+            raise NotImplementedError("use_point_mass with Poisson gravity (the point mass is excluded from the right-hand side "
+                                      "and added to the solution) is a follow-up")
+        if int(check_int) > 0:
+            raise NotImplementedError("check_int with Poisson gravity: a bit-faithful restart needs phi, the solver's starting "
+                                      "guess, in the checkpoint (the reference's SD_1) -- a follow-up")
+        poisson.bind(self, hydro_alloc)
+        self.poisson = poisson
+        self.gravbox = (tuple(x - 1 for x in self.lo), tuple(x + 1 for x in self.hi))
+        self.grav_old = hydro_alloc(3, *self.gravbox)
+        self.grav_new = hydro_alloc(3, *self.gravbox)
+
+    def phi_grav(self, new=True):
+        """the potential of the last new-time (or old-time) solve: the tensor (1, nz + 2, ny + 2, nx + 2), whose ghost zones
+        outside the domain hold the multipole boundary values on the domain faces"""
+        if self.poisson is None:
+            raise RuntimeError("phi_grav() needs Castro(do_grav=True, poisson=PoissonGravity(...))")
+        return self.poisson.phi_new if new else self.poisson.phi_old
+
+    def poisson_stats(self):
+        """{"first": ..., "old": ..., "new": ...}: cycles, final residual norm and norm history of the first solve of the run (from
+        zero) and of the last old-time and new-time solves (warm-started)"""
+        if self.poisson is None:
+            raise RuntimeError("poisson_stats() needs Castro(do_grav=True, poisson=PoissonGravity(...))")
+        return dict(self.poisson.stats)
+
     def monopole_params(self):
         """castro_amd_monopole_params of this run: n1d of the domain, max_radius_all_in_domain about the problem centre"""
         from . import diag
@@ -878,6 +930,8 @@ class Castro(CheckpointMixin):
         the monopole interpolation, then -- last -- the point mass over the whole grown FAB."""
         if self.monopole:
             self._monopole_gravity(S, grav)
+        elif self.poisson is not None:
+            self.poisson.construct(S, grav, grav is self.grav_new)
         else:
             grav.zero_()                        # grav.setVal(0.0, ng); grav.setVal(const_grav, AMREX_SPACEDIM - 1, 1, ng)
             grav[2].fill_(self.grav[2])
@@ -1339,6 +1393,8 @@ class Castro(CheckpointMixin):
 
     def _swap_state_time_levels(self):
         self.S_old_b, self.S_new_b = self.S_new_b, self.S_old_b
+        if self.poisson is not None:
+            self.poisson.swap_time_levels()
 
     def _save_old_state(self):
         return self.S_old_b.clone()

@@ -686,6 +686,7 @@ class CheckpointMixin:
         more than one rank: every rank writes its own boxes, rank 0 the text files; the rename follows a barrier.
         background=True: the pack launch and an asynchronous copy to pinned host memory are queued and the call returns; one
         thread writes the files; checkpoint_wait(), close() and the next writeCheckpoint join it and re-raise what it raised."""
+        self._refuse_poisson("writeCheckpoint")
         if dirname is None:
             dirname = "%s%05d" % (self.check_file, self.nstep)
         self._last_check = self.nstep
@@ -703,7 +704,13 @@ class CheckpointMixin:
 
     def restart(self, dirname):
         """Castro::restart: instead of initData, on an object made with the arguments of the run that wrote `dirname`"""
+        self._refuse_poisson("restart")
         return restart_from(dirname, self)
+
+    def _refuse_poisson(self, what):
+        if getattr(self, "poisson", None) is not None:
+            raise NotImplementedError("%s with Poisson gravity: a bit-faithful restart needs phi, the solver's starting guess, in "
+                                      "the checkpoint (the reference's SD_1) -- a follow-up" % what)
 
     def _checkpoint_due(self):
         return self.check_int > 0 and self.nstep % self.check_int == 0 and self.__dict__.get("_last_check") != self.nstep

@@ -39,6 +39,8 @@ struct castro_amd_ctx {
     TrMigrateWorkspace tr_migrate;                  // castro_amd_tracer_migrate_count -> _pack: per-block counts per rank
     StagedTable pack_arena;                         // castro_amd_fab_pack / castro_amd_fab_unpack
     DiagWorkspace pack_ws;                          // castro_amd_fab_pack: one (min, max) pair per workgroup
+    StagedTable mp_arena;                           // castro_amd_multipole_moments_mf
+    DiagWorkspace mp_ws;                            // its rows of partial sums, one per workgroup and order m
 };
 
 namespace cad {
@@ -249,8 +251,9 @@ void castro_amd_ctx_destroy(castro_amd_ctx* c)
     if (c->ev_join) hipEventDestroy(c->ev_join);
     if (c->mf_fork) hipEventDestroy(c->mf_fork);
     if (c->mf_join) hipEventDestroy(c->mf_join);
-    for (StagedTable* t : { &c->ops_arena, &c->level_arena, &c->diff_arena, &c->diag_arena, &c->pack_arena }) t->release();
+    for (StagedTable* t : { &c->ops_arena, &c->level_arena, &c->diff_arena, &c->diag_arena, &c->pack_arena, &c->mp_arena }) t->release();
     if (c->diag_ws.p) hipFree(c->diag_ws.p);
+    if (c->mp_ws.p) hipFree(c->mp_ws.p);
     if (c->pack_ws.p) hipFree(c->pack_ws.p);
     mono_workspace_free(&c->mono_ws);
     c->pm_tables.release();
@@ -1052,6 +1055,157 @@ int castro_amd_monopole_grav_fab(castro_amd_ctx* c, const double* d_radial_grav,
     if (rg != CASTRO_AMD_OK) return rg;
     hipSetDevice(c->device);
     return launch_monopole_grav(d_radial_grav, G, to_dfab(grav_fab), grav_fab->lo, grav_fab->hi, (hipStream_t)stream, &c->prof);
+}
+
+// ---- Poisson gravity on a single level (poisson_kernels.hip) -------------------------------------------------------------------
+// Cartesian, and every face a Dirichlet face of the potential: not periodic / interior (0), not Symmetry (3)
+static int poisson_geom_ok(const castro_amd_geom* geom)
+{
+    if (!geom) return CASTRO_AMD_ERR_ARG;
+    if (geom->coord != 0) return CASTRO_AMD_ERR_UNSUPPORTED;
+    for (int d = 0; d < 3; ++d) {
+        if (!(geom->dx[d] > 0.0) || geom->domhi[d] < geom->domlo[d]) return CASTRO_AMD_ERR_ARG;
+        if (geom->lo_bc[d] == 0 || geom->hi_bc[d] == 0 || geom->lo_bc[d] == 3 || geom->hi_bc[d] == 3) return CASTRO_AMD_ERR_UNSUPPORTED;
+    }
+    return CASTRO_AMD_OK;
+}
+
+static int mp_geom(const castro_amd_geom* geom, const castro_amd_multipole* mp, MpGeom& G)
+{
+    if (!mp) return CASTRO_AMD_ERR_ARG;
+    const int rg = poisson_geom_ok(geom);
+    if (rg != CASTRO_AMD_OK) return rg;
+    if (mp->lnum < 0 || !(mp->rmax > 0.0)) return CASTRO_AMD_ERR_ARG;
+    if (mp->lnum > CASTRO_AMD_MAX_MULTIPOLE) return CASTRO_AMD_ERR_UNSUPPORTED;
+    for (int d = 0; d < 3; ++d) {
+        G.dx[d] = geom->dx[d]; G.problo[d] = geom->problo[d]; G.center[d] = mp->center[d];
+        G.domlo[d] = geom->domlo[d]; G.domhi[d] = geom->domhi[d];
+    }
+    G.rmax = mp->rmax; G.Gconst = mp->Gconst; G.lnum = mp->lnum;
+    return CASTRO_AMD_OK;
+}
+
+int castro_amd_multipole_moments_mf(castro_amd_ctx* c, int nboxes, const castro_amd_diag_box* boxes, const castro_amd_geom* geom,
+                                    const castro_amd_multipole* mp, double* d_moments, void* stream)
+{
+    if (!c || !d_moments) return CASTRO_AMD_ERR_ARG;
+    MpGeom G;
+    const int rg = mp_geom(geom, mp, G);
+    if (rg != CASTRO_AMD_OK) return rg;
+    std::vector<DiagBoxDev> tab;
+    const int rt = diag_table(nboxes, boxes, tab);
+    if (rt != CASTRO_AMD_OK) return rt;
+    hipSetDevice(c->device);
+    return launch_multipole_moments(nboxes, tab.data(), G, &c->mp_arena, &c->mp_ws, d_moments, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_multipole_phi_bc_fab(castro_amd_ctx* c, const castro_amd_fab* phi_fab, const castro_amd_geom* geom,
+                                    const castro_amd_multipole* mp, const double* d_moments, void* stream)
+{
+    if (!c || !phi_fab || !phi_fab->p || phi_fab->ncomp != 1 || !d_moments) return CASTRO_AMD_ERR_ARG;
+    MpGeom G;
+    const int rg = mp_geom(geom, mp, G);
+    if (rg != CASTRO_AMD_OK) return rg;
+    for (int d = 0; d < 3; ++d) if (phi_fab->hi[d] < phi_fab->lo[d]) return CASTRO_AMD_ERR_ARG;
+    hipSetDevice(c->device);
+    return launch_multipole_phi_bc(to_dfab(phi_fab), phi_fab->lo, phi_fab->hi, G, d_moments, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_poisson_plan_create(castro_amd_ctx* c, const castro_amd_geom* geom, castro_amd_poisson_plan** plan)
+{
+    if (!c || !plan) return CASTRO_AMD_ERR_ARG;
+    const int rg = poisson_geom_ok(geom);
+    if (rg != CASTRO_AMD_OK) return rg;
+    int n[3];
+    for (int d = 0; d < 3; ++d) n[d] = geom->domhi[d] - geom->domlo[d] + 1;
+    // the level table first: a refusal costs no device memory (and needs no device)
+    std::vector<MgLevel> lev;
+    const int rl = poisson_levels(n, geom->domlo, geom->dx, lev);
+    if (rl != 0) return rl;
+    hipSetDevice(c->device);
+    PoissonPlan* P = nullptr;
+    const int rc = poisson_plan_make(n, geom->domlo, geom->dx, &P);
+    if (rc != 0) return rc;
+    *plan = reinterpret_cast<castro_amd_poisson_plan*>(P);
+    return CASTRO_AMD_OK;
+}
+
+void castro_amd_poisson_plan_destroy(castro_amd_ctx* c, castro_amd_poisson_plan* plan)
+{
+    if (!c || !plan) return;
+    hipSetDevice(c->device);
+    hipDeviceSynchronize();
+    poisson_plan_free(reinterpret_cast<PoissonPlan*>(plan));
+}
+
+// does `f` hold the box of level L grown by ng zones?
+static bool mg_fab_ok(const castro_amd_fab* f, const MgLevel& L, int ng)
+{
+    if (!f || !f->p || f->ncomp < 1) return false;
+    int lo[3], hi[3];
+    for (int d = 0; d < 3; ++d) { lo[d] = L.lo[d] - ng; hi[d] = L.lo[d] + L.n[d] - 1 + ng; }
+    return fab_contains(f, lo, hi);
+}
+
+int castro_amd_poisson_solve(castro_amd_ctx* c, castro_amd_poisson_plan* plan, const castro_amd_fab* phi_fab,
+                             const castro_amd_fab* rho_fab, int rho_comp, double fourpiG, double reltol, double abstol, int maxiter,
+                             int* cycles, int* converged, double* final_norm, double* h_history, void* stream)
+{
+    if (!c || !plan || !cycles || !converged || !final_norm || maxiter < 0) return CASTRO_AMD_ERR_ARG;
+    PoissonPlan* P = reinterpret_cast<PoissonPlan*>(plan);
+    const MgLevel& L0 = P->lev[0];
+    if (!mg_fab_ok(phi_fab, L0, 1) || phi_fab->ncomp != 1 || !mg_fab_ok(rho_fab, L0, 0)) return CASTRO_AMD_ERR_ARG;
+    if (rho_comp < 0 || rho_comp >= rho_fab->ncomp) return CASTRO_AMD_ERR_ARG;
+    hipSetDevice(c->device);
+    return launch_poisson_solve(P, to_dfab(phi_fab), to_dfab(rho_fab), rho_comp, fourpiG, reltol, abstol, maxiter, cycles, converged,
+                                final_norm, h_history, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_poisson_level_op(castro_amd_ctx* c, castro_amd_poisson_plan* plan, int op, int level, int colour,
+                                const castro_amd_fab* a, const castro_amd_fab* b, const castro_amd_fab* f3, double* d_out, void* stream)
+{
+    if (!c || !plan) return CASTRO_AMD_ERR_ARG;
+    PoissonPlan* P = reinterpret_cast<PoissonPlan*>(plan);
+    const int nl = (int)P->lev.size();
+    if (level < 0 || level >= nl) return CASTRO_AMD_ERR_ARG;
+    const MgLevel& L = P->lev[(size_t)level];
+    hipStream_t s = (hipStream_t)stream;
+    hipSetDevice(c->device);
+    switch (op) {
+    case CASTRO_AMD_MG_SMOOTH:
+        if ((colour != 0 && colour != 1) || !mg_fab_ok(a, L, 1) || !mg_fab_ok(b, L, 0)) return CASTRO_AMD_ERR_ARG;
+        return launch_mg_smooth(to_dfab(a), to_dfab(b), L, colour, s, &c->prof);
+    case CASTRO_AMD_MG_RESIDUAL:
+        if (!mg_fab_ok(a, L, 1) || !mg_fab_ok(b, L, 0) || !mg_fab_ok(f3, L, 0)) return CASTRO_AMD_ERR_ARG;
+        return launch_mg_residual(to_dfab(a), to_dfab(b), to_dfab(f3), L, s, &c->prof);
+    case CASTRO_AMD_MG_RESTRICT:
+        if (level + 1 >= nl) return CASTRO_AMD_ERR_ARG;
+        if (!mg_fab_ok(a, L, 0) || !mg_fab_ok(b, P->lev[(size_t)level + 1], 0) || !mg_fab_ok(f3, P->lev[(size_t)level + 1], 0)) return CASTRO_AMD_ERR_ARG;
+        return launch_mg_restrict(to_dfab(a), L, to_dfab(b), to_dfab(f3), P->lev[(size_t)level + 1], s, &c->prof);
+    case CASTRO_AMD_MG_PROLONG:
+        if (level + 1 >= nl) return CASTRO_AMD_ERR_ARG;
+        if (!mg_fab_ok(a, P->lev[(size_t)level + 1], 0) || !mg_fab_ok(b, L, 0)) return CASTRO_AMD_ERR_ARG;
+        return launch_mg_prolong(to_dfab(a), P->lev[(size_t)level + 1], to_dfab(b), L, s, &c->prof);
+    case CASTRO_AMD_MG_NORM:
+        if (!mg_fab_ok(a, L, 0) || !d_out) return CASTRO_AMD_ERR_ARG;
+        return launch_mg_norm(to_dfab(a), L, P->norm_ws, d_out, s, &c->prof);
+    default:
+        return CASTRO_AMD_ERR_ARG;
+    }
+}
+
+int castro_amd_grad_phi_to_grav_fab(castro_amd_ctx* c, const castro_amd_fab* phi_fab, const castro_amd_fab* grav_fab,
+                                    const castro_amd_geom* geom, void* stream)
+{
+    if (!c) return CASTRO_AMD_ERR_ARG;
+    const int rg = poisson_geom_ok(geom);
+    if (rg != CASTRO_AMD_OK) return rg;
+    MgLevel L;
+    std::memset(&L, 0, sizeof(L));
+    for (int d = 0; d < 3; ++d) { L.lo[d] = geom->domlo[d]; L.n[d] = geom->domhi[d] - geom->domlo[d] + 1; }
+    if (!mg_fab_ok(phi_fab, L, 1) || phi_fab->ncomp != 1 || !mg_fab_ok(grav_fab, L, 0) || grav_fab->ncomp != 3) return CASTRO_AMD_ERR_ARG;
+    hipSetDevice(c->device);
+    return launch_grad_phi(to_dfab(phi_fab), to_dfab(grav_fab), L, geom->dx, (hipStream_t)stream, &c->prof);
 }
 
 // a gravity FAB of the _gfab source calls: 3 components, one ghost zone around [lo, hi] where the energy term reads neighbours

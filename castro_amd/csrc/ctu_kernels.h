@@ -230,6 +230,36 @@ int launch_grav_bc_fill(const DFab& F, const int flo[3], const int fhi[3], const
 int launch_radial_gravity(const MonoGeom& G, const double* d_mass_vol, double* d_radial_grav, hipStream_t stream, Profiler* prof);
 int launch_monopole_grav(const double* d_radial_grav, const MonoGeom& G, const DFab& F, const int lo[3], const int hi[3],
                          hipStream_t stream, Profiler* prof);
+// Poisson gravity (poisson_kernels.hip).  One level of the multigrid: its box [lo, lo + n), cx = 1 / (hx hx) ... and
+// cdiag = 2 ((cx + cy) + cz), formed on the host (poisson_levels) so that a restatement can form the same bits
+constexpr int MG_MAX_LEVELS = 32;
+constexpr int MG_NPRE = 2, MG_NPOST = 2, MG_NBOTTOM = 32;      // red-black sweeps before / after the coarser levels, and of the bottom solve
+struct MgLevel { int n[3], lo[3]; double cx, cy, cz, cdiag; };
+// what a plan owns: the levels, the arrays of every level (phi[0] is the caller's FAB, set per solve; the ghost zones of the
+// coarser phi stay zero), two device norms per reduction, the workgroup maxima behind them and a pinned host copy
+struct PoissonPlan {
+    std::vector<MgLevel> lev;
+    std::vector<DFab> phi, rhs, res;
+    std::vector<double*> owned;
+    double dx[3];
+    double* d_norm = nullptr; double* norm_ws = nullptr; double* h_norm = nullptr;
+};
+int poisson_levels(const int n[3], const int lo[3], const double dx[3], std::vector<MgLevel>& lev);
+int poisson_plan_make(const int n[3], const int lo[3], const double dx[3], PoissonPlan** out);
+void poisson_plan_free(PoissonPlan* P);
+int launch_mg_smooth(const DFab& P, const DFab& B, const MgLevel& L, int colour, hipStream_t s, Profiler* prof);
+int launch_mg_residual(const DFab& P, const DFab& B, const DFab& R, const MgLevel& L, hipStream_t s, Profiler* prof);
+int launch_mg_restrict(const DFab& RF, const MgLevel& LF, const DFab& BC, const DFab& PC, const MgLevel& LC, hipStream_t s, Profiler* prof);
+int launch_mg_prolong(const DFab& PC, const MgLevel& LC, const DFab& PF, const MgLevel& LF, hipStream_t s, Profiler* prof);
+int launch_mg_norm(const DFab& X, const MgLevel& L, double* ws, double* d_out, hipStream_t s, Profiler* prof);
+// h_history (or nullptr): ||b||, max b, the norm of the starting residual, then the norm after every cycle (maxiter + 3 doubles)
+int launch_poisson_solve(PoissonPlan* P, const DFab& phi, const DFab& U, int comp, double fourpiG, double reltol, double abstol,
+                         int maxiter, int* cycles, int* converged, double* final_norm, double* h_history, hipStream_t s, Profiler* prof);
+int launch_grad_phi(const DFab& phi, const DFab& G, const MgLevel& L, const double dx[3], hipStream_t s, Profiler* prof);
+struct MpGeom { double dx[3], problo[3], center[3]; double rmax, Gconst; int lnum; int domlo[3], domhi[3]; };
+// d_out: 3 (lnum + 1)^2 doubles, [kind][l][m], kind 0 = qL0 (m = 0), 1 = qLC, 2 = qLS; ws: rows of MP_NC doubles
+int launch_multipole_moments(int nbox, DiagBoxDev* boxes, const MpGeom& G, StagedTable* arena, DiagWorkspace* ws, double* d_out,
+                             hipStream_t stream, Profiler* prof);
 // the central point mass (pointmass_kernels.hip).  One gravity FAB of a castro_amd_add_pointmass_* launch: its whole box
 // [lo, lo + n), ghost zones included; start: the first thread of the FAB, set by the launcher.  One box of a
 // castro_amd_pointmass_delta_mf / _apply_mf launch: the valid zones [lo, hi] of the old and the new state.  Both tables are
@@ -323,6 +353,9 @@ inline Slabs shell_slabs(const int flo[3], const int fhi[3], const int blo[3], c
     }
     return S;
 }
+// the multipole boundary potential on the zones of [flo, fhi] outside the domain (poisson_kernels.hip)
+int launch_multipole_phi_bc(const DFab& F, const int flo[3], const int fhi[3], const MpGeom& G, const double* d_q, hipStream_t stream,
+                            Profiler* prof);
 // the second half of the physical-boundary fill of a state FAB (extbc_kernels.hip): ambient_fill, then hse_fill
 int launch_ext_bc_fill(const DFab& U, const int flo[3], const int fhi[3], const ::castro_amd_geom* geom, const DevParams& P,
                        const ::castro_amd_ext_bc* ext, int* d_unconverged, hipStream_t stream, Profiler* prof);

@@ -1,0 +1,754 @@
+// poisson_kernels.hip -- gravity.gravity_type = "PoissonGrav" on a single level, 3-D Cartesian, Dirichlet on all six faces:
+//   k_mg_rhs                              b = (4 pi G) * rho
+//   k_mg_smooth, k_mg_bottom              red-black Gauss-Seidel on one level; the bottom solve is the same sweep, all of them
+//                                         in one launch of one workgroup
+//   k_mg_residual, k_mg_restrict, k_mg_prolong, k_mg_norm_partial + k_mg_norm_final
+//                                         the other four passes of the V-cycle
+//   k_grad_phi                            g = -grad(phi) on the valid zones (Gravity.cpp:874-878 over MLMG's getGradSolution)
+//   k_mp_partial + k_mp_final             the multipole moments of Gravity::fill_multipole_BCs (Gravity.cpp:1742-2032, multipole_add
+//                                         of Gravity_util.H) with boundary_only = 1: every zone falls in the last radial bin
+//   k_mp_phi_bc                           the boundary potential (Gravity.cpp:2066-2216) on the zones of a FAB outside the domain
+// The multigrid is AMReX's [3P]: its arithmetic is not in the reference tree and is not pinned.  It is
+// written so that a restatement with the same order of operations reproduces the `exact` build bit for bit: the header comment
+// of every pass gives that order, and the passes hold no transcendental.  The `contract` build fuses these passes' multiply-adds.
+// The multipole kernels (the second half of the file) are compiled without contraction in BOTH builds: their terms go through
+// pow / atan2 / sin / cos, whose arguments must be the restatement's bits for a per-call allowance to mean anything (the Makefile
+// gives this file -ffp-contract=fast-honor-pragmas in the `contract` build, so that the pragma in front of them holds).
+// No floating-point atomics anywhere: the moments are summed in two stages in an order fixed by the box table (the same bits on
+// every call; across streams as long as the host orders the calls of a context, which has one workspace), the norm is a
+// maximum.  A zone centred exactly on the multipole centre has r = 0 and cosTheta = 0 / 0, here as in Gravity.cpp:1917: NaN
+// moments for l >= 1 (include/castro_hydro_amd.h).  Everything runs on the caller's stream; the solve reads one norm back per V-cycle.
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <cstring>
+#include <cmath>
+#include <vector>
+#include "../../include/castro_hydro_amd.h"
+#include "hydro_device.h"
+#include "ctu_kernels.h"
+
+namespace cad {
+
+constexpr int MG_WG = 256;
+constexpr int MG_BOTTOM_WG = 1024;
+constexpr int MG_NORM_MAX_WG = 1024;
+
+__device__ __forceinline__ long mg_at(const DFab& F, int i, int j, int k)
+{
+    return (long)(i - F.lo[0]) + F.sy * (long)(j - F.lo[1]) + F.sz * (long)(k - F.lo[2]);
+}
+
+// thread q of a colour launch -> the zone (ii, jj, kk) of that colour, relative to the level's box: the row (jj, kk) is cut into
+// x-pairs (2 ip, 2 ip + 1) and the thread takes the one with (ii + jj + kk) & 1 == colour.  false: no such zone
+__device__ __forceinline__ bool mg_colour_zone(long q, const MgLevel& L, int colour, int& ii, int& jj, int& kk)
+{
+    const int npair = (L.n[0] + 1) >> 1;
+    const int ip = (int)(q % npair);
+    const long r = q / npair;
+    jj = (int)(r % L.n[1]);
+    kk = (int)(r / L.n[1]);
+    ii = 2 * ip + ((jj + kk + colour) & 1);
+    return ii < L.n[0];
+}
+
+// The smoother, one zone.  With p the zone's value, the six neighbours xm, xp, ym, yp, zm, zp and the right-hand side b:
+//   a neighbour beyond a domain face is replaced by 2.0 * (the ghost value), the ghost holding phi ON the face (level 0) or 0
+//   (coarser levels); the - p of the linear ghost 2 phi_face - p goes to the diagonal:
+//   dg = cdiag; if (low x face) dg = dg + cx; if (high x face) dg = dg + cx; then y, then z (cdiag = 2.0 * ((cx + cy) + cz),
+//   cx = 1.0 / (hx * hx), ... formed on the host)
+//   p = (((cx * (xm + xp) + cy * (ym + yp)) + cz * (zm + zp)) - b) / dg
+__device__ __forceinline__ double mg_relax(const DFab& P, const DFab& B, const MgLevel& L, int ii, int jj, int kk)
+{
+    const long c = mg_at(P, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk);
+    const double* p = P.p + c;
+    const bool xl = ii == 0, xh = ii == L.n[0] - 1, yl = jj == 0, yh = jj == L.n[1] - 1, zl = kk == 0, zh = kk == L.n[2] - 1;
+    double xm = p[-1], xp = p[1], ym = p[-P.sy], yp = p[P.sy], zm = p[-P.sz], zp = p[P.sz];
+    double dg = L.cdiag;
+    if (xl) { xm = 2.0 * xm; dg = dg + L.cx; }
+    if (xh) { xp = 2.0 * xp; dg = dg + L.cx; }
+    if (yl) { ym = 2.0 * ym; dg = dg + L.cy; }
+    if (yh) { yp = 2.0 * yp; dg = dg + L.cy; }
+    if (zl) { zm = 2.0 * zm; dg = dg + L.cz; }
+    if (zh) { zp = 2.0 * zp; dg = dg + L.cz; }
+    const double b = B.p[mg_at(B, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk)];
+    const double off = (L.cx * (xm + xp) + L.cy * (ym + yp)) + L.cz * (zm + zp);
+    return (off - b) / dg;
+}
+
+// One sweep of one colour: every zone of that colour is replaced by mg_relax of its neighbours, which are all of the other
+// colour -- the order of the zones within the sweep does not matter
+__global__ void __launch_bounds__(MG_WG) k_mg_smooth(DFab P, DFab B, MgLevel L, int colour)
+{
+    const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
+    const int npair = (L.n[0] + 1) >> 1;
+    if (q >= (long)npair * L.n[1] * L.n[2]) return;
+    int ii, jj, kk;
+    if (!mg_colour_zone(q, L, colour, ii, jj, kk)) return;
+    const double v = mg_relax(P, B, L, ii, jj, kk);
+    P.p[mg_at(P, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk)] = v;
+}
+
+// The bottom solve: `sweeps` times colour 0, then colour 1, of k_mg_smooth's arithmetic by ONE workgroup (the coarsest level holds
+// at most CASTRO_AMD_POISSON_MAX_BOTTOM zones); a barrier separates the colours
+__global__ void __launch_bounds__(MG_BOTTOM_WG) k_mg_bottom(DFab P, DFab B, MgLevel L, int sweeps)
+{
+    const int npair = (L.n[0] + 1) >> 1;
+    const long nq = (long)npair * L.n[1] * L.n[2];
+    for (int s = 0; s < sweeps; ++s) {
+        for (int colour = 0; colour < 2; ++colour) {
+            for (long q = threadIdx.x; q < nq; q += MG_BOTTOM_WG) {
+                int ii, jj, kk;
+                if (!mg_colour_zone(q, L, colour, ii, jj, kk)) continue;
+                const double v = mg_relax(P, B, L, ii, jj, kk);
+                P.p[mg_at(P, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk)] = v;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// The residual.  A neighbour beyond a domain face is the linear ghost 2.0 * (ghost value) - p;
+//   lap = (cx * ((xm + xp) - 2.0 * p) + cy * ((ym + yp) - 2.0 * p)) + cz * ((zm + zp) - 2.0 * p);   r = b - lap
+__global__ void __launch_bounds__(MG_WG) k_mg_residual(DFab P, DFab B, DFab R, MgLevel L)
+{
+    const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
+    if (q >= (long)L.n[0] * L.n[1] * L.n[2]) return;
+    const int ii = (int)(q % L.n[0]);
+    const long rr = q / L.n[0];
+    const int jj = (int)(rr % L.n[1]), kk = (int)(rr / L.n[1]);
+    const int i = L.lo[0] + ii, j = L.lo[1] + jj, k = L.lo[2] + kk;
+    const double* p = P.p + mg_at(P, i, j, k);
+    const double pc = p[0];
+    double xm = p[-1], xp = p[1], ym = p[-P.sy], yp = p[P.sy], zm = p[-P.sz], zp = p[P.sz];
+    if (ii == 0) xm = 2.0 * xm - pc;
+    if (ii == L.n[0] - 1) xp = 2.0 * xp - pc;
+    if (jj == 0) ym = 2.0 * ym - pc;
+    if (jj == L.n[1] - 1) yp = 2.0 * yp - pc;
+    if (kk == 0) zm = 2.0 * zm - pc;
+    if (kk == L.n[2] - 1) zp = 2.0 * zp - pc;
+    const double tp = 2.0 * pc;
+    const double lap = (L.cx * ((xm + xp) - tp) + L.cy * ((ym + yp) - tp)) + L.cz * ((zm + zp) - tp);
+    R.p[mg_at(R, i, j, k)] = B.p[mg_at(B, i, j, k)] - lap;
+}
+
+// The restriction onto the coarse zone (I, J, K) of the level L (the COARSE one; its children are 2 I + a, 2 J + b, 2 K + c
+// relative to the fine box, whose low corner is flo): with r_abc the children's residuals,
+//   b_c = (((((((r000 + r100) + r010) + r110) + r001) + r101) + r011) + r111) * 0.125
+// and the coarse correction starts from zero: phi_c = 0
+__global__ void __launch_bounds__(MG_WG) k_mg_restrict(DFab RF, int flo0, int flo1, int flo2, DFab BC, DFab PC, MgLevel L)
+{
+    const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
+    if (q >= (long)L.n[0] * L.n[1] * L.n[2]) return;
+    const int ii = (int)(q % L.n[0]);
+    const long rr = q / L.n[0];
+    const int jj = (int)(rr % L.n[1]), kk = (int)(rr / L.n[1]);
+    const double* r = RF.p + mg_at(RF, flo0 + 2 * ii, flo1 + 2 * jj, flo2 + 2 * kk);
+    double s = r[0] + r[1];
+    s = s + r[RF.sy];
+    s = s + r[RF.sy + 1];
+    s = s + r[RF.sz];
+    s = s + r[RF.sz + 1];
+    s = s + r[RF.sz + RF.sy];
+    s = s + r[RF.sz + RF.sy + 1];
+    const int i = L.lo[0] + ii, j = L.lo[1] + jj, k = L.lo[2] + kk;
+    BC.p[mg_at(BC, i, j, k)] = s * 0.125;
+    PC.p[mg_at(PC, i, j, k)] = 0.0;
+}
+
+// The prolongation onto the fine zone (ii, jj, kk) of the level L (the FINE one; clo: the low corner of the coarse box):
+//   phi_f = phi_f + phi_c(ii / 2, jj / 2, kk / 2)
+__global__ void __launch_bounds__(MG_WG) k_mg_prolong(DFab PC, int clo0, int clo1, int clo2, DFab PF, MgLevel L)
+{
+    const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
+    if (q >= (long)L.n[0] * L.n[1] * L.n[2]) return;
+    const int ii = (int)(q % L.n[0]);
+    const long rr = q / L.n[0];
+    const int jj = (int)(rr % L.n[1]), kk = (int)(rr / L.n[1]);
+    const long f = mg_at(PF, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk);
+    PF.p[f] = PF.p[f] + PC.p[mg_at(PC, clo0 + (ii >> 1), clo1 + (jj >> 1), clo2 + (kk >> 1))];
+}
+
+// b = fourpiG * rho on the zones of level 0
+__global__ void __launch_bounds__(MG_WG) k_mg_rhs(DFab U, int comp, DFab B, MgLevel L, double fourpiG)
+{
+    const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
+    if (q >= (long)L.n[0] * L.n[1] * L.n[2]) return;
+    const int i = L.lo[0] + (int)(q % L.n[0]);
+    const long rr = q / L.n[0];
+    const int j = L.lo[1] + (int)(rr % L.n[1]), k = L.lo[2] + (int)(rr / L.n[1]);
+    B.p[mg_at(B, i, j, k)] = fourpiG * U.p[mg_at(U, i, j, k) + U.sn * comp];
+}
+
+// a maximum that keeps a NaN once it has seen one
+__device__ __forceinline__ double mg_max(double m, double v) { return (v > m || v != v) ? v : m; }
+
+// The norm.  out[0] = max |x|, out[1] = max x over the zones of the level; a NaN anywhere gives NaN.  A maximum does not depend
+// on the order it is taken in
+__global__ void __launch_bounds__(MG_WG) k_mg_norm_partial(DFab X, MgLevel L, double* __restrict__ ws)
+{
+    const long total = (long)L.n[0] * L.n[1] * L.n[2];
+    double ma = 0.0, mx = -HUGE_VAL;
+    for (long q = (long)blockIdx.x * MG_WG + threadIdx.x; q < total; q += (long)gridDim.x * MG_WG) {
+        const int i = L.lo[0] + (int)(q % L.n[0]);
+        const long rr = q / L.n[0];
+        const int j = L.lo[1] + (int)(rr % L.n[1]), k = L.lo[2] + (int)(rr / L.n[1]);
+        const double v = X.p[mg_at(X, i, j, k)];
+        ma = mg_max(ma, fabs(v));
+        mx = mg_max(mx, v);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        ma = mg_max(ma, __shfl_down(ma, off, 64));
+        mx = mg_max(mx, __shfl_down(mx, off, 64));
+    }
+    __shared__ double sa[MG_WG / 64][2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { sa[wave][0] = ma; sa[wave][1] = mx; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        double m = sa[0][threadIdx.x];
+        for (int w = 1; w < MG_WG / 64; ++w) m = mg_max(m, sa[w][threadIdx.x]);
+        ws[2 * (long)blockIdx.x + threadIdx.x] = m;
+    }
+}
+
+__global__ void __launch_bounds__(MG_NORM_MAX_WG) k_mg_norm_final(const double* __restrict__ ws, int nrows, double* __restrict__ out)
+{
+    double ma = 0.0, mx = -HUGE_VAL;
+    if ((int)threadIdx.x < nrows) { ma = ws[2 * threadIdx.x]; mx = ws[2 * threadIdx.x + 1]; }
+    for (int off = 32; off > 0; off >>= 1) {
+        ma = mg_max(ma, __shfl_down(ma, off, 64));
+        mx = mg_max(mx, __shfl_down(mx, off, 64));
+    }
+    __shared__ double sa[MG_NORM_MAX_WG / 64][2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { sa[wave][0] = ma; sa[wave][1] = mx; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        double m = sa[0][threadIdx.x];
+        for (int w = 1; w < MG_NORM_MAX_WG / 64; ++w) m = mg_max(m, sa[w][threadIdx.x]);
+        out[threadIdx.x] = m;
+    }
+}
+
+// Gravity from phi on the zones of level 0 (one ghost zone of phi holds the face values): face gradients
+//   gl = (p - xm) / hx, gh = (xp - p) / hx, at a domain face gl = (2.0 * (p - xm)) / hx, gh = (2.0 * (xp - p)) / hx (the linear ghost);
+//   g_x = -(0.5 * (gl + gh)), and the same in y and z
+__global__ void __launch_bounds__(MG_WG) k_grad_phi(DFab P, DFab G, MgLevel L, double hx, double hy, double hz)
+{
+    const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
+    if (q >= (long)L.n[0] * L.n[1] * L.n[2]) return;
+    const int ii = (int)(q % L.n[0]);
+    const long rr = q / L.n[0];
+    const int jj = (int)(rr % L.n[1]), kk = (int)(rr / L.n[1]);
+    const int i = L.lo[0] + ii, j = L.lo[1] + jj, k = L.lo[2] + kk;
+    const double* p = P.p + mg_at(P, i, j, k);
+    const double pc = p[0];
+    double dl[3] = { pc - p[-1], pc - p[-P.sy], pc - p[-P.sz] };
+    double dh[3] = { p[1] - pc, p[P.sy] - pc, p[P.sz] - pc };
+    const int rel[3] = { ii, jj, kk };
+    const double h[3] = { hx, hy, hz };
+    const long g = mg_at(G, i, j, k);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        if (rel[d] == 0) dl[d] = 2.0 * dl[d];
+        if (rel[d] == L.n[d] - 1) dh[d] = 2.0 * dh[d];
+        const double gl = dl[d] / h[d], gh = dh[d] / h[d];
+        G.p[g + G.sn * d] = -(0.5 * (gl + gh));
+    }
+}
+
+// ---- the plan and the V-cycle -------------------------------------------------------------------------------------------------
+static unsigned mg_blocks(long n) { return (unsigned)((n + MG_WG - 1) / MG_WG); }
+static long mg_zones(const MgLevel& L) { return (long)L.n[0] * L.n[1] * L.n[2]; }
+static long mg_pairs(const MgLevel& L) { return (long)((L.n[0] + 1) >> 1) * L.n[1] * L.n[2]; }
+
+int poisson_levels(const int n[3], const int lo[3], const double dx[3], std::vector<MgLevel>& lev)
+{
+    lev.clear();
+    MgLevel L;
+    std::memset(&L, 0, sizeof(L));
+    double h[3];
+    for (int d = 0; d < 3; ++d) {
+        if (n[d] < 1 || !(dx[d] > 0.0)) return CASTRO_AMD_ERR_ARG;
+        L.n[d] = n[d]; L.lo[d] = lo[d]; h[d] = dx[d];
+    }
+    for (;;) {
+        L.cx = 1.0 / (h[0] * h[0]); L.cy = 1.0 / (h[1] * h[1]); L.cz = 1.0 / (h[2] * h[2]);
+        L.cdiag = 2.0 * ((L.cx + L.cy) + L.cz);
+        lev.push_back(L);
+        bool more = (int)lev.size() < MG_MAX_LEVELS;
+        for (int d = 0; d < 3; ++d) more = more && L.n[d] % 2 == 0 && L.n[d] / 2 >= 2;
+        if (!more) break;
+        for (int d = 0; d < 3; ++d) { L.n[d] /= 2; L.lo[d] = L.lo[d] >> 1; h[d] = 2.0 * h[d]; }
+    }
+    if (mg_zones(lev.back()) > CASTRO_AMD_POISSON_MAX_BOTTOM) return CASTRO_AMD_ERR_UNSUPPORTED;
+    return 0;
+}
+
+void poisson_plan_free(PoissonPlan* P)
+{
+    if (!P) return;
+    for (double* q : P->owned) if (q) (void)hipFree(q);
+    if (P->h_norm) (void)hipHostFree(P->h_norm);
+    delete P;
+}
+
+// a plan-owned array of level L with `ng` ghost zones, zeroed
+static int plan_array(PoissonPlan* P, const MgLevel& L, int ng, DFab& F)
+{
+    const long nx = L.n[0] + 2 * ng, ny = L.n[1] + 2 * ng, nz = L.n[2] + 2 * ng;
+    double* q = nullptr;
+    if (hipMalloc(&q, (size_t)(nx * ny * nz) * sizeof(double)) != hipSuccess) return CASTRO_AMD_ERR_NOMEM;
+    P->owned.push_back(q);
+    if (hipMemset(q, 0, (size_t)(nx * ny * nz) * sizeof(double)) != hipSuccess) return CASTRO_AMD_ERR_HIP;
+    F.p = q;
+    for (int d = 0; d < 3; ++d) F.lo[d] = L.lo[d] - ng;
+    F.sy = nx; F.sz = nx * ny; F.sn = nx * ny * nz;
+    return 0;
+}
+
+int poisson_plan_make(const int n[3], const int lo[3], const double dx[3], PoissonPlan** out)
+{
+    std::vector<MgLevel> lev;
+    const int rl = poisson_levels(n, lo, dx, lev);
+    if (rl != 0) return rl;
+    PoissonPlan* P = new (std::nothrow) PoissonPlan();
+    if (!P) return CASTRO_AMD_ERR_NOMEM;
+    P->lev = lev;
+    const size_t nl = lev.size();
+    P->phi.resize(nl); P->rhs.resize(nl); P->res.resize(nl);
+    for (int d = 0; d < 3; ++d) P->dx[d] = dx[d];
+    int rc = 0;
+    for (size_t l = 0; l < nl && rc == 0; ++l) {
+        // the ghost zones of a coarser level's correction stay zero for the life of the plan: no kernel writes them
+        if (l > 0) rc = plan_array(P, lev[l], 1, P->phi[l]);
+        if (rc == 0) rc = plan_array(P, lev[l], 0, P->rhs[l]);
+        if (rc == 0 && l + 1 < nl) rc = plan_array(P, lev[l], 0, P->res[l]);
+    }
+    if (rc == 0 && nl == 1) rc = plan_array(P, lev[0], 0, P->res[0]);
+    double* q = nullptr;
+    if (rc == 0 && hipMalloc(&q, (4 + 2 * MG_NORM_MAX_WG) * sizeof(double)) != hipSuccess) rc = CASTRO_AMD_ERR_NOMEM;
+    if (rc == 0) { P->owned.push_back(q); P->d_norm = q; P->norm_ws = q + 4; }
+    if (rc == 0 && hipHostMalloc(&P->h_norm, 4 * sizeof(double)) != hipSuccess) rc = CASTRO_AMD_ERR_NOMEM;
+    if (rc != 0) { poisson_plan_free(P); return rc; }
+    *out = P;
+    return 0;
+}
+
+static int mg_check(hipStream_t) { return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP; }
+
+int launch_mg_smooth(const DFab& P, const DFab& B, const MgLevel& L, int colour, hipStream_t s, Profiler* prof)
+{
+    prof_begin(prof, "k_mg_smooth", s);
+    hipLaunchKernelGGL(k_mg_smooth, dim3(mg_blocks(mg_pairs(L))), dim3(MG_WG), 0, s, P, B, L, colour);
+    prof_end(prof, s);
+    return mg_check(s);
+}
+
+int launch_mg_residual(const DFab& P, const DFab& B, const DFab& R, const MgLevel& L, hipStream_t s, Profiler* prof)
+{
+    prof_begin(prof, "k_mg_residual", s);
+    hipLaunchKernelGGL(k_mg_residual, dim3(mg_blocks(mg_zones(L))), dim3(MG_WG), 0, s, P, B, R, L);
+    prof_end(prof, s);
+    return mg_check(s);
+}
+
+int launch_mg_restrict(const DFab& RF, const MgLevel& LF, const DFab& BC, const DFab& PC, const MgLevel& LC, hipStream_t s, Profiler* prof)
+{
+    prof_begin(prof, "k_mg_restrict", s);
+    hipLaunchKernelGGL(k_mg_restrict, dim3(mg_blocks(mg_zones(LC))), dim3(MG_WG), 0, s, RF, LF.lo[0], LF.lo[1], LF.lo[2], BC, PC, LC);
+    prof_end(prof, s);
+    return mg_check(s);
+}
+
+int launch_mg_prolong(const DFab& PC, const MgLevel& LC, const DFab& PF, const MgLevel& LF, hipStream_t s, Profiler* prof)
+{
+    prof_begin(prof, "k_mg_prolong", s);
+    hipLaunchKernelGGL(k_mg_prolong, dim3(mg_blocks(mg_zones(LF))), dim3(MG_WG), 0, s, PC, LC.lo[0], LC.lo[1], LC.lo[2], PF, LF);
+    prof_end(prof, s);
+    return mg_check(s);
+}
+
+int launch_mg_norm(const DFab& X, const MgLevel& L, double* ws, double* d_out, hipStream_t s, Profiler* prof)
+{
+    unsigned nb = mg_blocks(mg_zones(L));
+    if (nb > (unsigned)MG_NORM_MAX_WG) nb = MG_NORM_MAX_WG;
+    prof_begin(prof, "k_mg_norm_partial", s);
+    hipLaunchKernelGGL(k_mg_norm_partial, dim3(nb), dim3(MG_WG), 0, s, X, L, ws);
+    prof_end(prof, s);
+    prof_begin(prof, "k_mg_norm_final", s);
+    hipLaunchKernelGGL(k_mg_norm_final, dim3(1), dim3(MG_NORM_MAX_WG), 0, s, (const double*)ws, (int)nb, d_out);
+    prof_end(prof, s);
+    return mg_check(s);
+}
+
+static int mg_bottom(const DFab& P, const DFab& B, const MgLevel& L, hipStream_t s, Profiler* prof)
+{
+    prof_begin(prof, "k_mg_bottom", s);
+    hipLaunchKernelGGL(k_mg_bottom, dim3(1), dim3(MG_BOTTOM_WG), 0, s, P, B, L, MG_NBOTTOM);
+    prof_end(prof, s);
+    return mg_check(s);
+}
+
+// One V-cycle from level l down: MG_NPRE sweeps (colour 0, colour 1), residual, restriction, the coarser levels, prolongation,
+// MG_NPOST sweeps; the coarsest level is the bottom solve alone
+static int mg_vcycle(PoissonPlan* P, size_t l, hipStream_t s, Profiler* prof)
+{
+    const MgLevel& L = P->lev[l];
+    int rc = 0;
+    if (l + 1 == P->lev.size()) return mg_bottom(P->phi[l], P->rhs[l], L, s, prof);
+    for (int it = 0; it < MG_NPRE && rc == 0; ++it)
+        for (int colour = 0; colour < 2 && rc == 0; ++colour) rc = launch_mg_smooth(P->phi[l], P->rhs[l], L, colour, s, prof);
+    if (rc == 0) rc = launch_mg_residual(P->phi[l], P->rhs[l], P->res[l], L, s, prof);
+    if (rc == 0) rc = launch_mg_restrict(P->res[l], L, P->rhs[l + 1], P->phi[l + 1], P->lev[l + 1], s, prof);
+    if (rc == 0) rc = mg_vcycle(P, l + 1, s, prof);
+    if (rc == 0) rc = launch_mg_prolong(P->phi[l + 1], P->lev[l + 1], P->phi[l], L, s, prof);
+    for (int it = 0; it < MG_NPOST && rc == 0; ++it)
+        for (int colour = 0; colour < 2 && rc == 0; ++colour) rc = launch_mg_smooth(P->phi[l], P->rhs[l], L, colour, s, prof);
+    return rc;
+}
+
+// the residual of level 0 into the scratch of the plan (res[0]; the V-cycle overwrites it again), its norm into d_norm[at..at+1]
+static int mg_residual_norm(PoissonPlan* P, int at, hipStream_t s, Profiler* prof)
+{
+    int rc = launch_mg_residual(P->phi[0], P->rhs[0], P->res[0], P->lev[0], s, prof);
+    if (rc == 0) rc = launch_mg_norm(P->res[0], P->lev[0], P->norm_ws, P->d_norm + at, s, prof);
+    return rc;
+}
+
+static int mg_read(PoissonPlan* P, int n, hipStream_t s)
+{
+    if (hipMemcpyAsync(P->h_norm, P->d_norm, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess) return CASTRO_AMD_ERR_HIP;
+    return hipStreamSynchronize(s) == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
+}
+
+int launch_poisson_solve(PoissonPlan* P, const DFab& phi, const DFab& U, int comp, double fourpiG, double reltol, double abstol,
+                         int maxiter, int* cycles, int* converged, double* final_norm, double* h_history, hipStream_t s, Profiler* prof)
+{
+    P->phi[0] = phi;
+    const MgLevel& L0 = P->lev[0];
+    prof_begin(prof, "k_mg_rhs", s);
+    hipLaunchKernelGGL(k_mg_rhs, dim3(mg_blocks(mg_zones(L0))), dim3(MG_WG), 0, s, U, comp, P->rhs[0], L0, fourpiG);
+    prof_end(prof, s);
+    int rc = mg_check(s);
+    if (rc == 0) rc = launch_mg_norm(P->rhs[0], L0, P->norm_ws, P->d_norm, s, prof);
+    if (rc == 0) rc = mg_residual_norm(P, 2, s, prof);
+    if (rc == 0) rc = mg_read(P, 4, s);
+    if (rc != 0) return rc;
+    const double bnorm = P->h_norm[0], max_rhs = P->h_norm[1];
+    double rnorm = P->h_norm[2];
+    const double t1 = reltol * bnorm, t2 = abstol * max_rhs;
+    const double tol = t1 > t2 ? t1 : t2;
+    if (h_history) { h_history[0] = bnorm; h_history[1] = max_rhs; h_history[2] = rnorm; }
+    int n = 0;
+    while (!(rnorm <= tol) && n < maxiter) {
+        rc = mg_vcycle(P, 0, s, prof);
+        if (rc == 0) rc = mg_residual_norm(P, 0, s, prof);
+        if (rc == 0) rc = mg_read(P, 1, s);
+        if (rc != 0) return rc;
+        rnorm = P->h_norm[0];
+        ++n;
+        if (h_history) h_history[2 + n] = rnorm;
+    }
+    *cycles = n;
+    *converged = rnorm <= tol ? 1 : 0;
+    *final_norm = rnorm;
+    return 0;
+}
+
+int launch_grad_phi(const DFab& phi, const DFab& G, const MgLevel& L, const double dx[3], hipStream_t s, Profiler* prof)
+{
+    prof_begin(prof, "k_grad_phi", s);
+    hipLaunchKernelGGL(k_grad_phi, dim3(mg_blocks(mg_zones(L))), dim3(MG_WG), 0, s, phi, G, L, dx[0], dx[1], dx[2]);
+    prof_end(prof, s);
+    return mg_check(s);
+}
+
+} // namespace cad
+
+// ---- multipole moments and the boundary potential: no contraction in either build --------------------------------------------
+#pragma clang fp contract(off)
+
+namespace cad {
+
+constexpr int MP_MAX = CASTRO_AMD_MAX_MULTIPOLE;
+constexpr int MP_NC = 2 * (MP_MAX + 1);          // accumulators of a thread: cosine and sine parts of l = 0 .. MP_MAX
+constexpr int MP_WG = 256;
+constexpr int MP_MAX_WG = 1024;                  // workgroups per m: a thread takes more zones rather than the grid growing beyond it
+constexpr int MP_FINAL_GROUPS = 16;
+constexpr int MP_FINAL_WG = 576;                 // MP_FINAL_GROUPS * MP_NC = 544 threads at work, rounded up to whole waves
+static_assert(MP_FINAL_GROUPS * MP_NC <= MP_FINAL_WG && MP_FINAL_WG % 64 == 0, "k_mp_final's thread layout");
+
+// factorial of Gravity_util.H
+__host__ __device__ inline double mp_factorial(int n)
+{
+    double fact = 1.0;
+    for (int i = 2; i <= n; ++i) fact *= (double)i;
+    return fact;
+}
+
+// calcLegPolyL of Gravity_util.H
+__device__ __forceinline__ void mp_leg(int l, double& p, double& p1, double& p2, double x)
+{
+    if (l == 0) p = 1.0;
+    else if (l == 1) { p1 = p; p = x; }
+    else { p2 = p1; p1 = p; p = ((2 * l - 1) * x * p1 - (l - 1) * p2) / l; }
+}
+
+// calcAssocLegPolyLM of Gravity_util.H
+__device__ __forceinline__ void mp_assoc(int l, int m, double& a, double& a1, double& a2, double x)
+{
+    if (l == m) {
+        a = ((m & 1) ? -1.0 : 1.0) * pow((1.0 - x) * (1.0 + x), m * 0.5);        // std::pow(-1, m) is exactly -1 or 1
+        for (int n = 2 * m - 1; n >= 3; n = n - 2) a *= n;
+    } else if (l == m + 1) {
+        a1 = a;
+        a = x * (2 * m + 1) * a1;
+    } else {
+        a2 = a1; a1 = a;
+        a = (x * (2 * l - 1) * a1 - (l + m - 1) * a2) / (l - m);
+    }
+}
+
+// The moments of order m = blockIdx.y.  A workgroup takes the zones base + it * MP_WG + thread, it = 0 .. iters - 1, of one box (x
+// fastest); a thread adds the terms of its zones in that order -- for m = 0 dQL0(l) = ((legPolyL * (rho * pow(r, l))) * vol), for
+// m > 0 dQLC(l, m) = ((((assoc * cos(m * phiAngle)) * (rho * pow(r, l))) * vol) * factArray(l, m)) and the same with sin,
+// l = m .. lnum (multipole_add, volumeFactor = 1 and the parity factors 1: no Symmetry face) --, the 64 lanes of a wave are added
+// pairwise (32, 16, ... 1), the four waves in wave order, and the workgroup stores ONE row of MP_NC doubles.
+__global__ void __launch_bounds__(MP_WG) k_mp_partial(const DiagBoxDev* __restrict__ tab, const int* __restrict__ start, int nbox,
+                                                     int iters, MpGeom G, double* __restrict__ ws)
+{
+    const int m = blockIdx.y, lnum = G.lnum;
+    __shared__ double sfact[MP_MAX + 1];
+    if ((int)threadIdx.x <= MP_MAX) {
+        const int l = threadIdx.x;
+        sfact[l] = (m >= 1 && l >= m && l <= lnum) ? 2.0 * mp_factorial(l - m) / mp_factorial(l + m) : 0.0;
+    }
+    __syncthreads();
+    const unsigned bid = blockIdx.x;
+    int b0 = 0, b1 = nbox - 1;
+    while (b0 < b1) {
+        const int mid = (b0 + b1 + 1) >> 1;
+        if ((unsigned)start[mid] <= bid) b0 = mid; else b1 = mid - 1;
+    }
+    const DiagBoxDev B = tab[b0];
+    const long total = (long)B.n[0] * B.n[1] * B.n[2];
+    const long base = (long)(bid - (unsigned)start[b0]) * MP_WG * iters + threadIdx.x;
+
+    double ac[MP_MAX + 1], as[MP_MAX + 1];
+#pragma unroll
+    for (int l = 0; l <= MP_MAX; ++l) { ac[l] = 0.0; as[l] = 0.0; }
+
+    const double rmax_cubed_inv = 1.0 / (G.rmax * G.rmax * G.rmax);
+    const double vol = (G.dx[0] * G.dx[1] * G.dx[2]) * rmax_cubed_inv;
+    for (int it = 0; it < iters; ++it) {
+        const long q = base + (long)it * MP_WG;
+        if (q >= total) break;
+        const int ii = (int)(q % B.n[0]);
+        const long rr = q / B.n[0];
+        const int jj = (int)(rr % B.n[1]), kk = (int)(rr / B.n[1]);
+        if (B.mask && B.mask[q] == 0) continue;
+        const int i = B.lo[0] + ii, j = B.lo[1] + jj, k = B.lo[2] + kk;
+        const double rho = B.U.p[(long)(i - B.U.lo[0]) + B.U.sy * (long)(j - B.U.lo[1]) + B.U.sz * (long)(k - B.U.lo[2]) + B.U.sn * URHO];
+        const double x = (G.problo[0] + ((double)i + 0.5) * G.dx[0] - G.center[0]) / G.rmax;
+        const double y = (G.problo[1] + ((double)j + 0.5) * G.dx[1] - G.center[1]) / G.rmax;
+        const double z = (G.problo[2] + ((double)k + 0.5) * G.dx[2] - G.center[2]) / G.rmax;
+        const double r = sqrt(x * x + y * y + z * z);
+        const double cosTheta = z / r;
+        // the loop over l is not unrolled (one copy of pow); the accumulator of l -- a register -- is picked by a uniform test
+        double cm = 0.0, sm = 0.0;
+        if (m > 0) {
+            const double phiAngle = atan2(y, x);
+            cm = cos(m * phiAngle);
+            sm = sin(m * phiAngle);
+        }
+        double a = 0.0, a1 = 0.0, a2 = 0.0;
+#pragma nounroll
+        for (int l = m; l <= lnum; ++l) {
+            const double rho_r_L = rho * pow(r, (double)l);
+            double tc, ts = 0.0;
+            if (m == 0) {
+                mp_leg(l, a, a1, a2, cosTheta);
+                tc = a * rho_r_L * vol;
+            } else {
+                mp_assoc(l, m, a, a1, a2, cosTheta);
+                tc = a * cm * rho_r_L * vol * sfact[l];
+                ts = a * sm * rho_r_L * vol * sfact[l];
+            }
+#pragma unroll
+            for (int ll = 0; ll <= MP_MAX; ++ll)
+                if (ll == l) { ac[ll] += tc; as[ll] += ts; }
+        }
+    }
+
+    __shared__ double sa[MP_WG / 64][MP_NC];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int l = 0; l <= MP_MAX; ++l) {
+        double c = ac[l], s = as[l];
+        for (int off = 32; off > 0; off >>= 1) { c += __shfl_down(c, off, 64); s += __shfl_down(s, off, 64); }
+        if (lane == 0) { sa[wave][2 * l] = c; sa[wave][2 * l + 1] = s; }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < MP_NC) {
+        const int t = threadIdx.x;
+        ws[((long)m * gridDim.x + bid) * MP_NC + t] = ((sa[0][t] + sa[1][t]) + sa[2][t]) + sa[3][t];
+    }
+}
+
+// m = blockIdx.x: group g adds the rows g, g + 16, g + 32, ... of that m in row order, then the 16 groups are added in group
+// order.  out[((kind * (lnum + 1)) + l) * (lnum + 1) + m]: kind 0 = qL0 (m = 0), 1 = qLC, 2 = qLS; the caller has zeroed `out`
+__global__ void __launch_bounds__(MP_FINAL_WG) k_mp_final(const double* __restrict__ ws, int nrows, int lnum, double* __restrict__ out)
+{
+    __shared__ double sg[MP_FINAL_GROUPS][MP_NC];
+    const int m = blockIdx.x;
+    const int col = threadIdx.x % MP_NC, grp = threadIdx.x / MP_NC;
+    if (grp < MP_FINAL_GROUPS) {
+        double acc = 0.0;
+        for (int r = grp; r < nrows; r += MP_FINAL_GROUPS) acc += ws[((long)m * nrows + r) * MP_NC + col];
+        sg[grp][col] = acc;
+    }
+    __syncthreads();
+    if (grp == 0) {
+        double s = sg[0][col];
+        for (int g = 1; g < MP_FINAL_GROUPS; ++g) s += sg[g][col];
+        const int l = col >> 1, sine = col & 1, n1 = lnum + 1;
+        if (l <= lnum && l >= m) {
+            if (m == 0) { if (!sine) out[l * n1] = s; }
+            else out[((1 + sine) * n1 + l) * n1 + m] = s;
+        }
+    }
+}
+
+// The boundary potential (Gravity.cpp:2078-2216) of the zones of the six slabs of [flo, fhi] outside the domain; a zone of the
+// domain is never written.  The coordinate of a direction in which the zone lies outside sits on the domain face.
+__global__ void __launch_bounds__(256) k_mp_phi_bc(DFab F, Slabs S, MpGeom G, const double* __restrict__ q)
+{
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= S.start[6]) return;
+    int r = 0;
+    while (tid >= S.start[r + 1]) ++r;
+    const long t = tid - S.start[r];
+    int ijk[3];
+    ijk[0] = S.lo[r][0] + (int)(t % S.nn[r][0]);
+    const long rr = t / S.nn[r][0];
+    ijk[1] = S.lo[r][1] + (int)(rr % S.nn[r][1]);
+    ijk[2] = S.lo[r][2] + (int)(rr / S.nn[r][1]);
+    double loc[3];
+    bool outside = false;
+    for (int d = 0; d < 3; ++d) {
+        double v;
+        if (ijk[d] > G.domhi[d]) { v = G.problo[d] + ((double)ijk[d]) * G.dx[d] - G.center[d]; outside = true; }
+        else if (ijk[d] < G.domlo[d]) { v = G.problo[d] + ((double)(ijk[d] + 1)) * G.dx[d] - G.center[d]; outside = true; }
+        else v = G.problo[d] + ((double)ijk[d] + 0.5) * G.dx[d] - G.center[d];
+        loc[d] = v / G.rmax;
+    }
+    if (!outside) return;
+    double* dst = F.p + mg_at(F, ijk[0], ijk[1], ijk[2]);
+    const double x = loc[0], y = loc[1], z = loc[2];
+    const double r_ = sqrt(x * x + y * y + z * z);
+    if (r_ < 1.0e-12) { *dst = 0.0; return; }
+    const double rmax_cubed = G.rmax * G.rmax * G.rmax;
+    const double cosTheta = z / r_;
+    const double phiAngle = atan2(y, x);
+    const int lnum = G.lnum, n1 = lnum + 1;
+    double phi = 0.0;
+    {
+        double p = 0.0, p1 = 0.0, p2 = 0.0;
+        for (int l = 0; l <= lnum; ++l) {
+            mp_leg(l, p, p1, p2, cosTheta);
+            const double r_U = pow(r_, (double)(-l - 1));
+            phi += q[l * n1] * p * r_U * rmax_cubed;
+        }
+    }
+    for (int m = 1; m <= lnum; ++m) {
+        double a = 0.0, a1 = 0.0, a2 = 0.0;
+        for (int l = m; l <= lnum; ++l) {
+            mp_assoc(l, m, a, a1, a2, cosTheta);
+            const double r_U = pow(r_, (double)(-l - 1));
+            phi += (q[(n1 + l) * n1 + m] * cos(m * phiAngle) + q[(2 * n1 + l) * n1 + m] * sin(m * phiAngle)) * a * r_U * rmax_cubed;
+        }
+    }
+    *dst = -G.Gconst * phi / G.rmax;
+}
+
+// start[r]: first workgroup of box r; iters: zones a thread takes
+static int mp_layout(int nbox, const DiagBoxDev* boxes, std::vector<int>& start, int& iters)
+{
+    start.assign((size_t)nbox + 1, 0);
+    for (iters = 1; ; iters *= 2) {
+        long tot = 0;
+        for (int r = 0; r < nbox; ++r) {
+            const DiagBoxDev& B = boxes[r];
+            const long zones = (B.n[0] > 0 && B.n[1] > 0 && B.n[2] > 0) ? (long)B.n[0] * B.n[1] * B.n[2] : 0;
+            const long per = (long)MP_WG * iters;
+            tot += (zones + per - 1) / per;
+            start[(size_t)r + 1] = (int)(tot < 0x3fffffffL ? tot : 0x3fffffffL);
+        }
+        if (tot <= MP_MAX_WG || iters >= (1 << 20)) {
+            if (tot > 0xffffL) return CASTRO_AMD_ERR_ARG;
+            break;
+        }
+    }
+    return 0;
+}
+
+int launch_multipole_moments(int nbox, DiagBoxDev* boxes, const MpGeom& G, StagedTable* arena, DiagWorkspace* ws, double* d_out,
+                             hipStream_t stream, Profiler* prof)
+{
+    if (G.lnum < 0 || !(G.rmax > 0.0)) return CASTRO_AMD_ERR_ARG;
+    if (G.lnum > MP_MAX) return CASTRO_AMD_ERR_UNSUPPORTED;
+    const int n1 = G.lnum + 1;
+    if (hipMemsetAsync(d_out, 0, (size_t)(3 * n1 * n1) * sizeof(double), stream) != hipSuccess) return CASTRO_AMD_ERR_HIP;
+    std::vector<int> start;
+    int iters = 1;
+    if (nbox > 0) {
+        for (int r = 0; r < nbox; ++r) boxes[r].npr = 0;
+        const int rc = mp_layout(nbox, boxes, start, iters);
+        if (rc != 0) return rc;
+    }
+    const int nb = nbox > 0 ? start.back() : 0;
+    if (nb == 0) return 0;
+    const size_t rows = (size_t)nb * (size_t)n1;
+    if (rows > ws->rows) {
+        const size_t want = rows > (size_t)MP_MAX_WG * (MP_MAX + 1) ? rows : (size_t)MP_MAX_WG * (MP_MAX + 1);
+        if (ws->p) { (void)hipStreamSynchronize(stream); (void)hipFree(ws->p); ws->p = nullptr; ws->rows = 0; }
+        if (hipMalloc(&ws->p, want * MP_NC * sizeof(double)) != hipSuccess) return CASTRO_AMD_ERR_NOMEM;
+        ws->rows = want;
+    }
+    const DiagBoxDev* dbox;
+    const int* dstart;
+    const int rt = arena->stage(boxes, (size_t)nbox, start.data(), start.size(), stream, dbox, dstart);
+    if (rt != 0) return rt;
+    prof_begin(prof, "k_mp_partial", stream);
+    hipLaunchKernelGGL(k_mp_partial, dim3((unsigned)nb, (unsigned)n1), dim3(MP_WG), 0, stream, dbox, dstart, nbox, iters, G, ws->p);
+    prof_end(prof, stream);
+    if (hipGetLastError() != hipSuccess) return CASTRO_AMD_ERR_HIP;
+    prof_begin(prof, "k_mp_final", stream);
+    hipLaunchKernelGGL(k_mp_final, dim3((unsigned)n1), dim3(MP_FINAL_WG), 0, stream, (const double*)ws->p, nb, G.lnum, d_out);
+    prof_end(prof, stream);
+    return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
+}
+
+int launch_multipole_phi_bc(const DFab& F, const int flo[3], const int fhi[3], const MpGeom& G, const double* d_q, hipStream_t stream,
+                            Profiler* prof)
+{
+    if (G.lnum < 0 || !(G.rmax > 0.0)) return CASTRO_AMD_ERR_ARG;
+    if (G.lnum > MP_MAX) return CASTRO_AMD_ERR_UNSUPPORTED;
+    // the part of the FAB inside the domain: the six slabs around it are the zones to fill
+    int blo[3], bhi[3];
+    for (int d = 0; d < 3; ++d) {
+        blo[d] = flo[d] > G.domlo[d] ? flo[d] : G.domlo[d];
+        bhi[d] = fhi[d] < G.domhi[d] ? fhi[d] : G.domhi[d];
+        if (bhi[d] < blo[d]) return CASTRO_AMD_ERR_ARG;
+    }
+    const Slabs S = shell_slabs(flo, fhi, blo, bhi);
+    const long n = S.start[6];
+    if (n <= 0) return 0;
+    prof_begin(prof, "k_mp_phi_bc", stream);
+    hipLaunchKernelGGL(k_mp_phi_bc, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, F, S, G, d_q);
+    prof_end(prof, stream);
+    return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
+}
+
+} // namespace cad

@@ -20,6 +20,10 @@
                                      update(): Castro::pointmass_update (Source/gravity/Castro_pointmass.cpp), two launches with
                                      the sum over the ranks between them and no host round trip.
 
+  PoissonGravity                     gravity.gravity_type = "PoissonGrav" on a single level (castro_amd.Castro(poisson=...)): the
+                                     multipole boundary values, the multigrid solve and g = -grad(phi) of one time level, and the
+                                     old / new potentials of the run (the class at the end of this file).
+
 Levels finer than `level` do not enter.  Not provided: GR_GRAV, gravity.max_solve_level, a potential (phiGrav), domains with a periodic direction (the Gravity_Type FillPatch across a periodic boundary is not built), thermal
 diffusion on AMR levels, constant gravity plus a point mass on AMR levels.
 """
@@ -221,3 +225,118 @@ class MonopoleGravity:
         ent, n = self._arrays(level), self.n1d(level)
         mv = ent.get("last_summed", ent["mv"]).cpu().numpy()
         return mv[:n].copy(), mv[n:].copy(), ent["old"].cpu().numpy().copy(), ent["new"].cpu().numpy().copy()
+
+
+class PoissonGravity:
+    """gravity.gravity_type = "PoissonGrav" on a single level: castro_amd.Castro(do_grav=True, poisson=PoissonGravity(...)).
+
+    Every construction of the gravity of a time level (Castro::construct_old_gravity / construct_new_gravity,
+    Source/gravity/Castro_gravity.cpp) is: the multipole moments of the valid zones of the state (Gravity::fill_multipole_BCs),
+    the boundary potential on the ghost shell of phi, the multigrid solve of lap(phi) = 4 pi G rho from the level's starting
+    guess, g = -grad(phi) on the valid zones, and the Gravity_Type boundary fill of the ghost zone of g.  Time levels: at the
+    start of a step phi_old <- phi_new; the old-time solve starts from phi_old, the new-time solve from a copy of phi_old
+    (Castro_gravity.cpp:146); the first solve of a run starts from zero.  The reference's extra solve in post_init is not made.
+
+    max_multipole_order: gravity.max_multipole_order (lnum); reltol / abstol: gravity.rel_tol / abs_tol of the stopping rule
+    ||r|| <= max(reltol ||b||, abstol max(b)); maxiter: V-cycles before RuntimeError (the reference aborts there); Gconst:
+    C::Gconst; center: problem::center, default the driver's `center`, else the middle of the domain.
+    Not built (each refused by the driver): AMR levels, more than one rank, periodic or Symmetry faces, the point mass,
+    checkpoints, gravity.mlmg_maxorder > 2, direct_sum_bcs."""
+
+    OPERATIONS = ("multipole_moments_mf", "multipole_phi_bc", "poisson_solve", "grad_phi_to_grav")
+
+    def __init__(self, max_multipole_order=0, reltol=1.e-10, abstol=1.e-10, maxiter=40, Gconst=L.GCONST, center=None):
+        self.lnum = int(max_multipole_order)
+        if self.lnum < 0:
+            raise ValueError("gravity.max_multipole_order must not be negative, not %d" % self.lnum)
+        if self.lnum > L.MAX_MULTIPOLE:
+            raise ValueError("gravity.max_multipole_order = %d is above the %d the kernels are built for (the reference's "
+                             "lnum_max is 30): a follow-up raises CASTRO_AMD_MAX_MULTIPOLE" % (self.lnum, L.MAX_MULTIPOLE))
+        self.reltol, self.abstol, self.maxiter = float(reltol), float(abstol), int(maxiter)
+        self.Gconst = float(Gconst)
+        self.center = None if center is None else tuple(float(x) for x in center)
+        self.driver = None
+        self.plan = None
+        self.stats = {"first": None, "old": None, "new": None}
+
+    def bind(self, c, hydro_alloc):
+        """the checks of the driver `c` this object belongs to, and its arrays: phi_old / phi_new with one ghost zone, the moments"""
+        if self.driver is not None and self.driver is not c:
+            raise ValueError("a PoissonGravity object belongs to one Castro")
+        h = c.hydro
+        missing = [name for name in self.OPERATIONS + ("poisson_plan_create", "grav_bc_fill") if not hasattr(h, name)]
+        if missing:
+            raise NotImplementedError("Poisson gravity: this backend has no %s; there is no host fallback" % ", ".join(missing))
+        for d in range(3):
+            for bc in (c.lo_bc[d], c.hi_bc[d]):
+                if bc == 0 or bc == 3:
+                    raise NotImplementedError("Poisson gravity with a %s face: the mass offset of a periodic domain and the "
+                                              "reflected moments / Neumann faces of a Symmetry one are a follow-up; all six faces "
+                                              "must be Dirichlet faces of the potential" % ("periodic" if bc == 0 else "Symmetry"))
+        coarsest = L.poisson_level_extents(c.n_cell)[-1]
+        if coarsest[0] * coarsest[1] * coarsest[2] > L.POISSON_MAX_BOTTOM:
+            raise ValueError("Poisson gravity: n_cell = %s coarsens to %s, more than the %d zones the bottom solver of the multigrid "
+                             "takes: n_cell needs more factors of 2" % (c.n_cell, coarsest, L.POISSON_MAX_BOTTOM))
+        self.driver = c
+        self.phibox = (tuple(x - 1 for x in c.lo), tuple(x + 1 for x in c.hi))
+        self.phi_old = hydro_alloc(1, *self.phibox)
+        self.phi_new = hydro_alloc(1, *self.phibox)
+        n1 = self.lnum + 1
+        self.moments = hydro_alloc(1, (0, 0, 0), (3 * n1 * n1 - 1, 0, 0))
+        self._tables = {}
+        if self.phi_old is not None:
+            self.plan = h.poisson_plan_create(c.geom)
+
+    def close(self):
+        if self.plan is not None and self.driver is not None:
+            self.driver.hydro.poisson_plan_destroy(self.plan)
+        self.plan = None
+
+    def __del__(self):
+        try:
+            # a finaliser that runs in the middle of a stream capture must not free device memory (HipHydro.__del__)
+            import torch
+            if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                return
+            self.close()
+        except Exception:
+            pass
+
+    def swap_time_levels(self):
+        """swap_state_time_levels of PhiGrav_Type: the new data of the last step are the old data of this one"""
+        self.phi_old, self.phi_new = self.phi_new, self.phi_old
+
+    def multipole(self):
+        """castro_amd_multipole of the run"""
+        from . import diag
+        c = self.driver
+        return L.make_multipole(c.geom, self.center if self.center is not None else diag.domain_center(c), self.lnum, self.Gconst)
+
+    def construct(self, S, grav, new):
+        """Gravity::solve_for_phi and get_old / get_new_grav_vector of the level at one time level: `grav` from the state S"""
+        import math
+        c = self.driver
+        h = c.hydro
+        if self.plan is None:                           # after Castro.close(): the plan is made again
+            self.plan = h.poisson_plan_create(c.geom)
+        if new:
+            self.phi_new.copy_(self.phi_old)            # the "old" phi of the step is the guess (Castro_gravity.cpp:146)
+        phi = self.phi_new if new else self.phi_old
+        mp = self.multipole()
+        key = S.data_ptr()                              # the two state buffers swap roles every step: one table each
+        if key not in self._tables:
+            self._tables[key] = h.make_diag_boxes([(c.lo, c.hi, (S, c.gbox), None)])
+        mom = self.moments.reshape(-1)
+        h.multipole_moments_mf(self._tables[key], c.geom, mp, mom)
+        h.multipole_phi_bc(phi, self.phibox, c.geom, mp, mom)
+        cycles, ok, norm, hist = h.poisson_solve(self.plan, phi, self.phibox, S, c.gbox, L.URHO, 4.0 * math.pi * self.Gconst,
+                                                 self.reltol, self.abstol, self.maxiter)
+        self.stats["new" if new else "old"] = {"cycles": cycles, "norm": norm, "history": hist}
+        if self.stats["first"] is None:
+            self.stats["first"] = self.stats["new" if new else "old"]
+        if not ok:
+            raise RuntimeError("Poisson gravity: the multigrid did not reach max(%g * %g, %g * %g) in %d V-cycles; the last two "
+                               "residual norms are %r and %r" % (self.reltol, hist[0], self.abstol, hist[1], self.maxiter,
+                                                                  hist[-2], hist[-1]))
+        h.grad_phi_to_grav(phi, self.phibox, grav, c.gravbox, c.geom)
+        h.grav_bc_fill(grav, c.gravbox, c.geom)

@@ -262,6 +262,63 @@ class HipHydro:
             arr[i] = L.fab_of(g, *box)
         return arr
 
+    # ---- Poisson gravity on a single level (Source/gravity/Gravity.cpp; castro_amd/csrc/poisson_kernels.hip) ---------------
+    def multipole_moments_mf(self, boxes, geom, mp, out, stream=None):
+        """castro_amd_multipole_moments_mf: qL0, qLC, qLS of the density over the valid zones of `boxes` (make_diag_boxes) into
+        `out`, a device tensor of 3 * (lnum + 1)**2 doubles ([kind][l][m]), overwritten.  The same boxes give the same bits
+        (calls of one context on different streams must be ordered by the host: one workspace).  A zone centred exactly on
+        mp.center gives NaN for l >= 1, as in the reference."""
+        arr, n = boxes
+        L.check(self.lib.castro_amd_multipole_moments_mf(self.h, n, arr, C.byref(geom), C.byref(mp), C.c_void_p(out.data_ptr()),
+                                                         _stream_ptr(stream)), "multipole_moments_mf")
+
+    def multipole_phi_bc(self, phi, phi_box, geom, mp, moments, stream=None):
+        """castro_amd_multipole_phi_bc_fab: the multipole potential on the zones of the one-component FAB `phi` outside the domain"""
+        L.check(self.lib.castro_amd_multipole_phi_bc_fab(self.h, C.byref(L.fab_of(phi, *phi_box)), C.byref(geom), C.byref(mp),
+                                                         C.c_void_p(moments.data_ptr()), _stream_ptr(stream)), "multipole_phi_bc_fab")
+
+    def poisson_plan_create(self, geom):
+        """castro_amd_poisson_plan_create: the multigrid levels of the domain of `geom` and their arrays; a handle for
+        poisson_solve / poisson_level_op, freed by poisson_plan_destroy.  ValueError when the coarsest level would hold more
+        than _lib.POISSON_MAX_BOTTOM zones."""
+        plan = C.c_void_p()
+        rc = self.lib.castro_amd_poisson_plan_create(self.h, C.byref(geom), C.byref(plan))
+        if rc == L.ERR_UNSUPPORTED:
+            n_cell = tuple(geom.domhi[d] - geom.domlo[d] + 1 for d in range(3))
+            raise ValueError("poisson_plan_create: n_cell = %s (coarsest multigrid level %s) on a Cartesian domain without periodic "
+                             "or Symmetry faces is all this solver takes, with at most %d zones on the coarsest level"
+                             % (n_cell, L.poisson_level_extents(n_cell)[-1], L.POISSON_MAX_BOTTOM))
+        L.check(rc, "poisson_plan_create")
+        return plan
+
+    def poisson_plan_destroy(self, plan):
+        if plan is not None and getattr(self, "h", None):
+            self.lib.castro_amd_poisson_plan_destroy(self.h, plan)
+
+    def poisson_solve(self, plan, phi, phi_box, rho, rho_box, rho_comp, fourpiG, reltol=1.e-10, abstol=1.e-10, maxiter=40,
+                      stream=None):
+        """castro_amd_poisson_solve: V-cycles on `phi` (in place) until the residual meets the stopping rule or maxiter cycles.
+        Returns (cycles, converged, final_norm, history) -- history: ||b||, max b, the starting norm, then one norm per cycle."""
+        cycles, conv, norm = C.c_int(0), C.c_int(0), C.c_double(0.0)
+        hist = (C.c_double * (int(maxiter) + 3))()
+        L.check(self.lib.castro_amd_poisson_solve(self.h, plan, C.byref(L.fab_of(phi, *phi_box)), C.byref(L.fab_of(rho, *rho_box)),
+                                                  int(rho_comp), float(fourpiG), float(reltol), float(abstol), int(maxiter),
+                                                  C.byref(cycles), C.byref(conv), C.byref(norm), hist, _stream_ptr(stream)),
+                "poisson_solve")
+        return cycles.value, bool(conv.value), norm.value, list(hist[:cycles.value + 3])
+
+    def poisson_level_op(self, plan, op, level, a, b=None, c=None, colour=0, out=None, stream=None):
+        """castro_amd_poisson_level_op: one pass (_lib.MG_*) on the (tensor, box) pairs a, b, c with the coefficients of `level`"""
+        fabs = [C.byref(L.fab_of(*x[:1], *x[1])) if x is not None else None for x in (a, b, c)]
+        L.check(self.lib.castro_amd_poisson_level_op(self.h, plan, int(op), int(level), int(colour), fabs[0], fabs[1], fabs[2],
+                                                     C.c_void_p(out.data_ptr()) if out is not None else None, _stream_ptr(stream)),
+                "poisson_level_op")
+
+    def grad_phi_to_grav(self, phi, phi_box, grav, grav_box, geom, stream=None):
+        """castro_amd_grad_phi_to_grav_fab: g = -grad(phi) on the zones of the domain of the 3-component FAB `grav`"""
+        L.check(self.lib.castro_amd_grad_phi_to_grav_fab(self.h, C.byref(L.fab_of(phi, *phi_box)), C.byref(L.fab_of(grav, *grav_box)),
+                                                         C.byref(geom), _stream_ptr(stream)), "grad_phi_to_grav_fab")
+
     # ---- the central point mass (castro.use_point_mass; Gravity.cpp:2903-2948, Castro_pointmass.cpp) ---------------------
     def add_pointmass(self, grav, grav_box, pm, geom, mass, stream=None):
         """castro_amd_add_pointmass_fab: Gravity::add_pointmass_to_gravity over the whole box of the 3-component FAB `grav`; pm:

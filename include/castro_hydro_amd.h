@@ -71,6 +71,9 @@ extern "C" {
  *      castro_amd_tracer_advect_mf / _sample_mf / _count_mf, which refused it before.
  *      castro_amd_fab_pack, castro_amd_fab_unpack (struct castro_amd_pack_entry): the valid zones of many FABs into one
  *      contiguous buffer and back, for checkpoints.
+ *      castro_amd_multipole_moments_mf, castro_amd_multipole_phi_bc_fab (struct castro_amd_multipole),
+ *      castro_amd_poisson_plan_create / _destroy, castro_amd_poisson_solve, castro_amd_poisson_level_op,
+ *      castro_amd_grad_phi_to_grav_fab: Poisson self-gravity on a single level.
  * A caller checks `castro_amd_abi_version() == CASTRO_AMD_ABI_VERSION` once after loading the library; a mismatch means
  * the library was built from another revision of this header (a 0.2 caller with 2-double vectors would be written 8 bytes
  * out of bounds by a 0.3 library). */
@@ -619,6 +622,82 @@ int castro_amd_radial_combine(castro_amd_ctx *ctx, int level, const double *cons
  * grav_fab (CASTRO_AMD_ERR_ARG otherwise).  The coarse-fine part of that FillPatch is CASTRO_AMD_OP_INTERP /
  * castro_amd_cc_interp_fab with 3 components. */
 int castro_amd_grav_bc_fill_fab(castro_amd_ctx *ctx, const castro_amd_fab *grav_fab, const castro_amd_geom *geom, void *stream);
+
+/* gravity.gravity_type = "PoissonGrav" on a single level: 3-D Cartesian, every face of the domain a Dirichlet face of the
+ * potential (no periodic and no Symmetry face: CASTRO_AMD_ERR_UNSUPPORTED).  Everything is FP64 and runs on `stream` alone.
+ *
+ * The multipole boundary values (Gravity::fill_multipole_BCs, Gravity.cpp:1742-2216, with multipole_add, calcLegPolyL and
+ * calcAssocLegPolyLM of Gravity_util.H and the factors of init_multipole_grav) with boundary_only = 1: every zone falls in the
+ * last radial bin, so there is ONE set of moments.  Distances are divided by rmax = 0.5 * (the widest extent of the domain) *
+ * sqrt(3), the volume of a zone by rmax^3; factArray(l, m) = 2 (l - m)! / (l + m)!; volumeFactor and the parity factors are 1.
+ * lnum = gravity.max_multipole_order, 0 .. CASTRO_AMD_MAX_MULTIPOLE (above it: CASTRO_AMD_ERR_UNSUPPORTED; the reference stops
+ * at lnum_max = 30). */
+#define CASTRO_AMD_MAX_MULTIPOLE 16
+typedef struct castro_amd_multipole {
+    int lnum;
+    double rmax;
+    double center[3];             /* problem::center */
+    double Gconst;
+} castro_amd_multipole;
+/* The moments of the density (component 0 of box.state) over the valid zones of `boxes`, masked zones skipped, into d_moments:
+ * 3 (lnum + 1)^2 device doubles, overwritten, entry ((kind * (lnum + 1)) + l) * (lnum + 1) + m with kind 0 = qL0(l) (m = 0),
+ * 1 = qLC(l, m), 2 = qLS(l, m), 1 <= m <= l; every other entry is zero.  Two stages in an order fixed by the box table, no
+ * floating-point atomics: the same boxes give the same bits on every call, and on every stream as long as the calls of one
+ * context are ordered by the host -- the context has ONE workspace of partial sums and one staged box table (as for
+ * castro_amd_integrated_quantities_mf): a call that grows it synchronises its own stream only, and two calls in flight on two
+ * streams would share it.
+ * As in the reference (Gravity.cpp:1917), cosTheta = z / r has no guard: a zone whose centre coincides with `center` (an odd
+ * extent with the centre in the middle of the domain) has r = 0 and gives NaN in every moment with l >= 1; lnum = 0 is not
+ * affected (pow(0, 0) = 1 and cosTheta is not read).  Put the centre on a zone corner, or mask the zone. */
+int castro_amd_multipole_moments_mf(castro_amd_ctx *ctx, int nboxes, const castro_amd_diag_box *boxes, const castro_amd_geom *geom,
+                                    const castro_amd_multipole *mp, double *d_moments, void *stream);
+/* The boundary potential (Gravity.cpp:2066-2216) of every zone of phi_fab (1 component) outside the domain -- faces, edges and
+ * corners: phi = -G / rmax * sum(...  r^(-l-1) rmax^3) at the zone centre moved onto the domain face in every direction in which
+ * the zone lies outside (i dx beyond the high face, (i + 1) dx below the low face); 0 where r < 1e-12.  Zones of the domain are
+ * not written.  phi_fab must overlap the domain. */
+int castro_amd_multipole_phi_bc_fab(castro_amd_ctx *ctx, const castro_amd_fab *phi_fab, const castro_amd_geom *geom,
+                                    const castro_amd_multipole *mp, const double *d_moments, void *stream);
+/* Geometric multigrid for lap(phi) = 4 pi G rho with the 7-point cell-centred Laplacian on the domain of `geom` (dx, dy, dz may
+ * differ).  Level 0: the ghost zone of phi holds phi ON the domain face and the stencil's ghost is 2 phi_face - phi_inside
+ * (AMReX's maxorder = 2 form); coarser levels are homogeneous.  Levels: coarsened by 2 while every extent is even and the
+ * coarsened extent is at least 2.  A V-cycle: 2 red-black Gauss-Seidel sweeps, residual, restriction (the mean of the 8
+ * children), the coarser levels, piecewise-constant prolongation, 2 sweeps; the coarsest level is 32 sweeps in one launch.
+ * The plan owns the arrays of every level.  CASTRO_AMD_ERR_UNSUPPORTED when the coarsest level would hold more than
+ * CASTRO_AMD_POISSON_MAX_BOTTOM zones (too few factors of 2 in the extents for this bottom solver), for a non-Cartesian
+ * geometry and for a periodic or Symmetry face. */
+#define CASTRO_AMD_POISSON_MAX_BOTTOM 4096
+typedef struct castro_amd_poisson_plan castro_amd_poisson_plan;
+int castro_amd_poisson_plan_create(castro_amd_ctx *ctx, const castro_amd_geom *geom, castro_amd_poisson_plan **plan);
+void castro_amd_poisson_plan_destroy(castro_amd_ctx *ctx, castro_amd_poisson_plan *plan);
+/* Solve from the phi the valid zones of phi_fab hold (1 component, the domain grown by one zone inside it; the ghost zones
+ * outside the domain hold the boundary values), b = fourpiG * component rho_comp of rho_fab.  V-cycles until
+ * ||r||_inf <= max(reltol * ||b||_inf, abstol * max(b)) (Gravity.cpp:3447-3558: setAlwaysUseBNorm(true), abs_eps = abs_tol *
+ * max_rhs) or maxiter cycles; one norm is read back per cycle (the call synchronises `stream`).  *cycles: the cycles run (0 when
+ * the start already meets the rule), *converged: 1 / 0, *final_norm: the last ||r||_inf.  h_history (host, maxiter + 3 doubles, or
+ * NULL): ||b||_inf, max(b), the norm of the starting residual, then the norm after every cycle. */
+int castro_amd_poisson_solve(castro_amd_ctx *ctx, castro_amd_poisson_plan *plan, const castro_amd_fab *phi_fab,
+                             const castro_amd_fab *rho_fab, int rho_comp, double fourpiG, double reltol, double abstol, int maxiter,
+                             int *cycles, int *converged, double *final_norm, double *h_history, void *stream);
+/* One pass of the V-cycle on caller-owned FABs with the coefficients of level `level` of the plan (level 0: the domain; the box
+ * of a coarser level is the coarsened domain).  phi-like FABs hold the level's box grown by one zone, the others the box.
+ *   CASTRO_AMD_MG_SMOOTH    a = phi, b = rhs: one sweep of the zones with (i + j + k - lo) & 1 == colour
+ *   CASTRO_AMD_MG_RESIDUAL  a = phi, b = rhs, c = residual (written)
+ *   CASTRO_AMD_MG_RESTRICT  a = residual of `level`, b = rhs of level + 1 (written), c = phi of level + 1 (valid zones zeroed)
+ *   CASTRO_AMD_MG_PROLONG   a = phi of level + 1, b = phi of `level` (added to)
+ *   CASTRO_AMD_MG_NORM      a = any FAB on the box; d_out[0] = max |a|, d_out[1] = max a (device doubles) */
+#define CASTRO_AMD_MG_SMOOTH 0
+#define CASTRO_AMD_MG_RESIDUAL 1
+#define CASTRO_AMD_MG_RESTRICT 2
+#define CASTRO_AMD_MG_PROLONG 3
+#define CASTRO_AMD_MG_NORM 4
+int castro_amd_poisson_level_op(castro_amd_ctx *ctx, castro_amd_poisson_plan *plan, int op, int level, int colour,
+                                const castro_amd_fab *a, const castro_amd_fab *b, const castro_amd_fab *c, double *d_out,
+                                void *stream);
+/* g = -grad(phi) (get_old / get_new_grav_vector, Gravity.cpp:874-878, over MLMG's getGradSolution) into the zones of the domain of
+ * grav_fab (3 components): the mean of the two face gradients (phi_i - phi_{i-1}) / dx of a zone, negated; at a domain face the
+ * linear ghost gives 2 (phi_1 - phi_face) / dx.  The zones outside the domain are left to castro_amd_grav_bc_fill_fab. */
+int castro_amd_grad_phi_to_grav_fab(castro_amd_ctx *ctx, const castro_amd_fab *phi_fab, const castro_amd_fab *grav_fab,
+                                    const castro_amd_geom *geom, void *stream);
 /* castro_amd_sources_mf with the gravity of every box read from its Gravity_Type FABs: grav_old[i] / grav_new[i] (3
  * components, one ghost zone around [lo, hi] of box i for grav_source_type = 4; grav_new is read by stage 1 only and may be
  * NULL for stage 0) take the place of the one vector -- the zone functions of castro_amd_old/new_gravity_source_gfab inside
