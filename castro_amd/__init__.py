@@ -6,7 +6,7 @@ Layout:
   hydro.py         HipHydro: the reference's per-FAB hydro interface over the C ABI
   castro.py        Castro: single-level driver (FillPatch halo exchange over RCCL, dt control, retry, gravity, rotation, thermal diffusion, sponge)
   amr.py           CastroAmr: coarse level + one refined patch with subcycling, reflux, avgDown
-  gravity.py       MonopoleGravity: monopole self-gravity over the levels of CastroAmr (radial arrays, level combination); PointMass: the central point mass; PoissonGravity: Poisson self-gravity of a single level (multipole boundary values, multigrid)
+  gravity.py       MonopoleGravity: monopole self-gravity over the levels of CastroAmr (radial arrays, level combination); PointMass: the central point mass; PoissonGravity: Poisson self-gravity of a single level (multipole boundary values, multigrid) and of the levels of CastroAmr (level solves)
   particles.py     TracerParticles: tracer particles over the levels of Castro / CastroAmr (advect, redistribute, timestamp, particle_count)
   plotfile.py      Castro plotfile writer / reader
   checkpoint.py    checkpoint / restart of Castro and CastroAmr (write_checkpoint, restart_from, read_checkpoint)

@@ -81,6 +81,7 @@ EXPORTED_SYMBOLS = (
     "castro_amd_fab_pack", "castro_amd_fab_unpack",
     "castro_amd_multipole_moments_mf", "castro_amd_multipole_phi_bc_fab", "castro_amd_poisson_plan_create",
     "castro_amd_poisson_plan_destroy", "castro_amd_poisson_solve", "castro_amd_poisson_level_op", "castro_amd_grad_phi_to_grav_fab",
+    "castro_amd_poisson_cf_bc_fab",
 )
 
 
@@ -628,6 +629,8 @@ def load(numerics=None):
                                                C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
         L.castro_amd_poisson_level_op.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, PF, PF, PF, C.c_void_p, C.c_void_p]
         L.castro_amd_grad_phi_to_grav_fab.argtypes = [C.c_void_p, PF, PF, C.POINTER(Geom), C.c_void_p]
+    if hasattr(L, "castro_amd_poisson_cf_bc_fab"):          # absent from A/B builds of revisions before the level solves
+        L.castro_amd_poisson_cf_bc_fab.argtypes = [C.c_void_p, PF, I3, I3, PF, PF, C.c_double, C.c_void_p]
     L.castro_amd_step_control.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_double, C.c_double,
                                           C.c_double, C.c_int, C.c_void_p]
     L.castro_amd_clean_state_fab.argtypes = [C.c_void_p, PF, I3, I3, C.POINTER(Params), C.c_int, C.c_void_p]

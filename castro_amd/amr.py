@@ -609,6 +609,9 @@ class _Level:
     def _swap_state_time_levels(self):
         for b in self.mine:
             b._swap_state_time_levels()
+        G = self.amr.gravity
+        if G is not None and hasattr(G, "swap_level"):          # PhiGrav_Type of a PoissonGravity: phi_old <- phi_new
+            G.swap_level(self.l)
 
     def _zero_fluxes(self):
         for b in self.mine:
@@ -864,7 +867,7 @@ class CastroAmr(CheckpointMixin):
                  diffusion=None, sum_interval=-1, show_center_of_mass=False, diag_dir=None, gravity_type="constant", gravity=None,
                  sponge=None, use_point_mass=False, point_mass=0.0, point_mass_fix_solution=False, ext_bc=None,
                  update_sources_after_reflux=False, tracers=None, check_int=-1, check_file="chk", poisson=None):
-        """poisson: refused -- castro_amd.PoissonGravity is the single-level form (castro_amd.Castro).
+        """poisson: refused -- the keyword of the single-level driver (castro_amd.Castro); a hierarchy takes gravity=PoissonGravity(...).
         check_int, check_file (amr.check_int, default -1: never / amr.check_file): evolve() writes the checkpoint
         check_file + "%05d" % nstep after every coarse step with nstep % check_int == 0, in the background
         (castro_amd/checkpoint.py: writeCheckpoint, restart -- the box lists of every level come from the file, nothing is
@@ -887,7 +890,11 @@ class CastroAmr(CheckpointMixin):
         sponge: _lib.make_sponge(timescale, ...) -- castro.do_sponge = 1 on every box of every level (zone-local: a refined
         level needs nothing from the coarser one), as in castro_amd.Castro.
         gravity: castro_amd.MonopoleGravity(drdxfac=..., Gconst=...) with do_grav=True -- monopole self-gravity on every
-        level (castro_amd/gravity.py: the object spans the levels like the reference's Gravity).
+        level (castro_amd/gravity.py: the object spans the levels like the reference's Gravity); or
+        castro_amd.PoissonGravity(..., max_solve_level=None) -- Poisson self-gravity with every level solving on its own box
+        (gravity.no_sync = 1, gravity.no_composite = 1): one rank, level 0 and every refined level ONE box, the refined ones
+        inside the domain; phi_grav(level) and poisson_stats(level) read the potentials and the cycle counts, close() gives the
+        multigrid plans back.
         gravity_type: "constant" only (the bare string "monopole" carries neither drdxfac nor Gconst and is refused).
         sum_interval, show_center_of_mass, diag_dir: as in castro_amd.Castro -- sum_integrated_quantities() over the composite
         grid after initData and after every coarse step with nstep % sum_interval == 0 (self.diag_history, the three data logs).
@@ -910,6 +917,10 @@ class CastroAmr(CheckpointMixin):
             raise NotImplementedError("CastroAmr: Poisson gravity (poisson=...) is built for a single level only -- the level "
                                       "solves, gravity_sync and the composite correction of the hierarchy are a follow-up; use "
                                       "castro_amd.Castro")
+        from .gravity import PoissonGravity
+        if diffusion is not None and isinstance(gravity, PoissonGravity):
+            raise ValueError("CastroAmr: gravity=PoissonGravity(...) not together with diffusion=...: thermal diffusion is built for "
+                             "a single level only")
         if diffusion is not None:
             # the operator of a refined level needs AMReX's coarse-fine boundary stencil [3P], which is not restated
             raise NotImplementedError("CastroAmr: thermal diffusion (diffusion=...) is built for a single level only; "
@@ -923,10 +934,12 @@ class CastroAmr(CheckpointMixin):
                                       "Gconst=...)")
         if gravity is not None:
             from .gravity import MonopoleGravity
-            if not isinstance(gravity, MonopoleGravity):
-                raise TypeError("gravity must be a castro_amd.MonopoleGravity, not %r" % (type(gravity),))
+            if not isinstance(gravity, (MonopoleGravity, PoissonGravity)):
+                raise TypeError("gravity must be a castro_amd.MonopoleGravity or a castro_amd.PoissonGravity, not %r" % (type(gravity),))
             if not do_grav:
-                raise ValueError("gravity=MonopoleGravity(...) needs do_grav=True")
+                raise ValueError("gravity=%s(...) needs do_grav=True" % type(gravity).__name__)
+            if isinstance(gravity, PoissonGravity):
+                self._refuse_for_poisson(comm, base_grid, use_point_mass, check_int, ext_bc, n_cell, prob_lo, prob_hi, lo_bc, hi_bc)
             gravity.bind(self, lo_bc, hi_bc)
         self.gravity = gravity
         self.pm = None
@@ -1015,6 +1028,41 @@ class CastroAmr(CheckpointMixin):
         from .diag import DiagLog
         self.diag = DiagLog(sum_interval, show_center_of_mass, diag_dir, io_rank=self.rank == 0)
         self._diag_out = None
+
+    # ---- gravity=PoissonGravity(...): the level solves (castro_amd/gravity.py) ------------------------------------------------
+    @staticmethod
+    def _refuse_for_poisson(comm, base_grid, use_point_mass, check_int, ext_bc, n_cell, prob_lo, prob_hi, lo_bc, hi_bc):
+        if comm is not None and comm.size > 1:
+            raise NotImplementedError("CastroAmr: Poisson gravity on more than one rank: the multigrid needs a halo exchange of phi "
+                                      "on every level and the moments a sum over the ranks; a follow-up")
+        if base_grid is not None and tuple(base_grid) != (1, 1, 1):
+            raise NotImplementedError("CastroAmr: Poisson gravity with base_grid: level 0 must be one box -- the multigrid has no "
+                                      "halo exchange of phi between boxes; a follow-up")
+        if use_point_mass:
+            raise NotImplementedError("CastroAmr: use_point_mass with Poisson gravity (the point mass is excluded from the "
+                                      "right-hand side and added to the gradient) is not built")
+        if int(check_int) > 0:
+            raise NotImplementedError("CastroAmr: check_int with Poisson gravity: a bit-faithful restart needs phi of every level, "
+                                      "the solver's starting guess, in the checkpoint (the reference's SD_1) -- a follow-up")
+        if ext_bc is not None and L.ext_bc_hse_faces(ext_bc, L.make_geom(n_cell, prob_lo, prob_hi, lo_bc, hi_bc)):
+            raise ValueError("HSE boundaries assume constant gravity: not with gravity=PoissonGravity(...)")
+
+    def _poisson_gravity(self, what):
+        from .gravity import PoissonGravity
+        if not isinstance(self.gravity, PoissonGravity):
+            raise RuntimeError("%s needs CastroAmr(do_grav=True, gravity=PoissonGravity(...))" % what)
+        return self.gravity
+
+    def phi_grav(self, level=0, new=True):
+        """PhiGrav_Type of `level`: the potential of its last new-time (or old-time) construction as a (1, nz + 2, ny + 2, nx + 2)
+        tensor.  A level that solves keeps the boundary values ON the faces of its box in the ghost zone (edges and corners: 0
+        on a refined level); a level above max_solve_level holds the interpolated coarse potential in every zone."""
+        return self._poisson_gravity("phi_grav()").phi_level(level, new)
+
+    def poisson_stats(self, level=0):
+        """{"first", "old", "new"} of `level`: V-cycles, final residual norm and norm history of the first solve of the level
+        and of its last old- and new-time solves (None where none was made)"""
+        return self._poisson_gravity("poisson_stats()").stats_level(level)
 
     use_point_mass = property(lambda self: self.pm is not None)
     point_mass = property(lambda self: self.pm.value() if self.pm is not None else None,
@@ -1230,6 +1278,8 @@ class CastroAmr(CheckpointMixin):
         lev = self._make_level(len(self.lev), pboxes)
         if self.gravity is not None:
             self.gravity.check_level(len(self.lev), lev.geom)
+            if hasattr(self.gravity, "check_boxes"):            # Poisson gravity: one box per level, inside the domain
+                self.gravity.check_boxes(len(self.lev), lev.box_list(), self.lev[-1].box_list())
         self.lev.append(lev)
         lev.bind()
         self._diag_masks, self._diag_tables = {}, {}    # the zones of the level below that are covered have changed
@@ -1748,8 +1798,11 @@ class CastroAmr(CheckpointMixin):
         return self.nstep
 
     def close(self):
-        """join a checkpoint in flight and re-raise what its thread raised (collective on more than one rank)"""
+        """join a checkpoint in flight and re-raise what its thread raised (collective on more than one rank); with Poisson
+        gravity, give back the multigrid plans of the levels (a later step makes them again)"""
         self.checkpoint_wait()
+        if hasattr(getattr(self, "gravity", None), "close"):
+            self.gravity.close()
 
     def __del__(self):
         try:

@@ -708,7 +708,8 @@ class CheckpointMixin:
         return restart_from(dirname, self)
 
     def _refuse_poisson(self, what):
-        if getattr(self, "poisson", None) is not None:
+        from .gravity import PoissonGravity
+        if getattr(self, "poisson", None) is not None or isinstance(getattr(self, "gravity", None), PoissonGravity):
             raise NotImplementedError("%s with Poisson gravity: a bit-faithful restart needs phi, the solver's starting guess, in "
                                       "the checkpoint (the reference's SD_1) -- a follow-up" % what)
 

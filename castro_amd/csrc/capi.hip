@@ -1208,6 +1208,31 @@ int castro_amd_grad_phi_to_grav_fab(castro_amd_ctx* c, const castro_amd_fab* phi
     return launch_grad_phi(to_dfab(phi_fab), to_dfab(grav_fab), L, geom->dx, (hipStream_t)stream, &c->prof);
 }
 
+// the Dirichlet data of a refined level's own solve: the fine box (ratio 2: even low, odd high corner) grown by one inside
+// phi_fine_fab, the coarsened box grown by one inside both coarse FABs
+int castro_amd_poisson_cf_bc_fab(castro_amd_ctx* c, const castro_amd_fab* phi_fine_fab, const int fine_lo[3], const int fine_hi[3],
+                                 const castro_amd_fab* crse_old_fab, const castro_amd_fab* crse_new_fab, double a, void* stream)
+{
+    if (!c || !fine_lo || !fine_hi || !(a - a == 0.0)) return CASTRO_AMD_ERR_ARG;
+    const castro_amd_fab* fabs[3] = { phi_fine_fab, crse_old_fab, crse_new_fab };
+    for (const castro_amd_fab* f : fabs) {
+        if (!f || !f->p || f->ncomp != 1) return CASTRO_AMD_ERR_ARG;
+        for (int d = 0; d < 3; ++d) if (f->hi[d] < f->lo[d]) return CASTRO_AMD_ERR_ARG;
+    }
+    int clo[3], chi[3];
+    for (int d = 0; d < 3; ++d) {
+        if (fine_hi[d] < fine_lo[d] || (fine_lo[d] & 1) != 0 || (fine_hi[d] & 1) != 1) return CASTRO_AMD_ERR_ARG;
+        if (fine_lo[d] < -(1 << 30) || fine_hi[d] > (1 << 30)) return CASTRO_AMD_ERR_ARG;
+        clo[d] = (fine_lo[d] >> 1) - 1;
+        chi[d] = (fine_hi[d] >> 1) + 1;
+    }
+    if (!fab_contains_grown1(phi_fine_fab, fine_lo, fine_hi) || !fab_contains(crse_old_fab, clo, chi) || !fab_contains(crse_new_fab, clo, chi))
+        return CASTRO_AMD_ERR_ARG;
+    hipSetDevice(c->device);
+    return launch_phi_cf_bc(to_dfab(phi_fine_fab), fine_lo, fine_hi, to_dfab(crse_old_fab), to_dfab(crse_new_fab), a, (hipStream_t)stream,
+                            &c->prof);
+}
+
 // a gravity FAB of the _gfab source calls: 3 components, one ghost zone around [lo, hi] where the energy term reads neighbours
 static bool grav_fab_ok(const castro_amd_fab* g, const int lo[3], const int hi[3], int grav_source_type)
 {

@@ -356,6 +356,9 @@ inline Slabs shell_slabs(const int flo[3], const int fhi[3], const int blo[3], c
 // the multipole boundary potential on the zones of [flo, fhi] outside the domain (poisson_kernels.hip)
 int launch_multipole_phi_bc(const DFab& F, const int flo[3], const int fhi[3], const MpGeom& G, const double* d_q, hipStream_t stream,
                             Profiler* prof);
+// the one-zone shell of the fine box [flo, fhi] of F from the coarse potentials O / N of the level below at weight a (k_phi_cf_bc)
+int launch_phi_cf_bc(const DFab& F, const int flo[3], const int fhi[3], const DFab& O, const DFab& N, double a, hipStream_t stream,
+                     Profiler* prof);
 // the second half of the physical-boundary fill of a state FAB (extbc_kernels.hip): ambient_fill, then hse_fill
 int launch_ext_bc_fill(const DFab& U, const int flo[3], const int fhi[3], const ::castro_amd_geom* geom, const DevParams& P,
                        const ::castro_amd_ext_bc* ext, int* d_unconverged, hipStream_t stream, Profiler* prof);

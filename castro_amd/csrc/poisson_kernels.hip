@@ -8,6 +8,7 @@
 //   k_mp_partial + k_mp_final             the multipole moments of Gravity::fill_multipole_BCs (Gravity.cpp:1742-2032, multipole_add
 //                                         of Gravity_util.H) with boundary_only = 1: every zone falls in the last radial bin
 //   k_mp_phi_bc                           the boundary potential (Gravity.cpp:2066-2216) on the zones of a FAB outside the domain
+//   k_phi_cf_bc                           the coarse-fine boundary potential of a refined level's own solve (the end of the file)
 // The multigrid is AMReX's [3P]: its arithmetic is not in the reference tree and is not pinned.  It is
 // written so that a restatement with the same order of operations reproduces the `exact` build bit for bit: the header comment
 // of every pass gives that order, and the passes hold no transcendental.  The `contract` build fuses these passes' multiply-adds.
@@ -657,7 +658,9 @@ __global__ void __launch_bounds__(256) k_mp_phi_bc(DFab F, Slabs S, MpGeom G, co
         double p = 0.0, p1 = 0.0, p2 = 0.0;
         for (int l = 0; l <= lnum; ++l) {
             mp_leg(l, p, p1, p2, cosTheta);
-            const double r_U = pow(r_, (double)(-l - 1));
+            // r^(-1) of the monopole term is one correctly rounded division, not a library call: with lnum = 0 the whole
+            // boundary potential is then arithmetic a restatement reproduces bit for bit (the level solves' driver test does)
+            const double r_U = l == 0 ? 1.0 / r_ : pow(r_, (double)(-l - 1));
             phi += q[l * n1] * p * r_U * rmax_cubed;
         }
     }
@@ -747,6 +750,104 @@ int launch_multipole_phi_bc(const DFab& F, const int flo[3], const int fhi[3], c
     if (n <= 0) return 0;
     prof_begin(prof, "k_mp_phi_bc", stream);
     hipLaunchKernelGGL(k_mp_phi_bc, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, F, S, G, d_q);
+    prof_end(prof, stream);
+    return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
+}
+
+// ---- the coarse-fine boundary of the potential of a refined level (level solves: gravity.no_sync = 1, no_composite = 1) ----------
+// The one-zone shell of the fine box [flo, fhi] in the fine FAB F, from the coarse potentials O (old) and N (new) of the level
+// below (refinement ratio 2) at the fine level's time: c = oma * O + a * N with oma = 1.0 - a formed on the host (GetCrsePhi; the
+// order of k_lincomb).  A face zone gets the value ON the fine face, which is what the solver keeps in its ghost zone.  Beyond an
+// x face, with the fine transverse indices (j, k), J = j >> 1, K = k >> 1, I_out = i >> 1 the coarse zone under the ghost zone and
+// I_in the one across the face:
+//   m(J, K) = 0.5 * (c(I_out, J, K) + c(I_in, J, K))
+//   value = (m(J, K) + s_j * (0.125 * (m(J + 1, K) - m(J - 1, K)))) + s_k * (0.125 * (m(J, K + 1) - m(J, K - 1)))
+// s = -1.0 for an even fine index, +1.0 for an odd one; the y faces take (i, k), the z faces (i, j), the lower direction first.
+// Edge and corner zones of the shell are read by no pass of the solver: 0.  Coarse zones read: the coarsened box grown by one.
+// Threads: the two z layers ((nx + 2) (ny + 2) zones each, edges and corners in them), the two y layers ((nx + 2) nz), the two x
+// layers (ny nz); x runs fastest in the z and y layers.  No atomics, no LDS; nothing but the shell is written.
+struct CfShell { int flo[3], fhi[3]; long start[4]; };
+
+__device__ __forceinline__ double cf_crse(const DFab& O, const DFab& N, double oma, double a, const int c[3])
+{
+    return oma * O.p[mg_at(O, c[0], c[1], c[2])] + a * N.p[mg_at(N, c[0], c[1], c[2])];
+}
+
+// m of the coarse transverse position c (c[d] is ignored): the mean of the coarse zones on the two sides of the face
+__device__ __forceinline__ double cf_face_mean(const DFab& O, const DFab& N, double oma, double a, int d, int c_out, int c_in, const int c[3])
+{
+    int p[3] = { c[0], c[1], c[2] };
+    p[d] = c_out;
+    const double vo = cf_crse(O, N, oma, a, p);
+    p[d] = c_in;
+    const double vi = cf_crse(O, N, oma, a, p);
+    return 0.5 * (vo + vi);
+}
+
+__global__ void __launch_bounds__(256) k_phi_cf_bc(DFab F, DFab O, DFab N, CfShell S, double oma, double a)
+{
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= S.start[3]) return;
+    const int nxg = S.fhi[0] - S.flo[0] + 3, nyg = S.fhi[1] - S.flo[1] + 3;
+    const int ny = nyg - 2, nz = S.fhi[2] - S.flo[2] + 1;
+    int d, side, g[3];
+    if (tid < S.start[1]) {
+        const long per = (long)nxg * nyg;
+        const long r = tid % per;
+        d = 2; side = (int)(tid / per);
+        g[0] = S.flo[0] - 1 + (int)(r % nxg);
+        g[1] = S.flo[1] - 1 + (int)(r / nxg);
+    } else if (tid < S.start[2]) {
+        const long t = tid - S.start[1], per = (long)nxg * nz;
+        const long r = t % per;
+        d = 1; side = (int)(t / per);
+        g[0] = S.flo[0] - 1 + (int)(r % nxg);
+        g[2] = S.flo[2] + (int)(r / nxg);
+    } else {
+        const long t = tid - S.start[2], per = (long)ny * nz;
+        const long r = t % per;
+        d = 0; side = (int)(t / per);
+        g[1] = S.flo[1] + (int)(r % ny);
+        g[2] = S.flo[2] + (int)(r / ny);
+    }
+    g[d] = side ? S.fhi[d] + 1 : S.flo[d] - 1;
+    double* dst = F.p + mg_at(F, g[0], g[1], g[2]);
+    int nout = 0;
+    for (int e = 0; e < 3; ++e) nout += (g[e] < S.flo[e] || g[e] > S.fhi[e]) ? 1 : 0;
+    if (nout != 1) { *dst = 0.0; return; }
+    const int t1 = d == 0 ? 1 : 0, t2 = d == 2 ? 1 : 2;
+    const int c_out = g[d] >> 1, c_in = side ? c_out - 1 : c_out + 1;
+    int c[3] = { g[0] >> 1, g[1] >> 1, g[2] >> 1 };
+    const double m0 = cf_face_mean(O, N, oma, a, d, c_out, c_in, c);
+    c[t1] += 1;
+    const double m1p = cf_face_mean(O, N, oma, a, d, c_out, c_in, c);
+    c[t1] -= 2;
+    const double m1m = cf_face_mean(O, N, oma, a, d, c_out, c_in, c);
+    c[t1] += 1;
+    c[t2] += 1;
+    const double m2p = cf_face_mean(O, N, oma, a, d, c_out, c_in, c);
+    c[t2] -= 2;
+    const double m2m = cf_face_mean(O, N, oma, a, d, c_out, c_in, c);
+    const double s1 = (g[t1] & 1) ? 1.0 : -1.0, s2 = (g[t2] & 1) ? 1.0 : -1.0;
+    *dst = (m0 + s1 * (0.125 * (m1p - m1m))) + s2 * (0.125 * (m2p - m2m));
+}
+
+int launch_phi_cf_bc(const DFab& F, const int flo[3], const int fhi[3], const DFab& O, const DFab& N, double a, hipStream_t stream,
+                     Profiler* prof)
+{
+    CfShell S;
+    long n[3];
+    for (int d = 0; d < 3; ++d) {
+        if (fhi[d] < flo[d]) return CASTRO_AMD_ERR_ARG;
+        S.flo[d] = flo[d]; S.fhi[d] = fhi[d];
+        n[d] = (long)fhi[d] - flo[d] + 1;
+    }
+    S.start[0] = 0;
+    S.start[1] = 2 * (n[0] + 2) * (n[1] + 2);
+    S.start[2] = S.start[1] + 2 * (n[0] + 2) * n[2];
+    S.start[3] = S.start[2] + 2 * n[1] * n[2];
+    prof_begin(prof, "k_phi_cf_bc", stream);
+    hipLaunchKernelGGL(k_phi_cf_bc, dim3((unsigned)((S.start[3] + 255) / 256)), dim3(256), 0, stream, F, O, N, S, 1.0 - a, a);
     prof_end(prof, stream);
     return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
 }

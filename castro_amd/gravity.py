@@ -22,9 +22,12 @@
 
   PoissonGravity                     gravity.gravity_type = "PoissonGrav" on a single level (castro_amd.Castro(poisson=...)): the
                                      multipole boundary values, the multigrid solve and g = -grad(phi) of one time level, and the
-                                     old / new potentials of the run (the class at the end of this file).
+                                     old / new potentials of the run (the class at the end of this file); and on the levels of
+                                     CastroAmr (gravity=PoissonGravity(...)) in the reference's level-solve configuration
+                                     (gravity.no_sync = 1, gravity.no_composite = 1, gravity.max_solve_level): every level solves on
+                                     its own box, a refined one with Dirichlet data from the level below at its own time.
 
-Levels finer than `level` do not enter.  Not provided: GR_GRAV, gravity.max_solve_level, a potential (phiGrav), domains with a periodic direction (the Gravity_Type FillPatch across a periodic boundary is not built), thermal
+Levels finer than `level` do not enter.  Not provided with monopole gravity: GR_GRAV, gravity.max_solve_level, a potential (phiGrav), domains with a periodic direction (the Gravity_Type FillPatch across a periodic boundary is not built), thermal
 diffusion on AMR levels, constant gravity plus a point mass on AMR levels.
 """
 from . import _lib as L
@@ -240,12 +243,32 @@ class PoissonGravity:
     max_multipole_order: gravity.max_multipole_order (lnum); reltol / abstol: gravity.rel_tol / abs_tol of the stopping rule
     ||r|| <= max(reltol ||b||, abstol max(b)); maxiter: V-cycles before RuntimeError (the reference aborts there); Gconst:
     C::Gconst; center: problem::center, default the driver's `center`, else the middle of the domain.
-    Not built (each refused by the driver): AMR levels, more than one rank, periodic or Symmetry faces, the point mass,
-    checkpoints, gravity.mlmg_maxorder > 2, direct_sum_bcs."""
+    Not built (each refused by the driver): more than one rank, periodic or Symmetry faces, the point mass,
+    checkpoints, gravity.mlmg_maxorder > 2, direct_sum_bcs.
+
+    On a hierarchy: castro_amd.CastroAmr(do_grav=True, gravity=PoissonGravity(..., max_solve_level=None)) -- the level solves of
+    the second half of this class.  max_solve_level: gravity.max_solve_level, the finest level that solves (None: every level, the
+    reference's default); a finer level takes phi and g from the level below by interpolation.  no_sync / no_composite:
+    gravity.no_sync / gravity.no_composite; only True is built (no composite solve, no gravity_sync, no composite correction).
+    One rank, refinement ratio 2, level 0 and every refined level ONE box, the refined ones inside the domain."""
 
     OPERATIONS = ("multipole_moments_mf", "multipole_phi_bc", "poisson_solve", "grad_phi_to_grav")
+    AMR_OPERATIONS = ("poisson_cf_bc", "lincomb", "cc_interp")
+    drdxfac = 1                                 # a box of a CastroAmr level copies it from its gravity object; not used here
 
-    def __init__(self, max_multipole_order=0, reltol=1.e-10, abstol=1.e-10, maxiter=40, Gconst=L.GCONST, center=None):
+    def __init__(self, max_multipole_order=0, reltol=1.e-10, abstol=1.e-10, maxiter=40, Gconst=L.GCONST, center=None,
+                 max_solve_level=None, no_sync=True, no_composite=True):
+        if not no_sync or not no_composite:
+            raise NotImplementedError("Poisson gravity: gravity.no_sync = 0 / gravity.no_composite = 0 -- the composite solve, "
+                                      "gravity_sync and the composite correction of the hierarchy -- are not built; the levels "
+                                      "solve for themselves (no_sync=True, no_composite=True)")
+        self.max_solve_level = None if max_solve_level is None else int(max_solve_level)
+        if self.max_solve_level is not None and self.max_solve_level < 0:
+            raise ValueError("gravity.max_solve_level must not be negative, not %d" % self.max_solve_level)
+        self.amr = None
+        self.point_mass = None
+        self._lev = {}
+        self.solve_log = []                     # (level, "old" | "new", a) of the last solves of a hierarchy, oldest first
         self.lnum = int(max_multipole_order)
         if self.lnum < 0:
             raise ValueError("gravity.max_multipole_order must not be negative, not %d" % self.lnum)
@@ -259,9 +282,29 @@ class PoissonGravity:
         self.plan = None
         self.stats = {"first": None, "old": None, "new": None}
 
-    def bind(self, c, hydro_alloc):
+    def bind(self, owner, *args):
+        """bind(castro, hydro_alloc): the single-level driver (Castro(poisson=...)); bind(amr, lo_bc, hi_bc): the hierarchy
+        (CastroAmr(gravity=...), the call MonopoleGravity answers too)"""
+        if len(args) == 1:
+            return self._bind_single(owner, args[0])
+        lo_bc, hi_bc = args
+        if self.driver is not None or (self.amr is not None and self.amr is not owner):
+            raise ValueError("a PoissonGravity object belongs to one Castro or one CastroAmr")
+        self._refuse_faces(lo_bc, hi_bc)
+        self.amr = owner
+
+    @staticmethod
+    def _refuse_faces(lo_bc, hi_bc):
+        for d in range(3):
+            for bc in (lo_bc[d], hi_bc[d]):
+                if bc == 0 or bc == 3:
+                    raise NotImplementedError("Poisson gravity with a %s face: the mass offset of a periodic domain and the "
+                                              "reflected moments / Neumann faces of a Symmetry one are a follow-up; all six faces "
+                                              "must be Dirichlet faces of the potential" % ("periodic" if bc == 0 else "Symmetry"))
+
+    def _bind_single(self, c, hydro_alloc):
         """the checks of the driver `c` this object belongs to, and its arrays: phi_old / phi_new with one ghost zone, the moments"""
-        if self.driver is not None and self.driver is not c:
+        if self.amr is not None or (self.driver is not None and self.driver is not c):
             raise ValueError("a PoissonGravity object belongs to one Castro")
         h = c.hydro
         missing = [name for name in self.OPERATIONS + ("poisson_plan_create", "grav_bc_fill") if not hasattr(h, name)]
@@ -291,6 +334,14 @@ class PoissonGravity:
         if self.plan is not None and self.driver is not None:
             self.driver.hydro.poisson_plan_destroy(self.plan)
         self.plan = None
+        for ent in self._lev.values():          # the plans of a hierarchy; phi stays, a later solve makes the plan again
+            self._free_plan(ent)
+
+    @staticmethod
+    def _free_plan(ent):
+        if ent.get("plan") is not None:
+            ent["hydro"].poisson_plan_destroy(ent["plan"])
+        ent["plan"] = None
 
     def __del__(self):
         try:
@@ -340,3 +391,174 @@ class PoissonGravity:
                                                                   hist[-2], hist[-1]))
         h.grad_phi_to_grav(phi, self.phibox, grav, c.gravbox, c.geom)
         h.grav_bc_fill(grav, c.gravbox, c.geom)
+
+    # ---- the levels of a CastroAmr hierarchy: level solves (gravity.no_sync = 1, gravity.no_composite = 1) -----------------
+    # Castro::construct_old_gravity / construct_new_gravity (Castro_gravity.cpp:14-232) and Gravity::solve_for_phi /
+    # get_old_grav_vector / get_new_grav_vector / GetCrsePhi (Gravity.cpp:418-485, 664-690, 838-981) on a hierarchy whose refined
+    # levels are one box each.  Level 0 is the single-level path above.  A level 0 < l <= max_solve_level solves on its own box
+    # -- a geometry whose domain is the box goes to the same entry points -- with Dirichlet data from the potential of the level
+    # below at its own time (castro_amd_poisson_cf_bc_fab).  A level above max_solve_level takes phi and g of its whole FABs from
+    # the level below (FillCoarsePatch: lincomb in time, cc_interp in space).
+    def solves(self, level):
+        return self.max_solve_level is None or level <= self.max_solve_level
+
+    def check_level(self, l, geom):
+        h = self.amr._hydro_for(l)
+        missing = [name for name in self.OPERATIONS + self.AMR_OPERATIONS + ("poisson_plan_create", "grav_bc_fill") if not hasattr(h, name)]
+        if missing:
+            raise NotImplementedError("Poisson gravity: this backend has no %s; there is no host fallback" % ", ".join(missing))
+        if l == 0:
+            n = tuple(geom.domhi[d] - geom.domlo[d] + 1 for d in range(3))
+            self._check_bottom(0, (tuple(geom.domlo[d] for d in range(3)), tuple(geom.domhi[d] for d in range(3))), n)
+
+    def _check_bottom(self, l, box, n):
+        coarsest = L.poisson_level_extents(n)[-1]
+        if coarsest[0] * coarsest[1] * coarsest[2] > L.POISSON_MAX_BOTTOM:
+            raise ValueError("Poisson gravity: the box %s of level %d (%s zones) coarsens to %s, more than the %d zones the bottom "
+                             "solver of the multigrid takes (CASTRO_AMD_POISSON_MAX_BOTTOM): its extents need more factors of 2 "
+                             "-- a blocking_factor of 16 or 32" % (box, l, n, coarsest, L.POISSON_MAX_BOTTOM))
+
+    def check_boxes(self, l, boxes, parents):
+        """the boxes (lo, hi) of the refined level l about to be made, in its own zones; parents: those of level l - 1"""
+        if len(boxes) != 1 or len(parents) != 1:
+            raise NotImplementedError("Poisson gravity: level %d would have %d boxes (level %d has %d) -- the level solves are "
+                                      "built for refined levels of ONE box; a level of several boxes needs the halo exchange of "
+                                      "phi between them" % (l, len(boxes), l - 1, len(parents)))
+        lo, hi = boxes[0]
+        dom = tuple((2 ** l) * x for x in self.amr.n_cell)
+        if any(lo[d] <= 0 or hi[d] >= dom[d] - 1 for d in range(3)):
+            raise NotImplementedError("Poisson gravity: the box %s of level %d touches the domain boundary -- the multipole "
+                                      "boundary values of a refined level are not built; the box must lie inside the domain"
+                                      % ((lo, hi), l))
+        if not self.solves(l):
+            return
+        plo, phi = parents[0]
+        if any((lo[d] >> 1) - 1 < plo[d] or (hi[d] >> 1) + 1 > phi[d] for d in range(3)):
+            raise ValueError("Poisson gravity: the box %s of level %d, coarsened and grown by one zone, does not lie inside the "
+                             "valid box %s of level %d: its boundary values would read ghost zones of the coarse potential"
+                             % ((lo, hi), l, (plo, phi), l - 1))
+        self._check_bottom(l, (lo, hi), tuple(hi[d] - lo[d] + 1 for d in range(3)))
+
+    def reset(self, from_level=0):
+        """regrid / _push_level / _drop_fine: the levels >= from_level are gone or re-made -- their potentials and plans go"""
+        for l in list(self._lev):
+            if l >= from_level:
+                self._free_plan(self._lev[l])
+                del self._lev[l]
+
+    def problem_center(self):
+        if self.center is not None:
+            return list(self.center)
+        g = self.amr.lev[0].geom
+        return [0.5 * (g.problo[d] + g.probhi[d]) for d in range(3)]
+
+    def _entry(self, l):
+        """phi_old / phi_new (one ghost zone), the plan and the scratch of level l, made for the box the level has now"""
+        lev = self.amr.lev[l]
+        b = lev.mine[0]
+        ent = self._lev.get(l)
+        if ent is not None and ent["key"] != b.bx:       # a plan is kept per level, keyed by the extents of its box
+            self._free_plan(ent)
+            ent = None
+        if ent is None:
+            h = lev.hydro
+            phibox = (tuple(x - 1 for x in b.lo), tuple(x + 1 for x in b.hi))
+            ent = self._lev[l] = dict(key=b.bx, hydro=h, phibox=phibox, phi_old=h.alloc(1, *phibox), phi_new=h.alloc(1, *phibox),
+                                      plan=None, have=(l == 0), tables={}, stats={"first": None, "old": None, "new": None})
+            if l == 0:
+                n1 = self.lnum + 1
+                ent["moments"] = h.alloc(1, (0, 0, 0), (3 * n1 * n1 - 1, 0, 0))
+                ent["geom"] = lev.geom
+            else:
+                g = L.Geom.from_buffer_copy(lev.geom)    # the level's dx and problo; the "domain" is the box, Dirichlet all round
+                for d in range(3):
+                    g.domlo[d], g.domhi[d], g.lo_bc[d], g.hi_bc[d] = b.lo[d], b.hi[d], 2, 2
+                ent["geom"] = g
+                # coarse zones under the box grown by one, grown by one more for the slopes of cc_interp
+                ent["cbox"] = (tuple((x >> 1) - 2 for x in b.lo), tuple((x >> 1) + 2 for x in b.hi))
+                ent["ctmp"] = h.alloc(1, *ent["cbox"])
+        return ent
+
+    def swap_level(self, l):
+        """swap_state_time_levels of PhiGrav_Type of level l, at the start of every advance of the level"""
+        ent = self._lev.get(l)
+        if ent is not None:
+            ent["phi_old"], ent["phi_new"] = ent["phi_new"], ent["phi_old"]
+
+    def _crse_at(self, l, ent, a):
+        """GetCrsePhi: (1 - a) phi_old + a phi_new of level l - 1 into the scratch of level l, where level l - 1 has data"""
+        P = self._entry(l - 1)
+        cb, pb = ent["cbox"], P["phibox"]
+        lo = tuple(max(cb[0][d], pb[0][d]) for d in range(3))
+        hi = tuple(min(cb[1][d], pb[1][d]) for d in range(3))
+        ent["hydro"].lincomb(ent["ctmp"], cb, 1.0 - a, P["phi_old"], pb, a, P["phi_new"], pb, 1, lo, hi)
+        return P
+
+    def _grav_vector(self, level, which, a):
+        import math
+        lev = self.amr.lev[level]
+        b = lev.mine[0]
+        h = lev.hydro
+        ent = self._entry(level)
+        name = "grav_" + which
+        grav = getattr(b, name)
+        phi, pbx = ent["phi_" + which], ent["phibox"]
+        if level > 0 and not self.solves(level):
+            # no solve above max_solve_level: phi and g of the whole FABs are the FillCoarsePatch of the level below
+            # (Gravity.cpp:466, 846-852, 919-925)
+            self._crse_at(level, ent, a)
+            h.cc_interp(ent["ctmp"], ent["cbox"], phi, pbx, pbx[0], pbx[1], 1)
+            ent["have"] = True
+            for p, (lo, hi) in b.gsrc + b.gsrc_valid:
+                h.lincomb(b.gctmp, b.gcbox, 1.0 - a, p.grav_old, p.gravbox, a, p.grav_new, p.gravbox, 3, lo, hi)
+            h.cc_interp(b.gctmp, b.gcbox, grav, b.gravbox, b.gravbox[0], b.gravbox[1], 3)
+            return
+        if not ent["have"]:
+            # the first solve of the level, or of a level a regrid has re-made: the level below, interpolated, is the guess
+            self._crse_at(level, ent, a)
+            h.cc_interp(ent["ctmp"], ent["cbox"], phi, pbx, b.lo, b.hi, 1)
+            ent["have"] = True
+        elif which == "new":
+            phi.copy_(ent["phi_old"])                    # the "old" phi of the step is the guess (Castro_gravity.cpp:146)
+        if ent["plan"] is None:                          # the first solve, or after close()
+            ent["plan"] = h.poisson_plan_create(ent["geom"])
+        S = b.S_old_b if which == "old" else b.S_new_b
+        if level == 0:
+            geom = ent["geom"]
+            mp = L.make_multipole(geom, self.problem_center(), self.lnum, self.Gconst)
+            key = S.data_ptr()
+            if key not in ent["tables"]:
+                ent["tables"][key] = h.make_diag_boxes([(b.lo, b.hi, (S, b.gbox), None)])
+            mom = ent["moments"].reshape(-1)
+            h.multipole_moments_mf(ent["tables"][key], geom, mp, mom)      # fill_multipole_BCs(level, level): this level alone
+            h.multipole_phi_bc(phi, pbx, geom, mp, mom)
+        else:
+            P = self._lev[level - 1]
+            h.poisson_cf_bc(phi, pbx, b.lo, b.hi, P["phi_old"], P["phibox"], P["phi_new"], P["phibox"], a)
+        cycles, ok, norm, hist = h.poisson_solve(ent["plan"], phi, pbx, S, b.gbox, L.URHO, 4.0 * math.pi * self.Gconst,
+                                                 self.reltol, self.abstol, self.maxiter)
+        st = ent["stats"]
+        st[which] = {"cycles": cycles, "norm": norm, "history": hist}
+        if st["first"] is None:
+            st["first"] = st[which]
+        self.solve_log.append((level, which, a))
+        del self.solve_log[:-256]
+        if not ok:
+            raise RuntimeError("Poisson gravity, level %d: the multigrid did not reach max(%g * %g, %g * %g) in %d V-cycles; the "
+                               "last two residual norms are %r and %r" % (level, self.reltol, hist[0], self.abstol, hist[1],
+                                                                          self.maxiter, hist[-2], hist[-1]))
+        h.grad_phi_to_grav(phi, pbx, grav, b.gravbox, ent["geom"])
+        lev.fill_grav(name, a)                           # the Gravity_Type FillPatch of the ghost zones of g
+
+    def get_old_grav_vector(self, level, time=None, a=0.0):
+        """phi_old and grav_old of `level` at the level's old time; a: where that time lies in the parent's [old, new]"""
+        self._grav_vector(level, "old", a)
+
+    def get_new_grav_vector(self, level, time=None, a=1.0):
+        self._grav_vector(level, "new", a)
+
+    def phi_level(self, level, new=True):
+        return self._entry(level)["phi_new" if new else "phi_old"]
+
+    def stats_level(self, level):
+        return dict(self._entry(level)["stats"])

@@ -319,6 +319,14 @@ class HipHydro:
         L.check(self.lib.castro_amd_grad_phi_to_grav_fab(self.h, C.byref(L.fab_of(phi, *phi_box)), C.byref(L.fab_of(grav, *grav_box)),
                                                          C.byref(geom), _stream_ptr(stream)), "grad_phi_to_grav_fab")
 
+    def poisson_cf_bc(self, phi, phi_box, fine_lo, fine_hi, crse_old, crse_old_box, crse_new, crse_new_box, a, stream=None):
+        """castro_amd_poisson_cf_bc_fab: the Dirichlet data of the level solve of the patch [fine_lo, fine_hi] into the one-zone
+        shell around it in `phi`, from the potentials of the level below: (1 - a) crse_old + a crse_new, the value on the fine face"""
+        rc = self.lib.castro_amd_poisson_cf_bc_fab(self.h, C.byref(L.fab_of(phi, *phi_box)), L.i3(fine_lo), L.i3(fine_hi),
+                                                   C.byref(L.fab_of(crse_old, *crse_old_box)), C.byref(L.fab_of(crse_new, *crse_new_box)),
+                                                   float(a), _stream_ptr(stream))
+        L.check(rc, "poisson_cf_bc_fab")
+
     # ---- the central point mass (castro.use_point_mass; Gravity.cpp:2903-2948, Castro_pointmass.cpp) ---------------------
     def add_pointmass(self, grav, grav_box, pm, geom, mass, stream=None):
         """castro_amd_add_pointmass_fab: Gravity::add_pointmass_to_gravity over the whole box of the 3-component FAB `grav`; pm:

@@ -74,6 +74,7 @@ extern "C" {
  *      castro_amd_multipole_moments_mf, castro_amd_multipole_phi_bc_fab (struct castro_amd_multipole),
  *      castro_amd_poisson_plan_create / _destroy, castro_amd_poisson_solve, castro_amd_poisson_level_op,
  *      castro_amd_grad_phi_to_grav_fab: Poisson self-gravity on a single level.
+ *      castro_amd_poisson_cf_bc_fab: the coarse-fine boundary potential of a refined level's own Poisson solve.
  * A caller checks `castro_amd_abi_version() == CASTRO_AMD_ABI_VERSION` once after loading the library; a mismatch means
  * the library was built from another revision of this header (a 0.2 caller with 2-double vectors would be written 8 bytes
  * out of bounds by a 0.3 library). */
@@ -654,7 +655,8 @@ int castro_amd_multipole_moments_mf(castro_amd_ctx *ctx, int nboxes, const castr
 /* The boundary potential (Gravity.cpp:2066-2216) of every zone of phi_fab (1 component) outside the domain -- faces, edges and
  * corners: phi = -G / rmax * sum(...  r^(-l-1) rmax^3) at the zone centre moved onto the domain face in every direction in which
  * the zone lies outside (i dx beyond the high face, (i + 1) dx below the low face); 0 where r < 1e-12.  Zones of the domain are
- * not written.  phi_fab must overlap the domain. */
+ * not written.  phi_fab must overlap the domain.  r^(-l-1) is pow(r, -l - 1) for l >= 1 and the division 1 / r for l = 0: with
+ * lnum = 0 the values hold no library call and are the same bits wherever IEEE arithmetic is. */
 int castro_amd_multipole_phi_bc_fab(castro_amd_ctx *ctx, const castro_amd_fab *phi_fab, const castro_amd_geom *geom,
                                     const castro_amd_multipole *mp, const double *d_moments, void *stream);
 /* Geometric multigrid for lap(phi) = 4 pi G rho with the 7-point cell-centred Laplacian on the domain of `geom` (dx, dy, dz may
@@ -698,6 +700,22 @@ int castro_amd_poisson_level_op(castro_amd_ctx *ctx, castro_amd_poisson_plan *pl
  * linear ghost gives 2 (phi_1 - phi_face) / dx.  The zones outside the domain are left to castro_amd_grav_bc_fill_fab. */
 int castro_amd_grad_phi_to_grav_fab(castro_amd_ctx *ctx, const castro_amd_fab *phi_fab, const castro_amd_fab *grav_fab,
                                     const castro_amd_geom *geom, void *stream);
+/* Poisson gravity on a refined level that solves for itself (gravity.no_sync = 1, gravity.no_composite = 1, refinement ratio 2):
+ * a patch [fine_lo, fine_hi] goes through the entry points above with a castro_amd_geom whose domlo / domhi are the patch (every
+ * bc a Dirichlet one), and this call puts the Dirichlet data into the one-zone shell of the patch in phi_fine_fab (1 component,
+ * the patch grown by one inside it).  The data come from the potential of the level below at the fine level's time,
+ * c = (1 - a) * crse_old + a * crse_new (Gravity::GetCrsePhi; (1 - a) is formed first, then the two products, then the sum),
+ * and are the value ON the fine face.  Beyond an x face, for the fine transverse indices (j, k): J = j >> 1, K = k >> 1, I_out
+ * and I_in the coarse zones outside and inside the face,
+ *   m(J, K) = 0.5 * (c(I_out, J, K) + c(I_in, J, K)),
+ *   value = (m(J, K) + s_j * 0.125 * (m(J + 1, K) - m(J - 1, K))) + s_k * 0.125 * (m(J, K + 1) - m(J, K - 1)),
+ * s = -1 for an even fine index and +1 for an odd one; the y and z faces alike, the lower transverse direction first.  The edge
+ * and corner zones of the shell are set to 0 (no pass of the solver reads them); nothing else of phi_fine_fab is written.
+ * Compiled without contraction in both numerics builds: the same bits.  CASTRO_AMD_ERR_ARG: a NULL or multi-component FAB, a
+ * fine box that is not the refinement of a coarse box (an odd low or an even high corner), a non-finite a, the patch grown by
+ * one not inside phi_fine_fab, or the coarsened patch grown by one not inside both coarse FABs. */
+int castro_amd_poisson_cf_bc_fab(castro_amd_ctx *ctx, const castro_amd_fab *phi_fine_fab, const int fine_lo[3], const int fine_hi[3],
+                                 const castro_amd_fab *crse_old_fab, const castro_amd_fab *crse_new_fab, double a, void *stream);
 /* castro_amd_sources_mf with the gravity of every box read from its Gravity_Type FABs: grav_old[i] / grav_new[i] (3
  * components, one ghost zone around [lo, hi] of box i for grav_source_type = 4; grav_new is read by stage 1 only and may be
  * NULL for stage 0) take the place of the one vector -- the zone functions of castro_amd_old/new_gravity_source_gfab inside
