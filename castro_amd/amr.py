@@ -917,7 +917,7 @@ class CastroAmr(CheckpointMixin):
             raise NotImplementedError("CastroAmr: Poisson gravity (poisson=...) is built for a single level only -- the level "
                                       "solves, gravity_sync and the composite correction of the hierarchy are a follow-up; use "
                                       "castro_amd.Castro")
-        from .gravity import PoissonGravity
+        from .gravity import PoissonGravity, refuse_for_poisson
         if diffusion is not None and isinstance(gravity, PoissonGravity):
             raise ValueError("CastroAmr: gravity=PoissonGravity(...) not together with diffusion=...: thermal diffusion is built for "
                              "a single level only")
@@ -939,7 +939,8 @@ class CastroAmr(CheckpointMixin):
             if not do_grav:
                 raise ValueError("gravity=%s(...) needs do_grav=True" % type(gravity).__name__)
             if isinstance(gravity, PoissonGravity):
-                self._refuse_for_poisson(comm, base_grid, use_point_mass, check_int, ext_bc, n_cell, prob_lo, prob_hi, lo_bc, hi_bc)
+                refuse_for_poisson("CastroAmr: ", comm, base_grid, use_point_mass, check_int, ext_bc,
+                                   L.make_geom(n_cell, prob_lo, prob_hi, lo_bc, hi_bc))
             gravity.bind(self, lo_bc, hi_bc)
         self.gravity = gravity
         self.pm = None
@@ -1030,23 +1031,6 @@ class CastroAmr(CheckpointMixin):
         self._diag_out = None
 
     # ---- gravity=PoissonGravity(...): the level solves (castro_amd/gravity.py) ------------------------------------------------
-    @staticmethod
-    def _refuse_for_poisson(comm, base_grid, use_point_mass, check_int, ext_bc, n_cell, prob_lo, prob_hi, lo_bc, hi_bc):
-        if comm is not None and comm.size > 1:
-            raise NotImplementedError("CastroAmr: Poisson gravity on more than one rank: the multigrid needs a halo exchange of phi "
-                                      "on every level and the moments a sum over the ranks; a follow-up")
-        if base_grid is not None and tuple(base_grid) != (1, 1, 1):
-            raise NotImplementedError("CastroAmr: Poisson gravity with base_grid: level 0 must be one box -- the multigrid has no "
-                                      "halo exchange of phi between boxes; a follow-up")
-        if use_point_mass:
-            raise NotImplementedError("CastroAmr: use_point_mass with Poisson gravity (the point mass is excluded from the "
-                                      "right-hand side and added to the gradient) is not built")
-        if int(check_int) > 0:
-            raise NotImplementedError("CastroAmr: check_int with Poisson gravity: a bit-faithful restart needs phi of every level, "
-                                      "the solver's starting guess, in the checkpoint (the reference's SD_1) -- a follow-up")
-        if ext_bc is not None and L.ext_bc_hse_faces(ext_bc, L.make_geom(n_cell, prob_lo, prob_hi, lo_bc, hi_bc)):
-            raise ValueError("HSE boundaries assume constant gravity: not with gravity=PoissonGravity(...)")
-
     def _poisson_gravity(self, what):
         from .gravity import PoissonGravity
         if not isinstance(self.gravity, PoissonGravity):

@@ -296,6 +296,8 @@ class Castro(CheckpointMixin):
         takes the `center` attribute of this object, else the middle of the domain, whenever a step needs it.
         gravity: the castro_amd.MonopoleGravity of the CastroAmr hierarchy this box belongs to (set by CastroAmr: the object
         spans the levels and constructs grav_old / grav_new of every box; a single-level run uses gravity_type="monopole").
+        A single-level run with per-zone gravity makes or binds its own object -- self.gravity: a MonopoleGravity, the
+        PoissonGravity of `poisson`, or a ConstantGravity under a point mass -- and is that object's hierarchy of one level.
         gravity_type (gravity.gravity_type): "constant" (ConstantGrav: const_grav along z) | "monopole" (MonopoleGrav: the radial
         self-gravity of the state about the centre sum_integrated_quantities uses -- the `center` attribute, else the middle of the
         domain; 3-D Cartesian, non-periodic, single level); drdxfac: gravity.drdxfac; Gconst: the reference takes C::Gconst from
@@ -373,8 +375,6 @@ class Castro(CheckpointMixin):
         if ext_bc is not None:
             if do_grav and (gravity_type == "monopole" or gravity is not None) and L.ext_bc_hse_faces(ext_bc, self.geom):
                 raise ValueError("HSE boundaries assume constant gravity: not with gravity_type=\"monopole\"")
-            if do_grav and poisson is not None and L.ext_bc_hse_faces(ext_bc, self.geom):
-                raise ValueError("HSE boundaries assume constant gravity: not with poisson=PoissonGravity(...)")
             L.check_ext_bc(ext_bc, self.geom)
             self.ext_bc = L.complete_ext_bc(ext_bc, self.params, const_grav if do_grav else 0.0)
             if alloc:
@@ -444,33 +444,30 @@ class Castro(CheckpointMixin):
         if self.use_point_mass and not self.do_grav:
             raise ValueError("use_point_mass needs do_grav=True: the point mass is a term of the gravity vector")
         self.pm = None
+        # the gravity object of a single-level run: this driver is its hierarchy of one level (gravity.SingleLevel) and asks it
+        # for grav_old / grav_new like a level of CastroAmr asks the hierarchy's.  None with the one vector self.grav, and for
+        # a box of a CastroAmr level (level_gravity)
+        self.gravity, self.poisson = None, None
+        if poisson is not None:
+            if not self.do_grav:
+                raise ValueError("poisson=PoissonGravity(...) needs do_grav=True")
+            if gravity_type == "monopole" or gravity is not None:
+                raise ValueError("poisson=PoissonGravity(...) selects the gravity by itself: not together with "
+                                 "gravity_type=\"monopole\" or gravity=MonopoleGravity(...)")
         if self.level_gravity is not None:
-            # a box of a CastroAmr level: Gravity_Type old / new data with one ghost zone; the radial arrays live in `gravity`
+            # a box of a CastroAmr level: the radial arrays / the potentials live in `gravity`
             self.gravity_type, self.drdxfac, self.Gconst = "monopole", gravity.drdxfac, gravity.Gconst
+            if gravity.center is not None:
+                self.center = gravity.center
+        elif self.do_grav and (self.monopole or poisson is not None or self.use_point_mass):
+            self._init_gravity(poisson, box, alloc, check_int, ext_bc, point_mass, point_mass_fix_solution)
+        # the gravity of a zone comes from grav_old / grav_new instead of the one vector self.grav: Gravity_Type old / new data
+        # with the one ghost zone the grav_source_type = 4 energy term reads
+        self.grav_fab = self.level_gravity is not None or self.gravity is not None
+        if self.grav_fab:
             self.gravbox = (tuple(x - 1 for x in self.lo), tuple(x + 1 for x in self.hi))
             self.grav_old = hydro_alloc(3, *self.gravbox)
             self.grav_new = hydro_alloc(3, *self.gravbox)
-            if gravity.center is not None:
-                self.center = gravity.center
-        elif self.monopole:
-            self._init_monopole(hydro_alloc, box)
-        self.poisson = None
-        if poisson is not None:
-            self._init_poisson(poisson, hydro_alloc, box, gravity_type, gravity, check_int)
-        if self.use_point_mass and self.level_gravity is None:
-            if box is not None:
-                raise NotImplementedError("a point mass on a refined patch belongs to the hierarchy: CastroAmr(use_point_mass=True, "
-                                          "gravity=MonopoleGravity(...))")
-            if alloc:
-                from .gravity import PointMass
-                self.pm = PointMass(hydro, point_mass, point_mass_fix_solution, self.Gconst)
-            if not self.monopole:
-                # ConstantGrav plus a point mass: Gravity_Type data like monopole gravity's (Gravity.cpp:859-866, 902-907)
-                self.gravbox = (tuple(x - 1 for x in self.lo), tuple(x + 1 for x in self.hi))
-                self.grav_old = hydro_alloc(3, *self.gravbox)
-                self.grav_new = hydro_alloc(3, *self.gravbox)
-        # the gravity of a zone comes from grav_old / grav_new instead of the one vector self.grav
-        self.grav_fab = self.monopole or self.poisson is not None or (self.use_point_mass and self.do_grav)
         # castro.do_rotation: `rotation` = _lib.make_rotation(rotational_period, rot_axis, ...)
         self.rotation = rotation
         # castro.diffuse_temp = 1: `diffusion` = _lib.make_diffusion(const_conductivity, ...); castro.do_hydro
@@ -841,103 +838,59 @@ class Castro(CheckpointMixin):
         U[L.UFS] = rho
         return U
 
-    # ---- gravity.gravity_type = MonopoleGrav (Source/gravity/Gravity.cpp) --------------------------------------------
-    def _init_monopole(self, hydro_alloc, box):
+    # ---- per-zone gravity of a single level: one gravity object (castro_amd/gravity.py), this driver its one level ---------------
+    def _init_gravity(self, poisson, box, alloc, check_int, ext_bc, point_mass, point_mass_fix_solution):
+        from . import gravity as G
         if box is not None:
-            raise NotImplementedError("monopole gravity on a refined patch: the level combination and the time interpolation of "
-                                      "Gravity::make_radial_gravity (Gravity.cpp:2962-3127) are not built")
-        if all(self.periodic):
-            raise ValueError("monopole gravity needs a non-periodic domain: a fully periodic one has no isolated mass to take "
-                             "the radial profile of")
-        if self.drdxfac < 1:
-            raise ValueError("gravity.drdxfac must be at least 1, not %d" % self.drdxfac)
-        dmax = L.monopole_max_drdxfac([self.geom.dx[d] for d in range(3)])
-        if self.drdxfac > dmax:
-            raise ValueError("gravity.drdxfac = %d is above the %d this geometry allows: the binning kernel holds the sub-zones of a "
-                             "brick of 8 x 8 x 4 zones in a window of 64 bins (drdxfac <= 5 for cubic zones)" % (self.drdxfac, dmax))
-        self.n1d = L.monopole_n1d(self.n_cell, self.drdxfac)
-        # Gravity_Type old / new data with the one ghost zone the grav_source_type = 4 energy term reads
-        self.gravbox = (tuple(x - 1 for x in self.lo), tuple(x + 1 for x in self.hi))
-        self.grav_old = hydro_alloc(3, *self.gravbox)
-        self.grav_new = hydro_alloc(3, *self.gravbox)
-        self._radial_mv = hydro_alloc(1, (0, 0, 0), (2 * self.n1d - 1, 0, 0))
-        self._radial_g = hydro_alloc(1, (0, 0, 0), (self.n1d - 1, 0, 0))
-        self._mono_tables = {}
+            if poisson is not None:
+                raise NotImplementedError("Poisson gravity on a refined patch belongs to the hierarchy: "
+                                          "CastroAmr(gravity=PoissonGravity(...))")
+            if self.monopole:
+                raise NotImplementedError("monopole gravity on a refined patch: the level combination and the time interpolation "
+                                          "of Gravity::make_radial_gravity (Gravity.cpp:2962-3127) belong to the hierarchy: "
+                                          "CastroAmr(gravity=MonopoleGravity(...))")
+            raise NotImplementedError("a point mass on a refined patch belongs to the hierarchy: CastroAmr(use_point_mass=True, "
+                                      "gravity=MonopoleGravity(...))")
+        if poisson is not None:
+            G.refuse_for_poisson("", self.comm, None, self.use_point_mass, check_int, ext_bc, self.geom)
+            obj = self.poisson = poisson
+        elif self.monopole:
+            obj = G.MonopoleGravity(self.drdxfac, self.Gconst)
+        else:
+            obj = G.ConstantGravity(self.grav[2])       # ConstantGrav plus a point mass: no longer one vector
+        obj.bind(G.SingleLevel(self), self.lo_bc, self.hi_bc)
+        obj.check_level(0, self.geom)
+        self.gravity = obj
+        if self.use_point_mass and alloc:
+            self.pm = obj.point_mass = G.PointMass(self.hydro, point_mass, point_mass_fix_solution, self.Gconst)
+        if poisson is not None and alloc:
+            poisson.plan_level(0)
 
-    # ---- gravity.gravity_type = PoissonGrav on a single level (castro_amd/gravity.py: PoissonGravity) ---------------------
-    def _init_poisson(self, poisson, hydro_alloc, box, gravity_type, gravity, check_int):
-        if not self.do_grav:
-            raise ValueError("poisson=PoissonGravity(...) needs do_grav=True")
-        if gravity_type == "monopole" or gravity is not None:
-            raise ValueError("poisson=PoissonGravity(...) selects the gravity by itself: not together with gravity_type=\"monopole\" "
-                             "or gravity=MonopoleGravity(...)")
-        if box is not None:
-            raise NotImplementedError("Poisson gravity on a refined patch: the level solves, gravity_sync and the composite "
-                                      "correction of the AMR hierarchy are a follow-up")
-        if self.comm.size > 1:
-            raise NotImplementedError("Poisson gravity on more than one rank: the multigrid needs a halo exchange of phi on every "
-                                      "level and the moments a sum over the ranks -- a follow-up")
-        if self.use_point_mass:
-            raise NotImplementedError("use_point_mass with Poisson gravity (the point mass is excluded from the right-hand side "
-                                      "and added to the solution) is a follow-up")
-        if int(check_int) > 0:
-            raise NotImplementedError("check_int with Poisson gravity: a bit-faithful restart needs phi, the solver's starting "
-                                      "guess, in the checkpoint (the reference's SD_1) -- a follow-up")
-        poisson.bind(self, hydro_alloc)
-        self.poisson = poisson
-        self.gravbox = (tuple(x - 1 for x in self.lo), tuple(x + 1 for x in self.hi))
-        self.grav_old = hydro_alloc(3, *self.gravbox)
-        self.grav_new = hydro_alloc(3, *self.gravbox)
+    monopole_gravity = property(lambda self: self.gravity if self.monopole else None,
+                                doc="the MonopoleGravity of a single-level run with gravity_type=\"monopole\", else None")
+    n1d = property(lambda self: self.monopole_gravity.n1d(0), doc="bins of the radial arrays (gravity_type=\"monopole\")")
 
     def phi_grav(self, new=True):
         """the potential of the last new-time (or old-time) solve: the tensor (1, nz + 2, ny + 2, nx + 2), whose ghost zones
         outside the domain hold the multipole boundary values on the domain faces"""
         if self.poisson is None:
             raise RuntimeError("phi_grav() needs Castro(do_grav=True, poisson=PoissonGravity(...))")
-        return self.poisson.phi_new if new else self.poisson.phi_old
+        return self.poisson.phi_level(0, new)
 
     def poisson_stats(self):
         """{"first": ..., "old": ..., "new": ...}: cycles, final residual norm and norm history of the first solve of the run (from
         zero) and of the last old-time and new-time solves (warm-started)"""
         if self.poisson is None:
             raise RuntimeError("poisson_stats() needs Castro(do_grav=True, poisson=PoissonGravity(...))")
-        return dict(self.poisson.stats)
+        return self.poisson.stats_level(0)
 
-    def monopole_params(self):
-        """castro_amd_monopole_params of this run: n1d of the domain, max_radius_all_in_domain about the problem centre"""
-        from . import diag
-        return L.make_monopole(self.n_cell, self.geom, diag.domain_center(self), self.drdxfac, self.Gconst)
-
-    def _monopole_gravity(self, S, grav):
-        """Gravity::construct_old_gravity / construct_new_gravity for MonopoleGrav (Castro_advance_ctu.cpp:122, 258): bin the valid
-        zones of S, sum over the ranks, integrate outwards, interpolate onto `grav` (ghost zone included) -- all on the device.
-        The reference bins the State_Type data, not Sborder: at the old-time point that is S_old_b, whose valid zones are the
-        cleaned old state (the FillPatch only adds ghost zones around them), at the new-time point S_new_b after the hydro
-        update and its clean_state."""
-        h = self.hydro
-        mono = self.monopole_params()
-        key = S.data_ptr()                      # the two state buffers swap roles every step: one table each
-        if key not in self._mono_tables:
-            self._mono_tables[key] = h.make_diag_boxes([(self.lo, self.hi, (S, self.gbox), None)])
-        mv = self._radial_mv.reshape(-1)
-        h.radial_mass_mf(self._mono_tables[key], self.geom, mono, mv)
-        self.comm.allreduce_sum(mv)
-        h.radial_gravity(mono, self.geom, mv, self._radial_g.reshape(-1))
-        h.monopole_grav(self._radial_g.reshape(-1), mono, self.geom, grav, self.gravbox)
-
-    def _construct_gravity(self, S, grav):
-        """get_old_grav_vector / get_new_grav_vector of a single level (Gravity.cpp:837-980) into `grav`: the constant vector or
-        the monopole interpolation, then -- last -- the point mass over the whole grown FAB."""
-        if self.monopole:
-            self._monopole_gravity(S, grav)
-        elif self.poisson is not None:
-            self.poisson.construct(S, grav, grav is self.grav_new)
-        else:
-            grav.zero_()                        # grav.setVal(0.0, ng); grav.setVal(const_grav, AMREX_SPACEDIM - 1, 1, ng)
-            grav[2].fill_(self.grav[2])
-        if self.pm is not None:
-            from . import diag
-            self.pm.add(self.hydro, self.hydro.make_grav_fabs([(grav, self.gravbox)]), diag.domain_center(self), self.geom)
+    def radial_gravity(self):
+        """(radial_mass, radial_vol, radial_grav) of the last gravity construction, as numpy arrays of n1d entries"""
+        g = self.monopole_gravity
+        if g is None:
+            raise RuntimeError("radial_gravity() needs Castro(do_grav=True, gravity_type=\"monopole\")")
+        mass, vol, old, new = g.radial_gravity(0)
+        return mass, vol, (old if g._arrays(0).get("last") == "old" else new)
 
     point_mass = property(lambda self: self.pm.value() if self.pm is not None else None,
                           doc="castro::point_mass as the device holds it (None without use_point_mass)")
@@ -1019,13 +972,6 @@ class Castro(CheckpointMixin):
             self.expand_state(self.S_new_b)         # ghost zones only: the next advance fills them again from the same zones
             tr.timestamp(0, self.time, lambda l: self._tracer_boxes("S_new_b"), geoms)
         tr.check_flags()
-
-    def radial_gravity(self):
-        """(radial_mass, radial_vol, radial_grav) of the last gravity construction, as numpy arrays of n1d entries"""
-        if not self.monopole or self.level_gravity is not None:
-            raise RuntimeError("radial_gravity() needs Castro(do_grav=True, gravity_type=\"monopole\")")
-        mv = self._radial_mv.reshape(-1).cpu().numpy()
-        return mv[:self.n1d].copy(), mv[self.n1d:].copy(), self._radial_g.reshape(-1).cpu().numpy().copy()
 
     # ---- Castro::sum_integrated_quantities (Source/driver/sum_integrated_quantities.cpp) ---------------------
     sum_interval = property(lambda self: self.diag.sum_interval)
@@ -1271,8 +1217,6 @@ class Castro(CheckpointMixin):
         h = self.hydro
         skw = {} if self.sponge is None else {"sponge": self._sponge_params()}     # sponge_src goes last
         if self.grav_fab:
-            if self.level_gravity is None:          # a single level constructs its own gravity; CastroAmr does it level-wide
-                self._construct_gravity(self.S_old_b if stage == 0 else self.S_new_b, self.grav_old if stage == 0 else self.grav_new)
             if grav_fabs is None:
                 grav_fabs = (h.make_grav_fabs([(self.grav_old, self.gravbox)]), h.make_grav_fabs([(self.grav_new, self.gravbox)]))
             h.sources_mf_g(stage, boxes or h.make_source_boxes([self._source_spec(stage)]), grav_fabs[0], grav_fabs[1],
@@ -1295,8 +1239,6 @@ class Castro(CheckpointMixin):
             if self.diffusion is not None:              # construct_old_diff_source: + 1.0 x DiffTerm(Sborder)
                 h.temp_diffusion(S, g, src, sbx, lo, hi, self.diffusion, self.geom, 1.0)
             if self.grav_fab:
-                if self.level_gravity is None:
-                    self._construct_gravity(S, self.grav_old)
                 h.old_gravity_source_gfab(S, g, src, sbx, lo, hi, self.grav_old, self.gravbox, self.grav_source_type, dt)
             elif self.do_grav:
                 h.old_gravity_source(S, g, src, sbx, lo, hi, self.grav, self.grav_source_type, dt)
@@ -1307,8 +1249,6 @@ class Castro(CheckpointMixin):
                 h.temp_diffusion(Sn, g, src, sbx, lo, hi, self.diffusion, self.geom, 0.5)
                 h.temp_diffusion(S, g, src, sbx, lo, hi, self.diffusion, self.geom, -0.5)
             if self.grav_fab:
-                if self.level_gravity is None:
-                    self._construct_gravity(Sn, self.grav_new)
                 h.new_gravity_source_gfab(S, g, Sn, g, src, sbx, self.mass_fluxes, self.flux_boxes, lo, hi, self.grav_old,
                                           self.grav_new, self.gravbox, self.grav_source_type, dt, self.geom)
             elif self.do_grav:
@@ -1344,6 +1284,10 @@ class Castro(CheckpointMixin):
         one_pass = (hasattr(h, "sources_mf") and os.environ.get("CASTRO_AMD_SOURCES_ONE_PASS", "1") != "0"
                     and (not getattr(self, "grav_fab", False) or (hasattr(h, "sources_mf_g") and self.diffusion is None)))
         sources = self._sources_one_pass if one_pass else self._source_stage
+        # construct_old_gravity in front of the old-time sources (Castro_advance_ctu.cpp:122), construct_new_gravity in front of
+        # the new-time ones (:258), as _Level._advance_with_sources_impl asks the hierarchy's object
+        if self.gravity is not None:
+            self.gravity.get_old_grav_vector(0, time)
         sources(0, dt)
         if self.do_hydro:
             # FillPatch of the source for the tracing
@@ -1372,6 +1316,8 @@ class Castro(CheckpointMixin):
             # FillPatches the new state with one ghost zone, Castro_diffusion.cpp:113).  The physical-boundary faces carry no
             # flux whatever their ghost zones hold, so no boundary fill.
             self.expand_state(self.S_new_b, bc=False)
+        if self.gravity is not None:
+            self.gravity.get_new_grav_vector(0, time + dt)
         sources(1, dt)
         # timestep validity check (:386-392)
         new_dt = self.estTimeStep()
@@ -1394,7 +1340,7 @@ class Castro(CheckpointMixin):
     def _swap_state_time_levels(self):
         self.S_old_b, self.S_new_b = self.S_new_b, self.S_old_b
         if self.poisson is not None:
-            self.poisson.swap_time_levels()
+            self.poisson.swap_level(0)              # PhiGrav_Type: phi_old <- phi_new
 
     def _save_old_state(self):
         return self.S_old_b.clone()

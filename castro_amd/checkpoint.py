@@ -709,7 +709,7 @@ class CheckpointMixin:
 
     def _refuse_poisson(self, what):
         from .gravity import PoissonGravity
-        if getattr(self, "poisson", None) is not None or isinstance(getattr(self, "gravity", None), PoissonGravity):
+        if isinstance(getattr(self, "gravity", None), PoissonGravity):      # Castro and CastroAmr keep their object there
             raise NotImplementedError("%s with Poisson gravity: a bit-faithful restart needs phi, the solver's starting guess, in "
                                       "the checkpoint (the reference's SD_1) -- a follow-up" % what)
 

@@ -20,12 +20,15 @@
                                      update(): Castro::pointmass_update (Source/gravity/Castro_pointmass.cpp), two launches with
                                      the sum over the ranks between them and no host round trip.
 
-  PoissonGravity                     gravity.gravity_type = "PoissonGrav" on a single level (castro_amd.Castro(poisson=...)): the
-                                     multipole boundary values, the multigrid solve and g = -grad(phi) of one time level, and the
-                                     old / new potentials of the run (the class at the end of this file); and on the levels of
-                                     CastroAmr (gravity=PoissonGravity(...)) in the reference's level-solve configuration
+  PoissonGravity                     gravity.gravity_type = "PoissonGrav" in the reference's level-solve configuration
                                      (gravity.no_sync = 1, gravity.no_composite = 1, gravity.max_solve_level): every level solves on
-                                     its own box, a refined one with Dirichlet data from the level below at its own time.
+                                     its own box -- level 0 with multipole boundary values, a refined one with Dirichlet data from
+                                     the level below at its own time --, then g = -grad(phi); the old / new potentials per level.
+
+  ConstantGravity                    ConstantGrav as Gravity_Type data, for the one case that needs them: a point mass on top.
+
+  SingleLevel                        castro_amd.Castro as a hierarchy of one level: the single-level driver gets its gravity field
+                                     from the same objects, through the same calls, as the levels of CastroAmr.
 
 Levels finer than `level` do not enter.  Not provided with monopole gravity: GR_GRAV, gravity.max_solve_level, a potential (phiGrav), domains with a periodic direction (the Gravity_Type FillPatch across a periodic boundary is not built), thermal
 diffusion on AMR levels, constant gravity plus a point mass on AMR levels.
@@ -83,27 +86,116 @@ class PointMass:
         self.nupdates += 1
 
 
-class MonopoleGravity:
+class SingleLevel:
+    """A single-level castro_amd.Castro as the gravity objects see a CastroAmr: the hierarchy and its level 0 in one object
+    (amr.lev[0] is amr), with the driver as the level's one box."""
+
+    def __init__(self, castro):
+        self.mine = [castro]
+        self.lev = [self]
+
+    n_cell = property(lambda self: self.mine[0].n_cell)
+    comm = property(lambda self: self.mine[0].comm)
+    hydro = property(lambda self: self.mine[0].hydro)
+    geom = property(lambda self: self.mine[0].geom)
+    center = property(lambda self: getattr(self.mine[0], "center", None))      # may be assigned after construction
+
+    def _hydro_for(self, l):
+        return self.hydro
+
+    def fill_grav(self, name, a):
+        """the Gravity_Type fill of the out-of-domain ghost zone of grav_old / grav_new (`name`)"""
+        c = self.mine[0]
+        if c.poisson is None:
+            # monopole and constant gravity keep what the construction left there -- the monopole interpolation at the ghost
+            # zone's own radius -- where the reference fills (DESIGN.md, f-row of monopole gravity: "follow-up").  Deleting
+            # this return closes that follow-up.
+            return
+        c.hydro.grav_bc_fill(getattr(c, name), c.gravbox, c.geom)
+
+
+class _Gravity:
+    """What the gravity objects share: the one hierarchy they belong to (a CastroAmr, or the SingleLevel of a Castro),
+    problem::center, the point mass, and the two calls of a level's advance."""
+    amr = None
+    center = None
+    point_mass = None                           # the PointMass of the run (use_point_mass=True)
+
+    def _belong_to(self, amr):
+        if self.amr is not None and self.amr is not amr:
+            raise ValueError("a %s object belongs to one Castro or one CastroAmr" % type(self).__name__)
+        self.amr = amr
+
+    def problem_center(self):
+        """problem::center, resolved at every construction: this object's `center`, else the driver's `center` attribute (which
+        may be assigned after construction), else the middle of the domain"""
+        c = self.center if self.center is not None else getattr(self.amr, "center", None)
+        if c is not None:
+            return list(c)
+        g = self.amr.lev[0].geom
+        return [0.5 * (g.problo[d] + g.probhi[d]) for d in range(3)]
+
+    def _add_point_mass(self, lev, name):
+        """add_pointmass_to_gravity comes last (Gravity.cpp:902-907, 975-980): on top of whatever the FillPatch has put into the
+        ghost zones -- on a refined level the coarse data with the coarse level's point-mass term"""
+        if self.point_mass is not None and lev.mine:
+            h = lev.hydro
+            fabs = h.make_grav_fabs([(getattr(b, name), b.gravbox) for b in lev.mine])       # descriptors are memoised
+            self.point_mass.add(h, fabs, self.problem_center(), lev.geom)
+
+    def check_level(self, l, geom):
+        pass
+
+    def get_old_grav_vector(self, level, time=None, a=0.0):
+        """grav_old of every box of `level` at the level's old time; a: where that time lies in the parent's [old, new]"""
+        self._grav_vector(level, "old", time, a)
+
+    def get_new_grav_vector(self, level, time=None, a=1.0):
+        self._grav_vector(level, "new", time, a)
+
+
+class ConstantGravity(_Gravity):
+    """gravity.gravity_type = "ConstantGrav" as Gravity_Type data (Gravity.cpp:859-866): zero, const_grav along z, then the point
+    mass (:902-907).  Made by the single-level driver for use_point_mass with constant gravity, the one case in which constant
+    gravity is not one vector; CastroAmr refuses that combination."""
+
+    def __init__(self, const_grav):
+        self.const_grav = float(const_grav)
+
+    def bind(self, amr, lo_bc, hi_bc):
+        self._belong_to(amr)
+
+    def _grav_vector(self, level, which, time, a):
+        lev = self.amr.lev[level]
+        name = "grav_" + which
+        for b in lev.mine:
+            grav = getattr(b, name)
+            grav.zero_()                        # grav.setVal(0.0, ng); grav.setVal(const_grav, AMREX_SPACEDIM - 1, 1, ng)
+            grav[2].fill_(self.const_grav)
+        lev.fill_grav(name, a)
+        self._add_point_mass(lev, name)
+
+
+class MonopoleGravity(_Gravity):
     def __init__(self, drdxfac=1, Gconst=L.GCONST, center=None):
         """drdxfac: gravity.drdxfac; Gconst: the reference takes C::Gconst from its Microphysics constants (the default is the cgs
-        value of that release); center: problem::center, default the middle of the domain."""
+        value of that release); center: problem::center, default the driver's `center`, else the middle of the domain."""
         self.drdxfac, self.Gconst = int(drdxfac), float(Gconst)
         self.center = None if center is None else tuple(float(x) for x in center)
         if self.drdxfac < 1:
             raise ValueError("gravity.drdxfac must be at least 1, not %d" % self.drdxfac)
-        self.amr = None
-        self.point_mass = None                  # the PointMass of the hierarchy (CastroAmr(use_point_mass=True))
         self._lev = {}
 
     # ---- the hierarchy this object belongs to ---------------------------------------------------------------
     def bind(self, amr, lo_bc, hi_bc):
         if any(lo_bc[d] == 0 or hi_bc[d] == 0 for d in range(3)):
-            raise (ValueError if all(lo_bc[d] == 0 and hi_bc[d] == 0 for d in range(3)) else NotImplementedError)(
-                "monopole gravity needs a non-periodic domain: a fully periodic one has no isolated mass to take the radial "
-                "profile of, and the Gravity_Type FillPatch across a periodic boundary of a partly periodic one is not built")
-        if self.amr is not None and self.amr is not amr:
-            raise ValueError("a MonopoleGravity object belongs to one CastroAmr")
-        self.amr = amr
+            if all(lo_bc[d] == 0 and hi_bc[d] == 0 for d in range(3)):
+                raise ValueError("monopole gravity needs a non-periodic domain: a fully periodic one has no isolated mass to take "
+                                 "the radial profile of")
+            if not isinstance(amr, SingleLevel):        # a SingleLevel makes no Gravity_Type FillPatch (SingleLevel.fill_grav)
+                raise NotImplementedError("monopole gravity on a partly periodic domain: the Gravity_Type FillPatch across a "
+                                          "periodic boundary is not built")
+        self._belong_to(amr)
 
     def check_level(self, l, geom):
         """the checks of the single-level driver with this level's dx"""
@@ -127,12 +219,6 @@ class MonopoleGravity:
     def n1d(self, l):
         """bins of level l: monopole_n1d of the level's domain (Gravity.cpp:315, Castro.cpp:3887-3913)"""
         return L.monopole_n1d(tuple((2 ** l) * x for x in self.amr.n_cell), self.drdxfac)
-
-    def problem_center(self):
-        if self.center is not None:
-            return list(self.center)
-        g = self.amr.lev[0].geom
-        return [0.5 * (g.problo[d] + g.probhi[d]) for d in range(3)]
 
     def params(self, l):
         """castro_amd_monopole_params of level l"""
@@ -202,36 +288,60 @@ class MonopoleGravity:
 
     # ---- Gravity::get_old_grav_vector / get_new_grav_vector -----------------------------------------------------
     def _grav_vector(self, level, which, time, a):
+        """the level's old / new time by default.  The reference bins the State_Type data, not Sborder: at the old-time point
+        S_old_b, whose valid zones are the cleaned old state (the FillPatch only adds ghost zones around them), at the new-time
+        point S_new_b after the hydro update and its clean_state."""
         lev = self.amr.lev[level]
+        if time is None and level > 0:                  # the time the coarser levels are binned at; level 0 has none below it
+            time = getattr(lev, "t_" + which)
         self.make_radial_gravity(level, time, which)
-        rg, mono = self._arrays(level)[which], self.params(level)
+        ent, mono = self._arrays(level), self.params(level)
+        ent["last"] = which
         name = "grav_" + which
         for b in lev.mine:
-            lev.hydro.monopole_grav(rg, mono, lev.geom, getattr(b, name), b.gravbox)
+            lev.hydro.monopole_grav(ent[which], mono, lev.geom, getattr(b, name), b.gravbox)
         lev.fill_grav(name, a)
-        if self.point_mass is not None and lev.mine:
-            # add_pointmass_to_gravity comes last (Gravity.cpp:902-907, 975-980): on top of whatever the FillPatch has put into
-            # the ghost zones -- on a refined level the coarse data with the coarse level's point-mass term
-            h = lev.hydro
-            fabs = h.make_grav_fabs([(getattr(b, name), b.gravbox) for b in lev.mine])       # descriptors are memoised
-            self.point_mass.add(h, fabs, self.problem_center(), lev.geom)
-
-    def get_old_grav_vector(self, level, time=None, a=0.0):
-        """grav_old of every box of `level` at the level's old time; a: where that time lies in the parent's [old, new]"""
-        self._grav_vector(level, "old", self.amr.lev[level].t_old if time is None else time, a)
-
-    def get_new_grav_vector(self, level, time=None, a=1.0):
-        self._grav_vector(level, "new", self.amr.lev[level].t_new if time is None else time, a)
+        self._add_point_mass(lev, name)
 
     def radial_gravity(self, level):
-        """(radial_mass_summed, radial_vol_summed, radial_grav_old, radial_grav_new) of `level` after its last construction, numpy"""
+        """(radial_mass_summed, radial_vol_summed, radial_grav_old, radial_grav_new) of `level` after its last construction
+        (_arrays(level)["last"]: "old" | "new"), numpy"""
         ent, n = self._arrays(level), self.n1d(level)
         mv = ent.get("last_summed", ent["mv"]).cpu().numpy()
         return mv[:n].copy(), mv[n:].copy(), ent["old"].cpu().numpy().copy(), ent["new"].cpu().numpy().copy()
 
 
-class PoissonGravity:
-    """gravity.gravity_type = "PoissonGrav" on a single level: castro_amd.Castro(do_grav=True, poisson=PoissonGravity(...)).
+def refuse_for_poisson(who, comm, base_grid, use_point_mass, check_int, ext_bc, geom):
+    """What Poisson gravity is not built for, asked by both drivers before anything is made.  who: "" | "CastroAmr: ";
+    geom: the geometry of level 0."""
+    if comm is not None and comm.size > 1:
+        raise NotImplementedError("%sPoisson gravity on more than one rank: the multigrid needs a halo exchange of phi on every "
+                                  "level and the moments a sum over the ranks -- a follow-up" % who)
+    if base_grid is not None and tuple(base_grid) != (1, 1, 1):
+        raise NotImplementedError("%sPoisson gravity with base_grid: level 0 must be one box -- the multigrid has no halo exchange "
+                                  "of phi between boxes; a follow-up" % who)
+    if use_point_mass:
+        raise NotImplementedError("%suse_point_mass with Poisson gravity (the point mass is excluded from the right-hand side "
+                                  "and added to the solution) is a follow-up" % who)
+    if int(check_int) > 0:
+        raise NotImplementedError("%scheck_int with Poisson gravity: a bit-faithful restart needs phi of every level, the solver's "
+                                  "starting guess, in the checkpoint (the reference's SD_1) -- a follow-up" % who)
+    if ext_bc is not None and L.ext_bc_hse_faces(ext_bc, geom):
+        raise ValueError("HSE boundaries assume constant gravity: not with PoissonGravity(...)")
+    for d in range(3):
+        for bc in (geom.lo_bc[d], geom.hi_bc[d]):
+            if bc == 0 or bc == 3:
+                raise NotImplementedError("Poisson gravity with a %s face: the mass offset of a periodic domain and the "
+                                          "reflected moments / Neumann faces of a Symmetry one are a follow-up; all six faces "
+                                          "must be Dirichlet faces of the potential" % ("periodic" if bc == 0 else "Symmetry"))
+    lo, hi = tuple(geom.domlo[d] for d in range(3)), tuple(geom.domhi[d] for d in range(3))
+    PoissonGravity._check_bottom(0, (lo, hi), tuple(hi[d] - lo[d] + 1 for d in range(3)))
+
+
+class PoissonGravity(_Gravity):
+    """gravity.gravity_type = "PoissonGrav": castro_amd.Castro(do_grav=True, poisson=PoissonGravity(...)) on a single level,
+    castro_amd.CastroAmr(do_grav=True, gravity=PoissonGravity(..., max_solve_level=None)) on a hierarchy -- one path: the single
+    level is level 0 of a hierarchy of one (SingleLevel).
 
     Every construction of the gravity of a time level (Castro::construct_old_gravity / construct_new_gravity,
     Source/gravity/Castro_gravity.cpp) is: the multipole moments of the valid zones of the state (Gravity::fill_multipole_BCs),
@@ -246,9 +356,8 @@ class PoissonGravity:
     Not built (each refused by the driver): more than one rank, periodic or Symmetry faces, the point mass,
     checkpoints, gravity.mlmg_maxorder > 2, direct_sum_bcs.
 
-    On a hierarchy: castro_amd.CastroAmr(do_grav=True, gravity=PoissonGravity(..., max_solve_level=None)) -- the level solves of
-    the second half of this class.  max_solve_level: gravity.max_solve_level, the finest level that solves (None: every level, the
-    reference's default); a finer level takes phi and g from the level below by interpolation.  no_sync / no_composite:
+    On a hierarchy the levels solve for themselves.  max_solve_level: gravity.max_solve_level, the finest level that solves (None:
+    every level, the reference's default); a finer level takes phi and g from the level below by interpolation.  no_sync / no_composite:
     gravity.no_sync / gravity.no_composite; only True is built (no composite solve, no gravity_sync, no composite correction).
     One rank, refinement ratio 2, level 0 and every refined level ONE box, the refined ones inside the domain."""
 
@@ -265,8 +374,6 @@ class PoissonGravity:
         self.max_solve_level = None if max_solve_level is None else int(max_solve_level)
         if self.max_solve_level is not None and self.max_solve_level < 0:
             raise ValueError("gravity.max_solve_level must not be negative, not %d" % self.max_solve_level)
-        self.amr = None
-        self.point_mass = None
         self._lev = {}
         self.solve_log = []                     # (level, "old" | "new", a) of the last solves of a hierarchy, oldest first
         self.lnum = int(max_multipole_order)
@@ -278,63 +385,15 @@ class PoissonGravity:
         self.reltol, self.abstol, self.maxiter = float(reltol), float(abstol), int(maxiter)
         self.Gconst = float(Gconst)
         self.center = None if center is None else tuple(float(x) for x in center)
-        self.driver = None
-        self.plan = None
-        self.stats = {"first": None, "old": None, "new": None}
 
-    def bind(self, owner, *args):
-        """bind(castro, hydro_alloc): the single-level driver (Castro(poisson=...)); bind(amr, lo_bc, hi_bc): the hierarchy
-        (CastroAmr(gravity=...), the call MonopoleGravity answers too)"""
-        if len(args) == 1:
-            return self._bind_single(owner, args[0])
-        lo_bc, hi_bc = args
-        if self.driver is not None or (self.amr is not None and self.amr is not owner):
-            raise ValueError("a PoissonGravity object belongs to one Castro or one CastroAmr")
-        self._refuse_faces(lo_bc, hi_bc)
-        self.amr = owner
+    def bind(self, amr, lo_bc=None, hi_bc=None):
+        """the call the other gravity objects answer too; the faces are among the checks of refuse_for_poisson"""
+        self._belong_to(amr)
 
-    @staticmethod
-    def _refuse_faces(lo_bc, hi_bc):
-        for d in range(3):
-            for bc in (lo_bc[d], hi_bc[d]):
-                if bc == 0 or bc == 3:
-                    raise NotImplementedError("Poisson gravity with a %s face: the mass offset of a periodic domain and the "
-                                              "reflected moments / Neumann faces of a Symmetry one are a follow-up; all six faces "
-                                              "must be Dirichlet faces of the potential" % ("periodic" if bc == 0 else "Symmetry"))
-
-    def _bind_single(self, c, hydro_alloc):
-        """the checks of the driver `c` this object belongs to, and its arrays: phi_old / phi_new with one ghost zone, the moments"""
-        if self.amr is not None or (self.driver is not None and self.driver is not c):
-            raise ValueError("a PoissonGravity object belongs to one Castro")
-        h = c.hydro
-        missing = [name for name in self.OPERATIONS + ("poisson_plan_create", "grav_bc_fill") if not hasattr(h, name)]
-        if missing:
-            raise NotImplementedError("Poisson gravity: this backend has no %s; there is no host fallback" % ", ".join(missing))
-        for d in range(3):
-            for bc in (c.lo_bc[d], c.hi_bc[d]):
-                if bc == 0 or bc == 3:
-                    raise NotImplementedError("Poisson gravity with a %s face: the mass offset of a periodic domain and the "
-                                              "reflected moments / Neumann faces of a Symmetry one are a follow-up; all six faces "
-                                              "must be Dirichlet faces of the potential" % ("periodic" if bc == 0 else "Symmetry"))
-        coarsest = L.poisson_level_extents(c.n_cell)[-1]
-        if coarsest[0] * coarsest[1] * coarsest[2] > L.POISSON_MAX_BOTTOM:
-            raise ValueError("Poisson gravity: n_cell = %s coarsens to %s, more than the %d zones the bottom solver of the multigrid "
-                             "takes: n_cell needs more factors of 2" % (c.n_cell, coarsest, L.POISSON_MAX_BOTTOM))
-        self.driver = c
-        self.phibox = (tuple(x - 1 for x in c.lo), tuple(x + 1 for x in c.hi))
-        self.phi_old = hydro_alloc(1, *self.phibox)
-        self.phi_new = hydro_alloc(1, *self.phibox)
-        n1 = self.lnum + 1
-        self.moments = hydro_alloc(1, (0, 0, 0), (3 * n1 * n1 - 1, 0, 0))
-        self._tables = {}
-        if self.phi_old is not None:
-            self.plan = h.poisson_plan_create(c.geom)
+    plan = property(lambda self: self._lev.get(0, {}).get("plan"), doc="the multigrid plan of level 0, None when there is none")
 
     def close(self):
-        if self.plan is not None and self.driver is not None:
-            self.driver.hydro.poisson_plan_destroy(self.plan)
-        self.plan = None
-        for ent in self._lev.values():          # the plans of a hierarchy; phi stays, a later solve makes the plan again
+        for ent in self._lev.values():          # phi stays, a later solve makes the plan again
             self._free_plan(ent)
 
     @staticmethod
@@ -342,6 +401,13 @@ class PoissonGravity:
         if ent.get("plan") is not None:
             ent["hydro"].poisson_plan_destroy(ent["plan"])
         ent["plan"] = None
+
+    def plan_level(self, l):
+        """the multigrid plan of level l, made if there is none: construction of a Castro, the first solve, or after close()"""
+        ent = self._entry(l)
+        if ent["plan"] is None:
+            ent["plan"] = ent["hydro"].poisson_plan_create(ent["geom"])
+        return ent["plan"]
 
     def __del__(self):
         try:
@@ -353,49 +419,11 @@ class PoissonGravity:
         except Exception:
             pass
 
-    def swap_time_levels(self):
-        """swap_state_time_levels of PhiGrav_Type: the new data of the last step are the old data of this one"""
-        self.phi_old, self.phi_new = self.phi_new, self.phi_old
-
-    def multipole(self):
-        """castro_amd_multipole of the run"""
-        from . import diag
-        c = self.driver
-        return L.make_multipole(c.geom, self.center if self.center is not None else diag.domain_center(c), self.lnum, self.Gconst)
-
-    def construct(self, S, grav, new):
-        """Gravity::solve_for_phi and get_old / get_new_grav_vector of the level at one time level: `grav` from the state S"""
-        import math
-        c = self.driver
-        h = c.hydro
-        if self.plan is None:                           # after Castro.close(): the plan is made again
-            self.plan = h.poisson_plan_create(c.geom)
-        if new:
-            self.phi_new.copy_(self.phi_old)            # the "old" phi of the step is the guess (Castro_gravity.cpp:146)
-        phi = self.phi_new if new else self.phi_old
-        mp = self.multipole()
-        key = S.data_ptr()                              # the two state buffers swap roles every step: one table each
-        if key not in self._tables:
-            self._tables[key] = h.make_diag_boxes([(c.lo, c.hi, (S, c.gbox), None)])
-        mom = self.moments.reshape(-1)
-        h.multipole_moments_mf(self._tables[key], c.geom, mp, mom)
-        h.multipole_phi_bc(phi, self.phibox, c.geom, mp, mom)
-        cycles, ok, norm, hist = h.poisson_solve(self.plan, phi, self.phibox, S, c.gbox, L.URHO, 4.0 * math.pi * self.Gconst,
-                                                 self.reltol, self.abstol, self.maxiter)
-        self.stats["new" if new else "old"] = {"cycles": cycles, "norm": norm, "history": hist}
-        if self.stats["first"] is None:
-            self.stats["first"] = self.stats["new" if new else "old"]
-        if not ok:
-            raise RuntimeError("Poisson gravity: the multigrid did not reach max(%g * %g, %g * %g) in %d V-cycles; the last two "
-                               "residual norms are %r and %r" % (self.reltol, hist[0], self.abstol, hist[1], self.maxiter,
-                                                                  hist[-2], hist[-1]))
-        h.grad_phi_to_grav(phi, self.phibox, grav, c.gravbox, c.geom)
-        h.grav_bc_fill(grav, c.gravbox, c.geom)
-
-    # ---- the levels of a CastroAmr hierarchy: level solves (gravity.no_sync = 1, gravity.no_composite = 1) -----------------
+    # ---- level solves (gravity.no_sync = 1, gravity.no_composite = 1) ---------------------------------------------------------
     # Castro::construct_old_gravity / construct_new_gravity (Castro_gravity.cpp:14-232) and Gravity::solve_for_phi /
-    # get_old_grav_vector / get_new_grav_vector / GetCrsePhi (Gravity.cpp:418-485, 664-690, 838-981) on a hierarchy whose refined
-    # levels are one box each.  Level 0 is the single-level path above.  A level 0 < l <= max_solve_level solves on its own box
+    # get_old_grav_vector / get_new_grav_vector / GetCrsePhi (Gravity.cpp:418-485, 664-690, 838-981) on a hierarchy whose levels
+    # are one box each.  Level 0 takes its boundary values from the multipole moments of its own valid zones.  A level
+    # 0 < l <= max_solve_level solves on its own box
     # -- a geometry whose domain is the box goes to the same entry points -- with Dirichlet data from the potential of the level
     # below at its own time (castro_amd_poisson_cf_bc_fab).  A level above max_solve_level takes phi and g of its whole FABs from
     # the level below (FillCoarsePatch: lincomb in time, cc_interp in space).
@@ -403,20 +431,20 @@ class PoissonGravity:
         return self.max_solve_level is None or level <= self.max_solve_level
 
     def check_level(self, l, geom):
+        """the operations a level needs of its backend; a SingleLevel never has a refined level"""
         h = self.amr._hydro_for(l)
-        missing = [name for name in self.OPERATIONS + self.AMR_OPERATIONS + ("poisson_plan_create", "grav_bc_fill") if not hasattr(h, name)]
+        needed = self.OPERATIONS + (() if isinstance(self.amr, SingleLevel) else self.AMR_OPERATIONS)
+        missing = [name for name in needed + ("poisson_plan_create", "grav_bc_fill") if not hasattr(h, name)]
         if missing:
             raise NotImplementedError("Poisson gravity: this backend has no %s; there is no host fallback" % ", ".join(missing))
-        if l == 0:
-            n = tuple(geom.domhi[d] - geom.domlo[d] + 1 for d in range(3))
-            self._check_bottom(0, (tuple(geom.domlo[d] for d in range(3)), tuple(geom.domhi[d] for d in range(3))), n)
 
-    def _check_bottom(self, l, box, n):
+    @staticmethod
+    def _check_bottom(l, box, n):
         coarsest = L.poisson_level_extents(n)[-1]
         if coarsest[0] * coarsest[1] * coarsest[2] > L.POISSON_MAX_BOTTOM:
-            raise ValueError("Poisson gravity: the box %s of level %d (%s zones) coarsens to %s, more than the %d zones the bottom "
-                             "solver of the multigrid takes (CASTRO_AMD_POISSON_MAX_BOTTOM): its extents need more factors of 2 "
-                             "-- a blocking_factor of 16 or 32" % (box, l, n, coarsest, L.POISSON_MAX_BOTTOM))
+            raise ValueError("Poisson gravity: the box %s of level %d with n_cell = %s coarsens to %s, more than the %d zones the "
+                             "bottom solver of the multigrid takes (CASTRO_AMD_POISSON_MAX_BOTTOM): its extents need more factors "
+                             "of 2 -- a blocking_factor of 16 or 32" % (box, l, n, coarsest, L.POISSON_MAX_BOTTOM))
 
     def check_boxes(self, l, boxes, parents):
         """the boxes (lo, hi) of the refined level l about to be made, in its own zones; parents: those of level l - 1"""
@@ -445,12 +473,6 @@ class PoissonGravity:
             if l >= from_level:
                 self._free_plan(self._lev[l])
                 del self._lev[l]
-
-    def problem_center(self):
-        if self.center is not None:
-            return list(self.center)
-        g = self.amr.lev[0].geom
-        return [0.5 * (g.problo[d] + g.probhi[d]) for d in range(3)]
 
     def _entry(self, l):
         """phi_old / phi_new (one ghost zone), the plan and the scratch of level l, made for the box the level has now"""
@@ -494,7 +516,8 @@ class PoissonGravity:
         ent["hydro"].lincomb(ent["ctmp"], cb, 1.0 - a, P["phi_old"], pb, a, P["phi_new"], pb, 1, lo, hi)
         return P
 
-    def _grav_vector(self, level, which, a):
+    def _grav_vector(self, level, which, time, a):
+        """phi and g of `level` at its old / new time (`time` itself is not read: a level solves from its own state)"""
         import math
         lev = self.amr.lev[level]
         b = lev.mine[0]
@@ -520,8 +543,7 @@ class PoissonGravity:
             ent["have"] = True
         elif which == "new":
             phi.copy_(ent["phi_old"])                    # the "old" phi of the step is the guess (Castro_gravity.cpp:146)
-        if ent["plan"] is None:                          # the first solve, or after close()
-            ent["plan"] = h.poisson_plan_create(ent["geom"])
+        plan = self.plan_level(level)
         S = b.S_old_b if which == "old" else b.S_new_b
         if level == 0:
             geom = ent["geom"]
@@ -535,7 +557,7 @@ class PoissonGravity:
         else:
             P = self._lev[level - 1]
             h.poisson_cf_bc(phi, pbx, b.lo, b.hi, P["phi_old"], P["phibox"], P["phi_new"], P["phibox"], a)
-        cycles, ok, norm, hist = h.poisson_solve(ent["plan"], phi, pbx, S, b.gbox, L.URHO, 4.0 * math.pi * self.Gconst,
+        cycles, ok, norm, hist = h.poisson_solve(plan, phi, pbx, S, b.gbox, L.URHO, 4.0 * math.pi * self.Gconst,
                                                  self.reltol, self.abstol, self.maxiter)
         st = ent["stats"]
         st[which] = {"cycles": cycles, "norm": norm, "history": hist}
@@ -549,13 +571,6 @@ class PoissonGravity:
                                                                           self.maxiter, hist[-2], hist[-1]))
         h.grad_phi_to_grav(phi, pbx, grav, b.gravbox, ent["geom"])
         lev.fill_grav(name, a)                           # the Gravity_Type FillPatch of the ghost zones of g
-
-    def get_old_grav_vector(self, level, time=None, a=0.0):
-        """phi_old and grav_old of `level` at the level's old time; a: where that time lies in the parent's [old, new]"""
-        self._grav_vector(level, "old", a)
-
-    def get_new_grav_vector(self, level, time=None, a=1.0):
-        self._grav_vector(level, "new", a)
 
     def phi_level(self, level, new=True):
         return self._entry(level)["phi_new" if new else "phi_old"]

@@ -144,3 +144,58 @@ def dust_amr_sensitivity(oracle, **kw):
     ulp, _ = dust_amr_run(lambda: MonopoleAmrOracleBackend(ulps=1), P(), **kw)
     s = [R.field_deviation(u, r) for u, r in zip(level_states(ulp), level_states(ref))]
     return ref, dts, s
+
+
+# ---- the single-level driver against a hierarchy with no refined level: one route to the field ------------------------------------
+def single_and_hierarchy(make_hydro, params, steps=2, **kw):
+    """(Castro(gravity_type="monopole"), CastroAmr(gravity=MonopoleGravity(...)) with no refined level) after `steps` steps of the
+    dust collapse"""
+    import castro_amd
+    c = castro_amd.Castro(AMR_N, params=params, hydro=make_hydro(), do_grav=True, gravity_type="monopole", drdxfac=AMR_DRDXFAC,
+                          **R.DUST_GEOM, **kw)
+    c.center = (0.0, 0.0, 0.0)
+    c.initData("dust_collapse", **R.DUST_PROB)
+    for _ in range(steps):
+        c.step()
+    a, _ = dust_amr_run(make_hydro, params, steps=steps, patches=[], **kw)
+    return c, a
+
+
+def assert_routes_agree_inside(c, a):
+    """the same bits in S_new, in the radial arrays and in grav_old / grav_new on every zone inside the domain"""
+    bits = lambda x: np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "cpu") else x).view(np.int64)
+    b = a.lev[0].boxes[0]
+    assert len(a.lev) == 1 and c.nstep == a.nstep and c.time == a.time
+    assert np.array_equal(bits(c.S_new()), bits(b.S_new()))
+    for name in ("grav_old", "grav_new"):
+        g = getattr(c, name)
+        assert float(g.abs().max()) > 0.0
+        assert np.array_equal(bits(g[:, 1:-1, 1:-1, 1:-1]), bits(getattr(b, name)[:, 1:-1, 1:-1, 1:-1])), name
+    (m, v, g), (am, av, _, agn) = c.radial_gravity(), a.gravity.radial_gravity(0)
+    assert m.shape == (c.n1d,) and m.sum() > 0.0
+    for x, y in ((m, am), (v, av), (g, agn)):
+        assert np.array_equal(bits(x), bits(y))
+
+
+def assert_ghost_zone_is_the_interpolation(c, exact):
+    """grav_new of a single-level Castro with monopole gravity: the ghost zone outside the domain holds the monopole
+    interpolation at that zone's own radius, not the Gravity_Type fill of the interior (the f-row of monopole
+    gravity).  exact: bit for bit; else within 1e-10 of the largest radial gravity (the bound of the interpolation kernel's test)"""
+    from castro_amd import _lib
+    rg = c.radial_gravity()[2]
+    mono = _lib.make_monopole(c.n_cell, c.geom, getattr(c, "center", None) or [0.5 * (c.geom.problo[d] + c.geom.probhi[d]) for d in range(3)],
+                              c.drdxfac, c.Gconst)
+    got = c.grav_new.cpu().numpy()
+    want = np.full(got.shape, np.nan)
+    index = R.interpolate(rg, c.geom, mono, want, c.gravbox)
+    ghost = np.ones(got.shape[1:], dtype=bool)
+    ghost[1:-1, 1:-1, 1:-1] = False
+    ghost &= index <= mono.n1d - 1
+    assert ghost.sum() > 0.9 * (18 ** 3 - 16 ** 3)
+    if exact:
+        assert np.array_equal(got[:, ghost], want[:, ghost])
+    else:
+        assert np.abs(got - want)[:, ghost].max() <= 1e-10 * np.abs(rg).max()
+    filled = got.copy()
+    grav_bc_fill(filled, c.gravbox, c.geom)
+    assert np.abs(got - filled)[:, ghost].max() > 1e-6 * np.abs(rg).max(), "not the extrapolated / reflected interior value"

@@ -211,6 +211,39 @@ def dust_amr_run(make_hydro, params, case="one", steps=AMR_STEPS, max_solve_leve
     return a, [a.step() for _ in range(steps)]
 
 
+def single_and_hierarchy(make_hydro, params, steps=2):
+    """(Castro(poisson=...), CastroAmr(gravity=...) with no refined level) after `steps` steps of the dust collapse from the same
+    state, lnum = 2"""
+    import castro_amd
+    c = castro_amd.Castro(AMR_N, params=params, hydro=make_hydro(), do_grav=True, poisson=castro_amd.PoissonGravity(max_multipole_order=2),
+                          **R.DUST_GEOM)
+    c.center = R.DUST_CENTER
+    a = castro_amd.CastroAmr(AMR_N, params=params, make_hydro=make_hydro, do_grav=True, patches=[],
+                             gravity=castro_amd.PoissonGravity(max_multipole_order=2, center=R.DUST_CENTER), **R.DUST_GEOM)
+    c.initData("dust_collapse", **R.DUST_PROB)
+    a.initData("dust_collapse", **R.DUST_PROB)
+    a.lev[0].boxes[0].S_new_b.copy_(c.S_new_b)
+    for _ in range(steps):
+        c.step()
+        a.step()
+    return c, a
+
+
+def assert_routes_agree(c, a):
+    """the two routes to the field of a single level leave the same bits: S_new, phi of both time levels with the ghost shell,
+    grav_old / grav_new with their ghost zones, and the statistics of the solves"""
+    bits = lambda t: t.cpu().numpy().view(np.int64)
+    b = a.lev[0].boxes[0]
+    assert len(a.lev) == 1 and c.nstep == a.nstep == 2 and c.time == a.time
+    for name in ("S_new_b", "grav_old", "grav_new"):
+        assert np.array_equal(bits(getattr(c, name)), bits(getattr(b, name))), name
+    for new in (True, False):
+        assert np.array_equal(bits(c.phi_grav(new)), bits(a.phi_grav(0, new))), new
+    assert c.phi_grav().shape == (1, 18, 18, 18) and float(c.phi_grav().abs().max()) > 0.0
+    st = c.poisson_stats()
+    assert st == a.poisson_stats(0) and st["first"]["cycles"] > 0 and st["new"] is not None and st["old"] is not None
+
+
 def level_fields(a):
     """[(S_new, phi_new, grav_new) of the box of every level] as numpy arrays"""
     out = []

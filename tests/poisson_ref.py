@@ -541,6 +541,18 @@ def dust_collapse_run(hydro, params, do_grav=True, steps=DUST_STEPS, lnum=0, n_c
     return c, [c.step() for _ in range(steps)]
 
 
+def assert_plan_lifetime(c):
+    """a PoissonGravity bound to the Castro `c`, which has made a step: exactly one plan, none after close(), one again after the
+    next step"""
+    plans = lambda: [e["plan"] for e in c.poisson._lev.values() if e["plan"] is not None]
+    assert list(c.poisson._lev) == [0] and len(plans()) == 1 and c.poisson.plan is plans()[0]
+    c.close()
+    assert plans() == [] and c.poisson.plan is None
+    c.close()                                   # idempotent
+    c.step()
+    assert len(plans()) == 1 and c.poisson.plan is plans()[0] and c.poisson_stats()["new"] is not None
+
+
 def dust_sensitivity(oracle):
     """(reference driver, its dts, s): the run on PoissonOracleBackend and the deviation per field of a second run whose moments
     are scaled by 1 + 2**-52 (monopole_ref.dust_sensitivity's convention): the tolerance of a comparison is max(1e-10, 100 s)"""

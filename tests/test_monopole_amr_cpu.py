@@ -306,3 +306,10 @@ def test_refine_tagging_runs_through_a_regrid(oracle):
     a.lev[1].t_old, a.lev[1].t_new, a.lev[1].alpha = a.time, a.time, 1.0
     g.get_new_grav_vector(1, time=a.time, a=1.0)
     assert fb.grav_new.abs().max() > 0.0 and np.isfinite(fb.grav_new.numpy()).all()
+
+
+def test_single_level_and_level_zero_are_one_route(oracle):
+    """grav_source_type = 2 reads no ghost zone of the field: Castro(gravity_type="monopole") and a CastroAmr with no refined
+    level agree bit for bit after two steps"""
+    A.assert_routes_agree_inside(*A.single_and_hierarchy(lambda: A.MonopoleAmrOracleBackend(), oracle.default_params(**R.DUST_PARAMS),
+                                                         grav_source_type=2))

@@ -297,3 +297,14 @@ def test_one_pass_and_separate_calls_agree(hydro):
         del os.environ["CASTRO_AMD_SOURCES_ONE_PASS"]
     for l, (x, y) in enumerate(zip(one, sep)):
         _close(hydro, x, y, "one-pass against separate calls, level %d" % l)
+
+
+def test_single_level_and_level_zero_are_one_route(hydro):
+    """grav_source_type = 2 reads no ghost zone of the field: Castro(gravity_type="monopole") and a CastroAmr with no refined
+    level agree bit for bit after two steps, in either build"""
+    import castro_amd
+    from castro_amd import _lib
+    c, a = A.single_and_hierarchy(lambda: castro_amd.HipHydro(0, numerics=hydro.numerics), _lib.default_params(**R.DUST_PARAMS),
+                                  grav_source_type=2)
+    torch.cuda.synchronize()
+    A.assert_routes_agree_inside(c, a)

@@ -183,3 +183,11 @@ def test_two_ranks_agree_with_one_within_the_summation_tolerance(tmp_path, oracl
     assert np.allclose(got["dts"], np.array(dts), rtol=1e-12, atol=0.0)
     g1 = ref.radial_gravity()[2]
     assert np.abs(got["grav"] - g1).max() <= 1e-12 * np.abs(g1).max()
+
+
+def test_out_of_domain_ghost_zone_keeps_the_interpolation(oracle):
+    """grav_source_type = 4 reads the ghost zone of grav_new: on a single level it holds the interpolated value"""
+    from tests import monopole_amr_ref as A
+    c, _ = R.dust_collapse_run(R.MonopoleOracleBackend(), oracle.default_params(**R.DUST_PARAMS), steps=1)
+    assert c.grav_source_type == 4
+    A.assert_ghost_zone_is_the_interpolation(c, exact=True)

@@ -280,3 +280,13 @@ def test_dust_collapse_driver_against_the_restatement(hydro, oracle):
     rc = (np.arange(c.n1d) + 0.5) * (c.geom.dx[0] / R.DUST_DRDXFAC)
     inside = rc < 0.9 * R.DUST_PROB["r_0"]
     assert np.all(grav[inside] < 0.0) and np.all(np.diff(grav[inside]) < 0.0)
+
+
+def test_out_of_domain_ghost_zone_keeps_the_interpolation(hydro):
+    """grav_source_type = 4 reads the ghost zone of grav_new: on a single level it holds the interpolated value"""
+    from castro_amd import _lib
+    from tests import monopole_amr_ref as A
+    c, _ = R.dust_collapse_run(hydro, _lib.default_params(**R.DUST_PARAMS), steps=1)
+    torch.cuda.synchronize()
+    assert c.grav_source_type == 4
+    A.assert_ghost_zone_is_the_interpolation(c, exact=hydro.numerics == "exact")

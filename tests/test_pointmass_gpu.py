@@ -263,7 +263,7 @@ def test_monopole_plus_point_mass_leaves_the_radial_arrays_alone(hydro):
                               drdxfac=R.DUST_DRDXFAC, use_point_mass=pm, point_mass=M, **R.DUST_GEOM)
         c.center = (0.0, 0.0, 0.0)
         c.initData("dust_collapse", **R.DUST_PROB)
-        c._construct_gravity(c.S_new_b, c.grav_new)
+        c.gravity.get_new_grav_vector(0)
         torch.cuda.synchronize()
         out.append((c.radial_gravity(), c.grav_new.cpu().numpy().copy(), c))
     for a, b in zip(out[0][0], out[1][0]):

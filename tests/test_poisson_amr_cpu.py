@@ -347,3 +347,9 @@ def test_a_regrid_that_moves_the_box_remakes_the_plan(oracle):
     assert g._lev[1]["plan"] is None and g._lev[0]["plan"] is None
     a.step()
     assert g._lev[1]["plan"] is not None
+
+
+def test_single_level_and_level_zero_are_one_route(oracle):
+    """Castro(poisson=...) and a CastroAmr(gravity=...) with no refined level, two whole steps from the same state: one path, one
+    set of bits"""
+    A.assert_routes_agree(*A.single_and_hierarchy(lambda: A.PoissonAmrOracleBackend(), oracle.default_params(**R.DUST_PARAMS)))

@@ -255,3 +255,15 @@ def test_dust_collapse_amr_driver_against_the_cpu_backend(hydro, oracle, case):
         assert np.allclose(np.array(gdts), np.array(dts), rtol=1e-12, atol=0.0), (gdts, dts)
     a.close()
     assert all(ent["plan"] is None for ent in a.gravity._lev.values())
+
+
+def test_single_level_and_level_zero_are_one_route(hydro):
+    """Castro(poisson=...) and a CastroAmr(gravity=...) with no refined level, two whole steps from the same state on the device:
+    the same launches on buffers of the same extents, so the same bits in either build"""
+    import castro_amd
+    from castro_amd import _lib
+    c, a = A.single_and_hierarchy(lambda: castro_amd.HipHydro(0, numerics=hydro.numerics), _lib.default_params(**R.DUST_PARAMS))
+    torch.cuda.synchronize()
+    A.assert_routes_agree(c, a)
+    c.close()
+    a.close()

@@ -382,3 +382,12 @@ def test_maxiter_one_raises(oracle):
     c.initData("dust_collapse", **R.DUST_PROB)
     with pytest.raises(RuntimeError, match="last two residual norms"):
         c.step()
+
+
+def test_plan_lifetime(oracle):
+    """one plan after a step, none after close(), one again after the next step; the object stays with its driver"""
+    import castro_amd
+    c, _ = R.dust_collapse_run(R.PoissonOracleBackend(), oracle.default_params(**R.DUST_PARAMS), steps=1)
+    R.assert_plan_lifetime(c)
+    with pytest.raises(ValueError, match="one Castro"):
+        castro_amd.Castro(R.DUST_N, poisson=c.poisson, **R.DUST_GEOM, **_kw(oracle))

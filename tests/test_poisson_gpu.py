@@ -356,3 +356,15 @@ def test_dust_collapse_driver_against_the_restatement(hydro, oracle):
     torch.cuda.synchronize()
     assert c.poisson.plan is not None and c.poisson_stats()["new"]["cycles"] >= 1
     c.close()
+
+
+def test_plan_lifetime(hydro):
+    """one plan after a step, none after close(), one again after the next step; the object stays with its driver"""
+    import castro_amd
+    from castro_amd import _lib
+    c, _ = R.dust_collapse_run(hydro, _lib.default_params(**R.DUST_PARAMS), steps=1)
+    torch.cuda.synchronize()
+    R.assert_plan_lifetime(c)
+    with pytest.raises(ValueError, match="one Castro"):
+        castro_amd.Castro(R.DUST_N, hydro=hydro, do_grav=True, poisson=c.poisson, **R.DUST_GEOM)
+    c.close()

@@ -47,26 +47,31 @@ def make_run(n, numerics, poisson, lnum=0):
     return c
 
 
+def _phibox(c):
+    """the box of the potential: the valid box grown by one zone"""
+    return tuple(x - 1 for x in c.lo), tuple(x + 1 for x in c.hi)
+
+
 def solve_leg(n, numerics, reps):
     import torch
     from castro_amd import _lib
     c = make_run(n, numerics, True)
     h, pg = c.hydro, c.poisson
     S = c.S_new_b
-    mp = pg.multipole()
+    mp = _lib.make_multipole(c.geom, pg.problem_center(), pg.lnum, pg.Gconst)
     table = h.make_diag_boxes([(c.lo, c.hi, (S, c.gbox), None)])
-    mom = pg.moments.reshape(-1)
+    mom = torch.zeros(3 * (pg.lnum + 1) ** 2, dtype=torch.float64, device="cuda")
     fourpiG = 4.0 * math.pi * pg.Gconst
-    phi = pg.phi_new
+    phi, phibox, plan = c.phi_grav(), _phibox(c), pg.plan_level(0)
     h.multipole_moments_mf(table, c.geom, mp, mom)
-    h.multipole_phi_bc(phi, pg.phibox, c.geom, mp, mom)
+    h.multipole_phi_bc(phi, phibox, c.geom, mp, mom)
 
     def solve(zero):
         if zero:
             phi[:, 1:-1, 1:-1, 1:-1] = 0.0
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        out = h.poisson_solve(pg.plan, phi, pg.phibox, S, c.gbox, _lib.URHO, fourpiG)
+        out = h.poisson_solve(plan, phi, phibox, S, c.gbox, _lib.URHO, fourpiG)
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3, out
 
@@ -100,7 +105,7 @@ def solve_leg(n, numerics, reps):
 def bc_leg(n, numerics, launches):
     import torch
     c = make_run(n, numerics, True)
-    h, pg = c.hydro, c.poisson
+    h, phi, phibox = c.hydro, c.phi_grav(), _phibox(c)
     out = dict(leg="bc", n=n, numerics=numerics, launches=launches)
     for lnum in (0, 6):
         from castro_amd import _lib
@@ -109,7 +114,7 @@ def bc_leg(n, numerics, launches):
         mom = torch.zeros(3 * (lnum + 1) ** 2, dtype=torch.float64, device="cuda")
         for _ in range(3):
             h.multipole_moments_mf(table, c.geom, mp, mom)
-            h.multipole_phi_bc(pg.phi_new, pg.phibox, c.geom, mp, mom)
+            h.multipole_phi_bc(phi, phibox, c.geom, mp, mom)
         times = {}
         for what in ("moments", "phi_bc", "both"):
             torch.cuda.synchronize()
@@ -118,7 +123,7 @@ def bc_leg(n, numerics, launches):
                 if what != "phi_bc":
                     h.multipole_moments_mf(table, c.geom, mp, mom)
                 if what != "moments":
-                    h.multipole_phi_bc(pg.phi_new, pg.phibox, c.geom, mp, mom)
+                    h.multipole_phi_bc(phi, phibox, c.geom, mp, mom)
             torch.cuda.synchronize()
             times[what] = (time.perf_counter() - t0) * 1e3 / launches
         out["lnum%d_ms" % lnum] = times
@@ -150,7 +155,7 @@ def sphere_leg(n, numerics):
     import numpy as np
     import torch
     c = make_run(n, numerics, True)
-    c._construct_gravity(c.S_new_b, c.grav_new)
+    c.gravity.get_new_grav_vector(0)
     torch.cuda.synchronize()
     phi = c.phi_grav().cpu().numpy()[0, 1:-1, 1:-1, 1:-1]
     rho = c.S_new().cpu().numpy()[0]
