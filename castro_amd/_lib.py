@@ -82,6 +82,8 @@ EXPORTED_SYMBOLS = (
     "castro_amd_multipole_moments_mf", "castro_amd_multipole_phi_bc_fab", "castro_amd_poisson_plan_create",
     "castro_amd_poisson_plan_destroy", "castro_amd_poisson_solve", "castro_amd_poisson_level_op", "castro_amd_grad_phi_to_grav_fab",
     "castro_amd_poisson_cf_bc_fab",
+    "castro_amd_poisson_boxes_plan_create", "castro_amd_poisson_boxes_cf_bc", "castro_amd_poisson_boxes_solve",
+    "castro_amd_grad_phi_to_grav_boxes", "castro_amd_poisson_boxes_level_op",
 )
 
 
@@ -231,6 +233,28 @@ def poisson_level_extents(n_cell):
         n = tuple(x // 2 for x in n)
         out.append(n)
     return out
+
+
+def poisson_boxes_levels(boxes):
+    """[(lo, n) of the bounding box >> m] of the multigrid levels of a union of boxes (lo, hi), in the zones of the level
+    (castro_amd_poisson_boxes_plan_create): coarsened while lo and hi + 1 of every box are divisible by 2^(m+1), every extent of
+    the bounding box is even with a half of at least 2, and fewer than 32 levels exist"""
+    lo = tuple(min(b[0][d] for b in boxes) for d in range(3))
+    n = tuple(max(b[1][d] for b in boxes) - lo[d] + 1 for d in range(3))
+    out = [(lo, n)]
+    while (len(out) < 32 and all(x % 2 == 0 and x // 2 >= 2 for x in n)
+           and all(b[0][d] % (1 << len(out)) == 0 and (b[1][d] + 1) % (1 << len(out)) == 0 for b in boxes for d in range(3))):
+        lo, n = tuple(x >> 1 for x in lo), tuple(x // 2 for x in n)
+        out.append((lo, n))
+    return out
+
+
+def poisson_boxes_alignment(boxes):
+    """the largest power of 2 that divides lo and hi + 1 of every box"""
+    k = 0
+    while k < 30 and all(b[0][d] % (2 << k) == 0 and (b[1][d] + 1) % (2 << k) == 0 for b in boxes for d in range(3)):
+        k += 1
+    return 1 << k
 
 
 class Rotation(C.Structure):
@@ -631,6 +655,16 @@ def load(numerics=None):
         L.castro_amd_grad_phi_to_grav_fab.argtypes = [C.c_void_p, PF, PF, C.POINTER(Geom), C.c_void_p]
     if hasattr(L, "castro_amd_poisson_cf_bc_fab"):          # absent from A/B builds of revisions before the level solves
         L.castro_amd_poisson_cf_bc_fab.argtypes = [C.c_void_p, PF, I3, I3, PF, PF, C.c_double, C.c_void_p]
+    if hasattr(L, "castro_amd_poisson_boxes_solve"):        # absent from A/B builds of revisions before levels of several boxes
+        PI = C.POINTER(C.c_int)
+        L.castro_amd_poisson_boxes_plan_create.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, PI, PI, C.POINTER(C.c_void_p)]
+        L.castro_amd_poisson_boxes_cf_bc.argtypes = [C.c_void_p, C.c_void_p, PF, PF, PF, C.c_double, C.c_void_p]
+        L.castro_amd_poisson_boxes_solve.argtypes = [C.c_void_p, C.c_void_p, PF, PF, C.c_int, PF, C.c_int, C.c_double, C.c_double,
+                                                     C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]
+        L.castro_amd_grad_phi_to_grav_boxes.argtypes = [C.c_void_p, C.c_void_p, PF, PF, C.c_int, PF, C.c_void_p]
+        L.castro_amd_poisson_boxes_level_op.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, PF, PF, PF, PF, C.c_void_p,
+                                                        C.c_void_p]
     L.castro_amd_step_control.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params), C.c_double, C.c_double,
                                           C.c_double, C.c_int, C.c_void_p]
     L.castro_amd_clean_state_fab.argtypes = [C.c_void_p, PF, I3, I3, C.POINTER(Params), C.c_int, C.c_void_p]

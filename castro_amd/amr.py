@@ -891,10 +891,11 @@ class CastroAmr(CheckpointMixin):
         level needs nothing from the coarser one), as in castro_amd.Castro.
         gravity: castro_amd.MonopoleGravity(drdxfac=..., Gconst=...) with do_grav=True -- monopole self-gravity on every
         level (castro_amd/gravity.py: the object spans the levels like the reference's Gravity); or
-        castro_amd.PoissonGravity(..., max_solve_level=None) -- Poisson self-gravity with every level solving on its own box
-        (gravity.no_sync = 1, gravity.no_composite = 1): one rank, level 0 and every refined level ONE box, the refined ones
-        inside the domain; phi_grav(level) and poisson_stats(level) read the potentials and the cycle counts, close() gives the
-        multigrid plans back.
+        castro_amd.PoissonGravity(..., max_solve_level=None) -- Poisson self-gravity with every level solving for itself
+        (gravity.no_sync = 1, gravity.no_composite = 1): one rank, level 0 ONE box, a refined level one box or several (fixed
+        patches=[[box, ...]] or refine= with cluster=True; a level of several is solved as one array over their bounding box),
+        every refined box inside the domain; phi_grav(level) -- phi_grav_level(level) for a level of several boxes -- and
+        poisson_stats(level) read the potentials and the cycle counts, close() gives the multigrid plans back.
         gravity_type: "constant" only (the bare string "monopole" carries neither drdxfac nor Gconst and is refused).
         sum_interval, show_center_of_mass, diag_dir: as in castro_amd.Castro -- sum_integrated_quantities() over the composite
         grid after initData and after every coarse step with nstep % sum_interval == 0 (self.diag_history, the three data logs).
@@ -1042,6 +1043,12 @@ class CastroAmr(CheckpointMixin):
         tensor.  A level that solves keeps the boundary values ON the faces of its box in the ghost zone (edges and corners: 0
         on a refined level); a level above max_solve_level holds the interpolated coarse potential in every zone."""
         return self._poisson_gravity("phi_grav()").phi_level(level, new)
+
+    def phi_grav_level(self, level=0, new=True):
+        """PhiGrav_Type of a level of any number of boxes: (box, phi, covered) as numpy -- the bounding box (lo, hi) of the level's
+        boxes, the level's potential on its zones (nz, ny, nx), and which of them lie in a box of the level.  A level of several
+        boxes keeps its potential as this one array; the zones that are not covered are never written by its solve."""
+        return self._poisson_gravity("phi_grav_level()").phi_level_boxes(level, new)
 
     def poisson_stats(self, level=0):
         """{"first", "old", "new"} of `level`: V-cycles, final residual norm and norm history of the first solve of the level
@@ -1262,7 +1269,7 @@ class CastroAmr(CheckpointMixin):
         lev = self._make_level(len(self.lev), pboxes)
         if self.gravity is not None:
             self.gravity.check_level(len(self.lev), lev.geom)
-            if hasattr(self.gravity, "check_boxes"):            # Poisson gravity: one box per level, inside the domain
+            if hasattr(self.gravity, "check_boxes"):            # Poisson gravity: boxes inside the domain, nested in the level below
                 self.gravity.check_boxes(len(self.lev), lev.box_list(), self.lev[-1].box_list())
         self.lev.append(lev)
         lev.bind()

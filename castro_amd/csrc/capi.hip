@@ -1153,6 +1153,7 @@ int castro_amd_poisson_solve(castro_amd_ctx* c, castro_amd_poisson_plan* plan, c
 {
     if (!c || !plan || !cycles || !converged || !final_norm || maxiter < 0) return CASTRO_AMD_ERR_ARG;
     PoissonPlan* P = reinterpret_cast<PoissonPlan*>(plan);
+    if (!P->flags.empty()) return CASTRO_AMD_ERR_ARG;      // the plan of a union of boxes: castro_amd_poisson_boxes_solve
     const MgLevel& L0 = P->lev[0];
     if (!mg_fab_ok(phi_fab, L0, 1) || phi_fab->ncomp != 1 || !mg_fab_ok(rho_fab, L0, 0)) return CASTRO_AMD_ERR_ARG;
     if (rho_comp < 0 || rho_comp >= rho_fab->ncomp) return CASTRO_AMD_ERR_ARG;
@@ -1167,7 +1168,7 @@ int castro_amd_poisson_level_op(castro_amd_ctx* c, castro_amd_poisson_plan* plan
     if (!c || !plan) return CASTRO_AMD_ERR_ARG;
     PoissonPlan* P = reinterpret_cast<PoissonPlan*>(plan);
     const int nl = (int)P->lev.size();
-    if (level < 0 || level >= nl) return CASTRO_AMD_ERR_ARG;
+    if (level < 0 || level >= nl || !P->flags.empty()) return CASTRO_AMD_ERR_ARG;
     const MgLevel& L = P->lev[(size_t)level];
     hipStream_t s = (hipStream_t)stream;
     hipSetDevice(c->device);
@@ -1231,6 +1232,138 @@ int castro_amd_poisson_cf_bc_fab(castro_amd_ctx* c, const castro_amd_fab* phi_fi
     hipSetDevice(c->device);
     return launch_phi_cf_bc(to_dfab(phi_fine_fab), fine_lo, fine_hi, to_dfab(crse_old_fab), to_dfab(crse_new_fab), a, (hipStream_t)stream,
                             &c->prof);
+}
+
+// ---- Poisson gravity on a refined level of several boxes: one array over their bounding box (poisson_kernels.hip, k_mgb_*) ------
+int castro_amd_poisson_boxes_plan_create(castro_amd_ctx* c, const double dx[3], int nboxes, const int* lo, const int* hi,
+                                         castro_amd_poisson_plan** plan)
+{
+    if (!c || !plan || !dx || nboxes < 1 || !lo || !hi) return CASTRO_AMD_ERR_ARG;
+    // the level table first: a refusal costs no device memory (and needs no device)
+    std::vector<MgLevel> lev;
+    const int rl = poisson_boxes_levels(nboxes, lo, hi, dx, lev);
+    if (rl != 0) return rl;
+    hipSetDevice(c->device);
+    PoissonPlan* P = nullptr;
+    const int rc = poisson_boxes_plan_make(nboxes, lo, hi, dx, &P);
+    if (rc != 0) return rc;
+    *plan = reinterpret_cast<castro_amd_poisson_plan*>(P);
+    return CASTRO_AMD_OK;
+}
+
+// the plan of a union of boxes, or nullptr
+static PoissonPlan* boxes_plan(castro_amd_poisson_plan* plan)
+{
+    PoissonPlan* P = reinterpret_cast<PoissonPlan*>(plan);
+    return P && !P->flags.empty() ? P : nullptr;
+}
+
+// does `f` hold the face values of level L: 3 components on the box with its high corner grown by one?
+static bool mgb_faces_ok(const castro_amd_fab* f, const MgLevel& L)
+{
+    if (!f || !f->p || f->ncomp != 3) return false;
+    int hi[3];
+    for (int d = 0; d < 3; ++d) hi[d] = L.lo[d] + L.n[d];
+    return fab_contains(f, L.lo, hi);
+}
+
+// the FABs of the boxes of the plan, each with `ncomp` components (0: at least comp + 1) around its own box
+static bool mgb_box_fabs(const PoissonPlan* P, int nboxes, const castro_amd_fab* fabs, int ncomp, int comp, std::vector<DFab>& out)
+{
+    if (!fabs || nboxes < 1 || (size_t)nboxes != P->boxes.size() / 6) return false;
+    out.resize((size_t)nboxes);
+    for (int b = 0; b < nboxes; ++b) {
+        const castro_amd_fab* f = fabs + b;
+        if (!f->p || (ncomp > 0 ? f->ncomp != ncomp : (comp < 0 || comp >= f->ncomp))) return false;
+        if (!fab_contains(f, &P->boxes[(size_t)(6 * b)], &P->boxes[(size_t)(6 * b + 3)])) return false;
+        out[(size_t)b] = to_dfab(f);
+    }
+    return true;
+}
+
+int castro_amd_poisson_boxes_cf_bc(castro_amd_ctx* c, castro_amd_poisson_plan* plan, const castro_amd_fab* faces_fab,
+                                   const castro_amd_fab* crse_old_fab, const castro_amd_fab* crse_new_fab, double a, void* stream)
+{
+    PoissonPlan* P = boxes_plan(plan);
+    if (!c || !P || !(a - a == 0.0) || !mgb_faces_ok(faces_fab, P->lev[0])) return CASTRO_AMD_ERR_ARG;
+    const MgLevel& L = P->lev[0];
+    int clo[3], chi[3];
+    for (int d = 0; d < 3; ++d) { clo[d] = (L.lo[d] >> 1) - 1; chi[d] = ((L.lo[d] + L.n[d] - 1) >> 1) + 1; }
+    for (const castro_amd_fab* f : { crse_old_fab, crse_new_fab })
+        if (!f || !f->p || f->ncomp != 1 || !fab_contains(f, clo, chi)) return CASTRO_AMD_ERR_ARG;
+    hipSetDevice(c->device);
+    return launch_phi_cf_boxes(P, to_dfab(faces_fab), to_dfab(crse_old_fab), to_dfab(crse_new_fab), a, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_poisson_boxes_solve(castro_amd_ctx* c, castro_amd_poisson_plan* plan, const castro_amd_fab* phi_fab,
+                                   const castro_amd_fab* faces_fab, int nboxes, const castro_amd_fab* rho_fabs, int rho_comp,
+                                   double fourpiG, double reltol, double abstol, int maxiter, int* cycles, int* converged,
+                                   double* final_norm, double* h_history, void* stream)
+{
+    PoissonPlan* P = boxes_plan(plan);
+    if (!c || !P || !cycles || !converged || !final_norm || maxiter < 0) return CASTRO_AMD_ERR_ARG;
+    const MgLevel& L0 = P->lev[0];
+    if (!mg_fab_ok(phi_fab, L0, 1) || phi_fab->ncomp != 1 || !mgb_faces_ok(faces_fab, L0)) return CASTRO_AMD_ERR_ARG;
+    std::vector<DFab> U;
+    if (!mgb_box_fabs(P, nboxes, rho_fabs, 0, rho_comp, U)) return CASTRO_AMD_ERR_ARG;
+    hipSetDevice(c->device);
+    return launch_poisson_boxes_solve(P, to_dfab(phi_fab), to_dfab(faces_fab), U.data(), rho_comp, fourpiG, reltol, abstol, maxiter,
+                                      cycles, converged, final_norm, h_history, (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_grad_phi_to_grav_boxes(castro_amd_ctx* c, castro_amd_poisson_plan* plan, const castro_amd_fab* phi_fab,
+                                      const castro_amd_fab* faces_fab, int nboxes, const castro_amd_fab* grav_fabs, void* stream)
+{
+    PoissonPlan* P = boxes_plan(plan);
+    if (!c || !P) return CASTRO_AMD_ERR_ARG;
+    const MgLevel& L0 = P->lev[0];
+    if (!mg_fab_ok(phi_fab, L0, 1) || phi_fab->ncomp != 1 || !mgb_faces_ok(faces_fab, L0)) return CASTRO_AMD_ERR_ARG;
+    std::vector<DFab> G;
+    if (!mgb_box_fabs(P, nboxes, grav_fabs, 3, 0, G)) return CASTRO_AMD_ERR_ARG;
+    hipSetDevice(c->device);
+    return launch_grad_phi_boxes(P, to_dfab(phi_fab), to_dfab(faces_fab), G.data(), (hipStream_t)stream, &c->prof);
+}
+
+int castro_amd_poisson_boxes_level_op(castro_amd_ctx* c, castro_amd_poisson_plan* plan, int op, int level, int colour,
+                                      const castro_amd_fab* a, const castro_amd_fab* b, const castro_amd_fab* f3,
+                                      const castro_amd_fab* faces_fab, double* d_out, void* stream)
+{
+    PoissonPlan* P = boxes_plan(plan);
+    if (!c || !P) return CASTRO_AMD_ERR_ARG;
+    const int nl = (int)P->lev.size();
+    if (level < 0 || level >= nl) return CASTRO_AMD_ERR_ARG;
+    const MgLevel& L = P->lev[(size_t)level];
+    const unsigned char* fl = P->flags[(size_t)level];
+    // face values belong to level 0 alone; without them (and on every coarser level) a flagged face holds 0.0
+    DFab X;
+    std::memset(&X, 0, sizeof(X));
+    if (faces_fab) {
+        if (level != 0 || !mgb_faces_ok(faces_fab, L)) return CASTRO_AMD_ERR_ARG;
+        X = to_dfab(faces_fab);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    hipSetDevice(c->device);
+    switch (op) {
+    case CASTRO_AMD_MG_SMOOTH:
+        if ((colour != 0 && colour != 1) || !mg_fab_ok(a, L, 1) || !mg_fab_ok(b, L, 0)) return CASTRO_AMD_ERR_ARG;
+        return launch_mgb_smooth(to_dfab(a), to_dfab(b), L, fl, X, colour, s, &c->prof);
+    case CASTRO_AMD_MG_RESIDUAL:
+        if (!mg_fab_ok(a, L, 1) || !mg_fab_ok(b, L, 0) || !mg_fab_ok(f3, L, 0)) return CASTRO_AMD_ERR_ARG;
+        return launch_mgb_residual(to_dfab(a), to_dfab(b), to_dfab(f3), L, fl, X, s, &c->prof);
+    case CASTRO_AMD_MG_RESTRICT:
+        if (level + 1 >= nl) return CASTRO_AMD_ERR_ARG;
+        if (!mg_fab_ok(a, L, 0) || !mg_fab_ok(b, P->lev[(size_t)level + 1], 0) || !mg_fab_ok(f3, P->lev[(size_t)level + 1], 0)) return CASTRO_AMD_ERR_ARG;
+        return launch_mgb_restrict(to_dfab(a), L, to_dfab(b), to_dfab(f3), P->lev[(size_t)level + 1], P->flags[(size_t)level + 1], s, &c->prof);
+    case CASTRO_AMD_MG_PROLONG:
+        if (level + 1 >= nl) return CASTRO_AMD_ERR_ARG;
+        if (!mg_fab_ok(a, P->lev[(size_t)level + 1], 0) || !mg_fab_ok(b, L, 0)) return CASTRO_AMD_ERR_ARG;
+        return launch_mgb_prolong(to_dfab(a), P->lev[(size_t)level + 1], to_dfab(b), L, fl, s, &c->prof);
+    case CASTRO_AMD_MG_NORM:
+        if (!mg_fab_ok(a, L, 0) || !d_out) return CASTRO_AMD_ERR_ARG;
+        return launch_mgb_norm(to_dfab(a), L, fl, P->norm_ws, d_out, s, &c->prof);
+    default:
+        return CASTRO_AMD_ERR_ARG;
+    }
 }
 
 // a gravity FAB of the _gfab source calls: 3 components, one ghost zone around [lo, hi] where the energy term reads neighbours

@@ -243,7 +243,38 @@ struct PoissonPlan {
     std::vector<double*> owned;
     double dx[3];
     double* d_norm = nullptr; double* norm_ws = nullptr; double* h_norm = nullptr;
+    // a plan of a union of boxes (poisson_boxes_plan_make; empty otherwise): lev[m] is the bounding box >> m, flags[m] one byte
+    // per zone of it (MGF_*, x fastest), boxes the union in the zones of level 0 (lo, hi: 6 ints per box), and the box tables
+    // of the right-hand side and of the gradient the plan has copied to the device
+    std::vector<unsigned char*> flags;
+    std::vector<int> boxes;
+    TableCache tables{8};
 };
+// flags of a zone of a union of boxes: covered, and "the neighbour across this face is not covered" for the face (d, side)
+constexpr unsigned MGF_COVERED = 1u;
+constexpr unsigned mgf_face(int d, int side) { return 2u << (2 * d + side); }
+// one box of the union with its own FAB (the state, or Gravity_Type data): thread range [start, start + n[0] n[1] n[2])
+struct MgBoxDev { DFab F; int lo[3], n[3]; long start; };
+int poisson_boxes_levels(int nbox, const int* lo, const int* hi, const double dx[3], std::vector<MgLevel>& lev);
+int poisson_boxes_plan_make(int nbox, const int* lo, const int* hi, const double dx[3], PoissonPlan** out);
+// X: the face values of level 0 (3 components over the bounding box with its high corner grown by one: component d at the
+// zone (i, j, k) is the low d-face of that zone); X.p == nullptr: every face value is 0.0 (the coarser levels)
+int launch_mgb_smooth(const DFab& P, const DFab& B, const MgLevel& L, const unsigned char* flags, const DFab& X, int colour,
+                      hipStream_t s, Profiler* prof);
+int launch_mgb_residual(const DFab& P, const DFab& B, const DFab& R, const MgLevel& L, const unsigned char* flags, const DFab& X,
+                        hipStream_t s, Profiler* prof);
+int launch_mgb_restrict(const DFab& RF, const MgLevel& LF, const DFab& BC, const DFab& PC, const MgLevel& LC,
+                        const unsigned char* cflags, hipStream_t s, Profiler* prof);
+int launch_mgb_prolong(const DFab& PC, const MgLevel& LC, const DFab& PF, const MgLevel& LF, const unsigned char* fflags,
+                       hipStream_t s, Profiler* prof);
+int launch_mgb_norm(const DFab& X, const MgLevel& L, const unsigned char* flags, double* ws, double* d_out, hipStream_t s,
+                    Profiler* prof);
+// U: the state FAB of every box of the plan, in the plan's order
+int launch_poisson_boxes_solve(PoissonPlan* P, const DFab& phi, const DFab& X, const DFab* U, int comp, double fourpiG, double reltol,
+                               double abstol, int maxiter, int* cycles, int* converged, double* final_norm, double* h_history,
+                               hipStream_t s, Profiler* prof);
+int launch_grad_phi_boxes(PoissonPlan* P, const DFab& phi, const DFab& X, const DFab* G, hipStream_t s, Profiler* prof);
+int launch_phi_cf_boxes(PoissonPlan* P, const DFab& X, const DFab& O, const DFab& N, double a, hipStream_t s, Profiler* prof);
 int poisson_levels(const int n[3], const int lo[3], const double dx[3], std::vector<MgLevel>& lev);
 int poisson_plan_make(const int n[3], const int lo[3], const double dx[3], PoissonPlan** out);
 void poisson_plan_free(PoissonPlan* P);

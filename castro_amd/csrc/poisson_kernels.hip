@@ -9,6 +9,8 @@
 //                                         of Gravity_util.H) with boundary_only = 1: every zone falls in the last radial bin
 //   k_mp_phi_bc                           the boundary potential (Gravity.cpp:2066-2216) on the zones of a FAB outside the domain
 //   k_phi_cf_bc                           the coarse-fine boundary potential of a refined level's own solve (the end of the file)
+//   k_mgb_*, k_phi_cf_boxes               the same passes, gradient and boundary values for a refined level of SEVERAL boxes: one
+//                                         array over their bounding box and a byte of coverage flags per zone
 // The multigrid is AMReX's [3P]: its arithmetic is not in the reference tree and is not pinned.  It is
 // written so that a restatement with the same order of operations reproduces the `exact` build bit for bit: the header comment
 // of every pass gives that order, and the passes hold no transcendental.  The `contract` build fuses these passes' multiply-adds.
@@ -290,6 +292,8 @@ void poisson_plan_free(PoissonPlan* P)
 {
     if (!P) return;
     for (double* q : P->owned) if (q) (void)hipFree(q);
+    for (unsigned char* q : P->flags) if (q) (void)hipFree(q);
+    P->tables.release();
     if (P->h_norm) (void)hipHostFree(P->h_norm);
     delete P;
 }
@@ -461,6 +465,479 @@ int launch_grad_phi(const DFab& phi, const DFab& G, const MgLevel& L, const doub
 {
     prof_begin(prof, "k_grad_phi", s);
     hipLaunchKernelGGL(k_grad_phi, dim3(mg_blocks(mg_zones(L))), dim3(MG_WG), 0, s, phi, G, L, dx[0], dx[1], dx[2]);
+    prof_end(prof, s);
+    return mg_check(s);
+}
+
+// ---- a level that is a union of boxes: ONE array over the bounding box, a byte of flags per zone -----------------------------------
+// The arithmetic of the passes above; "beyond a domain face" becomes "the neighbour across this face is not covered" (a flag bit
+// made on the host), and the value ON such a face is read from the face array X of level 0 -- an uncovered zone at a concave
+// corner of the union is the neighbour of two covered zones across two faces with two values, so it cannot hold them -- or is 0.0
+// on the coarser levels.  Zones that are not covered are never written.  L is the bounding box >> m; colours are relative to
+// its low corner.  The kernels above are not touched: a level of one box keeps its launches and its bits.
+__device__ __forceinline__ long mgb_flag_at(const MgLevel& L, int ii, int jj, int kk)
+{
+    return (long)ii + (long)L.n[0] * ((long)jj + (long)L.n[1] * kk);
+}
+
+// the value on the (d, side) face of the zone (i, j, k): the low d-face of the zone (i, j, k) + side * e_d
+__device__ __forceinline__ double mgb_face_value(const DFab& X, int d, int side, int i, int j, int k)
+{
+    if (!X.p) return 0.0;
+    return X.p[mg_at(X, i + (d == 0 ? side : 0), j + (d == 1 ? side : 0), k + (d == 2 ? side : 0)) + X.sn * d];
+}
+
+// mg_relax with f the value on a face whose flag is set: xm = 2.0 * f; dg = dg + cx; ... in mg_relax's order (x low, x high, y, z)
+__device__ __forceinline__ double mgb_relax(const DFab& P, const DFab& B, const MgLevel& L, unsigned fl, const DFab& X, int ii, int jj, int kk)
+{
+    const int i = L.lo[0] + ii, j = L.lo[1] + jj, k = L.lo[2] + kk;
+    const double* p = P.p + mg_at(P, i, j, k);
+    double xm = p[-1], xp = p[1], ym = p[-P.sy], yp = p[P.sy], zm = p[-P.sz], zp = p[P.sz];
+    double dg = L.cdiag;
+    if (fl & ~MGF_COVERED) {
+        if (fl & mgf_face(0, 0)) { xm = 2.0 * mgb_face_value(X, 0, 0, i, j, k); dg = dg + L.cx; }
+        if (fl & mgf_face(0, 1)) { xp = 2.0 * mgb_face_value(X, 0, 1, i, j, k); dg = dg + L.cx; }
+        if (fl & mgf_face(1, 0)) { ym = 2.0 * mgb_face_value(X, 1, 0, i, j, k); dg = dg + L.cy; }
+        if (fl & mgf_face(1, 1)) { yp = 2.0 * mgb_face_value(X, 1, 1, i, j, k); dg = dg + L.cy; }
+        if (fl & mgf_face(2, 0)) { zm = 2.0 * mgb_face_value(X, 2, 0, i, j, k); dg = dg + L.cz; }
+        if (fl & mgf_face(2, 1)) { zp = 2.0 * mgb_face_value(X, 2, 1, i, j, k); dg = dg + L.cz; }
+    }
+    const double b = B.p[mg_at(B, i, j, k)];
+    const double off = (L.cx * (xm + xp) + L.cy * (ym + yp)) + L.cz * (zm + zp);
+    return (off - b) / dg;
+}
+
+__global__ void __launch_bounds__(MG_WG) k_mgb_smooth(DFab P, DFab B, MgLevel L, const unsigned char* __restrict__ flags, DFab X, int colour)
+{
+    const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
+    const int npair = (L.n[0] + 1) >> 1;
+    if (q >= (long)npair * L.n[1] * L.n[2]) return;
+    int ii, jj, kk;
+    if (!mg_colour_zone(q, L, colour, ii, jj, kk)) return;
+    const unsigned fl = flags[mgb_flag_at(L, ii, jj, kk)];
+    if (!(fl & MGF_COVERED)) return;
+    const double v = mgb_relax(P, B, L, fl, X, ii, jj, kk);
+    P.p[mg_at(P, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk)] = v;
+}
+
+// k_mg_bottom over the covered zones of the coarsest level (at most CASTRO_AMD_POISSON_MAX_BOTTOM zones of its bounding box)
+__global__ void __launch_bounds__(MG_BOTTOM_WG) k_mgb_bottom(DFab P, DFab B, MgLevel L, const unsigned char* __restrict__ flags, DFab X,
+                                                            int sweeps)
+{
+    const int npair = (L.n[0] + 1) >> 1;
+    const long nq = (long)npair * L.n[1] * L.n[2];
+    for (int s = 0; s < sweeps; ++s) {
+        for (int colour = 0; colour < 2; ++colour) {
+            for (long q = threadIdx.x; q < nq; q += MG_BOTTOM_WG) {
+                int ii, jj, kk;
+                if (!mg_colour_zone(q, L, colour, ii, jj, kk)) continue;
+                const unsigned fl = flags[mgb_flag_at(L, ii, jj, kk)];
+                if (!(fl & MGF_COVERED)) continue;
+                const double v = mgb_relax(P, B, L, fl, X, ii, jj, kk);
+                P.p[mg_at(P, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk)] = v;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// k_mg_residual on the covered zones: across a flagged face the linear ghost 2.0 * f - p
+__global__ void __launch_bounds__(MG_WG) k_mgb_residual(DFab P, DFab B, DFab R, MgLevel L, const unsigned char* __restrict__ flags, DFab X)
+{
+    const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
+    if (q >= (long)L.n[0] * L.n[1] * L.n[2]) return;
+    const unsigned fl = flags[q];
+    if (!(fl & MGF_COVERED)) return;
+    const int ii = (int)(q % L.n[0]);
+    const long rr = q / L.n[0];
+    const int jj = (int)(rr % L.n[1]), kk = (int)(rr / L.n[1]);
+    const int i = L.lo[0] + ii, j = L.lo[1] + jj, k = L.lo[2] + kk;
+    const double* p = P.p + mg_at(P, i, j, k);
+    const double pc = p[0];
+    double xm = p[-1], xp = p[1], ym = p[-P.sy], yp = p[P.sy], zm = p[-P.sz], zp = p[P.sz];
+    if (fl & ~MGF_COVERED) {
+        if (fl & mgf_face(0, 0)) xm = 2.0 * mgb_face_value(X, 0, 0, i, j, k) - pc;
+        if (fl & mgf_face(0, 1)) xp = 2.0 * mgb_face_value(X, 0, 1, i, j, k) - pc;
+        if (fl & mgf_face(1, 0)) ym = 2.0 * mgb_face_value(X, 1, 0, i, j, k) - pc;
+        if (fl & mgf_face(1, 1)) yp = 2.0 * mgb_face_value(X, 1, 1, i, j, k) - pc;
+        if (fl & mgf_face(2, 0)) zm = 2.0 * mgb_face_value(X, 2, 0, i, j, k) - pc;
+        if (fl & mgf_face(2, 1)) zp = 2.0 * mgb_face_value(X, 2, 1, i, j, k) - pc;
+    }
+    const double tp = 2.0 * pc;
+    const double lap = (L.cx * ((xm + xp) - tp) + L.cy * ((ym + yp) - tp)) + L.cz * ((zm + zp) - tp);
+    R.p[mg_at(R, i, j, k)] = B.p[mg_at(B, i, j, k)] - lap;
+}
+
+// k_mg_restrict on the covered zones of the COARSE level L (cflags): the 8 children of a covered coarse zone are all covered
+__global__ void __launch_bounds__(MG_WG) k_mgb_restrict(DFab RF, int flo0, int flo1, int flo2, DFab BC, DFab PC, MgLevel L,
+                                                       const unsigned char* __restrict__ cflags)
+{
+    const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
+    if (q >= (long)L.n[0] * L.n[1] * L.n[2]) return;
+    if (!(cflags[q] & MGF_COVERED)) return;
+    const int ii = (int)(q % L.n[0]);
+    const long rr = q / L.n[0];
+    const int jj = (int)(rr % L.n[1]), kk = (int)(rr / L.n[1]);
+    const double* r = RF.p + mg_at(RF, flo0 + 2 * ii, flo1 + 2 * jj, flo2 + 2 * kk);
+    double s = r[0] + r[1];
+    s = s + r[RF.sy];
+    s = s + r[RF.sy + 1];
+    s = s + r[RF.sz];
+    s = s + r[RF.sz + 1];
+    s = s + r[RF.sz + RF.sy];
+    s = s + r[RF.sz + RF.sy + 1];
+    const int i = L.lo[0] + ii, j = L.lo[1] + jj, k = L.lo[2] + kk;
+    BC.p[mg_at(BC, i, j, k)] = s * 0.125;
+    PC.p[mg_at(PC, i, j, k)] = 0.0;
+}
+
+// k_mg_prolong on the covered zones of the FINE level L (fflags)
+__global__ void __launch_bounds__(MG_WG) k_mgb_prolong(DFab PC, int clo0, int clo1, int clo2, DFab PF, MgLevel L,
+                                                      const unsigned char* __restrict__ fflags)
+{
+    const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
+    if (q >= (long)L.n[0] * L.n[1] * L.n[2]) return;
+    if (!(fflags[q] & MGF_COVERED)) return;
+    const int ii = (int)(q % L.n[0]);
+    const long rr = q / L.n[0];
+    const int jj = (int)(rr % L.n[1]), kk = (int)(rr / L.n[1]);
+    const long f = mg_at(PF, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk);
+    PF.p[f] = PF.p[f] + PC.p[mg_at(PC, clo0 + (ii >> 1), clo1 + (jj >> 1), clo2 + (kk >> 1))];
+}
+
+// the box of the table that holds thread t, and the zone of it
+__device__ __forceinline__ bool mgb_box_zone(const MgBoxDev* __restrict__ tab, int nbox, long t, int& b, int& i, int& j, int& k)
+{
+    int b0 = 0, b1 = nbox - 1;
+    while (b0 < b1) {
+        const int mid = (b0 + b1 + 1) >> 1;
+        if (tab[mid].start <= t) b0 = mid; else b1 = mid - 1;
+    }
+    const long r = t - tab[b0].start;
+    const int n0 = tab[b0].n[0], n1 = tab[b0].n[1], n2 = tab[b0].n[2];
+    if (r >= (long)n0 * n1 * n2) return false;
+    const long rr = r / n0;
+    b = b0;
+    i = tab[b0].lo[0] + (int)(r % n0); j = tab[b0].lo[1] + (int)(rr % n1); k = tab[b0].lo[2] + (int)(rr / n1);
+    return true;
+}
+
+// k_mg_rhs gathered from the boxes' own state FABs: b = fourpiG * rho on the zones of every box of the table
+__global__ void __launch_bounds__(MG_WG) k_mgb_rhs(const MgBoxDev* __restrict__ tab, int nbox, long total, int comp, DFab B, double fourpiG)
+{
+    const long t = (long)blockIdx.x * MG_WG + threadIdx.x;
+    if (t >= total) return;
+    int b, i, j, k;
+    if (!mgb_box_zone(tab, nbox, t, b, i, j, k)) return;
+    const DFab U = tab[b].F;
+    B.p[mg_at(B, i, j, k)] = fourpiG * U.p[mg_at(U, i, j, k) + U.sn * comp];
+}
+
+// k_mg_norm_partial over the covered zones
+__global__ void __launch_bounds__(MG_WG) k_mgb_norm_partial(DFab X, MgLevel L, const unsigned char* __restrict__ flags, double* __restrict__ ws)
+{
+    const long total = (long)L.n[0] * L.n[1] * L.n[2];
+    double ma = 0.0, mx = -HUGE_VAL;
+    for (long q = (long)blockIdx.x * MG_WG + threadIdx.x; q < total; q += (long)gridDim.x * MG_WG) {
+        if (!(flags[q] & MGF_COVERED)) continue;
+        const int i = L.lo[0] + (int)(q % L.n[0]);
+        const long rr = q / L.n[0];
+        const int j = L.lo[1] + (int)(rr % L.n[1]), k = L.lo[2] + (int)(rr / L.n[1]);
+        const double v = X.p[mg_at(X, i, j, k)];
+        ma = mg_max(ma, fabs(v));
+        mx = mg_max(mx, v);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        ma = mg_max(ma, __shfl_down(ma, off, 64));
+        mx = mg_max(mx, __shfl_down(mx, off, 64));
+    }
+    __shared__ double sa[MG_WG / 64][2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { sa[wave][0] = ma; sa[wave][1] = mx; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        double m = sa[0][threadIdx.x];
+        for (int w = 1; w < MG_WG / 64; ++w) m = mg_max(m, sa[w][threadIdx.x]);
+        ws[2 * (long)blockIdx.x + threadIdx.x] = m;
+    }
+}
+
+// k_grad_phi on the zones of every box of the table, into that box's own FAB: a neighbour in a sibling box is an ordinary
+// neighbour; across a flagged face dl = 2.0 * (p - f), dh = 2.0 * (f - p)
+__global__ void __launch_bounds__(MG_WG) k_mgb_grad(const MgBoxDev* __restrict__ tab, int nbox, long total, DFab P, MgLevel L,
+                                                   const unsigned char* __restrict__ flags, DFab X, double hx, double hy, double hz)
+{
+    const long t = (long)blockIdx.x * MG_WG + threadIdx.x;
+    if (t >= total) return;
+    int b, i, j, k;
+    if (!mgb_box_zone(tab, nbox, t, b, i, j, k)) return;
+    const DFab G = tab[b].F;
+    const unsigned fl = flags[mgb_flag_at(L, i - L.lo[0], j - L.lo[1], k - L.lo[2])];
+    const double* p = P.p + mg_at(P, i, j, k);
+    const double pc = p[0];
+    double dl[3] = { pc - p[-1], pc - p[-P.sy], pc - p[-P.sz] };
+    double dh[3] = { p[1] - pc, p[P.sy] - pc, p[P.sz] - pc };
+    const double h[3] = { hx, hy, hz };
+    const long g = mg_at(G, i, j, k);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        if (fl & mgf_face(d, 0)) dl[d] = 2.0 * (pc - mgb_face_value(X, d, 0, i, j, k));
+        if (fl & mgf_face(d, 1)) dh[d] = 2.0 * (mgb_face_value(X, d, 1, i, j, k) - pc);
+        const double gl = dl[d] / h[d], gh = dh[d] / h[d];
+        G.p[g + G.sn * d] = -(0.5 * (gl + gh));
+    }
+}
+
+// The levels of a union of boxes (lo, hi: 3 ints per box, in the zones of level 0): level m is the bounding box >> m.  Coarsened
+// while every box's lo and hi + 1 are divisible by 2^(m+1) -- the 8 children of a coarse zone are then all covered or all not --,
+// the extents of the bounding box are even with n / 2 >= 2 (poisson_levels' rule), and there are fewer than MG_MAX_LEVELS levels
+int poisson_boxes_levels(int nbox, const int* lo, const int* hi, const double dx[3], std::vector<MgLevel>& lev)
+{
+    lev.clear();
+    if (nbox < 1 || !lo || !hi) return CASTRO_AMD_ERR_ARG;
+    MgLevel L;
+    std::memset(&L, 0, sizeof(L));
+    double h[3];
+    int bhi[3];
+    for (int d = 0; d < 3; ++d) {
+        if (!(dx[d] > 0.0)) return CASTRO_AMD_ERR_ARG;
+        h[d] = dx[d];
+        L.lo[d] = lo[d]; bhi[d] = hi[d];
+    }
+    for (int b = 0; b < nbox; ++b)
+        for (int d = 0; d < 3; ++d) {
+            const int l = lo[3 * b + d], u = hi[3 * b + d];
+            // the refinement of a coarse box inside a non-negative index space
+            if (u < l || l < 0 || u > (1 << 30) || (l & 1) != 0 || (u & 1) != 1) return CASTRO_AMD_ERR_ARG;
+            if (l < L.lo[d]) L.lo[d] = l;
+            if (u > bhi[d]) bhi[d] = u;
+        }
+    for (int b = 0; b < nbox; ++b)
+        for (int c = 0; c < b; ++c) {
+            bool apart = false;
+            for (int d = 0; d < 3; ++d) apart = apart || hi[3 * b + d] < lo[3 * c + d] || hi[3 * c + d] < lo[3 * b + d];
+            if (!apart) return CASTRO_AMD_ERR_ARG;
+        }
+    for (int d = 0; d < 3; ++d) L.n[d] = bhi[d] - L.lo[d] + 1;
+    for (;;) {
+        L.cx = 1.0 / (h[0] * h[0]); L.cy = 1.0 / (h[1] * h[1]); L.cz = 1.0 / (h[2] * h[2]);
+        L.cdiag = 2.0 * ((L.cx + L.cy) + L.cz);
+        lev.push_back(L);
+        bool more = (int)lev.size() < MG_MAX_LEVELS;
+        for (int d = 0; d < 3; ++d) more = more && L.n[d] % 2 == 0 && L.n[d] / 2 >= 2;
+        const int m1 = (1 << (int)lev.size()) - 1;
+        for (int q = 0; q < 3 * nbox && more; ++q) more = (lo[q] & m1) == 0 && ((hi[q] + 1) & m1) == 0;
+        if (!more) break;
+        for (int d = 0; d < 3; ++d) { L.n[d] /= 2; L.lo[d] = L.lo[d] >> 1; h[d] = 2.0 * h[d]; }
+    }
+    if (mg_zones(lev.back()) > CASTRO_AMD_POISSON_MAX_BOTTOM) return CASTRO_AMD_ERR_UNSUPPORTED;
+    return 0;
+}
+
+// the flags of level m (shift = m) of the union
+static void mgb_flags(int nbox, const int* lo, const int* hi, const MgLevel& L, int shift, std::vector<unsigned char>& f)
+{
+    const long n0 = L.n[0], n1 = L.n[1], n2 = L.n[2];
+    f.assign((size_t)(n0 * n1 * n2), 0);
+    for (int b = 0; b < nbox; ++b) {
+        int l[3], u[3];
+        for (int d = 0; d < 3; ++d) { l[d] = (lo[3 * b + d] >> shift) - L.lo[d]; u[d] = (hi[3 * b + d] >> shift) - L.lo[d]; }
+        for (int k = l[2]; k <= u[2]; ++k)
+            for (int j = l[1]; j <= u[1]; ++j)
+                for (int i = l[0]; i <= u[0]; ++i) f[(size_t)(i + n0 * (j + n1 * k))] = MGF_COVERED;
+    }
+    const long st[3] = { 1, n0, n0 * n1 };
+    for (long k = 0; k < n2; ++k)
+        for (long j = 0; j < n1; ++j)
+            for (long i = 0; i < n0; ++i) {
+                const long q = i + n0 * (j + n1 * k);
+                if (!(f[(size_t)q] & MGF_COVERED)) continue;
+                const long at[3] = { i, j, k }, n[3] = { n0, n1, n2 };
+                unsigned v = f[(size_t)q];
+                for (int d = 0; d < 3; ++d) {
+                    if (at[d] == 0 || !(f[(size_t)(q - st[d])] & MGF_COVERED)) v |= mgf_face(d, 0);
+                    if (at[d] == n[d] - 1 || !(f[(size_t)(q + st[d])] & MGF_COVERED)) v |= mgf_face(d, 1);
+                }
+                f[(size_t)q] = (unsigned char)v;
+            }
+}
+
+int poisson_boxes_plan_make(int nbox, const int* lo, const int* hi, const double dx[3], PoissonPlan** out)
+{
+    std::vector<MgLevel> lev;
+    const int rl = poisson_boxes_levels(nbox, lo, hi, dx, lev);
+    if (rl != 0) return rl;
+    PoissonPlan* P = nullptr;
+    const int rp = poisson_plan_make(lev[0].n, lev[0].lo, dx, &P);
+    if (rp != 0) return rp;
+    // the alignment of the boxes may stop the coarsening before the extents do: the levels below are not used
+    P->lev.resize(lev.size());
+    P->boxes.resize((size_t)(6 * nbox));
+    for (int b = 0; b < nbox; ++b)
+        for (int d = 0; d < 3; ++d) { P->boxes[(size_t)(6 * b + d)] = lo[3 * b + d]; P->boxes[(size_t)(6 * b + 3 + d)] = hi[3 * b + d]; }
+    std::vector<unsigned char> f;
+    for (size_t m = 0; m < lev.size(); ++m) {
+        mgb_flags(nbox, lo, hi, lev[m], (int)m, f);
+        unsigned char* q = nullptr;
+        if (hipMalloc(&q, f.size()) != hipSuccess) { poisson_plan_free(P); return CASTRO_AMD_ERR_NOMEM; }
+        P->flags.push_back(q);
+        if (hipMemcpy(q, f.data(), f.size(), hipMemcpyHostToDevice) != hipSuccess) { poisson_plan_free(P); return CASTRO_AMD_ERR_HIP; }
+    }
+    *out = P;
+    return 0;
+}
+
+int launch_mgb_smooth(const DFab& P, const DFab& B, const MgLevel& L, const unsigned char* flags, const DFab& X, int colour,
+                      hipStream_t s, Profiler* prof)
+{
+    prof_begin(prof, "k_mgb_smooth", s);
+    hipLaunchKernelGGL(k_mgb_smooth, dim3(mg_blocks(mg_pairs(L))), dim3(MG_WG), 0, s, P, B, L, flags, X, colour);
+    prof_end(prof, s);
+    return mg_check(s);
+}
+
+int launch_mgb_residual(const DFab& P, const DFab& B, const DFab& R, const MgLevel& L, const unsigned char* flags, const DFab& X,
+                        hipStream_t s, Profiler* prof)
+{
+    prof_begin(prof, "k_mgb_residual", s);
+    hipLaunchKernelGGL(k_mgb_residual, dim3(mg_blocks(mg_zones(L))), dim3(MG_WG), 0, s, P, B, R, L, flags, X);
+    prof_end(prof, s);
+    return mg_check(s);
+}
+
+int launch_mgb_restrict(const DFab& RF, const MgLevel& LF, const DFab& BC, const DFab& PC, const MgLevel& LC,
+                        const unsigned char* cflags, hipStream_t s, Profiler* prof)
+{
+    prof_begin(prof, "k_mgb_restrict", s);
+    hipLaunchKernelGGL(k_mgb_restrict, dim3(mg_blocks(mg_zones(LC))), dim3(MG_WG), 0, s, RF, LF.lo[0], LF.lo[1], LF.lo[2], BC, PC, LC, cflags);
+    prof_end(prof, s);
+    return mg_check(s);
+}
+
+int launch_mgb_prolong(const DFab& PC, const MgLevel& LC, const DFab& PF, const MgLevel& LF, const unsigned char* fflags,
+                       hipStream_t s, Profiler* prof)
+{
+    prof_begin(prof, "k_mgb_prolong", s);
+    hipLaunchKernelGGL(k_mgb_prolong, dim3(mg_blocks(mg_zones(LF))), dim3(MG_WG), 0, s, PC, LC.lo[0], LC.lo[1], LC.lo[2], PF, LF, fflags);
+    prof_end(prof, s);
+    return mg_check(s);
+}
+
+int launch_mgb_norm(const DFab& X, const MgLevel& L, const unsigned char* flags, double* ws, double* d_out, hipStream_t s,
+                    Profiler* prof)
+{
+    unsigned nb = mg_blocks(mg_zones(L));
+    if (nb > (unsigned)MG_NORM_MAX_WG) nb = MG_NORM_MAX_WG;
+    prof_begin(prof, "k_mgb_norm_partial", s);
+    hipLaunchKernelGGL(k_mgb_norm_partial, dim3(nb), dim3(MG_WG), 0, s, X, L, flags, ws);
+    prof_end(prof, s);
+    prof_begin(prof, "k_mg_norm_final", s);
+    hipLaunchKernelGGL(k_mg_norm_final, dim3(1), dim3(MG_NORM_MAX_WG), 0, s, (const double*)ws, (int)nb, d_out);
+    prof_end(prof, s);
+    return mg_check(s);
+}
+
+// mg_vcycle with the masked passes; X: the face values of level 0
+static int mgb_vcycle(PoissonPlan* P, size_t l, const DFab& X, hipStream_t s, Profiler* prof)
+{
+    const MgLevel& L = P->lev[l];
+    DFab none;
+    std::memset(&none, 0, sizeof(none));
+    const DFab& Xl = l == 0 ? X : none;
+    int rc = 0;
+    if (l + 1 == P->lev.size()) {
+        prof_begin(prof, "k_mgb_bottom", s);
+        hipLaunchKernelGGL(k_mgb_bottom, dim3(1), dim3(MG_BOTTOM_WG), 0, s, P->phi[l], P->rhs[l], L, (const unsigned char*)P->flags[l], Xl, MG_NBOTTOM);
+        prof_end(prof, s);
+        return mg_check(s);
+    }
+    for (int it = 0; it < MG_NPRE && rc == 0; ++it)
+        for (int colour = 0; colour < 2 && rc == 0; ++colour) rc = launch_mgb_smooth(P->phi[l], P->rhs[l], L, P->flags[l], Xl, colour, s, prof);
+    if (rc == 0) rc = launch_mgb_residual(P->phi[l], P->rhs[l], P->res[l], L, P->flags[l], Xl, s, prof);
+    if (rc == 0) rc = launch_mgb_restrict(P->res[l], L, P->rhs[l + 1], P->phi[l + 1], P->lev[l + 1], P->flags[l + 1], s, prof);
+    if (rc == 0) rc = mgb_vcycle(P, l + 1, X, s, prof);
+    if (rc == 0) rc = launch_mgb_prolong(P->phi[l + 1], P->lev[l + 1], P->phi[l], L, P->flags[l], s, prof);
+    for (int it = 0; it < MG_NPOST && rc == 0; ++it)
+        for (int colour = 0; colour < 2 && rc == 0; ++colour) rc = launch_mgb_smooth(P->phi[l], P->rhs[l], L, P->flags[l], Xl, colour, s, prof);
+    return rc;
+}
+
+static int mgb_residual_norm(PoissonPlan* P, const DFab& X, int at, hipStream_t s, Profiler* prof)
+{
+    int rc = launch_mgb_residual(P->phi[0], P->rhs[0], P->res[0], P->lev[0], P->flags[0], X, s, prof);
+    if (rc == 0) rc = launch_mgb_norm(P->res[0], P->lev[0], P->flags[0], P->norm_ws, P->d_norm + at, s, prof);
+    return rc;
+}
+
+// the table of the boxes of the plan with the FABs F, on the device (a table the plan has seen costs no copy)
+static int mgb_table(PoissonPlan* P, const DFab* F, hipStream_t s, const MgBoxDev*& dtab, long& total)
+{
+    const size_t nbox = P->boxes.size() / 6;
+    std::vector<MgBoxDev> tab(nbox);
+    std::memset((void*)tab.data(), 0, nbox * sizeof(MgBoxDev));
+    total = 0;
+    for (size_t b = 0; b < nbox; ++b) {
+        tab[b].F = F[b];
+        long n = 1;
+        for (int d = 0; d < 3; ++d) {
+            tab[b].lo[d] = P->boxes[6 * b + d];
+            tab[b].n[d] = P->boxes[6 * b + 3 + d] - P->boxes[6 * b + d] + 1;
+            n *= tab[b].n[d];
+        }
+        tab[b].start = total;
+        total += n;
+    }
+    return P->tables.find(tab.data(), nbox, s, dtab);
+}
+
+int launch_poisson_boxes_solve(PoissonPlan* P, const DFab& phi, const DFab& X, const DFab* U, int comp, double fourpiG, double reltol,
+                               double abstol, int maxiter, int* cycles, int* converged, double* final_norm, double* h_history,
+                               hipStream_t s, Profiler* prof)
+{
+    P->phi[0] = phi;
+    const MgLevel& L0 = P->lev[0];
+    const MgBoxDev* dtab;
+    long total;
+    int rc = mgb_table(P, U, s, dtab, total);
+    if (rc != 0) return rc;
+    prof_begin(prof, "k_mgb_rhs", s);
+    hipLaunchKernelGGL(k_mgb_rhs, dim3(mg_blocks(total)), dim3(MG_WG), 0, s, dtab, (int)(P->boxes.size() / 6), total, comp, P->rhs[0], fourpiG);
+    prof_end(prof, s);
+    rc = mg_check(s);
+    if (rc == 0) rc = launch_mgb_norm(P->rhs[0], L0, P->flags[0], P->norm_ws, P->d_norm, s, prof);
+    if (rc == 0) rc = mgb_residual_norm(P, X, 2, s, prof);
+    if (rc == 0) rc = mg_read(P, 4, s);
+    if (rc != 0) return rc;
+    const double bnorm = P->h_norm[0], max_rhs = P->h_norm[1];
+    double rnorm = P->h_norm[2];
+    const double t1 = reltol * bnorm, t2 = abstol * max_rhs;
+    const double tol = t1 > t2 ? t1 : t2;
+    if (h_history) { h_history[0] = bnorm; h_history[1] = max_rhs; h_history[2] = rnorm; }
+    int n = 0;
+    while (!(rnorm <= tol) && n < maxiter) {
+        rc = mgb_vcycle(P, 0, X, s, prof);
+        if (rc == 0) rc = mgb_residual_norm(P, X, 0, s, prof);
+        if (rc == 0) rc = mg_read(P, 1, s);
+        if (rc != 0) return rc;
+        rnorm = P->h_norm[0];
+        ++n;
+        if (h_history) h_history[2 + n] = rnorm;
+    }
+    *cycles = n;
+    *converged = rnorm <= tol ? 1 : 0;
+    *final_norm = rnorm;
+    return 0;
+}
+
+int launch_grad_phi_boxes(PoissonPlan* P, const DFab& phi, const DFab& X, const DFab* G, hipStream_t s, Profiler* prof)
+{
+    const MgBoxDev* dtab;
+    long total;
+    const int rc = mgb_table(P, G, s, dtab, total);
+    if (rc != 0) return rc;
+    prof_begin(prof, "k_mgb_grad", s);
+    hipLaunchKernelGGL(k_mgb_grad, dim3(mg_blocks(total)), dim3(MG_WG), 0, s, dtab, (int)(P->boxes.size() / 6), total, phi, P->lev[0],
+                       (const unsigned char*)P->flags[0], X, P->dx[0], P->dx[1], P->dx[2]);
     prof_end(prof, s);
     return mg_check(s);
 }
@@ -784,6 +1261,26 @@ __device__ __forceinline__ double cf_face_mean(const DFab& O, const DFab& N, dou
     return 0.5 * (vo + vi);
 }
 
+// the value on the face between the fine zone g, which lies outside, and its neighbour across the (d, side) face of the fine region
+__device__ __forceinline__ double cf_face_value(const DFab& O, const DFab& N, double oma, double a, int d, int side, const int g[3])
+{
+    const int t1 = d == 0 ? 1 : 0, t2 = d == 2 ? 1 : 2;
+    const int c_out = g[d] >> 1, c_in = side ? c_out - 1 : c_out + 1;
+    int c[3] = { g[0] >> 1, g[1] >> 1, g[2] >> 1 };
+    const double m0 = cf_face_mean(O, N, oma, a, d, c_out, c_in, c);
+    c[t1] += 1;
+    const double m1p = cf_face_mean(O, N, oma, a, d, c_out, c_in, c);
+    c[t1] -= 2;
+    const double m1m = cf_face_mean(O, N, oma, a, d, c_out, c_in, c);
+    c[t1] += 1;
+    c[t2] += 1;
+    const double m2p = cf_face_mean(O, N, oma, a, d, c_out, c_in, c);
+    c[t2] -= 2;
+    const double m2m = cf_face_mean(O, N, oma, a, d, c_out, c_in, c);
+    const double s1 = (g[t1] & 1) ? 1.0 : -1.0, s2 = (g[t2] & 1) ? 1.0 : -1.0;
+    return (m0 + s1 * (0.125 * (m1p - m1m))) + s2 * (0.125 * (m2p - m2m));
+}
+
 __global__ void __launch_bounds__(256) k_phi_cf_bc(DFab F, DFab O, DFab N, CfShell S, double oma, double a)
 {
     const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -815,21 +1312,7 @@ __global__ void __launch_bounds__(256) k_phi_cf_bc(DFab F, DFab O, DFab N, CfShe
     int nout = 0;
     for (int e = 0; e < 3; ++e) nout += (g[e] < S.flo[e] || g[e] > S.fhi[e]) ? 1 : 0;
     if (nout != 1) { *dst = 0.0; return; }
-    const int t1 = d == 0 ? 1 : 0, t2 = d == 2 ? 1 : 2;
-    const int c_out = g[d] >> 1, c_in = side ? c_out - 1 : c_out + 1;
-    int c[3] = { g[0] >> 1, g[1] >> 1, g[2] >> 1 };
-    const double m0 = cf_face_mean(O, N, oma, a, d, c_out, c_in, c);
-    c[t1] += 1;
-    const double m1p = cf_face_mean(O, N, oma, a, d, c_out, c_in, c);
-    c[t1] -= 2;
-    const double m1m = cf_face_mean(O, N, oma, a, d, c_out, c_in, c);
-    c[t1] += 1;
-    c[t2] += 1;
-    const double m2p = cf_face_mean(O, N, oma, a, d, c_out, c_in, c);
-    c[t2] -= 2;
-    const double m2m = cf_face_mean(O, N, oma, a, d, c_out, c_in, c);
-    const double s1 = (g[t1] & 1) ? 1.0 : -1.0, s2 = (g[t2] & 1) ? 1.0 : -1.0;
-    *dst = (m0 + s1 * (0.125 * (m1p - m1m))) + s2 * (0.125 * (m2p - m2m));
+    *dst = cf_face_value(O, N, oma, a, d, side, g);
 }
 
 int launch_phi_cf_bc(const DFab& F, const int flo[3], const int fhi[3], const DFab& O, const DFab& N, double a, hipStream_t stream,
@@ -848,6 +1331,39 @@ int launch_phi_cf_bc(const DFab& F, const int flo[3], const int fhi[3], const DF
     S.start[3] = S.start[2] + 2 * n[1] * n[2];
     prof_begin(prof, "k_phi_cf_bc", stream);
     hipLaunchKernelGGL(k_phi_cf_bc, dim3((unsigned)((S.start[3] + 255) / 256)), dim3(256), 0, stream, F, O, N, S, 1.0 - a, a);
+    prof_end(prof, stream);
+    return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
+}
+
+// The coarse-fine boundary values of a level that is a union of boxes, into the face array X of its plan: thread t takes the
+// face r = t / zones (x low, x high, y low, ...) of the zone t % zones of the bounding box L; a covered zone whose flag of that
+// face is set writes k_phi_cf_bc's value of the face zone -- its uncovered neighbour -- into the slot of the face.  A face between
+// two boxes of the level, and every other slot of X, is not written.
+__global__ void __launch_bounds__(256) k_phi_cf_boxes(DFab X, DFab O, DFab N, MgLevel L, const unsigned char* __restrict__ flags,
+                                                     double oma, double a)
+{
+    const long zones = (long)L.n[0] * L.n[1] * L.n[2];
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 6 * zones) return;
+    const int r = (int)(t / zones);
+    const long q = t % zones;
+    const int d = r >> 1, side = r & 1;
+    if (!(flags[q] & MGF_COVERED) || !(flags[q] & mgf_face(d, side))) return;
+    const long rr = q / L.n[0];
+    const int z[3] = { L.lo[0] + (int)(q % L.n[0]), L.lo[1] + (int)(rr % L.n[1]), L.lo[2] + (int)(rr / L.n[1]) };
+    int g[3] = { z[0], z[1], z[2] }, f[3] = { z[0], z[1], z[2] };
+    g[d] += side ? 1 : -1;
+    f[d] += side;
+    X.p[mg_at(X, f[0], f[1], f[2]) + X.sn * d] = cf_face_value(O, N, oma, a, d, side, g);
+}
+
+int launch_phi_cf_boxes(PoissonPlan* P, const DFab& X, const DFab& O, const DFab& N, double a, hipStream_t stream, Profiler* prof)
+{
+    const MgLevel& L = P->lev[0];
+    const long n = 6 * (long)L.n[0] * L.n[1] * L.n[2];
+    prof_begin(prof, "k_phi_cf_boxes", stream);
+    hipLaunchKernelGGL(k_phi_cf_boxes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, X, O, N, L,
+                       (const unsigned char*)P->flags[0], 1.0 - a, a);
     prof_end(prof, stream);
     return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
 }

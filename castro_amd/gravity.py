@@ -22,8 +22,9 @@
 
   PoissonGravity                     gravity.gravity_type = "PoissonGrav" in the reference's level-solve configuration
                                      (gravity.no_sync = 1, gravity.no_composite = 1, gravity.max_solve_level): every level solves on
-                                     its own box -- level 0 with multipole boundary values, a refined one with Dirichlet data from
-                                     the level below at its own time --, then g = -grad(phi); the old / new potentials per level.
+                                     its own box or boxes -- level 0 with multipole boundary values, a refined one with Dirichlet
+                                     data from the level below at its own time; a level of several boxes as one array over their
+                                     bounding box --, then g = -grad(phi); the old / new potentials per level.
 
   ConstantGravity                    ConstantGrav as Gravity_Type data, for the one case that needs them: a point mass on top.
 
@@ -359,10 +360,16 @@ class PoissonGravity(_Gravity):
     On a hierarchy the levels solve for themselves.  max_solve_level: gravity.max_solve_level, the finest level that solves (None:
     every level, the reference's default); a finer level takes phi and g from the level below by interpolation.  no_sync / no_composite:
     gravity.no_sync / gravity.no_composite; only True is built (no composite solve, no gravity_sync, no composite correction).
-    One rank, refinement ratio 2, level 0 and every refined level ONE box, the refined ones inside the domain."""
+    One rank, refinement ratio 2, level 0 ONE box, every refined box inside the domain.  A refined level is one box or several
+    (patches=[[box, ...]], refine= with cluster=True): a level of several boxes is solved as ONE array over their bounding box
+    with a coverage mask (BOXES_OPERATIONS of the backend: castro_amd_poisson_boxes_*) -- the coarsened boxes, grown by one zone,
+    must lie inside the boxes of the level below, and the level coarsens only while every box does (ValueError names the level,
+    the bounding box and the alignment when the coarsest level would hold more than CASTRO_AMD_POISSON_MAX_BOTTOM zones)."""
 
     OPERATIONS = ("multipole_moments_mf", "multipole_phi_bc", "poisson_solve", "grad_phi_to_grav")
     AMR_OPERATIONS = ("poisson_cf_bc", "lincomb", "cc_interp")
+    # a refined level of several boxes: one array over their bounding box (a backend without them keeps the refusal of such levels)
+    BOXES_OPERATIONS = ("poisson_boxes_plan_create", "poisson_boxes_cf_bc", "poisson_boxes_solve", "grad_phi_to_grav_boxes")
     drdxfac = 1                                 # a box of a CastroAmr level copies it from its gravity object; not used here
 
     def __init__(self, max_multipole_order=0, reltol=1.e-10, abstol=1.e-10, maxiter=40, Gconst=L.GCONST, center=None,
@@ -406,7 +413,10 @@ class PoissonGravity(_Gravity):
         """the multigrid plan of level l, made if there is none: construction of a Castro, the first solve, or after close()"""
         ent = self._entry(l)
         if ent["plan"] is None:
-            ent["plan"] = ent["hydro"].poisson_plan_create(ent["geom"])
+            if ent["boxes"] is None:
+                ent["plan"] = ent["hydro"].poisson_plan_create(ent["geom"])
+            else:
+                ent["plan"] = ent["hydro"].poisson_boxes_plan_create([ent["geom"].dx[d] for d in range(3)], ent["boxes"])
         return ent["plan"]
 
     def __del__(self):
@@ -422,7 +432,7 @@ class PoissonGravity(_Gravity):
     # ---- level solves (gravity.no_sync = 1, gravity.no_composite = 1) ---------------------------------------------------------
     # Castro::construct_old_gravity / construct_new_gravity (Castro_gravity.cpp:14-232) and Gravity::solve_for_phi /
     # get_old_grav_vector / get_new_grav_vector / GetCrsePhi (Gravity.cpp:418-485, 664-690, 838-981) on a hierarchy whose levels
-    # are one box each.  Level 0 takes its boundary values from the multipole moments of its own valid zones.  A level
+    # are one box each (a level of several boxes: the same sequence on its level array, ent["boxes"]).  Level 0 takes its boundary values from the multipole moments of its own valid zones.  A level
     # 0 < l <= max_solve_level solves on its own box
     # -- a geometry whose domain is the box goes to the same entry points -- with Dirichlet data from the potential of the level
     # below at its own time (castro_amd_poisson_cf_bc_fab).  A level above max_solve_level takes phi and g of its whole FABs from
@@ -446,26 +456,72 @@ class PoissonGravity(_Gravity):
                              "bottom solver of the multigrid takes (CASTRO_AMD_POISSON_MAX_BOTTOM): its extents need more factors "
                              "of 2 -- a blocking_factor of 16 or 32" % (box, l, n, coarsest, L.POISSON_MAX_BOTTOM))
 
+    @staticmethod
+    def _check_bottom_boxes(l, boxes):
+        lev = L.poisson_boxes_levels(boxes)
+        (clo, cn), (lo, n) = lev[-1], lev[0]
+        if cn[0] * cn[1] * cn[2] > L.POISSON_MAX_BOTTOM:
+            bb = (lo, tuple(lo[d] + n[d] - 1 for d in range(3)))
+            raise ValueError("Poisson gravity: the %d boxes of level %d with the bounding box %s (%s zones), aligned to %d zones, "
+                             "coarsen to %s, more than the %d zones the bottom solver of the multigrid takes "
+                             "(CASTRO_AMD_POISSON_MAX_BOTTOM): the level coarsens only while every box coarsens -- a larger "
+                             "blocking_factor aligns the boxes to more factors of 2"
+                             % (len(boxes), l, bb, n, L.poisson_boxes_alignment(boxes), cn, L.POISSON_MAX_BOTTOM))
+
+    @staticmethod
+    def _inside_union(box, parents):
+        """does the box (lo, hi) lie inside the union of the boxes `parents`?"""
+        import numpy as np
+        lo, hi = box
+        cov = np.zeros(tuple(hi[d] - lo[d] + 1 for d in (2, 1, 0)), dtype=bool)
+        for plo, phi in parents:
+            a = [max(plo[d], lo[d]) - lo[d] for d in range(3)]
+            b = [min(phi[d], hi[d]) - lo[d] + 1 for d in range(3)]
+            if all(b[d] > a[d] for d in range(3)):
+                cov[a[2]:b[2], a[1]:b[1], a[0]:b[0]] = True
+        return bool(cov.all())
+
     def check_boxes(self, l, boxes, parents):
-        """the boxes (lo, hi) of the refined level l about to be made, in its own zones; parents: those of level l - 1"""
-        if len(boxes) != 1 or len(parents) != 1:
-            raise NotImplementedError("Poisson gravity: level %d would have %d boxes (level %d has %d) -- the level solves are "
-                                      "built for refined levels of ONE box; a level of several boxes needs the halo exchange of "
-                                      "phi between them" % (l, len(boxes), l - 1, len(parents)))
-        lo, hi = boxes[0]
+        """the boxes (lo, hi) of the refined level l about to be made, in its own zones; parents: those of level l - 1.  A level
+        of several boxes, or over several parents, needs the operations of a level array (BOXES_OPERATIONS) of its backend."""
+        several = len(boxes) != 1 or len(parents) != 1
+        if len(boxes) != 1:
+            h = self.amr._hydro_for(l)
+            missing = [name for name in self.BOXES_OPERATIONS if not hasattr(h, name)]
+            if missing:
+                raise NotImplementedError("Poisson gravity: level %d would have %d boxes (level %d has %d) -- this backend has no "
+                                          "%s: a level of several boxes is solved as one array over its bounding box, with a "
+                                          "coverage mask" % (l, len(boxes), l - 1, len(parents), ", ".join(missing)))
         dom = tuple((2 ** l) * x for x in self.amr.n_cell)
-        if any(lo[d] <= 0 or hi[d] >= dom[d] - 1 for d in range(3)):
-            raise NotImplementedError("Poisson gravity: the box %s of level %d touches the domain boundary -- the multipole "
-                                      "boundary values of a refined level are not built; the box must lie inside the domain"
-                                      % ((lo, hi), l))
+        for lo, hi in boxes:
+            if any(lo[d] <= 0 or hi[d] >= dom[d] - 1 for d in range(3)):
+                raise NotImplementedError("Poisson gravity: the box %s of level %d touches the domain boundary -- the multipole "
+                                          "boundary values of a refined level are not built; the box must lie inside the domain"
+                                          % ((lo, hi), l))
+        if not several:
+            if not self.solves(l):
+                return
+            (lo, hi), (plo, phi) = boxes[0], parents[0]
+            if any((lo[d] >> 1) - 1 < plo[d] or (hi[d] >> 1) + 1 > phi[d] for d in range(3)):
+                raise ValueError("Poisson gravity: the box %s of level %d, coarsened and grown by one zone, does not lie inside the "
+                                 "valid box %s of level %d: its boundary values would read ghost zones of the coarse potential"
+                                 % ((lo, hi), l, (plo, phi), l - 1))
+            self._check_bottom(l, (lo, hi), tuple(hi[d] - lo[d] + 1 for d in range(3)))
+            return
+        # the coarse zones the boundary values and the interpolated guess read (edges included: the transverse slopes) must be
+        # valid zones of level l - 1: an uncovered or ghost zone of the coarse potential is never read
+        for lo, hi in boxes:
+            need = (tuple((x >> 1) - 1 for x in lo), tuple((x >> 1) + 1 for x in hi))
+            if not self._inside_union(need, parents):
+                raise ValueError("Poisson gravity: the box %s of level %d, coarsened and grown by one zone, does not lie inside the "
+                                 "union of the %d boxes of level %d: its boundary values would read zones of the coarse potential "
+                                 "that level %d does not cover" % ((lo, hi), l, len(parents), l - 1, l - 1))
         if not self.solves(l):
             return
-        plo, phi = parents[0]
-        if any((lo[d] >> 1) - 1 < plo[d] or (hi[d] >> 1) + 1 > phi[d] for d in range(3)):
-            raise ValueError("Poisson gravity: the box %s of level %d, coarsened and grown by one zone, does not lie inside the "
-                             "valid box %s of level %d: its boundary values would read ghost zones of the coarse potential"
-                             % ((lo, hi), l, (plo, phi), l - 1))
-        self._check_bottom(l, (lo, hi), tuple(hi[d] - lo[d] + 1 for d in range(3)))
+        if len(boxes) == 1:
+            self._check_bottom(l, boxes[0], tuple(boxes[0][1][d] - boxes[0][0][d] + 1 for d in range(3)))
+        else:
+            self._check_bottom_boxes(l, boxes)
 
     def reset(self, from_level=0):
         """regrid / _push_level / _drop_fine: the levels >= from_level are gone or re-made -- their potentials and plans go"""
@@ -475,19 +531,31 @@ class PoissonGravity(_Gravity):
                 del self._lev[l]
 
     def _entry(self, l):
-        """phi_old / phi_new (one ghost zone), the plan and the scratch of level l, made for the box the level has now"""
+        """phi_old / phi_new (one ghost zone), the plan and the scratch of level l, made for the box the level has now -- for the
+        boxes: a level of several is ONE array over their bounding box, with three face-centred arrays for its boundary values"""
         lev = self.amr.lev[l]
         b = lev.mine[0]
+        boxes = tuple(x.bx for x in lev.mine) if len(lev.mine) > 1 else None
+        key = b.bx if boxes is None else boxes
         ent = self._lev.get(l)
-        if ent is not None and ent["key"] != b.bx:       # a plan is kept per level, keyed by the extents of its box
+        if ent is not None and ent["key"] != key:        # a plan is kept per level, keyed by the extents of its box(es)
             self._free_plan(ent)
             ent = None
         if ent is None:
             h = lev.hydro
-            phibox = (tuple(x - 1 for x in b.lo), tuple(x + 1 for x in b.hi))
-            ent = self._lev[l] = dict(key=b.bx, hydro=h, phibox=phibox, phi_old=h.alloc(1, *phibox), phi_new=h.alloc(1, *phibox),
-                                      plan=None, have=(l == 0), tables={}, stats={"first": None, "old": None, "new": None})
-            if l == 0:
+            bb = b.bx if boxes is None else (tuple(min(x[0][d] for x in boxes) for d in range(3)),
+                                             tuple(max(x[1][d] for x in boxes) for d in range(3)))
+            phibox = (tuple(x - 1 for x in bb[0]), tuple(x + 1 for x in bb[1]))
+            ent = self._lev[l] = dict(key=key, hydro=h, phibox=phibox, phi_old=h.alloc(1, *phibox), phi_new=h.alloc(1, *phibox),
+                                      plan=None, have=(l == 0), tables={}, stats={"first": None, "old": None, "new": None},
+                                      boxes=boxes, bb=bb)
+            if boxes is not None:
+                ent["geom"] = lev.geom
+                ent["facebox"] = (bb[0], tuple(x + 1 for x in bb[1]))
+                ent["faces"] = h.alloc(3, *ent["facebox"])
+                ent["cbox"] = (tuple((x >> 1) - 2 for x in bb[0]), tuple((x >> 1) + 2 for x in bb[1]))
+                ent["ctmp"] = h.alloc(1, *ent["cbox"])
+            elif l == 0:
                 n1 = self.lnum + 1
                 ent["moments"] = h.alloc(1, (0, 0, 0), (3 * n1 * n1 - 1, 0, 0))
                 ent["geom"] = lev.geom
@@ -526,20 +594,26 @@ class PoissonGravity(_Gravity):
         name = "grav_" + which
         grav = getattr(b, name)
         phi, pbx = ent["phi_" + which], ent["phibox"]
+        boxes = ent["boxes"]
         if level > 0 and not self.solves(level):
             # no solve above max_solve_level: phi and g of the whole FABs are the FillCoarsePatch of the level below
-            # (Gravity.cpp:466, 846-852, 919-925)
+            # (Gravity.cpp:466, 846-852, 919-925); on a level of several boxes, box by box -- phi on the valid zones of each
             self._crse_at(level, ent, a)
-            h.cc_interp(ent["ctmp"], ent["cbox"], phi, pbx, pbx[0], pbx[1], 1)
+            if boxes is None:
+                h.cc_interp(ent["ctmp"], ent["cbox"], phi, pbx, pbx[0], pbx[1], 1)
             ent["have"] = True
-            for p, (lo, hi) in b.gsrc + b.gsrc_valid:
-                h.lincomb(b.gctmp, b.gcbox, 1.0 - a, p.grav_old, p.gravbox, a, p.grav_new, p.gravbox, 3, lo, hi)
-            h.cc_interp(b.gctmp, b.gcbox, grav, b.gravbox, b.gravbox[0], b.gravbox[1], 3)
+            for x in lev.mine:
+                if boxes is not None:
+                    h.cc_interp(ent["ctmp"], ent["cbox"], phi, pbx, x.lo, x.hi, 1)
+                for p, (lo, hi) in x.gsrc + x.gsrc_valid:
+                    h.lincomb(x.gctmp, x.gcbox, 1.0 - a, p.grav_old, p.gravbox, a, p.grav_new, p.gravbox, 3, lo, hi)
+                h.cc_interp(x.gctmp, x.gcbox, getattr(x, name), x.gravbox, x.gravbox[0], x.gravbox[1], 3)
             return
         if not ent["have"]:
             # the first solve of the level, or of a level a regrid has re-made: the level below, interpolated, is the guess
             self._crse_at(level, ent, a)
-            h.cc_interp(ent["ctmp"], ent["cbox"], phi, pbx, b.lo, b.hi, 1)
+            for x in lev.mine:
+                h.cc_interp(ent["ctmp"], ent["cbox"], phi, pbx, x.lo, x.hi, 1)
             ent["have"] = True
         elif which == "new":
             phi.copy_(ent["phi_old"])                    # the "old" phi of the step is the guess (Castro_gravity.cpp:146)
@@ -554,11 +628,19 @@ class PoissonGravity(_Gravity):
             mom = ent["moments"].reshape(-1)
             h.multipole_moments_mf(ent["tables"][key], geom, mp, mom)      # fill_multipole_BCs(level, level): this level alone
             h.multipole_phi_bc(phi, pbx, geom, mp, mom)
-        else:
+        elif boxes is None:
             P = self._lev[level - 1]
             h.poisson_cf_bc(phi, pbx, b.lo, b.hi, P["phi_old"], P["phibox"], P["phi_new"], P["phibox"], a)
-        cycles, ok, norm, hist = h.poisson_solve(plan, phi, pbx, S, b.gbox, L.URHO, 4.0 * math.pi * self.Gconst,
-                                                 self.reltol, self.abstol, self.maxiter)
+        else:
+            P = self._lev[level - 1]
+            h.poisson_boxes_cf_bc(plan, ent["faces"], ent["facebox"], P["phi_old"], P["phibox"], P["phi_new"], P["phibox"], a)
+        if boxes is None:
+            cycles, ok, norm, hist = h.poisson_solve(plan, phi, pbx, S, b.gbox, L.URHO, 4.0 * math.pi * self.Gconst,
+                                                     self.reltol, self.abstol, self.maxiter)
+        else:
+            rhos = [(x.S_old_b if which == "old" else x.S_new_b, x.gbox) for x in lev.mine]
+            cycles, ok, norm, hist = h.poisson_boxes_solve(plan, phi, pbx, ent["faces"], ent["facebox"], rhos, L.URHO,
+                                                           4.0 * math.pi * self.Gconst, self.reltol, self.abstol, self.maxiter)
         st = ent["stats"]
         st[which] = {"cycles": cycles, "norm": norm, "history": hist}
         if st["first"] is None:
@@ -569,11 +651,29 @@ class PoissonGravity(_Gravity):
             raise RuntimeError("Poisson gravity, level %d: the multigrid did not reach max(%g * %g, %g * %g) in %d V-cycles; the "
                                "last two residual norms are %r and %r" % (level, self.reltol, hist[0], self.abstol, hist[1],
                                                                           self.maxiter, hist[-2], hist[-1]))
-        h.grad_phi_to_grav(phi, pbx, grav, b.gravbox, ent["geom"])
+        if boxes is None:
+            h.grad_phi_to_grav(phi, pbx, grav, b.gravbox, ent["geom"])
+        else:
+            h.grad_phi_to_grav_boxes(plan, phi, pbx, ent["faces"], ent["facebox"], [(getattr(x, name), x.gravbox) for x in lev.mine])
         lev.fill_grav(name, a)                           # the Gravity_Type FillPatch of the ghost zones of g
 
     def phi_level(self, level, new=True):
-        return self._entry(level)["phi_new" if new else "phi_old"]
+        ent = self._entry(level)
+        if ent["boxes"] is not None:
+            raise ValueError("phi_grav(%d): level %d has %d boxes and its potential is one array over their bounding box with a "
+                             "coverage mask -- phi_grav_level(%d) returns it" % (level, level, len(ent["boxes"]), level))
+        return ent["phi_new" if new else "phi_old"]
+
+    def phi_level_boxes(self, level, new=True):
+        """(bounding box, phi on its zones, covered) of `level` as numpy arrays (nz, ny, nx): a level of one box is all covered"""
+        import numpy as np
+        ent = self._entry(level)
+        (lo, hi) = bb = ent["bb"]
+        phi = ent["phi_new" if new else "phi_old"].cpu().numpy()[0, 1:-1, 1:-1, 1:-1].copy()
+        cov = np.zeros(phi.shape, dtype=bool)
+        for blo, bhi in ent["boxes"] or (bb,):
+            cov[tuple(slice(blo[d] - lo[d], bhi[d] - lo[d] + 1) for d in (2, 1, 0))] = True
+        return bb, phi, cov
 
     def stats_level(self, level):
         return dict(self._entry(level)["stats"])

@@ -327,6 +327,53 @@ class HipHydro:
                                                    float(a), _stream_ptr(stream))
         L.check(rc, "poisson_cf_bc_fab")
 
+    # ---- a refined level of several boxes as ONE array over their bounding box BB (k_mgb_* of poisson_kernels.hip).  phi: one
+    #      component on BB grown by one; faces: three components on [BB.lo, BB.hi + 1], component d at a zone the value ON its low
+    #      d-face ------------------------------------------------------------------------------------------------------------------
+    def poisson_boxes_plan_create(self, dx, boxes):
+        """castro_amd_poisson_boxes_plan_create: the multigrid levels and coverage flags of the union of `boxes` [(lo, hi)], in
+        the zones of the level; freed by poisson_plan_destroy.  Every refusal is a RuntimeError with the error code."""
+        n = len(boxes)
+        lo = (C.c_int * (3 * max(n, 1)))(*[int(x) for b in boxes for x in b[0]])
+        hi = (C.c_int * (3 * max(n, 1)))(*[int(x) for b in boxes for x in b[1]])
+        plan = C.c_void_p()
+        L.check(self.lib.castro_amd_poisson_boxes_plan_create(self.h, (C.c_double * 3)(*[float(x) for x in dx]), n, lo, hi,
+                                                              C.byref(plan)), "poisson_boxes_plan_create")
+        return plan
+
+    def poisson_boxes_cf_bc(self, plan, faces, faces_box, crse_old, crse_old_box, crse_new, crse_new_box, a, stream=None):
+        """castro_amd_poisson_boxes_cf_bc: the coarse-fine boundary values of the union into the slots of `faces` that lie between
+        a covered and an uncovered zone, from the potentials of the level below: (1 - a) crse_old + a crse_new"""
+        L.check(self.lib.castro_amd_poisson_boxes_cf_bc(self.h, plan, C.byref(L.fab_of(faces, *faces_box)),
+                                                        C.byref(L.fab_of(crse_old, *crse_old_box)),
+                                                        C.byref(L.fab_of(crse_new, *crse_new_box)), float(a), _stream_ptr(stream)),
+                "poisson_boxes_cf_bc")
+
+    def poisson_boxes_solve(self, plan, phi, phi_box, faces, faces_box, rhos, rho_comp, fourpiG, reltol=1.e-10, abstol=1.e-10,
+                            maxiter=40, stream=None):
+        """castro_amd_poisson_boxes_solve: poisson_solve on the union; rhos: [(state, box)] of every box of the plan, in its order"""
+        cycles, conv, norm = C.c_int(0), C.c_int(0), C.c_double(0.0)
+        hist = (C.c_double * (int(maxiter) + 3))()
+        L.check(self.lib.castro_amd_poisson_boxes_solve(self.h, plan, C.byref(L.fab_of(phi, *phi_box)), C.byref(L.fab_of(faces, *faces_box)),
+                                                        len(rhos), self.make_grav_fabs(rhos), int(rho_comp), float(fourpiG),
+                                                        float(reltol), float(abstol), int(maxiter), C.byref(cycles), C.byref(conv),
+                                                        C.byref(norm), hist, _stream_ptr(stream)), "poisson_boxes_solve")
+        return cycles.value, bool(conv.value), norm.value, list(hist[:cycles.value + 3])
+
+    def grad_phi_to_grav_boxes(self, plan, phi, phi_box, faces, faces_box, gravs, stream=None):
+        """castro_amd_grad_phi_to_grav_boxes: g = -grad(phi) on the zones of every box into its own FAB; gravs: [(grav, box)]"""
+        L.check(self.lib.castro_amd_grad_phi_to_grav_boxes(self.h, plan, C.byref(L.fab_of(phi, *phi_box)),
+                                                           C.byref(L.fab_of(faces, *faces_box)), len(gravs), self.make_grav_fabs(gravs),
+                                                           _stream_ptr(stream)), "grad_phi_to_grav_boxes")
+
+    def poisson_boxes_level_op(self, plan, op, level, a, b=None, c=None, faces=None, colour=0, out=None, stream=None):
+        """castro_amd_poisson_boxes_level_op: one masked pass (_lib.MG_*) on the (tensor, box) pairs a, b, c over the bounding box
+        >> level; faces: the (tensor, box) of the face values (level 0), None: every boundary face holds 0.0"""
+        fabs = [C.byref(L.fab_of(*x[:1], *x[1])) if x is not None else None for x in (a, b, c, faces)]
+        L.check(self.lib.castro_amd_poisson_boxes_level_op(self.h, plan, int(op), int(level), int(colour), fabs[0], fabs[1], fabs[2],
+                                                           fabs[3], C.c_void_p(out.data_ptr()) if out is not None else None,
+                                                           _stream_ptr(stream)), "poisson_boxes_level_op")
+
     # ---- the central point mass (castro.use_point_mass; Gravity.cpp:2903-2948, Castro_pointmass.cpp) ---------------------
     def add_pointmass(self, grav, grav_box, pm, geom, mass, stream=None):
         """castro_amd_add_pointmass_fab: Gravity::add_pointmass_to_gravity over the whole box of the 3-component FAB `grav`; pm:

@@ -75,6 +75,8 @@ extern "C" {
  *      castro_amd_poisson_plan_create / _destroy, castro_amd_poisson_solve, castro_amd_poisson_level_op,
  *      castro_amd_grad_phi_to_grav_fab: Poisson self-gravity on a single level.
  *      castro_amd_poisson_cf_bc_fab: the coarse-fine boundary potential of a refined level's own Poisson solve.
+ *      castro_amd_poisson_boxes_plan_create, castro_amd_poisson_boxes_cf_bc, castro_amd_poisson_boxes_solve,
+ *      castro_amd_grad_phi_to_grav_boxes, castro_amd_poisson_boxes_level_op: the level solve of a refined level of several boxes.
  * A caller checks `castro_amd_abi_version() == CASTRO_AMD_ABI_VERSION` once after loading the library; a mismatch means
  * the library was built from another revision of this header (a 0.2 caller with 2-double vectors would be written 8 bytes
  * out of bounds by a 0.3 library). */
@@ -716,6 +718,66 @@ int castro_amd_grad_phi_to_grav_fab(castro_amd_ctx *ctx, const castro_amd_fab *p
  * one not inside phi_fine_fab, or the coarsened patch grown by one not inside both coarse FABs. */
 int castro_amd_poisson_cf_bc_fab(castro_amd_ctx *ctx, const castro_amd_fab *phi_fine_fab, const int fine_lo[3], const int fine_hi[3],
                                  const castro_amd_fab *crse_old_fab, const castro_amd_fab *crse_new_fab, double a, void *stream);
+/* Poisson gravity on a refined level that is a union of SEVERAL boxes (tagged and clustered grids), all of them on this device:
+ * the level is solved as ONE array over the bounding box BB of its disjoint boxes B_1 .. B_n, with a byte of coverage flags per
+ * zone -- no exchange of phi between the boxes.  lo / hi: 3 ints per box, in the zones of the level; every box is the refinement
+ * of a coarse box (even low, odd high corner) at non-negative indices.
+ *
+ * Multigrid level m lives on BB >> m; a zone of it is covered if it lies in some B_i >> m.  Level m + 1 exists while (a) lo and
+ * hi + 1 of every box are divisible by 2^(m+1) -- the 8 children of a coarse zone are then all covered or all not --, (b) the
+ * extents of BB >> m are even and their halves at least 2 (castro_amd_poisson_plan_create's rule), (c) fewer than 32 levels
+ * exist.  Flags of a zone, made on the host at plan creation: bit 0 = covered; bit 1 + 2 d + side = the neighbour across the low
+ * (side 0) / high (side 1) face of direction d is not covered (a zone beyond BB is not covered).
+ * CASTRO_AMD_ERR_ARG: a box that is not such a refinement, two boxes that overlap.  CASTRO_AMD_ERR_UNSUPPORTED: the coarsest
+ * level holds more than CASTRO_AMD_POISSON_MAX_BOTTOM zones of its bounding box.  Nothing is allocated or launched on a refusal.
+ * The plan is freed by castro_amd_poisson_plan_destroy; the one-box entry points above refuse it (CASTRO_AMD_ERR_ARG), as the
+ * entry points below refuse a plan of castro_amd_poisson_plan_create.
+ *
+ * Arrays.  phi_fab: 1 component, BB grown by one zone inside it.  faces_fab: 3 components, [BB.lo, BB.hi + 1] inside it;
+ * component d at the zone (i, j, k) is the value of phi ON the low d-face of that zone (so the high x-face of (i, j, k) is the
+ * entry (i + 1, j, k) of component 0).  It is read only where a flag bit is set: an uncovered zone at a concave corner of the
+ * union is the neighbour of two covered zones across two faces with two values, so the values cannot live in phi's zones.
+ *
+ * The passes are those of castro_amd_poisson_solve with "beyond a domain face" replaced by "the flag of this face is set", f the
+ * face value of level 0 and 0.0 on the coarser levels, and only covered zones written:
+ *   smoother   dg = cdiag; low x: xm = 2.0 * f, dg = dg + cx; high x: xp = 2.0 * f, dg = dg + cx; then y, then z;
+ *              p = (((cx * (xm + xp) + cy * (ym + yp)) + cz * (zm + zp)) - b) / dg; the colour of a zone is the parity of
+ *              (ii + jj + kk) relative to the low corner of BB >> m; the bottom solve is 32 x (colour 0, colour 1) in one launch
+ *   residual   across a flagged face the neighbour is 2.0 * f - p; lap = (cx * ((xm + xp) - 2.0 * p) + cy * ((ym + yp) - 2.0 * p))
+ *              + cz * ((zm + zp) - 2.0 * p); r = b - lap
+ *   restrict   on covered coarse zones: (((((((r000 + r100) + r010) + r110) + r001) + r101) + r011) + r111) * 0.125, phi_c = 0
+ *   prolong    on covered fine zones: phi_f = phi_f + phi_c(ii / 2, jj / 2, kk / 2)
+ *   norms      max |x| and max x over the covered zones
+ *   rhs        b = fourpiG * component rho_comp of the state FAB of the box that holds the zone (rho_fabs[i] belongs to box i)
+ * With this order a union that tiles a rectangular box gives, in the `exact` build, the bits of castro_amd_poisson_solve on that
+ * box -- phi, norm history and cycle count -- unless the alignment of the tiles stops the coarsening before the extents do.
+ * No floating-point atomics; everything on `stream`; one norm read back per V-cycle. */
+int castro_amd_poisson_boxes_plan_create(castro_amd_ctx *ctx, const double dx[3], int nboxes, const int *lo, const int *hi,
+                                         castro_amd_poisson_plan **plan);
+/* The coarse-fine boundary values of the level: for every face of a covered zone of level 0 whose flag is set, the value of
+ * castro_amd_poisson_cf_bc_fab for the face zone (the uncovered neighbour) -- the same formula, the same roundings, no
+ * contraction in either build -- into the slot of that face in faces_fab.  A face between two boxes of the level and every other
+ * slot is not written.  crse_old_fab / crse_new_fab (1 component each): the potentials of the level below; both must hold the
+ * coarsened BB grown by one zone, of which the zones under the union grown by one are read.  CASTRO_AMD_ERR_ARG: a non-finite a,
+ * a FAB that does not hold this. */
+int castro_amd_poisson_boxes_cf_bc(castro_amd_ctx *ctx, castro_amd_poisson_plan *plan, const castro_amd_fab *faces_fab,
+                                   const castro_amd_fab *crse_old_fab, const castro_amd_fab *crse_new_fab, double a, void *stream);
+/* castro_amd_poisson_solve on the union: phi_fab holds the starting guess on the covered zones (the others are neither read nor
+ * written), rho_fabs[i] the state of box i (nboxes: the plan's), its box inside it.  The outputs as castro_amd_poisson_solve. */
+int castro_amd_poisson_boxes_solve(castro_amd_ctx *ctx, castro_amd_poisson_plan *plan, const castro_amd_fab *phi_fab,
+                                   const castro_amd_fab *faces_fab, int nboxes, const castro_amd_fab *rho_fabs, int rho_comp,
+                                   double fourpiG, double reltol, double abstol, int maxiter, int *cycles, int *converged,
+                                   double *final_norm, double *h_history, void *stream);
+/* g = -grad(phi) on the zones of box i into grav_fabs[i] (3 components, the box inside it): castro_amd_grad_phi_to_grav_fab's
+ * arithmetic -- gl = (p - xm) / hx, gh = (xp - p) / hx, g_x = -(0.5 * (gl + gh)) --; a neighbour in a sibling box is an ordinary
+ * neighbour, across a flagged face gl = (2.0 * (p - f)) / hx, gh = (2.0 * (f - p)) / hx.  Nothing outside the boxes is written. */
+int castro_amd_grad_phi_to_grav_boxes(castro_amd_ctx *ctx, castro_amd_poisson_plan *plan, const castro_amd_fab *phi_fab,
+                                      const castro_amd_fab *faces_fab, int nboxes, const castro_amd_fab *grav_fabs, void *stream);
+/* castro_amd_poisson_level_op for a plan of a union: one masked pass on caller-owned FABs over BB >> level (phi-like FABs grown
+ * by one zone).  faces_fab: the face values, level 0 only; NULL (required on a coarser level): every flagged face holds 0.0. */
+int castro_amd_poisson_boxes_level_op(castro_amd_ctx *ctx, castro_amd_poisson_plan *plan, int op, int level, int colour,
+                                      const castro_amd_fab *a, const castro_amd_fab *b, const castro_amd_fab *c,
+                                      const castro_amd_fab *faces_fab, double *d_out, void *stream);
 /* castro_amd_sources_mf with the gravity of every box read from its Gravity_Type FABs: grav_old[i] / grav_new[i] (3
  * components, one ghost zone around [lo, hi] of box i for grav_source_type = 4; grav_new is read by stage 1 only and may be
  * NULL for stage 0) take the place of the one vector -- the zone functions of castro_amd_old/new_gravity_source_gfab inside

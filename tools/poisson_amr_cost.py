@@ -12,7 +12,16 @@ zones each.  Reported:
             (profiling slows the host: that step's time is not reported), those of the multigrid, and the share of k_phi_cf_bc in
             launches and in kernel time
 
-    python tools/poisson_amr_cost.py [--base 64] [--steps 3] [--reps 3] [--numerics contract] [--out file.json]
+    python tools/poisson_amr_cost.py [--base 64] [--steps 3] [--reps 3] [--numerics contract] [--out file.json] [--clustered]
+
+--clustered: the same problem with tagged, clustered grids instead (a density-gradient tag, cluster=True, max_grid_size = 32 zones
+of the new level, the smallest blocking factor of 8, 16, 32 the bottom solver accepts; --r0, the radius of the ball, keeps the
+tagged shell off the domain boundary): every refined level is a union of several boxes, solved as ONE array over their bounding
+box BB with a coverage mask (k_mgb_*).  After two coarse steps, for every such level: the masked solve from phi = 0 with the
+level's own density and boundary values, beside the one-box solve of BB (what a level of one bounding box costs: the same
+entry points the parent revision has; its density is the level's, the ambient value where no box is) -- ms per solve and per
+V-cycle over --reps repeats (median, min, max), the cycles, and the covered fraction of BB.  A hierarchy of hundreds of boxes is
+made and stepped box by box on the host: the default --base of this leg, 32, keeps that to seconds.
 """
 import argparse
 import json
@@ -47,17 +56,108 @@ def make_run(n, numerics, max_solve_level=None):
     return a
 
 
+def _stats(v):
+    return dict(median=_median(v), min=min(v), max=max(v))
+
+
+def clustered_leg(a):
+    """the masked solve of every refined level of several boxes beside the one-box solve of its bounding box"""
+    import math
+    import torch
+    import castro_amd
+    from castro_amd import _lib
+    amr, err = None, None
+    for bf in (8, 16, 32):
+        try:
+            amr = castro_amd.CastroAmr((a.base,) * 3, params=_lib.default_params(**PARAMS), do_grav=True, max_level=2, cluster=True,
+                                       refine=[("density", "gradient", 1.e8)], max_grid_size=32, blocking_factor=bf, regrid_int=2,
+                                       make_hydro=lambda: castro_amd.HipHydro(0, numerics=a.numerics),
+                                       gravity=castro_amd.PoissonGravity(center=CENTER), **GEOM)
+            amr.initData("dust_collapse", **dict(PROB, r_0=a.r0))
+            break
+        except (ValueError, NotImplementedError) as e:      # the bottom limit of a union, a box on the domain boundary
+            amr, err = None, "blocking_factor %d: %s" % (bf, e)
+    if amr is None:
+        sys.exit("no hierarchy the level solves accept: " + err)
+    print("hierarchy: blocking_factor %d, boxes per level %s" % (bf, [len(lev.boxes) for lev in amr.lev]), file=sys.stderr, flush=True)
+    for _ in range(2):
+        amr.step()
+    torch.cuda.synchronize()
+    print("two coarse steps made", file=sys.stderr, flush=True)
+    g, fourpiG = amr.gravity, 4.0 * math.pi * amr.gravity.Gconst
+    levels = []
+    for l in range(1, len(amr.lev)):
+        lev, ent, par = amr.lev[l], g._entry(l), g._entry(l - 1)
+        if ent["boxes"] is None:
+            levels.append(dict(level=l, boxes=1, note="one box: nothing to compare"))
+            continue
+        h, bb, pbx = lev.hydro, ent["bb"], ent["phibox"]
+        n = tuple(bb[1][d] - bb[0][d] + 1 for d in range(3))
+        covered = sum(b.n[0] * b.n[1] * b.n[2] for b in lev.mine)
+        plan = g.plan_level(l)
+        rhos = [(b.S_new_b, b.gbox) for b in lev.mine]
+        h.poisson_boxes_cf_bc(plan, ent["faces"], ent["facebox"], par["phi_old"], par["phibox"], par["phi_new"], par["phibox"], 1.0)
+        # the bounding box as ONE box: its density gathered from the boxes, the ambient value elsewhere
+        geom = _lib.Geom.from_buffer_copy(lev.geom)
+        for d in range(3):
+            geom.domlo[d], geom.domhi[d], geom.lo_bc[d], geom.hi_bc[d] = bb[0][d], bb[1][d], 2, 2
+        oplan = h.poisson_plan_create(geom)
+        U = h.alloc(1, *bb)
+        U.fill_(PROB["rho_ambient"])
+        sl = lambda box, lo, hi: tuple(slice(lo[d] - box[0][d], hi[d] - box[0][d] + 1) for d in (2, 1, 0))
+        for b in lev.mine:
+            U[0][sl(bb, b.lo, b.hi)] = b.S_new_b[_lib.URHO][sl(b.gbox, b.lo, b.hi)]
+        phi, one = h.alloc(1, *pbx), h.alloc(1, *pbx)
+        t = {"masked": [], "one_box": []}
+        cyc = {}
+        for rep in range(a.reps + 1):                            # the first repeat warms up and is dropped
+            for k in ("masked", "one_box"):                      # alternating: a drift of the machine meets both alike
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                if k == "masked":
+                    phi.zero_()
+                    out = h.poisson_boxes_solve(plan, phi, pbx, ent["faces"], ent["facebox"], rhos, _lib.URHO, fourpiG,
+                                                g.reltol, g.abstol, g.maxiter)
+                else:
+                    one.zero_()
+                    h.poisson_cf_bc(one, pbx, bb[0], bb[1], par["phi_old"], par["phibox"], par["phi_new"], par["phibox"], 1.0)
+                    out = h.poisson_solve(oplan, one, pbx, U, bb, 0, fourpiG, g.reltol, g.abstol, g.maxiter)
+                torch.cuda.synchronize()
+                if rep > 0:
+                    t[k].append((time.perf_counter() - t0) * 1e3)
+                cyc[k] = (out[0], bool(out[1]))
+        h.poisson_plan_destroy(oplan)
+        levels.append(dict(level=l, boxes=len(lev.mine), bounding_box=bb, zones_of_bb=n[0] * n[1] * n[2], covered_fraction=covered / float(n[0] * n[1] * n[2]),
+                           multigrid_levels=dict(masked=len(_lib.poisson_boxes_levels(ent["boxes"])), one_box=len(_lib.poisson_level_extents(n))),
+                           cycles={k: v[0] for k, v in cyc.items()}, converged={k: v[1] for k, v in cyc.items()},
+                           ms_per_solve={k: _stats(v) for k, v in t.items()},
+                           ms_per_vcycle={k: _stats([x / max(cyc[k][0], 1) for x in v]) for k, v in t.items()}))
+    out = dict(leg="clustered", base=a.base, numerics=a.numerics, r0=a.r0, blocking_factor=bf, max_grid_size=32, reps=a.reps,
+               boxes_per_level=[len(lev.boxes) for lev in amr.lev], levels=levels)
+    print(json.dumps(out), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+    amr.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--base", type=int, default=64)
+    ap.add_argument("--clustered", action="store_true")
+    ap.add_argument("--r0", type=float, default=3.0e8)
+    ap.add_argument("--base", type=int, default=None, help="zones per direction of level 0: 64, with --clustered 32")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--numerics", default="contract")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.base is None:
+        a.base = 32 if a.clustered else 64
     import torch
     if not torch.cuda.is_available():
         sys.exit("tools/poisson_amr_cost.py measures on a GPU; there is none")
+    if a.clustered:
+        return clustered_leg(a)
     runs = {"level_solves": make_run(a.base, a.numerics), "max_solve_level_0": make_run(a.base, a.numerics, 0)}
     for r in runs.values():
         r.step()
