@@ -1162,37 +1162,47 @@ int castro_amd_poisson_solve(castro_amd_ctx* c, castro_amd_poisson_plan* plan, c
                                 final_norm, h_history, (hipStream_t)stream, &c->prof);
 }
 
-int castro_amd_poisson_level_op(castro_amd_ctx* c, castro_amd_poisson_plan* plan, int op, int level, int colour,
-                                const castro_amd_fab* a, const castro_amd_fab* b, const castro_amd_fab* f3, double* d_out, void* stream)
+// one pass on the level `level` (inside the plan) of a plan of either kind; e: the edge of that level, cflags: the coverage of the
+// next coarser level of a union, or nullptr
+static int mg_level_op(castro_amd_ctx* c, PoissonPlan* P, int op, int level, int colour, const castro_amd_fab* a, const castro_amd_fab* b,
+                       const castro_amd_fab* f3, const MgEdge& e, const unsigned char* cflags, double* d_out, void* stream)
 {
-    if (!c || !plan) return CASTRO_AMD_ERR_ARG;
-    PoissonPlan* P = reinterpret_cast<PoissonPlan*>(plan);
     const int nl = (int)P->lev.size();
-    if (level < 0 || level >= nl || !P->flags.empty()) return CASTRO_AMD_ERR_ARG;
     const MgLevel& L = P->lev[(size_t)level];
     hipStream_t s = (hipStream_t)stream;
     hipSetDevice(c->device);
     switch (op) {
     case CASTRO_AMD_MG_SMOOTH:
         if ((colour != 0 && colour != 1) || !mg_fab_ok(a, L, 1) || !mg_fab_ok(b, L, 0)) return CASTRO_AMD_ERR_ARG;
-        return launch_mg_smooth(to_dfab(a), to_dfab(b), L, colour, s, &c->prof);
+        return launch_mg_smooth(to_dfab(a), to_dfab(b), L, e, colour, s, &c->prof);
     case CASTRO_AMD_MG_RESIDUAL:
         if (!mg_fab_ok(a, L, 1) || !mg_fab_ok(b, L, 0) || !mg_fab_ok(f3, L, 0)) return CASTRO_AMD_ERR_ARG;
-        return launch_mg_residual(to_dfab(a), to_dfab(b), to_dfab(f3), L, s, &c->prof);
+        return launch_mg_residual(to_dfab(a), to_dfab(b), to_dfab(f3), L, e, s, &c->prof);
     case CASTRO_AMD_MG_RESTRICT:
         if (level + 1 >= nl) return CASTRO_AMD_ERR_ARG;
         if (!mg_fab_ok(a, L, 0) || !mg_fab_ok(b, P->lev[(size_t)level + 1], 0) || !mg_fab_ok(f3, P->lev[(size_t)level + 1], 0)) return CASTRO_AMD_ERR_ARG;
-        return launch_mg_restrict(to_dfab(a), L, to_dfab(b), to_dfab(f3), P->lev[(size_t)level + 1], s, &c->prof);
+        return launch_mg_restrict(to_dfab(a), L, to_dfab(b), to_dfab(f3), P->lev[(size_t)level + 1], cflags, s, &c->prof);
     case CASTRO_AMD_MG_PROLONG:
         if (level + 1 >= nl) return CASTRO_AMD_ERR_ARG;
         if (!mg_fab_ok(a, P->lev[(size_t)level + 1], 0) || !mg_fab_ok(b, L, 0)) return CASTRO_AMD_ERR_ARG;
-        return launch_mg_prolong(to_dfab(a), P->lev[(size_t)level + 1], to_dfab(b), L, s, &c->prof);
+        return launch_mg_prolong(to_dfab(a), P->lev[(size_t)level + 1], to_dfab(b), L, e.flags, s, &c->prof);
     case CASTRO_AMD_MG_NORM:
         if (!mg_fab_ok(a, L, 0) || !d_out) return CASTRO_AMD_ERR_ARG;
-        return launch_mg_norm(to_dfab(a), L, P->norm_ws, d_out, s, &c->prof);
+        return launch_mg_norm(to_dfab(a), L, e.flags, P->norm_ws, d_out, s, &c->prof);
     default:
         return CASTRO_AMD_ERR_ARG;
     }
+}
+
+int castro_amd_poisson_level_op(castro_amd_ctx* c, castro_amd_poisson_plan* plan, int op, int level, int colour,
+                                const castro_amd_fab* a, const castro_amd_fab* b, const castro_amd_fab* f3, double* d_out, void* stream)
+{
+    if (!c || !plan) return CASTRO_AMD_ERR_ARG;
+    PoissonPlan* P = reinterpret_cast<PoissonPlan*>(plan);
+    if (level < 0 || level >= (int)P->lev.size() || !P->flags.empty()) return CASTRO_AMD_ERR_ARG;
+    MgEdge e;
+    std::memset(&e, 0, sizeof(e));
+    return mg_level_op(c, P, op, level, colour, a, b, f3, e, nullptr, d_out, stream);
 }
 
 int castro_amd_grad_phi_to_grav_fab(castro_amd_ctx* c, const castro_amd_fab* phi_fab, const castro_amd_fab* grav_fab,
@@ -1234,7 +1244,7 @@ int castro_amd_poisson_cf_bc_fab(castro_amd_ctx* c, const castro_amd_fab* phi_fi
                             &c->prof);
 }
 
-// ---- Poisson gravity on a refined level of several boxes: one array over their bounding box (poisson_kernels.hip, k_mgb_*) ------
+// ---- Poisson gravity on a refined level of several boxes: one array over their bounding box (poisson_kernels.hip, MgBoxes) -----
 int castro_amd_poisson_boxes_plan_create(castro_amd_ctx* c, const double dx[3], int nboxes, const int* lo, const int* hi,
                                          castro_amd_poisson_plan** plan)
 {
@@ -1332,38 +1342,15 @@ int castro_amd_poisson_boxes_level_op(castro_amd_ctx* c, castro_amd_poisson_plan
     if (!c || !P) return CASTRO_AMD_ERR_ARG;
     const int nl = (int)P->lev.size();
     if (level < 0 || level >= nl) return CASTRO_AMD_ERR_ARG;
-    const MgLevel& L = P->lev[(size_t)level];
-    const unsigned char* fl = P->flags[(size_t)level];
     // face values belong to level 0 alone; without them (and on every coarser level) a flagged face holds 0.0
-    DFab X;
-    std::memset(&X, 0, sizeof(X));
+    MgEdge e;
+    std::memset(&e, 0, sizeof(e));
+    e.flags = P->flags[(size_t)level];
     if (faces_fab) {
-        if (level != 0 || !mgb_faces_ok(faces_fab, L)) return CASTRO_AMD_ERR_ARG;
-        X = to_dfab(faces_fab);
+        if (level != 0 || !mgb_faces_ok(faces_fab, P->lev[0])) return CASTRO_AMD_ERR_ARG;
+        e.X = to_dfab(faces_fab);
     }
-    hipStream_t s = (hipStream_t)stream;
-    hipSetDevice(c->device);
-    switch (op) {
-    case CASTRO_AMD_MG_SMOOTH:
-        if ((colour != 0 && colour != 1) || !mg_fab_ok(a, L, 1) || !mg_fab_ok(b, L, 0)) return CASTRO_AMD_ERR_ARG;
-        return launch_mgb_smooth(to_dfab(a), to_dfab(b), L, fl, X, colour, s, &c->prof);
-    case CASTRO_AMD_MG_RESIDUAL:
-        if (!mg_fab_ok(a, L, 1) || !mg_fab_ok(b, L, 0) || !mg_fab_ok(f3, L, 0)) return CASTRO_AMD_ERR_ARG;
-        return launch_mgb_residual(to_dfab(a), to_dfab(b), to_dfab(f3), L, fl, X, s, &c->prof);
-    case CASTRO_AMD_MG_RESTRICT:
-        if (level + 1 >= nl) return CASTRO_AMD_ERR_ARG;
-        if (!mg_fab_ok(a, L, 0) || !mg_fab_ok(b, P->lev[(size_t)level + 1], 0) || !mg_fab_ok(f3, P->lev[(size_t)level + 1], 0)) return CASTRO_AMD_ERR_ARG;
-        return launch_mgb_restrict(to_dfab(a), L, to_dfab(b), to_dfab(f3), P->lev[(size_t)level + 1], P->flags[(size_t)level + 1], s, &c->prof);
-    case CASTRO_AMD_MG_PROLONG:
-        if (level + 1 >= nl) return CASTRO_AMD_ERR_ARG;
-        if (!mg_fab_ok(a, P->lev[(size_t)level + 1], 0) || !mg_fab_ok(b, L, 0)) return CASTRO_AMD_ERR_ARG;
-        return launch_mgb_prolong(to_dfab(a), P->lev[(size_t)level + 1], to_dfab(b), L, fl, s, &c->prof);
-    case CASTRO_AMD_MG_NORM:
-        if (!mg_fab_ok(a, L, 0) || !d_out) return CASTRO_AMD_ERR_ARG;
-        return launch_mgb_norm(to_dfab(a), L, fl, P->norm_ws, d_out, s, &c->prof);
-    default:
-        return CASTRO_AMD_ERR_ARG;
-    }
+    return mg_level_op(c, P, op, level, colour, a, b, f3, e, level + 1 < nl ? P->flags[(size_t)level + 1] : nullptr, d_out, stream);
 }
 
 // a gravity FAB of the _gfab source calls: 3 components, one ghost zone around [lo, hi] where the energy term reads neighbours

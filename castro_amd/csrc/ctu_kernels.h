@@ -257,18 +257,11 @@ constexpr unsigned mgf_face(int d, int side) { return 2u << (2 * d + side); }
 struct MgBoxDev { DFab F; int lo[3], n[3]; long start; };
 int poisson_boxes_levels(int nbox, const int* lo, const int* hi, const double dx[3], std::vector<MgLevel>& lev);
 int poisson_boxes_plan_make(int nbox, const int* lo, const int* hi, const double dx[3], PoissonPlan** out);
-// X: the face values of level 0 (3 components over the bounding box with its high corner grown by one: component d at the
-// zone (i, j, k) is the low d-face of that zone); X.p == nullptr: every face value is 0.0 (the coarser levels)
-int launch_mgb_smooth(const DFab& P, const DFab& B, const MgLevel& L, const unsigned char* flags, const DFab& X, int colour,
-                      hipStream_t s, Profiler* prof);
-int launch_mgb_residual(const DFab& P, const DFab& B, const DFab& R, const MgLevel& L, const unsigned char* flags, const DFab& X,
-                        hipStream_t s, Profiler* prof);
-int launch_mgb_restrict(const DFab& RF, const MgLevel& LF, const DFab& BC, const DFab& PC, const MgLevel& LC,
-                        const unsigned char* cflags, hipStream_t s, Profiler* prof);
-int launch_mgb_prolong(const DFab& PC, const MgLevel& LC, const DFab& PF, const MgLevel& LF, const unsigned char* fflags,
-                       hipStream_t s, Profiler* prof);
-int launch_mgb_norm(const DFab& X, const MgLevel& L, const unsigned char* flags, double* ws, double* d_out, hipStream_t s,
-                    Profiler* prof);
+// The edge of a level, as the launchers of the passes take it.  flags == nullptr: the level is the one box of L, the values on
+// its faces are in the ghost zones of phi.  Otherwise the flags of a union of boxes and X, the face values of level 0 (3
+// components over the bounding box with its high corner grown by one: component d at the zone (i, j, k) is the low d-face of
+// that zone); X.p == nullptr: every face value is 0.0 (the coarser levels)
+struct MgEdge { const unsigned char* flags; DFab X; };
 // U: the state FAB of every box of the plan, in the plan's order
 int launch_poisson_boxes_solve(PoissonPlan* P, const DFab& phi, const DFab& X, const DFab* U, int comp, double fourpiG, double reltol,
                                double abstol, int maxiter, int* cycles, int* converged, double* final_norm, double* h_history,
@@ -278,11 +271,13 @@ int launch_phi_cf_boxes(PoissonPlan* P, const DFab& X, const DFab& O, const DFab
 int poisson_levels(const int n[3], const int lo[3], const double dx[3], std::vector<MgLevel>& lev);
 int poisson_plan_make(const int n[3], const int lo[3], const double dx[3], PoissonPlan** out);
 void poisson_plan_free(PoissonPlan* P);
-int launch_mg_smooth(const DFab& P, const DFab& B, const MgLevel& L, int colour, hipStream_t s, Profiler* prof);
-int launch_mg_residual(const DFab& P, const DFab& B, const DFab& R, const MgLevel& L, hipStream_t s, Profiler* prof);
-int launch_mg_restrict(const DFab& RF, const MgLevel& LF, const DFab& BC, const DFab& PC, const MgLevel& LC, hipStream_t s, Profiler* prof);
-int launch_mg_prolong(const DFab& PC, const MgLevel& LC, const DFab& PF, const MgLevel& LF, hipStream_t s, Profiler* prof);
-int launch_mg_norm(const DFab& X, const MgLevel& L, double* ws, double* d_out, hipStream_t s, Profiler* prof);
+int launch_mg_smooth(const DFab& P, const DFab& B, const MgLevel& L, const MgEdge& e, int colour, hipStream_t s, Profiler* prof);
+int launch_mg_residual(const DFab& P, const DFab& B, const DFab& R, const MgLevel& L, const MgEdge& e, hipStream_t s, Profiler* prof);
+int launch_mg_restrict(const DFab& RF, const MgLevel& LF, const DFab& BC, const DFab& PC, const MgLevel& LC, const unsigned char* cflags,
+                       hipStream_t s, Profiler* prof);
+int launch_mg_prolong(const DFab& PC, const MgLevel& LC, const DFab& PF, const MgLevel& LF, const unsigned char* fflags, hipStream_t s,
+                      Profiler* prof);
+int launch_mg_norm(const DFab& X, const MgLevel& L, const unsigned char* flags, double* ws, double* d_out, hipStream_t s, Profiler* prof);
 // h_history (or nullptr): ||b||, max b, the norm of the starting residual, then the norm after every cycle (maxiter + 3 doubles)
 int launch_poisson_solve(PoissonPlan* P, const DFab& phi, const DFab& U, int comp, double fourpiG, double reltol, double abstol,
                          int maxiter, int* cycles, int* converged, double* final_norm, double* h_history, hipStream_t s, Profiler* prof);

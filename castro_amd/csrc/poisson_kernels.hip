@@ -1,16 +1,18 @@
-// poisson_kernels.hip -- gravity.gravity_type = "PoissonGrav" on a single level, 3-D Cartesian, Dirichlet on all six faces:
-//   k_mg_rhs                              b = (4 pi G) * rho
+// poisson_kernels.hip -- gravity.gravity_type = "PoissonGrav" on a level, 3-D Cartesian, Dirichlet on every edge of the level.
+// ONE set of multigrid passes, each a template over what it has to know about the edge of the level, instantiated twice:
+// MgOneBox (the level is one box; profiler names k_mg_*, k_grad_phi) and MgBoxes (a refined level of SEVERAL boxes: one array
+// over their bounding box, a byte of coverage flags per zone and an array of face values; profiler names k_mgb_*)
+//   k_mg_rhs, k_mgb_rhs                   b = (4 pi G) * rho, from one FAB / from the boxes' own FABs
 //   k_mg_smooth, k_mg_bottom              red-black Gauss-Seidel on one level; the bottom solve is the same sweep, all of them
 //                                         in one launch of one workgroup
 //   k_mg_residual, k_mg_restrict, k_mg_prolong, k_mg_norm_partial + k_mg_norm_final
 //                                         the other four passes of the V-cycle
-//   k_grad_phi                            g = -grad(phi) on the valid zones (Gravity.cpp:874-878 over MLMG's getGradSolution)
+//   k_grad_phi, k_mgb_grad                g = -grad(phi) on the valid zones (Gravity.cpp:874-878 over MLMG's getGradSolution)
 //   k_mp_partial + k_mp_final             the multipole moments of Gravity::fill_multipole_BCs (Gravity.cpp:1742-2032, multipole_add
 //                                         of Gravity_util.H) with boundary_only = 1: every zone falls in the last radial bin
 //   k_mp_phi_bc                           the boundary potential (Gravity.cpp:2066-2216) on the zones of a FAB outside the domain
-//   k_phi_cf_bc                           the coarse-fine boundary potential of a refined level's own solve (the end of the file)
-//   k_mgb_*, k_phi_cf_boxes               the same passes, gradient and boundary values for a refined level of SEVERAL boxes: one
-//                                         array over their bounding box and a byte of coverage flags per zone
+//   k_phi_cf_bc, k_phi_cf_boxes           the coarse-fine boundary potential of a refined level's own solve (the end of the file),
+//                                         into the ghost zones of phi / into the face array of a union of boxes
 // The multigrid is AMReX's [3P]: its arithmetic is not in the reference tree and is not pinned.  It is
 // written so that a restatement with the same order of operations reproduces the `exact` build bit for bit: the header comment
 // of every pass gives that order, and the passes hold no transcendental.  The `contract` build fuses these passes' multiply-adds.
@@ -54,97 +56,171 @@ __device__ __forceinline__ bool mg_colour_zone(long q, const MgLevel& L, int col
     return ii < L.n[0];
 }
 
+// zone q of the box of L, x fastest, relative to its low corner
+__device__ __forceinline__ void mg_zone(long q, const MgLevel& L, int& ii, int& jj, int& kk)
+{
+    ii = (int)(q % L.n[0]);
+    const long rr = q / L.n[0];
+    jj = (int)(rr % L.n[1]);
+    kk = (int)(rr / L.n[1]);
+}
+
+__device__ __forceinline__ long mg_flag_at(const MgLevel& L, int ii, int jj, int kk)
+{
+    return (long)ii + (long)L.n[0] * ((long)jj + (long)L.n[1] * kk);
+}
+
+// the value on the (d, side) face of the zone (i, j, k): the low d-face of the zone (i, j, k) + side * e_d
+__device__ __forceinline__ double mgb_face_value(const DFab& X, int d, int side, int i, int j, int k)
+{
+    if (!X.p) return 0.0;
+    return X.p[mg_at(X, i + (d == 0 ? side : 0), j + (d == 1 ? side : 0), k + (d == 2 ? side : 0)) + X.sn * d];
+}
+
+// ---- the edge of a level ------------------------------------------------------------------------------------------------------
+// A pass asks two questions of the level it runs on: is this zone part of the level, and is this face of the zone an edge of the
+// level -- and if so, which value sits ON it.  The two sets of answers:
+//   MgOneBox  the level is the box L.  Every zone is part of it, a face is an edge where the zone is the first or the last of its
+//             row, and the value on it is the neighbour the pass has loaded: the ghost zone of phi, which holds phi ON the face
+//             (level 0) or 0 (the coarser levels, whose ghost zones stay zero).  All of it is known when the pass is compiled
+//   MgBoxes   the level is a union of boxes inside L, the bounding box >> m; colours are relative to its low corner.  A byte of
+//             flags per zone of L, made on the host (MGF_*), says "covered" and "the neighbour across this face is not covered",
+//             and the value ON such a face is read from the face array X of level 0 -- an uncovered zone at a concave corner of
+//             the union is the neighbour of two covered zones across two faces with two values, so it cannot hold them -- or is
+//             0.0 on the coarser levels (X.p == nullptr).  Zones that are not covered are never written
+// zone(q) loads what the other queries are asked with (q: mg_flag_at).  The passes that ask the first question only take the base
+// types.  As kernel arguments the types are laid out as (L) and (L, flags, X).
+struct MgWhole {
+    MgLevel L;
+    __device__ unsigned zone(long) const { return 0u; }
+    static __device__ bool covered(unsigned) { return true; }
+};
+struct MgMasked {
+    MgLevel L;
+    const unsigned char* __restrict__ flags;
+    __device__ unsigned zone(long q) const { return flags[q]; }
+    static __device__ bool covered(unsigned fl) { return fl & MGF_COVERED; }
+};
+struct MgOneBox : MgWhole {
+    static __device__ bool any_edge(unsigned) { return true; }
+    __device__ bool edge(unsigned, const int rel[3], int d, int side) const { return rel[d] == (side ? L.n[d] - 1 : 0); }
+    __device__ double on_edge(int, int, int, int, int, double neighbour) const { return neighbour; }
+};
+struct MgBoxes : MgMasked {
+    DFab X;
+    static __device__ bool any_edge(unsigned fl) { return fl & ~MGF_COVERED; }
+    __device__ bool edge(unsigned fl, const int[3], int d, int side) const { return fl & mgf_face(d, side); }
+    __device__ double on_edge(int d, int side, int i, int j, int k, double) const { return mgb_face_value(X, d, side, i, j, k); }
+};
+
 // The smoother, one zone.  With p the zone's value, the six neighbours xm, xp, ym, yp, zm, zp and the right-hand side b:
-//   a neighbour beyond a domain face is replaced by 2.0 * (the ghost value), the ghost holding phi ON the face (level 0) or 0
-//   (coarser levels); the - p of the linear ghost 2 phi_face - p goes to the diagonal:
+//   a neighbour across an edge of the level is replaced by 2.0 * f, f the value ON the face; the - p of the linear ghost
+//   2 f - p goes to the diagonal:
 //   dg = cdiag; if (low x face) dg = dg + cx; if (high x face) dg = dg + cx; then y, then z (cdiag = 2.0 * ((cx + cy) + cz),
 //   cx = 1.0 / (hx * hx), ... formed on the host)
 //   p = (((cx * (xm + xp) + cy * (ym + yp)) + cz * (zm + zp)) - b) / dg
-__device__ __forceinline__ double mg_relax(const DFab& P, const DFab& B, const MgLevel& L, int ii, int jj, int kk)
+template <class E>
+__device__ __forceinline__ double mg_relax(const DFab& P, const DFab& B, const E& e, unsigned fl, int ii, int jj, int kk)
 {
-    const long c = mg_at(P, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk);
-    const double* p = P.p + c;
-    const bool xl = ii == 0, xh = ii == L.n[0] - 1, yl = jj == 0, yh = jj == L.n[1] - 1, zl = kk == 0, zh = kk == L.n[2] - 1;
+    const MgLevel& L = e.L;
+    const int i = L.lo[0] + ii, j = L.lo[1] + jj, k = L.lo[2] + kk, rel[3] = { ii, jj, kk };
+    const double* p = P.p + mg_at(P, i, j, k);
     double xm = p[-1], xp = p[1], ym = p[-P.sy], yp = p[P.sy], zm = p[-P.sz], zp = p[P.sz];
     double dg = L.cdiag;
-    if (xl) { xm = 2.0 * xm; dg = dg + L.cx; }
-    if (xh) { xp = 2.0 * xp; dg = dg + L.cx; }
-    if (yl) { ym = 2.0 * ym; dg = dg + L.cy; }
-    if (yh) { yp = 2.0 * yp; dg = dg + L.cy; }
-    if (zl) { zm = 2.0 * zm; dg = dg + L.cz; }
-    if (zh) { zp = 2.0 * zp; dg = dg + L.cz; }
-    const double b = B.p[mg_at(B, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk)];
+    if (E::any_edge(fl)) {
+        if (e.edge(fl, rel, 0, 0)) { xm = 2.0 * e.on_edge(0, 0, i, j, k, xm); dg = dg + L.cx; }
+        if (e.edge(fl, rel, 0, 1)) { xp = 2.0 * e.on_edge(0, 1, i, j, k, xp); dg = dg + L.cx; }
+        if (e.edge(fl, rel, 1, 0)) { ym = 2.0 * e.on_edge(1, 0, i, j, k, ym); dg = dg + L.cy; }
+        if (e.edge(fl, rel, 1, 1)) { yp = 2.0 * e.on_edge(1, 1, i, j, k, yp); dg = dg + L.cy; }
+        if (e.edge(fl, rel, 2, 0)) { zm = 2.0 * e.on_edge(2, 0, i, j, k, zm); dg = dg + L.cz; }
+        if (e.edge(fl, rel, 2, 1)) { zp = 2.0 * e.on_edge(2, 1, i, j, k, zp); dg = dg + L.cz; }
+    }
+    const double b = B.p[mg_at(B, i, j, k)];
     const double off = (L.cx * (xm + xp) + L.cy * (ym + yp)) + L.cz * (zm + zp);
     return (off - b) / dg;
 }
 
+// thread q of a sweep of one colour: its zone, where the level has one, is replaced by mg_relax of its neighbours
+template <class E>
+__device__ __forceinline__ void mg_sweep_zone(const DFab& P, const DFab& B, const E& e, long q, int colour)
+{
+    int ii, jj, kk;
+    if (!mg_colour_zone(q, e.L, colour, ii, jj, kk)) return;
+    const unsigned fl = e.zone(mg_flag_at(e.L, ii, jj, kk));
+    if (!E::covered(fl)) return;
+    const double v = mg_relax(P, B, e, fl, ii, jj, kk);
+    P.p[mg_at(P, e.L.lo[0] + ii, e.L.lo[1] + jj, e.L.lo[2] + kk)] = v;
+}
+
 // One sweep of one colour: every zone of that colour is replaced by mg_relax of its neighbours, which are all of the other
 // colour -- the order of the zones within the sweep does not matter
-__global__ void __launch_bounds__(MG_WG) k_mg_smooth(DFab P, DFab B, MgLevel L, int colour)
+template <class E>
+__global__ void __launch_bounds__(MG_WG) k_mg_smooth(DFab P, DFab B, E e, int colour)
 {
     const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
-    const int npair = (L.n[0] + 1) >> 1;
-    if (q >= (long)npair * L.n[1] * L.n[2]) return;
-    int ii, jj, kk;
-    if (!mg_colour_zone(q, L, colour, ii, jj, kk)) return;
-    const double v = mg_relax(P, B, L, ii, jj, kk);
-    P.p[mg_at(P, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk)] = v;
+    const int npair = (e.L.n[0] + 1) >> 1;
+    if (q >= (long)npair * e.L.n[1] * e.L.n[2]) return;
+    mg_sweep_zone(P, B, e, q, colour);
 }
 
 // The bottom solve: `sweeps` times colour 0, then colour 1, of k_mg_smooth's arithmetic by ONE workgroup (the coarsest level holds
-// at most CASTRO_AMD_POISSON_MAX_BOTTOM zones); a barrier separates the colours
-__global__ void __launch_bounds__(MG_BOTTOM_WG) k_mg_bottom(DFab P, DFab B, MgLevel L, int sweeps)
+// at most CASTRO_AMD_POISSON_MAX_BOTTOM zones of its box); a barrier separates the colours
+template <class E>
+__global__ void __launch_bounds__(MG_BOTTOM_WG) k_mg_bottom(DFab P, DFab B, E e, int sweeps)
 {
-    const int npair = (L.n[0] + 1) >> 1;
-    const long nq = (long)npair * L.n[1] * L.n[2];
+    const int npair = (e.L.n[0] + 1) >> 1;
+    const long nq = (long)npair * e.L.n[1] * e.L.n[2];
     for (int s = 0; s < sweeps; ++s) {
         for (int colour = 0; colour < 2; ++colour) {
-            for (long q = threadIdx.x; q < nq; q += MG_BOTTOM_WG) {
-                int ii, jj, kk;
-                if (!mg_colour_zone(q, L, colour, ii, jj, kk)) continue;
-                const double v = mg_relax(P, B, L, ii, jj, kk);
-                P.p[mg_at(P, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk)] = v;
-            }
+            for (long q = threadIdx.x; q < nq; q += MG_BOTTOM_WG) mg_sweep_zone(P, B, e, q, colour);
             __syncthreads();
         }
     }
 }
 
-// The residual.  A neighbour beyond a domain face is the linear ghost 2.0 * (ghost value) - p;
+// The residual.  A neighbour across an edge of the level is the linear ghost 2.0 * f - p, f the value ON the face;
 //   lap = (cx * ((xm + xp) - 2.0 * p) + cy * ((ym + yp) - 2.0 * p)) + cz * ((zm + zp) - 2.0 * p);   r = b - lap
-__global__ void __launch_bounds__(MG_WG) k_mg_residual(DFab P, DFab B, DFab R, MgLevel L)
+template <class E>
+__global__ void __launch_bounds__(MG_WG) k_mg_residual(DFab P, DFab B, DFab R, E e)
 {
+    const MgLevel& L = e.L;
     const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
     if (q >= (long)L.n[0] * L.n[1] * L.n[2]) return;
-    const int ii = (int)(q % L.n[0]);
-    const long rr = q / L.n[0];
-    const int jj = (int)(rr % L.n[1]), kk = (int)(rr / L.n[1]);
-    const int i = L.lo[0] + ii, j = L.lo[1] + jj, k = L.lo[2] + kk;
+    const unsigned fl = e.zone(q);
+    if (!E::covered(fl)) return;
+    int rel[3];
+    mg_zone(q, L, rel[0], rel[1], rel[2]);
+    const int i = L.lo[0] + rel[0], j = L.lo[1] + rel[1], k = L.lo[2] + rel[2];
     const double* p = P.p + mg_at(P, i, j, k);
     const double pc = p[0];
     double xm = p[-1], xp = p[1], ym = p[-P.sy], yp = p[P.sy], zm = p[-P.sz], zp = p[P.sz];
-    if (ii == 0) xm = 2.0 * xm - pc;
-    if (ii == L.n[0] - 1) xp = 2.0 * xp - pc;
-    if (jj == 0) ym = 2.0 * ym - pc;
-    if (jj == L.n[1] - 1) yp = 2.0 * yp - pc;
-    if (kk == 0) zm = 2.0 * zm - pc;
-    if (kk == L.n[2] - 1) zp = 2.0 * zp - pc;
+    if (E::any_edge(fl)) {
+        if (e.edge(fl, rel, 0, 0)) xm = 2.0 * e.on_edge(0, 0, i, j, k, xm) - pc;
+        if (e.edge(fl, rel, 0, 1)) xp = 2.0 * e.on_edge(0, 1, i, j, k, xp) - pc;
+        if (e.edge(fl, rel, 1, 0)) ym = 2.0 * e.on_edge(1, 0, i, j, k, ym) - pc;
+        if (e.edge(fl, rel, 1, 1)) yp = 2.0 * e.on_edge(1, 1, i, j, k, yp) - pc;
+        if (e.edge(fl, rel, 2, 0)) zm = 2.0 * e.on_edge(2, 0, i, j, k, zm) - pc;
+        if (e.edge(fl, rel, 2, 1)) zp = 2.0 * e.on_edge(2, 1, i, j, k, zp) - pc;
+    }
     const double tp = 2.0 * pc;
     const double lap = (L.cx * ((xm + xp) - tp) + L.cy * ((ym + yp) - tp)) + L.cz * ((zm + zp) - tp);
     R.p[mg_at(R, i, j, k)] = B.p[mg_at(B, i, j, k)] - lap;
 }
 
-// The restriction onto the coarse zone (I, J, K) of the level L (the COARSE one; its children are 2 I + a, 2 J + b, 2 K + c
-// relative to the fine box, whose low corner is flo): with r_abc the children's residuals,
+// The restriction onto the coarse zone (I, J, K) of the level c (the COARSE one; its children are 2 I + a, 2 J + b, 2 K + c
+// relative to the fine box, whose low corner is flo, and the 8 children of a zone of the level are all zones of the fine
+// level): with r_abc the children's residuals,
 //   b_c = (((((((r000 + r100) + r010) + r110) + r001) + r101) + r011) + r111) * 0.125
 // and the coarse correction starts from zero: phi_c = 0
-__global__ void __launch_bounds__(MG_WG) k_mg_restrict(DFab RF, int flo0, int flo1, int flo2, DFab BC, DFab PC, MgLevel L)
+template <class C>
+__global__ void __launch_bounds__(MG_WG) k_mg_restrict(DFab RF, int flo0, int flo1, int flo2, DFab BC, DFab PC, C c)
 {
+    const MgLevel& L = c.L;
     const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
     if (q >= (long)L.n[0] * L.n[1] * L.n[2]) return;
-    const int ii = (int)(q % L.n[0]);
-    const long rr = q / L.n[0];
-    const int jj = (int)(rr % L.n[1]), kk = (int)(rr / L.n[1]);
+    if (!C::covered(c.zone(q))) return;
+    int ii, jj, kk;
+    mg_zone(q, L, ii, jj, kk);
     const double* r = RF.p + mg_at(RF, flo0 + 2 * ii, flo1 + 2 * jj, flo2 + 2 * kk);
     double s = r[0] + r[1];
     s = s + r[RF.sy];
@@ -158,20 +234,23 @@ __global__ void __launch_bounds__(MG_WG) k_mg_restrict(DFab RF, int flo0, int fl
     PC.p[mg_at(PC, i, j, k)] = 0.0;
 }
 
-// The prolongation onto the fine zone (ii, jj, kk) of the level L (the FINE one; clo: the low corner of the coarse box):
+// The prolongation onto the fine zone (ii, jj, kk) of the level f (the FINE one; clo: the low corner of the coarse box):
 //   phi_f = phi_f + phi_c(ii / 2, jj / 2, kk / 2)
-__global__ void __launch_bounds__(MG_WG) k_mg_prolong(DFab PC, int clo0, int clo1, int clo2, DFab PF, MgLevel L)
+template <class C>
+__global__ void __launch_bounds__(MG_WG) k_mg_prolong(DFab PC, int clo0, int clo1, int clo2, DFab PF, C f)
 {
+    const MgLevel& L = f.L;
     const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
     if (q >= (long)L.n[0] * L.n[1] * L.n[2]) return;
-    const int ii = (int)(q % L.n[0]);
-    const long rr = q / L.n[0];
-    const int jj = (int)(rr % L.n[1]), kk = (int)(rr / L.n[1]);
-    const long f = mg_at(PF, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk);
-    PF.p[f] = PF.p[f] + PC.p[mg_at(PC, clo0 + (ii >> 1), clo1 + (jj >> 1), clo2 + (kk >> 1))];
+    if (!C::covered(f.zone(q))) return;
+    int ii, jj, kk;
+    mg_zone(q, L, ii, jj, kk);
+    const long at = mg_at(PF, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk);
+    PF.p[at] = PF.p[at] + PC.p[mg_at(PC, clo0 + (ii >> 1), clo1 + (jj >> 1), clo2 + (kk >> 1))];
 }
 
-// b = fourpiG * rho on the zones of level 0
+// b = fourpiG * rho on the zones of level 0: of the box of L, or (the union) gathered from the boxes' own state FABs on the
+// zones of every box of the table
 __global__ void __launch_bounds__(MG_WG) k_mg_rhs(DFab U, int comp, DFab B, MgLevel L, double fourpiG)
 {
     const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
@@ -182,16 +261,65 @@ __global__ void __launch_bounds__(MG_WG) k_mg_rhs(DFab U, int comp, DFab B, MgLe
     B.p[mg_at(B, i, j, k)] = fourpiG * U.p[mg_at(U, i, j, k) + U.sn * comp];
 }
 
+// the box of the table that holds thread t, and the zone of it
+__device__ __forceinline__ bool mgb_box_zone(const MgBoxDev* __restrict__ tab, int nbox, long t, int& b, int& i, int& j, int& k)
+{
+    int b0 = 0, b1 = nbox - 1;
+    while (b0 < b1) {
+        const int mid = (b0 + b1 + 1) >> 1;
+        if (tab[mid].start <= t) b0 = mid; else b1 = mid - 1;
+    }
+    const long r = t - tab[b0].start;
+    const int n0 = tab[b0].n[0], n1 = tab[b0].n[1], n2 = tab[b0].n[2];
+    if (r >= (long)n0 * n1 * n2) return false;
+    const long rr = r / n0;
+    b = b0;
+    i = tab[b0].lo[0] + (int)(r % n0); j = tab[b0].lo[1] + (int)(rr % n1); k = tab[b0].lo[2] + (int)(rr / n1);
+    return true;
+}
+
+__global__ void __launch_bounds__(MG_WG) k_mgb_rhs(const MgBoxDev* __restrict__ tab, int nbox, long total, int comp, DFab B, double fourpiG)
+{
+    const long t = (long)blockIdx.x * MG_WG + threadIdx.x;
+    if (t >= total) return;
+    int b, i, j, k;
+    if (!mgb_box_zone(tab, nbox, t, b, i, j, k)) return;
+    const DFab U = tab[b].F;
+    B.p[mg_at(B, i, j, k)] = fourpiG * U.p[mg_at(U, i, j, k) + U.sn * comp];
+}
+
 // a maximum that keeps a NaN once it has seen one
 __device__ __forceinline__ double mg_max(double m, double v) { return (v > m || v != v) ? v : m; }
 
+// the maxima of a workgroup of WG threads: across each wave, through the LDS, across the waves; threads 0 and 1 write them
+template <int WG>
+__device__ __forceinline__ void mg_max_workgroup(double ma, double mx, double* out)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        ma = mg_max(ma, __shfl_down(ma, off, 64));
+        mx = mg_max(mx, __shfl_down(mx, off, 64));
+    }
+    __shared__ double sa[WG / 64][2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { sa[wave][0] = ma; sa[wave][1] = mx; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        double m = sa[0][threadIdx.x];
+        for (int w = 1; w < WG / 64; ++w) m = mg_max(m, sa[w][threadIdx.x]);
+        out[threadIdx.x] = m;
+    }
+}
+
 // The norm.  out[0] = max |x|, out[1] = max x over the zones of the level; a NaN anywhere gives NaN.  A maximum does not depend
 // on the order it is taken in
-__global__ void __launch_bounds__(MG_WG) k_mg_norm_partial(DFab X, MgLevel L, double* __restrict__ ws)
+template <class C>
+__global__ void __launch_bounds__(MG_WG) k_mg_norm_partial(DFab X, C c, double* __restrict__ ws)
 {
+    const MgLevel& L = c.L;
     const long total = (long)L.n[0] * L.n[1] * L.n[2];
     double ma = 0.0, mx = -HUGE_VAL;
     for (long q = (long)blockIdx.x * MG_WG + threadIdx.x; q < total; q += (long)gridDim.x * MG_WG) {
+        if (!C::covered(c.zone(q))) continue;
         const int i = L.lo[0] + (int)(q % L.n[0]);
         const long rr = q / L.n[0];
         const int j = L.lo[1] + (int)(rr % L.n[1]), k = L.lo[2] + (int)(rr / L.n[1]);
@@ -199,65 +327,59 @@ __global__ void __launch_bounds__(MG_WG) k_mg_norm_partial(DFab X, MgLevel L, do
         ma = mg_max(ma, fabs(v));
         mx = mg_max(mx, v);
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        ma = mg_max(ma, __shfl_down(ma, off, 64));
-        mx = mg_max(mx, __shfl_down(mx, off, 64));
-    }
-    __shared__ double sa[MG_WG / 64][2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { sa[wave][0] = ma; sa[wave][1] = mx; }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        double m = sa[0][threadIdx.x];
-        for (int w = 1; w < MG_WG / 64; ++w) m = mg_max(m, sa[w][threadIdx.x]);
-        ws[2 * (long)blockIdx.x + threadIdx.x] = m;
-    }
+    mg_max_workgroup<MG_WG>(ma, mx, ws + 2 * (long)blockIdx.x);
 }
 
 __global__ void __launch_bounds__(MG_NORM_MAX_WG) k_mg_norm_final(const double* __restrict__ ws, int nrows, double* __restrict__ out)
 {
     double ma = 0.0, mx = -HUGE_VAL;
     if ((int)threadIdx.x < nrows) { ma = ws[2 * threadIdx.x]; mx = ws[2 * threadIdx.x + 1]; }
-    for (int off = 32; off > 0; off >>= 1) {
-        ma = mg_max(ma, __shfl_down(ma, off, 64));
-        mx = mg_max(mx, __shfl_down(mx, off, 64));
-    }
-    __shared__ double sa[MG_NORM_MAX_WG / 64][2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { sa[wave][0] = ma; sa[wave][1] = mx; }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        double m = sa[0][threadIdx.x];
-        for (int w = 1; w < MG_NORM_MAX_WG / 64; ++w) m = mg_max(m, sa[w][threadIdx.x]);
-        out[threadIdx.x] = m;
-    }
+    mg_max_workgroup<MG_NORM_MAX_WG>(ma, mx, out);
 }
 
-// Gravity from phi on the zones of level 0 (one ghost zone of phi holds the face values): face gradients
-//   gl = (p - xm) / hx, gh = (xp - p) / hx, at a domain face gl = (2.0 * (p - xm)) / hx, gh = (2.0 * (xp - p)) / hx (the linear ghost);
+// Gravity from phi on the zone (i, j, k) of level 0: face gradients
+//   gl = (p - xm) / hx, gh = (xp - p) / hx, across an edge of the level gl = (2.0 * (p - f)) / hx, gh = (2.0 * (f - p)) / hx (the
+//   linear ghost; f the value ON the face: one ghost zone of phi holds it, or the face array); a neighbour in a sibling box of a
+//   union is an ordinary neighbour;
 //   g_x = -(0.5 * (gl + gh)), and the same in y and z
-__global__ void __launch_bounds__(MG_WG) k_grad_phi(DFab P, DFab G, MgLevel L, double hx, double hy, double hz)
+template <class E>
+__device__ __forceinline__ void mg_grad_zone(const DFab& P, const DFab& G, const E& e, int i, int j, int k, double hx, double hy, double hz)
 {
-    const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
-    if (q >= (long)L.n[0] * L.n[1] * L.n[2]) return;
-    const int ii = (int)(q % L.n[0]);
-    const long rr = q / L.n[0];
-    const int jj = (int)(rr % L.n[1]), kk = (int)(rr / L.n[1]);
-    const int i = L.lo[0] + ii, j = L.lo[1] + jj, k = L.lo[2] + kk;
+    const int rel[3] = { i - e.L.lo[0], j - e.L.lo[1], k - e.L.lo[2] };
+    const unsigned fl = e.zone(mg_flag_at(e.L, rel[0], rel[1], rel[2]));
     const double* p = P.p + mg_at(P, i, j, k);
     const double pc = p[0];
-    double dl[3] = { pc - p[-1], pc - p[-P.sy], pc - p[-P.sz] };
-    double dh[3] = { p[1] - pc, p[P.sy] - pc, p[P.sz] - pc };
-    const int rel[3] = { ii, jj, kk };
+    const double lo[3] = { p[-1], p[-P.sy], p[-P.sz] }, hi[3] = { p[1], p[P.sy], p[P.sz] };
     const double h[3] = { hx, hy, hz };
     const long g = mg_at(G, i, j, k);
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
-        if (rel[d] == 0) dl[d] = 2.0 * dl[d];
-        if (rel[d] == L.n[d] - 1) dh[d] = 2.0 * dh[d];
-        const double gl = dl[d] / h[d], gh = dh[d] / h[d];
+        double dl = pc - lo[d], dh = hi[d] - pc;
+        if (e.edge(fl, rel, d, 0)) dl = 2.0 * (pc - e.on_edge(d, 0, i, j, k, lo[d]));
+        if (e.edge(fl, rel, d, 1)) dh = 2.0 * (e.on_edge(d, 1, i, j, k, hi[d]) - pc);
+        const double gl = dl / h[d], gh = dh / h[d];
         G.p[g + G.sn * d] = -(0.5 * (gl + gh));
     }
+}
+
+// on the zones of the box of L, and on the zones of every box of the table, into that box's own FAB
+__global__ void __launch_bounds__(MG_WG) k_grad_phi(DFab P, DFab G, MgLevel L, double hx, double hy, double hz)
+{
+    const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
+    if (q >= (long)L.n[0] * L.n[1] * L.n[2]) return;
+    int ii, jj, kk;
+    mg_zone(q, L, ii, jj, kk);
+    mg_grad_zone(P, G, MgOneBox{ { L } }, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk, hx, hy, hz);
+}
+
+__global__ void __launch_bounds__(MG_WG) k_mgb_grad(const MgBoxDev* __restrict__ tab, int nbox, long total, DFab P, MgBoxes e,
+                                                   double hx, double hy, double hz)
+{
+    const long t = (long)blockIdx.x * MG_WG + threadIdx.x;
+    if (t >= total) return;
+    int b, i, j, k;
+    if (!mgb_box_zone(tab, nbox, t, b, i, j, k)) return;
+    mg_grad_zone(P, tab[b].F, e, i, j, k, hx, hy, hz);
 }
 
 // ---- the plan and the V-cycle -------------------------------------------------------------------------------------------------
@@ -265,27 +387,37 @@ static unsigned mg_blocks(long n) { return (unsigned)((n + MG_WG - 1) / MG_WG); 
 static long mg_zones(const MgLevel& L) { return (long)L.n[0] * L.n[1] * L.n[2]; }
 static long mg_pairs(const MgLevel& L) { return (long)((L.n[0] + 1) >> 1) * L.n[1] * L.n[2]; }
 
-int poisson_levels(const int n[3], const int lo[3], const double dx[3], std::vector<MgLevel>& lev)
+// The levels below the box L (n and lo set) of zones dx: coarsened while the extents are even with n / 2 >= 2, there are fewer
+// than MG_MAX_LEVELS levels and -- a union of nbox boxes (lo, hi: 3 ints per box; nbox = 0: L is the level) -- every box's lo
+// and hi + 1 are divisible by 2^(m+1): the 8 children of a coarse zone are then all covered or all not
+static int mg_coarsen(MgLevel L, const double dx[3], int nbox, const int* lo, const int* hi, std::vector<MgLevel>& lev)
 {
-    lev.clear();
-    MgLevel L;
-    std::memset(&L, 0, sizeof(L));
-    double h[3];
-    for (int d = 0; d < 3; ++d) {
-        if (n[d] < 1 || !(dx[d] > 0.0)) return CASTRO_AMD_ERR_ARG;
-        L.n[d] = n[d]; L.lo[d] = lo[d]; h[d] = dx[d];
-    }
+    double h[3] = { dx[0], dx[1], dx[2] };
     for (;;) {
         L.cx = 1.0 / (h[0] * h[0]); L.cy = 1.0 / (h[1] * h[1]); L.cz = 1.0 / (h[2] * h[2]);
         L.cdiag = 2.0 * ((L.cx + L.cy) + L.cz);
         lev.push_back(L);
         bool more = (int)lev.size() < MG_MAX_LEVELS;
         for (int d = 0; d < 3; ++d) more = more && L.n[d] % 2 == 0 && L.n[d] / 2 >= 2;
+        const int m1 = (1 << (int)lev.size()) - 1;
+        for (int q = 0; q < 3 * nbox && more; ++q) more = (lo[q] & m1) == 0 && ((hi[q] + 1) & m1) == 0;
         if (!more) break;
         for (int d = 0; d < 3; ++d) { L.n[d] /= 2; L.lo[d] = L.lo[d] >> 1; h[d] = 2.0 * h[d]; }
     }
     if (mg_zones(lev.back()) > CASTRO_AMD_POISSON_MAX_BOTTOM) return CASTRO_AMD_ERR_UNSUPPORTED;
     return 0;
+}
+
+int poisson_levels(const int n[3], const int lo[3], const double dx[3], std::vector<MgLevel>& lev)
+{
+    lev.clear();
+    MgLevel L;
+    std::memset(&L, 0, sizeof(L));
+    for (int d = 0; d < 3; ++d) {
+        if (n[d] < 1 || !(dx[d] > 0.0)) return CASTRO_AMD_ERR_ARG;
+        L.n[d] = n[d]; L.lo[d] = lo[d];
+    }
+    return mg_coarsen(L, dx, 0, nullptr, nullptr, lev);
 }
 
 void poisson_plan_free(PoissonPlan* P)
@@ -340,84 +472,100 @@ int poisson_plan_make(const int n[3], const int lo[3], const double dx[3], Poiss
     return 0;
 }
 
-static int mg_check(hipStream_t) { return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP; }
-
-int launch_mg_smooth(const DFab& P, const DFab& B, const MgLevel& L, int colour, hipStream_t s, Profiler* prof)
+// one launch under its profiler name
+template <class... KA, class... A>
+static int mg_launch(Profiler* prof, const char* name, void (*kernel)(KA...), unsigned nblocks, int wg, hipStream_t s, const A&... a)
 {
-    prof_begin(prof, "k_mg_smooth", s);
-    hipLaunchKernelGGL(k_mg_smooth, dim3(mg_blocks(mg_pairs(L))), dim3(MG_WG), 0, s, P, B, L, colour);
+    prof_begin(prof, name, s);
+    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(wg), 0, s, a...);
     prof_end(prof, s);
-    return mg_check(s);
+    return hipGetLastError() == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
 }
 
-int launch_mg_residual(const DFab& P, const DFab& B, const DFab& R, const MgLevel& L, hipStream_t s, Profiler* prof)
+// The launchers pick the instantiation of a pass from the edge of the level (MgEdge, ctu_kernels.h): flags == nullptr is one box
+int launch_mg_smooth(const DFab& P, const DFab& B, const MgLevel& L, const MgEdge& e, int colour, hipStream_t s, Profiler* prof)
 {
-    prof_begin(prof, "k_mg_residual", s);
-    hipLaunchKernelGGL(k_mg_residual, dim3(mg_blocks(mg_zones(L))), dim3(MG_WG), 0, s, P, B, R, L);
-    prof_end(prof, s);
-    return mg_check(s);
+    const unsigned nb = mg_blocks(mg_pairs(L));
+    return e.flags ? mg_launch(prof, "k_mgb_smooth", k_mg_smooth<MgBoxes>, nb, MG_WG, s, P, B, MgBoxes{ { L, e.flags }, e.X }, colour)
+                   : mg_launch(prof, "k_mg_smooth", k_mg_smooth<MgOneBox>, nb, MG_WG, s, P, B, MgOneBox{ { L } }, colour);
 }
 
-int launch_mg_restrict(const DFab& RF, const MgLevel& LF, const DFab& BC, const DFab& PC, const MgLevel& LC, hipStream_t s, Profiler* prof)
+static int mg_bottom(const DFab& P, const DFab& B, const MgLevel& L, const MgEdge& e, hipStream_t s, Profiler* prof)
 {
-    prof_begin(prof, "k_mg_restrict", s);
-    hipLaunchKernelGGL(k_mg_restrict, dim3(mg_blocks(mg_zones(LC))), dim3(MG_WG), 0, s, RF, LF.lo[0], LF.lo[1], LF.lo[2], BC, PC, LC);
-    prof_end(prof, s);
-    return mg_check(s);
+    return e.flags ? mg_launch(prof, "k_mgb_bottom", k_mg_bottom<MgBoxes>, 1, MG_BOTTOM_WG, s, P, B, MgBoxes{ { L, e.flags }, e.X }, MG_NBOTTOM)
+                   : mg_launch(prof, "k_mg_bottom", k_mg_bottom<MgOneBox>, 1, MG_BOTTOM_WG, s, P, B, MgOneBox{ { L } }, MG_NBOTTOM);
 }
 
-int launch_mg_prolong(const DFab& PC, const MgLevel& LC, const DFab& PF, const MgLevel& LF, hipStream_t s, Profiler* prof)
+int launch_mg_residual(const DFab& P, const DFab& B, const DFab& R, const MgLevel& L, const MgEdge& e, hipStream_t s, Profiler* prof)
 {
-    prof_begin(prof, "k_mg_prolong", s);
-    hipLaunchKernelGGL(k_mg_prolong, dim3(mg_blocks(mg_zones(LF))), dim3(MG_WG), 0, s, PC, LC.lo[0], LC.lo[1], LC.lo[2], PF, LF);
-    prof_end(prof, s);
-    return mg_check(s);
+    const unsigned nb = mg_blocks(mg_zones(L));
+    return e.flags ? mg_launch(prof, "k_mgb_residual", k_mg_residual<MgBoxes>, nb, MG_WG, s, P, B, R, MgBoxes{ { L, e.flags }, e.X })
+                   : mg_launch(prof, "k_mg_residual", k_mg_residual<MgOneBox>, nb, MG_WG, s, P, B, R, MgOneBox{ { L } });
 }
 
-int launch_mg_norm(const DFab& X, const MgLevel& L, double* ws, double* d_out, hipStream_t s, Profiler* prof)
+// cflags, fflags, flags: the coverage of the coarse / the fine / the level, nullptr for one box
+int launch_mg_restrict(const DFab& RF, const MgLevel& LF, const DFab& BC, const DFab& PC, const MgLevel& LC, const unsigned char* cflags,
+                       hipStream_t s, Profiler* prof)
+{
+    const unsigned nb = mg_blocks(mg_zones(LC));
+    return cflags ? mg_launch(prof, "k_mgb_restrict", k_mg_restrict<MgMasked>, nb, MG_WG, s, RF, LF.lo[0], LF.lo[1], LF.lo[2], BC, PC, MgMasked{ LC, cflags })
+                  : mg_launch(prof, "k_mg_restrict", k_mg_restrict<MgWhole>, nb, MG_WG, s, RF, LF.lo[0], LF.lo[1], LF.lo[2], BC, PC, MgWhole{ LC });
+}
+
+int launch_mg_prolong(const DFab& PC, const MgLevel& LC, const DFab& PF, const MgLevel& LF, const unsigned char* fflags, hipStream_t s,
+                      Profiler* prof)
+{
+    const unsigned nb = mg_blocks(mg_zones(LF));
+    return fflags ? mg_launch(prof, "k_mgb_prolong", k_mg_prolong<MgMasked>, nb, MG_WG, s, PC, LC.lo[0], LC.lo[1], LC.lo[2], PF, MgMasked{ LF, fflags })
+                  : mg_launch(prof, "k_mg_prolong", k_mg_prolong<MgWhole>, nb, MG_WG, s, PC, LC.lo[0], LC.lo[1], LC.lo[2], PF, MgWhole{ LF });
+}
+
+int launch_mg_norm(const DFab& X, const MgLevel& L, const unsigned char* flags, double* ws, double* d_out, hipStream_t s, Profiler* prof)
 {
     unsigned nb = mg_blocks(mg_zones(L));
     if (nb > (unsigned)MG_NORM_MAX_WG) nb = MG_NORM_MAX_WG;
-    prof_begin(prof, "k_mg_norm_partial", s);
-    hipLaunchKernelGGL(k_mg_norm_partial, dim3(nb), dim3(MG_WG), 0, s, X, L, ws);
-    prof_end(prof, s);
-    prof_begin(prof, "k_mg_norm_final", s);
-    hipLaunchKernelGGL(k_mg_norm_final, dim3(1), dim3(MG_NORM_MAX_WG), 0, s, (const double*)ws, (int)nb, d_out);
-    prof_end(prof, s);
-    return mg_check(s);
+    const int rc = flags ? mg_launch(prof, "k_mgb_norm_partial", k_mg_norm_partial<MgMasked>, nb, MG_WG, s, X, MgMasked{ L, flags }, ws)
+                         : mg_launch(prof, "k_mg_norm_partial", k_mg_norm_partial<MgWhole>, nb, MG_WG, s, X, MgWhole{ L }, ws);
+    return rc != 0 ? rc : mg_launch(prof, "k_mg_norm_final", k_mg_norm_final, 1, MG_NORM_MAX_WG, s, ws, (int)nb, d_out);
 }
 
-static int mg_bottom(const DFab& P, const DFab& B, const MgLevel& L, hipStream_t s, Profiler* prof)
+// the edge of level l of the plan; X: the face values of level 0 of a union (the coarser levels have none: 0.0; X.p == nullptr for
+// one box, whose ghost zones of phi hold them)
+static MgEdge mg_edge(const PoissonPlan* P, size_t l, const DFab& X)
 {
-    prof_begin(prof, "k_mg_bottom", s);
-    hipLaunchKernelGGL(k_mg_bottom, dim3(1), dim3(MG_BOTTOM_WG), 0, s, P, B, L, MG_NBOTTOM);
-    prof_end(prof, s);
-    return mg_check(s);
+    MgEdge e;
+    std::memset(&e, 0, sizeof(e));
+    if (!P->flags.empty()) e.flags = P->flags[l];
+    if (l == 0) e.X = X;
+    return e;
 }
 
 // One V-cycle from level l down: MG_NPRE sweeps (colour 0, colour 1), residual, restriction, the coarser levels, prolongation,
 // MG_NPOST sweeps; the coarsest level is the bottom solve alone
-static int mg_vcycle(PoissonPlan* P, size_t l, hipStream_t s, Profiler* prof)
+static int mg_vcycle(PoissonPlan* P, size_t l, const DFab& X, hipStream_t s, Profiler* prof)
 {
     const MgLevel& L = P->lev[l];
+    const MgEdge e = mg_edge(P, l, X);
     int rc = 0;
-    if (l + 1 == P->lev.size()) return mg_bottom(P->phi[l], P->rhs[l], L, s, prof);
+    if (l + 1 == P->lev.size()) return mg_bottom(P->phi[l], P->rhs[l], L, e, s, prof);
+    const unsigned char* cflags = mg_edge(P, l + 1, X).flags;
     for (int it = 0; it < MG_NPRE && rc == 0; ++it)
-        for (int colour = 0; colour < 2 && rc == 0; ++colour) rc = launch_mg_smooth(P->phi[l], P->rhs[l], L, colour, s, prof);
-    if (rc == 0) rc = launch_mg_residual(P->phi[l], P->rhs[l], P->res[l], L, s, prof);
-    if (rc == 0) rc = launch_mg_restrict(P->res[l], L, P->rhs[l + 1], P->phi[l + 1], P->lev[l + 1], s, prof);
-    if (rc == 0) rc = mg_vcycle(P, l + 1, s, prof);
-    if (rc == 0) rc = launch_mg_prolong(P->phi[l + 1], P->lev[l + 1], P->phi[l], L, s, prof);
+        for (int colour = 0; colour < 2 && rc == 0; ++colour) rc = launch_mg_smooth(P->phi[l], P->rhs[l], L, e, colour, s, prof);
+    if (rc == 0) rc = launch_mg_residual(P->phi[l], P->rhs[l], P->res[l], L, e, s, prof);
+    if (rc == 0) rc = launch_mg_restrict(P->res[l], L, P->rhs[l + 1], P->phi[l + 1], P->lev[l + 1], cflags, s, prof);
+    if (rc == 0) rc = mg_vcycle(P, l + 1, X, s, prof);
+    if (rc == 0) rc = launch_mg_prolong(P->phi[l + 1], P->lev[l + 1], P->phi[l], L, e.flags, s, prof);
     for (int it = 0; it < MG_NPOST && rc == 0; ++it)
-        for (int colour = 0; colour < 2 && rc == 0; ++colour) rc = launch_mg_smooth(P->phi[l], P->rhs[l], L, colour, s, prof);
+        for (int colour = 0; colour < 2 && rc == 0; ++colour) rc = launch_mg_smooth(P->phi[l], P->rhs[l], L, e, colour, s, prof);
     return rc;
 }
 
 // the residual of level 0 into the scratch of the plan (res[0]; the V-cycle overwrites it again), its norm into d_norm[at..at+1]
-static int mg_residual_norm(PoissonPlan* P, int at, hipStream_t s, Profiler* prof)
+static int mg_residual_norm(PoissonPlan* P, const DFab& X, int at, hipStream_t s, Profiler* prof)
 {
-    int rc = launch_mg_residual(P->phi[0], P->rhs[0], P->res[0], P->lev[0], s, prof);
-    if (rc == 0) rc = launch_mg_norm(P->res[0], P->lev[0], P->norm_ws, P->d_norm + at, s, prof);
+    const MgEdge e = mg_edge(P, 0, X);
+    int rc = launch_mg_residual(P->phi[0], P->rhs[0], P->res[0], P->lev[0], e, s, prof);
+    if (rc == 0) rc = launch_mg_norm(P->res[0], P->lev[0], e.flags, P->norm_ws, P->d_norm + at, s, prof);
     return rc;
 }
 
@@ -427,17 +575,12 @@ static int mg_read(PoissonPlan* P, int n, hipStream_t s)
     return hipStreamSynchronize(s) == hipSuccess ? 0 : CASTRO_AMD_ERR_HIP;
 }
 
-int launch_poisson_solve(PoissonPlan* P, const DFab& phi, const DFab& U, int comp, double fourpiG, double reltol, double abstol,
-                         int maxiter, int* cycles, int* converged, double* final_norm, double* h_history, hipStream_t s, Profiler* prof)
+// V-cycles on phi[0] with the right-hand side rhs[0] of the plan until the residual norm is below the tolerance or maxiter is spent
+static int mg_solve(PoissonPlan* P, const DFab& X, double reltol, double abstol, int maxiter, int* cycles, int* converged,
+                    double* final_norm, double* h_history, hipStream_t s, Profiler* prof)
 {
-    P->phi[0] = phi;
-    const MgLevel& L0 = P->lev[0];
-    prof_begin(prof, "k_mg_rhs", s);
-    hipLaunchKernelGGL(k_mg_rhs, dim3(mg_blocks(mg_zones(L0))), dim3(MG_WG), 0, s, U, comp, P->rhs[0], L0, fourpiG);
-    prof_end(prof, s);
-    int rc = mg_check(s);
-    if (rc == 0) rc = launch_mg_norm(P->rhs[0], L0, P->norm_ws, P->d_norm, s, prof);
-    if (rc == 0) rc = mg_residual_norm(P, 2, s, prof);
+    int rc = launch_mg_norm(P->rhs[0], P->lev[0], mg_edge(P, 0, X).flags, P->norm_ws, P->d_norm, s, prof);
+    if (rc == 0) rc = mg_residual_norm(P, X, 2, s, prof);
     if (rc == 0) rc = mg_read(P, 4, s);
     if (rc != 0) return rc;
     const double bnorm = P->h_norm[0], max_rhs = P->h_norm[1];
@@ -447,8 +590,8 @@ int launch_poisson_solve(PoissonPlan* P, const DFab& phi, const DFab& U, int com
     if (h_history) { h_history[0] = bnorm; h_history[1] = max_rhs; h_history[2] = rnorm; }
     int n = 0;
     while (!(rnorm <= tol) && n < maxiter) {
-        rc = mg_vcycle(P, 0, s, prof);
-        if (rc == 0) rc = mg_residual_norm(P, 0, s, prof);
+        rc = mg_vcycle(P, 0, X, s, prof);
+        if (rc == 0) rc = mg_residual_norm(P, X, 0, s, prof);
         if (rc == 0) rc = mg_read(P, 1, s);
         if (rc != 0) return rc;
         rnorm = P->h_norm[0];
@@ -461,247 +604,35 @@ int launch_poisson_solve(PoissonPlan* P, const DFab& phi, const DFab& U, int com
     return 0;
 }
 
+int launch_poisson_solve(PoissonPlan* P, const DFab& phi, const DFab& U, int comp, double fourpiG, double reltol, double abstol,
+                         int maxiter, int* cycles, int* converged, double* final_norm, double* h_history, hipStream_t s, Profiler* prof)
+{
+    P->phi[0] = phi;
+    const MgLevel& L0 = P->lev[0];
+    const int rc = mg_launch(prof, "k_mg_rhs", k_mg_rhs, mg_blocks(mg_zones(L0)), MG_WG, s, U, comp, P->rhs[0], L0, fourpiG);
+    if (rc != 0) return rc;
+    DFab none;
+    std::memset(&none, 0, sizeof(none));
+    return mg_solve(P, none, reltol, abstol, maxiter, cycles, converged, final_norm, h_history, s, prof);
+}
+
 int launch_grad_phi(const DFab& phi, const DFab& G, const MgLevel& L, const double dx[3], hipStream_t s, Profiler* prof)
 {
-    prof_begin(prof, "k_grad_phi", s);
-    hipLaunchKernelGGL(k_grad_phi, dim3(mg_blocks(mg_zones(L))), dim3(MG_WG), 0, s, phi, G, L, dx[0], dx[1], dx[2]);
-    prof_end(prof, s);
-    return mg_check(s);
+    return mg_launch(prof, "k_grad_phi", k_grad_phi, mg_blocks(mg_zones(L)), MG_WG, s, phi, G, L, dx[0], dx[1], dx[2]);
 }
 
-// ---- a level that is a union of boxes: ONE array over the bounding box, a byte of flags per zone -----------------------------------
-// The arithmetic of the passes above; "beyond a domain face" becomes "the neighbour across this face is not covered" (a flag bit
-// made on the host), and the value ON such a face is read from the face array X of level 0 -- an uncovered zone at a concave
-// corner of the union is the neighbour of two covered zones across two faces with two values, so it cannot hold them -- or is 0.0
-// on the coarser levels.  Zones that are not covered are never written.  L is the bounding box >> m; colours are relative to
-// its low corner.  The kernels above are not touched: a level of one box keeps its launches and its bits.
-__device__ __forceinline__ long mgb_flag_at(const MgLevel& L, int ii, int jj, int kk)
-{
-    return (long)ii + (long)L.n[0] * ((long)jj + (long)L.n[1] * kk);
-}
-
-// the value on the (d, side) face of the zone (i, j, k): the low d-face of the zone (i, j, k) + side * e_d
-__device__ __forceinline__ double mgb_face_value(const DFab& X, int d, int side, int i, int j, int k)
-{
-    if (!X.p) return 0.0;
-    return X.p[mg_at(X, i + (d == 0 ? side : 0), j + (d == 1 ? side : 0), k + (d == 2 ? side : 0)) + X.sn * d];
-}
-
-// mg_relax with f the value on a face whose flag is set: xm = 2.0 * f; dg = dg + cx; ... in mg_relax's order (x low, x high, y, z)
-__device__ __forceinline__ double mgb_relax(const DFab& P, const DFab& B, const MgLevel& L, unsigned fl, const DFab& X, int ii, int jj, int kk)
-{
-    const int i = L.lo[0] + ii, j = L.lo[1] + jj, k = L.lo[2] + kk;
-    const double* p = P.p + mg_at(P, i, j, k);
-    double xm = p[-1], xp = p[1], ym = p[-P.sy], yp = p[P.sy], zm = p[-P.sz], zp = p[P.sz];
-    double dg = L.cdiag;
-    if (fl & ~MGF_COVERED) {
-        if (fl & mgf_face(0, 0)) { xm = 2.0 * mgb_face_value(X, 0, 0, i, j, k); dg = dg + L.cx; }
-        if (fl & mgf_face(0, 1)) { xp = 2.0 * mgb_face_value(X, 0, 1, i, j, k); dg = dg + L.cx; }
-        if (fl & mgf_face(1, 0)) { ym = 2.0 * mgb_face_value(X, 1, 0, i, j, k); dg = dg + L.cy; }
-        if (fl & mgf_face(1, 1)) { yp = 2.0 * mgb_face_value(X, 1, 1, i, j, k); dg = dg + L.cy; }
-        if (fl & mgf_face(2, 0)) { zm = 2.0 * mgb_face_value(X, 2, 0, i, j, k); dg = dg + L.cz; }
-        if (fl & mgf_face(2, 1)) { zp = 2.0 * mgb_face_value(X, 2, 1, i, j, k); dg = dg + L.cz; }
-    }
-    const double b = B.p[mg_at(B, i, j, k)];
-    const double off = (L.cx * (xm + xp) + L.cy * (ym + yp)) + L.cz * (zm + zp);
-    return (off - b) / dg;
-}
-
-__global__ void __launch_bounds__(MG_WG) k_mgb_smooth(DFab P, DFab B, MgLevel L, const unsigned char* __restrict__ flags, DFab X, int colour)
-{
-    const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
-    const int npair = (L.n[0] + 1) >> 1;
-    if (q >= (long)npair * L.n[1] * L.n[2]) return;
-    int ii, jj, kk;
-    if (!mg_colour_zone(q, L, colour, ii, jj, kk)) return;
-    const unsigned fl = flags[mgb_flag_at(L, ii, jj, kk)];
-    if (!(fl & MGF_COVERED)) return;
-    const double v = mgb_relax(P, B, L, fl, X, ii, jj, kk);
-    P.p[mg_at(P, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk)] = v;
-}
-
-// k_mg_bottom over the covered zones of the coarsest level (at most CASTRO_AMD_POISSON_MAX_BOTTOM zones of its bounding box)
-__global__ void __launch_bounds__(MG_BOTTOM_WG) k_mgb_bottom(DFab P, DFab B, MgLevel L, const unsigned char* __restrict__ flags, DFab X,
-                                                            int sweeps)
-{
-    const int npair = (L.n[0] + 1) >> 1;
-    const long nq = (long)npair * L.n[1] * L.n[2];
-    for (int s = 0; s < sweeps; ++s) {
-        for (int colour = 0; colour < 2; ++colour) {
-            for (long q = threadIdx.x; q < nq; q += MG_BOTTOM_WG) {
-                int ii, jj, kk;
-                if (!mg_colour_zone(q, L, colour, ii, jj, kk)) continue;
-                const unsigned fl = flags[mgb_flag_at(L, ii, jj, kk)];
-                if (!(fl & MGF_COVERED)) continue;
-                const double v = mgb_relax(P, B, L, fl, X, ii, jj, kk);
-                P.p[mg_at(P, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk)] = v;
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// k_mg_residual on the covered zones: across a flagged face the linear ghost 2.0 * f - p
-__global__ void __launch_bounds__(MG_WG) k_mgb_residual(DFab P, DFab B, DFab R, MgLevel L, const unsigned char* __restrict__ flags, DFab X)
-{
-    const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
-    if (q >= (long)L.n[0] * L.n[1] * L.n[2]) return;
-    const unsigned fl = flags[q];
-    if (!(fl & MGF_COVERED)) return;
-    const int ii = (int)(q % L.n[0]);
-    const long rr = q / L.n[0];
-    const int jj = (int)(rr % L.n[1]), kk = (int)(rr / L.n[1]);
-    const int i = L.lo[0] + ii, j = L.lo[1] + jj, k = L.lo[2] + kk;
-    const double* p = P.p + mg_at(P, i, j, k);
-    const double pc = p[0];
-    double xm = p[-1], xp = p[1], ym = p[-P.sy], yp = p[P.sy], zm = p[-P.sz], zp = p[P.sz];
-    if (fl & ~MGF_COVERED) {
-        if (fl & mgf_face(0, 0)) xm = 2.0 * mgb_face_value(X, 0, 0, i, j, k) - pc;
-        if (fl & mgf_face(0, 1)) xp = 2.0 * mgb_face_value(X, 0, 1, i, j, k) - pc;
-        if (fl & mgf_face(1, 0)) ym = 2.0 * mgb_face_value(X, 1, 0, i, j, k) - pc;
-        if (fl & mgf_face(1, 1)) yp = 2.0 * mgb_face_value(X, 1, 1, i, j, k) - pc;
-        if (fl & mgf_face(2, 0)) zm = 2.0 * mgb_face_value(X, 2, 0, i, j, k) - pc;
-        if (fl & mgf_face(2, 1)) zp = 2.0 * mgb_face_value(X, 2, 1, i, j, k) - pc;
-    }
-    const double tp = 2.0 * pc;
-    const double lap = (L.cx * ((xm + xp) - tp) + L.cy * ((ym + yp) - tp)) + L.cz * ((zm + zp) - tp);
-    R.p[mg_at(R, i, j, k)] = B.p[mg_at(B, i, j, k)] - lap;
-}
-
-// k_mg_restrict on the covered zones of the COARSE level L (cflags): the 8 children of a covered coarse zone are all covered
-__global__ void __launch_bounds__(MG_WG) k_mgb_restrict(DFab RF, int flo0, int flo1, int flo2, DFab BC, DFab PC, MgLevel L,
-                                                       const unsigned char* __restrict__ cflags)
-{
-    const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
-    if (q >= (long)L.n[0] * L.n[1] * L.n[2]) return;
-    if (!(cflags[q] & MGF_COVERED)) return;
-    const int ii = (int)(q % L.n[0]);
-    const long rr = q / L.n[0];
-    const int jj = (int)(rr % L.n[1]), kk = (int)(rr / L.n[1]);
-    const double* r = RF.p + mg_at(RF, flo0 + 2 * ii, flo1 + 2 * jj, flo2 + 2 * kk);
-    double s = r[0] + r[1];
-    s = s + r[RF.sy];
-    s = s + r[RF.sy + 1];
-    s = s + r[RF.sz];
-    s = s + r[RF.sz + 1];
-    s = s + r[RF.sz + RF.sy];
-    s = s + r[RF.sz + RF.sy + 1];
-    const int i = L.lo[0] + ii, j = L.lo[1] + jj, k = L.lo[2] + kk;
-    BC.p[mg_at(BC, i, j, k)] = s * 0.125;
-    PC.p[mg_at(PC, i, j, k)] = 0.0;
-}
-
-// k_mg_prolong on the covered zones of the FINE level L (fflags)
-__global__ void __launch_bounds__(MG_WG) k_mgb_prolong(DFab PC, int clo0, int clo1, int clo2, DFab PF, MgLevel L,
-                                                      const unsigned char* __restrict__ fflags)
-{
-    const long q = (long)blockIdx.x * MG_WG + threadIdx.x;
-    if (q >= (long)L.n[0] * L.n[1] * L.n[2]) return;
-    if (!(fflags[q] & MGF_COVERED)) return;
-    const int ii = (int)(q % L.n[0]);
-    const long rr = q / L.n[0];
-    const int jj = (int)(rr % L.n[1]), kk = (int)(rr / L.n[1]);
-    const long f = mg_at(PF, L.lo[0] + ii, L.lo[1] + jj, L.lo[2] + kk);
-    PF.p[f] = PF.p[f] + PC.p[mg_at(PC, clo0 + (ii >> 1), clo1 + (jj >> 1), clo2 + (kk >> 1))];
-}
-
-// the box of the table that holds thread t, and the zone of it
-__device__ __forceinline__ bool mgb_box_zone(const MgBoxDev* __restrict__ tab, int nbox, long t, int& b, int& i, int& j, int& k)
-{
-    int b0 = 0, b1 = nbox - 1;
-    while (b0 < b1) {
-        const int mid = (b0 + b1 + 1) >> 1;
-        if (tab[mid].start <= t) b0 = mid; else b1 = mid - 1;
-    }
-    const long r = t - tab[b0].start;
-    const int n0 = tab[b0].n[0], n1 = tab[b0].n[1], n2 = tab[b0].n[2];
-    if (r >= (long)n0 * n1 * n2) return false;
-    const long rr = r / n0;
-    b = b0;
-    i = tab[b0].lo[0] + (int)(r % n0); j = tab[b0].lo[1] + (int)(rr % n1); k = tab[b0].lo[2] + (int)(rr / n1);
-    return true;
-}
-
-// k_mg_rhs gathered from the boxes' own state FABs: b = fourpiG * rho on the zones of every box of the table
-__global__ void __launch_bounds__(MG_WG) k_mgb_rhs(const MgBoxDev* __restrict__ tab, int nbox, long total, int comp, DFab B, double fourpiG)
-{
-    const long t = (long)blockIdx.x * MG_WG + threadIdx.x;
-    if (t >= total) return;
-    int b, i, j, k;
-    if (!mgb_box_zone(tab, nbox, t, b, i, j, k)) return;
-    const DFab U = tab[b].F;
-    B.p[mg_at(B, i, j, k)] = fourpiG * U.p[mg_at(U, i, j, k) + U.sn * comp];
-}
-
-// k_mg_norm_partial over the covered zones
-__global__ void __launch_bounds__(MG_WG) k_mgb_norm_partial(DFab X, MgLevel L, const unsigned char* __restrict__ flags, double* __restrict__ ws)
-{
-    const long total = (long)L.n[0] * L.n[1] * L.n[2];
-    double ma = 0.0, mx = -HUGE_VAL;
-    for (long q = (long)blockIdx.x * MG_WG + threadIdx.x; q < total; q += (long)gridDim.x * MG_WG) {
-        if (!(flags[q] & MGF_COVERED)) continue;
-        const int i = L.lo[0] + (int)(q % L.n[0]);
-        const long rr = q / L.n[0];
-        const int j = L.lo[1] + (int)(rr % L.n[1]), k = L.lo[2] + (int)(rr / L.n[1]);
-        const double v = X.p[mg_at(X, i, j, k)];
-        ma = mg_max(ma, fabs(v));
-        mx = mg_max(mx, v);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        ma = mg_max(ma, __shfl_down(ma, off, 64));
-        mx = mg_max(mx, __shfl_down(mx, off, 64));
-    }
-    __shared__ double sa[MG_WG / 64][2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { sa[wave][0] = ma; sa[wave][1] = mx; }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        double m = sa[0][threadIdx.x];
-        for (int w = 1; w < MG_WG / 64; ++w) m = mg_max(m, sa[w][threadIdx.x]);
-        ws[2 * (long)blockIdx.x + threadIdx.x] = m;
-    }
-}
-
-// k_grad_phi on the zones of every box of the table, into that box's own FAB: a neighbour in a sibling box is an ordinary
-// neighbour; across a flagged face dl = 2.0 * (p - f), dh = 2.0 * (f - p)
-__global__ void __launch_bounds__(MG_WG) k_mgb_grad(const MgBoxDev* __restrict__ tab, int nbox, long total, DFab P, MgLevel L,
-                                                   const unsigned char* __restrict__ flags, DFab X, double hx, double hy, double hz)
-{
-    const long t = (long)blockIdx.x * MG_WG + threadIdx.x;
-    if (t >= total) return;
-    int b, i, j, k;
-    if (!mgb_box_zone(tab, nbox, t, b, i, j, k)) return;
-    const DFab G = tab[b].F;
-    const unsigned fl = flags[mgb_flag_at(L, i - L.lo[0], j - L.lo[1], k - L.lo[2])];
-    const double* p = P.p + mg_at(P, i, j, k);
-    const double pc = p[0];
-    double dl[3] = { pc - p[-1], pc - p[-P.sy], pc - p[-P.sz] };
-    double dh[3] = { p[1] - pc, p[P.sy] - pc, p[P.sz] - pc };
-    const double h[3] = { hx, hy, hz };
-    const long g = mg_at(G, i, j, k);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        if (fl & mgf_face(d, 0)) dl[d] = 2.0 * (pc - mgb_face_value(X, d, 0, i, j, k));
-        if (fl & mgf_face(d, 1)) dh[d] = 2.0 * (mgb_face_value(X, d, 1, i, j, k) - pc);
-        const double gl = dl[d] / h[d], gh = dh[d] / h[d];
-        G.p[g + G.sn * d] = -(0.5 * (gl + gh));
-    }
-}
-
-// The levels of a union of boxes (lo, hi: 3 ints per box, in the zones of level 0): level m is the bounding box >> m.  Coarsened
-// while every box's lo and hi + 1 are divisible by 2^(m+1) -- the 8 children of a coarse zone are then all covered or all not --,
-// the extents of the bounding box are even with n / 2 >= 2 (poisson_levels' rule), and there are fewer than MG_MAX_LEVELS levels
+// ---- the plan of a level that is a union of boxes: ONE array over the bounding box, a byte of flags per zone ------------------------
+// The levels of a union of boxes (lo, hi: 3 ints per box, in the zones of level 0): level m is the bounding box >> m, coarsened
+// by mg_coarsen's rule with the alignment of the boxes
 int poisson_boxes_levels(int nbox, const int* lo, const int* hi, const double dx[3], std::vector<MgLevel>& lev)
 {
     lev.clear();
     if (nbox < 1 || !lo || !hi) return CASTRO_AMD_ERR_ARG;
     MgLevel L;
     std::memset(&L, 0, sizeof(L));
-    double h[3];
     int bhi[3];
     for (int d = 0; d < 3; ++d) {
         if (!(dx[d] > 0.0)) return CASTRO_AMD_ERR_ARG;
-        h[d] = dx[d];
         L.lo[d] = lo[d]; bhi[d] = hi[d];
     }
     for (int b = 0; b < nbox; ++b)
@@ -719,19 +650,7 @@ int poisson_boxes_levels(int nbox, const int* lo, const int* hi, const double dx
             if (!apart) return CASTRO_AMD_ERR_ARG;
         }
     for (int d = 0; d < 3; ++d) L.n[d] = bhi[d] - L.lo[d] + 1;
-    for (;;) {
-        L.cx = 1.0 / (h[0] * h[0]); L.cy = 1.0 / (h[1] * h[1]); L.cz = 1.0 / (h[2] * h[2]);
-        L.cdiag = 2.0 * ((L.cx + L.cy) + L.cz);
-        lev.push_back(L);
-        bool more = (int)lev.size() < MG_MAX_LEVELS;
-        for (int d = 0; d < 3; ++d) more = more && L.n[d] % 2 == 0 && L.n[d] / 2 >= 2;
-        const int m1 = (1 << (int)lev.size()) - 1;
-        for (int q = 0; q < 3 * nbox && more; ++q) more = (lo[q] & m1) == 0 && ((hi[q] + 1) & m1) == 0;
-        if (!more) break;
-        for (int d = 0; d < 3; ++d) { L.n[d] /= 2; L.lo[d] = L.lo[d] >> 1; h[d] = 2.0 * h[d]; }
-    }
-    if (mg_zones(lev.back()) > CASTRO_AMD_POISSON_MAX_BOTTOM) return CASTRO_AMD_ERR_UNSUPPORTED;
-    return 0;
+    return mg_coarsen(L, dx, nbox, lo, hi, lev);
 }
 
 // the flags of level m (shift = m) of the union
@@ -787,88 +706,6 @@ int poisson_boxes_plan_make(int nbox, const int* lo, const int* hi, const double
     return 0;
 }
 
-int launch_mgb_smooth(const DFab& P, const DFab& B, const MgLevel& L, const unsigned char* flags, const DFab& X, int colour,
-                      hipStream_t s, Profiler* prof)
-{
-    prof_begin(prof, "k_mgb_smooth", s);
-    hipLaunchKernelGGL(k_mgb_smooth, dim3(mg_blocks(mg_pairs(L))), dim3(MG_WG), 0, s, P, B, L, flags, X, colour);
-    prof_end(prof, s);
-    return mg_check(s);
-}
-
-int launch_mgb_residual(const DFab& P, const DFab& B, const DFab& R, const MgLevel& L, const unsigned char* flags, const DFab& X,
-                        hipStream_t s, Profiler* prof)
-{
-    prof_begin(prof, "k_mgb_residual", s);
-    hipLaunchKernelGGL(k_mgb_residual, dim3(mg_blocks(mg_zones(L))), dim3(MG_WG), 0, s, P, B, R, L, flags, X);
-    prof_end(prof, s);
-    return mg_check(s);
-}
-
-int launch_mgb_restrict(const DFab& RF, const MgLevel& LF, const DFab& BC, const DFab& PC, const MgLevel& LC,
-                        const unsigned char* cflags, hipStream_t s, Profiler* prof)
-{
-    prof_begin(prof, "k_mgb_restrict", s);
-    hipLaunchKernelGGL(k_mgb_restrict, dim3(mg_blocks(mg_zones(LC))), dim3(MG_WG), 0, s, RF, LF.lo[0], LF.lo[1], LF.lo[2], BC, PC, LC, cflags);
-    prof_end(prof, s);
-    return mg_check(s);
-}
-
-int launch_mgb_prolong(const DFab& PC, const MgLevel& LC, const DFab& PF, const MgLevel& LF, const unsigned char* fflags,
-                       hipStream_t s, Profiler* prof)
-{
-    prof_begin(prof, "k_mgb_prolong", s);
-    hipLaunchKernelGGL(k_mgb_prolong, dim3(mg_blocks(mg_zones(LF))), dim3(MG_WG), 0, s, PC, LC.lo[0], LC.lo[1], LC.lo[2], PF, LF, fflags);
-    prof_end(prof, s);
-    return mg_check(s);
-}
-
-int launch_mgb_norm(const DFab& X, const MgLevel& L, const unsigned char* flags, double* ws, double* d_out, hipStream_t s,
-                    Profiler* prof)
-{
-    unsigned nb = mg_blocks(mg_zones(L));
-    if (nb > (unsigned)MG_NORM_MAX_WG) nb = MG_NORM_MAX_WG;
-    prof_begin(prof, "k_mgb_norm_partial", s);
-    hipLaunchKernelGGL(k_mgb_norm_partial, dim3(nb), dim3(MG_WG), 0, s, X, L, flags, ws);
-    prof_end(prof, s);
-    prof_begin(prof, "k_mg_norm_final", s);
-    hipLaunchKernelGGL(k_mg_norm_final, dim3(1), dim3(MG_NORM_MAX_WG), 0, s, (const double*)ws, (int)nb, d_out);
-    prof_end(prof, s);
-    return mg_check(s);
-}
-
-// mg_vcycle with the masked passes; X: the face values of level 0
-static int mgb_vcycle(PoissonPlan* P, size_t l, const DFab& X, hipStream_t s, Profiler* prof)
-{
-    const MgLevel& L = P->lev[l];
-    DFab none;
-    std::memset(&none, 0, sizeof(none));
-    const DFab& Xl = l == 0 ? X : none;
-    int rc = 0;
-    if (l + 1 == P->lev.size()) {
-        prof_begin(prof, "k_mgb_bottom", s);
-        hipLaunchKernelGGL(k_mgb_bottom, dim3(1), dim3(MG_BOTTOM_WG), 0, s, P->phi[l], P->rhs[l], L, (const unsigned char*)P->flags[l], Xl, MG_NBOTTOM);
-        prof_end(prof, s);
-        return mg_check(s);
-    }
-    for (int it = 0; it < MG_NPRE && rc == 0; ++it)
-        for (int colour = 0; colour < 2 && rc == 0; ++colour) rc = launch_mgb_smooth(P->phi[l], P->rhs[l], L, P->flags[l], Xl, colour, s, prof);
-    if (rc == 0) rc = launch_mgb_residual(P->phi[l], P->rhs[l], P->res[l], L, P->flags[l], Xl, s, prof);
-    if (rc == 0) rc = launch_mgb_restrict(P->res[l], L, P->rhs[l + 1], P->phi[l + 1], P->lev[l + 1], P->flags[l + 1], s, prof);
-    if (rc == 0) rc = mgb_vcycle(P, l + 1, X, s, prof);
-    if (rc == 0) rc = launch_mgb_prolong(P->phi[l + 1], P->lev[l + 1], P->phi[l], L, P->flags[l], s, prof);
-    for (int it = 0; it < MG_NPOST && rc == 0; ++it)
-        for (int colour = 0; colour < 2 && rc == 0; ++colour) rc = launch_mgb_smooth(P->phi[l], P->rhs[l], L, P->flags[l], Xl, colour, s, prof);
-    return rc;
-}
-
-static int mgb_residual_norm(PoissonPlan* P, const DFab& X, int at, hipStream_t s, Profiler* prof)
-{
-    int rc = launch_mgb_residual(P->phi[0], P->rhs[0], P->res[0], P->lev[0], P->flags[0], X, s, prof);
-    if (rc == 0) rc = launch_mgb_norm(P->res[0], P->lev[0], P->flags[0], P->norm_ws, P->d_norm + at, s, prof);
-    return rc;
-}
-
 // the table of the boxes of the plan with the FABs F, on the device (a table the plan has seen costs no copy)
 static int mgb_table(PoissonPlan* P, const DFab* F, hipStream_t s, const MgBoxDev*& dtab, long& total)
 {
@@ -895,38 +732,13 @@ int launch_poisson_boxes_solve(PoissonPlan* P, const DFab& phi, const DFab& X, c
                                hipStream_t s, Profiler* prof)
 {
     P->phi[0] = phi;
-    const MgLevel& L0 = P->lev[0];
     const MgBoxDev* dtab;
     long total;
     int rc = mgb_table(P, U, s, dtab, total);
     if (rc != 0) return rc;
-    prof_begin(prof, "k_mgb_rhs", s);
-    hipLaunchKernelGGL(k_mgb_rhs, dim3(mg_blocks(total)), dim3(MG_WG), 0, s, dtab, (int)(P->boxes.size() / 6), total, comp, P->rhs[0], fourpiG);
-    prof_end(prof, s);
-    rc = mg_check(s);
-    if (rc == 0) rc = launch_mgb_norm(P->rhs[0], L0, P->flags[0], P->norm_ws, P->d_norm, s, prof);
-    if (rc == 0) rc = mgb_residual_norm(P, X, 2, s, prof);
-    if (rc == 0) rc = mg_read(P, 4, s);
+    rc = mg_launch(prof, "k_mgb_rhs", k_mgb_rhs, mg_blocks(total), MG_WG, s, dtab, (int)(P->boxes.size() / 6), total, comp, P->rhs[0], fourpiG);
     if (rc != 0) return rc;
-    const double bnorm = P->h_norm[0], max_rhs = P->h_norm[1];
-    double rnorm = P->h_norm[2];
-    const double t1 = reltol * bnorm, t2 = abstol * max_rhs;
-    const double tol = t1 > t2 ? t1 : t2;
-    if (h_history) { h_history[0] = bnorm; h_history[1] = max_rhs; h_history[2] = rnorm; }
-    int n = 0;
-    while (!(rnorm <= tol) && n < maxiter) {
-        rc = mgb_vcycle(P, 0, X, s, prof);
-        if (rc == 0) rc = mgb_residual_norm(P, X, 0, s, prof);
-        if (rc == 0) rc = mg_read(P, 1, s);
-        if (rc != 0) return rc;
-        rnorm = P->h_norm[0];
-        ++n;
-        if (h_history) h_history[2 + n] = rnorm;
-    }
-    *cycles = n;
-    *converged = rnorm <= tol ? 1 : 0;
-    *final_norm = rnorm;
-    return 0;
+    return mg_solve(P, X, reltol, abstol, maxiter, cycles, converged, final_norm, h_history, s, prof);
 }
 
 int launch_grad_phi_boxes(PoissonPlan* P, const DFab& phi, const DFab& X, const DFab* G, hipStream_t s, Profiler* prof)
@@ -935,11 +747,8 @@ int launch_grad_phi_boxes(PoissonPlan* P, const DFab& phi, const DFab& X, const 
     long total;
     const int rc = mgb_table(P, G, s, dtab, total);
     if (rc != 0) return rc;
-    prof_begin(prof, "k_mgb_grad", s);
-    hipLaunchKernelGGL(k_mgb_grad, dim3(mg_blocks(total)), dim3(MG_WG), 0, s, dtab, (int)(P->boxes.size() / 6), total, phi, P->lev[0],
-                       (const unsigned char*)P->flags[0], X, P->dx[0], P->dx[1], P->dx[2]);
-    prof_end(prof, s);
-    return mg_check(s);
+    return mg_launch(prof, "k_mgb_grad", k_mgb_grad, mg_blocks(total), MG_WG, s, dtab, (int)(P->boxes.size() / 6), total, phi,
+                     MgBoxes{ { P->lev[0], P->flags[0] }, X }, P->dx[0], P->dx[1], P->dx[2]);
 }
 
 } // namespace cad

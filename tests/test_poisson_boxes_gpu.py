@@ -278,6 +278,66 @@ def test_single_passes_on_the_coarse_levels_of_the_ell(hydro, level):
         hydro.poisson_plan_destroy(dplan)
 
 
+def test_single_passes_on_level_0_of_the_ell_with_face_values(hydro):
+    """the smoother (both colours) and the residual on level 0 (bounding box 16 x 16 x 8) with a random face array that holds NaN
+    in every slot no flagged face owns -- a pass that reads a face value where no flag asks for it, or a neighbour's value where a
+    flag asks for the face's, shows.  The rule of the passes on the coarse levels: `exact` the restatement's bits, `contract`
+    8 * 2^-52 of a bound on the sum of the magnitudes of the terms.  With m = max(|p|, |f|) and at most one flagged face per
+    direction (the boxes are 8 zones wide) a flagged neighbour is 2 f in the smoother and 2 f - p in the residual: smoother
+    (3 (cx + cy + cz) m + |b|) / cdiag (the diagonal only grows), residual |b| + 6 (cx + cy + cz) m.  Zones that are not covered,
+    and the zones of the other colour, keep their bits."""
+    from castro_amd import _lib
+    plan = B.Plan(B.DX, B.LAYOUTS["ell"])
+    L, fl = plan.lev[0], plan.flags[0]
+    assert L.n == (16, 16, 8)
+    exact = hydro.numerics == "exact"
+    box, fbox = plan.bb, plan.facebox
+    cov = plan.covered()
+    rng = np.random.default_rng(23)
+    P0 = rng.normal(size=L.gshape) * 2.0 - 3.0
+    Bv = rng.normal(size=L.shape) * 40.0
+    nz, ny, nx = L.shape
+    owned = np.zeros((3,) + B.shape_of(fbox), dtype=bool)
+    for d in range(3):
+        for side in (0, 1):
+            off = [0, 0, 0]
+            off[2 - d] = side
+            owned[d][off[0]:off[0] + nz, off[1]:off[1] + ny, off[2]:off[2] + nx] |= (fl & B.face_bit(d, side)) != 0
+    assert owned.any() and not owned.all()
+    X = np.where(owned, rng.normal(size=owned.shape) * 2.0 - 3.0, np.nan)
+    csum = (L.cx + L.cy) + L.cz
+    pmax = max(np.abs(P0).max(), np.abs(X[owned]).max())
+    dplan = hydro.poisson_boxes_plan_create(B.DX, plan.boxes)
+
+    def close(got, want, bound, what):
+        assert np.isfinite(want).all(), what
+        if exact:
+            assert np.array_equal(_bits(got), _bits(want)), what
+        else:
+            assert np.all(np.abs(got - want) <= 8.0 * R.U52 * bound), (what, np.abs(got - want).max())
+
+    try:
+        Xd = (_dev(X), fbox)
+        for colour in (0, 1):
+            want = P0.copy()
+            B.smooth(L, fl, want, Bv, X, colour)
+            Pd = _dev(P0[None])
+            hydro.poisson_boxes_level_op(dplan, _lib.MG_SMOOTH, 0, (Pd, _grow(box, 1)), (_dev(Bv[None]), box), faces=Xd, colour=colour)
+            got = _host(Pd)[0]
+            sel = np.zeros(L.gshape, dtype=bool)
+            sel[1:-1, 1:-1, 1:-1] = cov & (B._parity(L) == colour)
+            assert sel.sum() > 0 and np.array_equal(_bits(got[~sel]), _bits(P0[~sel])), "only covered zones of the colour are written"
+            close(got[sel], want[sel], (3.0 * csum * pmax + np.abs(Bv).max()) / L.cdiag, "smooth %d" % colour)
+        want = B.residual(L, fl, P0, Bv, X, np.full(L.shape, SENT))
+        Rd = torch.full((1,) + L.shape, SENT, dtype=torch.float64, device="cuda")
+        hydro.poisson_boxes_level_op(dplan, _lib.MG_RESIDUAL, 0, (_dev(P0[None]), _grow(box, 1)), (_dev(Bv[None]), box), (Rd, box), faces=Xd)
+        got = _host(Rd)[0]
+        assert np.all(got[~cov] == SENT)
+        close(got[cov], want[cov], np.abs(Bv).max() + 6.0 * csum * pmax, "residual")
+    finally:
+        hydro.poisson_plan_destroy(dplan)
+
+
 # ---- 4. the refusals of the C entry points ------------------------------------------------------------------------------------------
 def test_refusals_of_the_c_entry(hydro):
     """each refusal returns its error code (a RuntimeError that names it) before anything is launched: the arrays keep their bits"""
