@@ -9,6 +9,7 @@ Arrays are (nz, ny, nx).  phi-like arrays hold BB grown by one zone; the face ar
 [BB.lo, BB.hi + 1]: X[d] at the zone (i, j, k) is the value on the low d-face of that zone."""
 import numpy as np
 
+from tests import grid_caps as GC
 from tests import monopole_ref as MR
 from tests import poisson_amr_ref as A
 from tests import poisson_ref as R
@@ -33,7 +34,12 @@ LAYOUTS = {
     "edge": [_cube((8, 8, 8)), _cube((16, 16, 8))],
     "disjoint": [_cube((4, 4, 4)), _cube((20, 20, 20))],
     "unequal": [_cube((8, 8, 8)), ((16, 12, 8), (19, 19, 15))],
+    # aligned to 2 only: the coarsening stops at level 1, 15 x 16 x 17 of the bounding box (78 % covered) -- a bottom solve of
+    # 2176 x-pairs per colour, more than one trip of its workgroup (tests/grid_caps.py)
+    "wide_bottom": GC.BOTTOM_UNION,
 }
+# the coarse box (grown by one) under each layout: the 16^3 level 0 of the tests, or what the layout needs
+CRSE_BOX = {"wide_bottom": GC.BOTTOM_UNION_CRSE_BOX}
 DX = (1.0 / 32,) * 3
 
 

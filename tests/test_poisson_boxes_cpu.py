@@ -80,7 +80,7 @@ def _case(name, seed=3):
     boxes = B.LAYOUTS[name]
     plan = B.Plan(B.DX, boxes)
     rng = np.random.default_rng(seed)
-    cbox = ((-1, -1, -1), (16, 16, 16))
+    cbox = B.CRSE_BOX.get(name, ((-1, -1, -1), (16, 16, 16)))
     co, cn = rng.normal(size=B.shape_of(cbox)) * 3.0 - 7.0, rng.normal(size=B.shape_of(cbox)) * 3.0 - 7.0
     rho = rng.uniform(0.5, 2.0, size=plan.lev[0].shape)
     start = np.zeros(plan.lev[0].gshape)
@@ -133,7 +133,7 @@ def test_disjoint_boxes_are_two_independent_solves():
     assert np.array_equal(_bits(phi[1:-1, 1:-1, 1:-1][unc]), _bits(start[1:-1, 1:-1, 1:-1][unc])), "uncovered zones are not written"
 
 
-@pytest.mark.parametrize("name", ["ell", "edge", "unequal"])
+@pytest.mark.parametrize("name", ["ell", "edge", "unequal", "wide_bottom"])
 def test_masked_solve_converges_on_the_irregular_layouts(name):
     plan, co, cn, cbox, rho, start, X = _case(name)
     phi = start.copy()

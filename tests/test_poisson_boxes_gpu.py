@@ -57,15 +57,16 @@ def _case(name, a=0.3):
     if key not in _CACHE:
         plan = B.Plan(B.DX, B.LAYOUTS[name])
         rng = np.random.default_rng(11)
-        co, cn = rng.normal(size=B.shape_of(CBOX)) * 3.0 - 7.0, rng.normal(size=B.shape_of(CBOX)) * 3.0 - 7.0
+        cbox = B.CRSE_BOX.get(name, CBOX)
+        co, cn = rng.normal(size=B.shape_of(cbox)) * 3.0 - 7.0, rng.normal(size=B.shape_of(cbox)) * 3.0 - 7.0
         rho = rng.uniform(0.5, 2.0, size=plan.lev[0].shape)
         start = np.zeros(plan.lev[0].gshape)
         start[1:-1, 1:-1, 1:-1] = rng.normal(size=plan.lev[0].shape) - 7.0
         X = np.full((3,) + B.shape_of(plan.facebox), SENT)
-        wrote = B.cf_faces(plan, X, co, CBOX, cn, CBOX, a)
+        wrote = B.cf_faces(plan, X, co, cbox, cn, cbox, a)
         phi = start.copy()
         out = B.solve(plan, phi, X, rho, FOURPI)
-        _CACHE[key] = dict(plan=plan, co=co, cn=cn, rho=rho, start=start, X=X, wrote=wrote, phi=phi, out=out)
+        _CACHE[key] = dict(plan=plan, cbox=cbox, co=co, cn=cn, rho=rho, start=start, X=X, wrote=wrote, phi=phi, out=out)
     return _CACHE[key]
 
 
@@ -82,7 +83,7 @@ def _rho_fabs(plan, rho):
 
 def _device_faces(hydro, c, dplan, a):
     X = torch.full((3,) + B.shape_of(c["plan"].facebox), SENT, dtype=torch.float64, device="cuda")
-    hydro.poisson_boxes_cf_bc(dplan, X, c["plan"].facebox, _dev(c["co"][None]), CBOX, _dev(c["cn"][None]), CBOX, a)
+    hydro.poisson_boxes_cf_bc(dplan, X, c["plan"].facebox, _dev(c["co"][None]), c["cbox"], _dev(c["cn"][None]), c["cbox"], a)
     return X
 
 
@@ -147,9 +148,7 @@ def test_a_tiling_is_the_one_box_solve(hydro, name):
 
 
 # ---- 2. the irregular layouts against the restatement -------------------------------------------------------------------------------
-@pytest.mark.parametrize("a", [0.0, 0.3, 1.0])
-@pytest.mark.parametrize("name", ["ell", "edge", "disjoint", "unequal"])
-def test_layout_against_the_restatement(hydro, name, a):
+def _layout_against_the_restatement(hydro, name, a):
     """Face values: the restatement's bits in both builds, every slot that is not a boundary face of the union keeps its sentinel.
     Solve: `exact` gives phi (uncovered zones and ghost zones keep their bits), norm history and cycle count of the restatement;
     `contract` meets the stopping rule on the float64 residual of the masked operator.  g per box: `exact` the restatement's
@@ -203,6 +202,21 @@ def test_layout_against_the_restatement(hydro, name, a):
                 assert np.all(np.abs(inner - w) <= 8.0 * R.U52 * mag[(slice(None),) + _sl(plan.bb, lo, hi)]), (lo, hi)
     finally:
         hydro.poisson_plan_destroy(dplan)
+
+
+@pytest.mark.parametrize("a", [0.0, 0.3, 1.0])
+@pytest.mark.parametrize("name", ["ell", "edge", "disjoint", "unequal"])
+def test_layout_against_the_restatement(hydro, name, a):
+    _layout_against_the_restatement(hydro, name, a)
+
+
+def test_layout_with_a_bottom_solve_of_three_trips_against_the_restatement(hydro):
+    """two boxes aligned to 2 only: the bottom solve runs on level 1, 15 x 16 x 17 of the bounding box with 78 % of it covered --
+    2176 x-pairs per colour for the 1024 threads of k_mgb_bottom, three trips with a barrier after each colour.  The assertions
+    of the other layouts, at a = 0.3."""
+    c = _case("wide_bottom", 0.3)
+    assert [L.n for L in c["plan"].lev] == [(30, 32, 34), (15, 16, 17)] and c["out"][1] and c["out"][0] >= 3
+    _layout_against_the_restatement(hydro, "wide_bottom", 0.3)
 
 
 # ---- 3. single passes on the two coarsest levels of the ell: boxes 2 and 1 zones wide ------------------------------------------------

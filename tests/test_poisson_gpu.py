@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import grid_caps as G
 from tests import monopole_ref as MR
 from tests import poisson_ref as R
 from tests.test_monopole_gpu import N_CELL, PROB_HI, _bin_boxes
@@ -14,7 +15,8 @@ from tests.test_monopole_gpu import N_CELL, PROB_HI, _bin_boxes
 pytestmark = pytest.mark.gpu
 
 U52 = 2.0 ** -52
-SHAPES = [(16, 16, 16), (16, 8, 12), (6, 10, 14), (5, 7, 9)]
+# the last two: bottom solves of 2176 and 1470 x-pairs per colour, three and two trips of the one workgroup (tests/grid_caps.py)
+SHAPES = [(16, 16, 16), (16, 8, 12), (6, 10, 14), (5, 7, 9)] + G.BOTTOM_ONE_BOX
 DX = (0.11, 0.13, 0.09)
 FOURPIG = 4.0 * np.pi * 6.67428e-8
 _CACHE = {}
@@ -43,7 +45,7 @@ def _dev(a):
 CENTERS = {"mid": (1.5, 1.25, 1.0), "off": (0.9, 1.7, 0.55)}
 
 
-@pytest.mark.parametrize("lnum", [0, 2, 6])
+@pytest.mark.parametrize("lnum", [0, 2, 6, G.MP_ORDER])           # the last: CASTRO_AMD_MAX_MULTIPOLE, every column of a row in use
 @pytest.mark.parametrize("where", ["mid", "off"])
 def test_multipole_moments(hydro, lnum, where):
     from castro_amd import _lib
@@ -93,7 +95,7 @@ def test_multipole_refuses_an_order_above_the_cap(hydro):
 
 
 # ---- boundary potential ----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("lnum,where", [(0, "mid"), (6, "off"), (2, "corner")])
+@pytest.mark.parametrize("lnum,where", [(0, "mid"), (6, "off"), (2, "corner"), (G.MP_ORDER, "off")])
 def test_multipole_phi_bc(hydro, lnum, where):
     """the ghost shell against the restatement from the same moments; valid zones keep their sentinel bits; with the centre on the
     high corner of the domain the corner ghost zone has r = 0 and phi exactly 0"""
