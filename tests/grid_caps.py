@@ -3,7 +3,11 @@ tests import them, and tests/test_grid_caps_cpu.py reads the caps out of the ker
 crosses its cap, and by how many trips -- a cap that is raised later fails that test instead of leaving the GPU tests below it.
 
 The layout functions restate the launchers (launch_mg_norm, k_mg_bottom's loop, mp_layout, diag_layout, pack_layout) with the caps
-as arguments; nothing here imports the product, torch or numpy."""
+as arguments; nothing here imports the product, torch or numpy.
+
+The second half holds the shapes that cross the CHUNK sizes -- work cut into pieces of a fixed size instead of a capped grid:
+the trips of k_tracer_scan, the tables of launch_clean_state_boxes, the chunks of group_chunks, the region tables of
+castro_amd_pack_regions_fab and the trips of k_estdt / k_clean_state_reduce (tests/test_chunk_caps_gpu.py)."""
 
 # ---- multigrid norm: more than MG_NORM_MAX_WG workgroups of MG_WG zones on level 0 ---------------------------------------------------
 MG_NORM_ONE_BOX = (64, 64, 80)                                   # 327 680 zones; coarsens to (4, 4, 5)
@@ -116,3 +120,130 @@ def pack_units(entries):
         out += [z // 2 if pack_vec2(e, offset) else z] * e["ncomp"]
         offset += z * e["ncomp"]
     return out
+
+
+# ======================================================================================================================================
+# Chunk sizes: work cut into fixed-size pieces instead of a capped grid (tests/test_chunk_caps_gpu.py)
+# ======================================================================================================================================
+
+# ---- tracer migration: k_tracer_scan takes the blocks of 256 particles in trips of 256 ------------------------------------------------
+TRACER_NS = (65537, 131073 + 300)                                # 257 blocks: two trips, the second of one block; 514: three trips
+TRACER_RANKS = (3, 256)
+TRACER_KINDS = ("stay", "one", "wave", "invalid", "outside", "mix")
+TRACER_SPREAD = ("wave", "mix")                                  # particles for every rank in every trip
+TRACER_WORKSPACE_NS = (1000, 131073 + 300, 1000)                 # the hist workspace grows, then holds a smaller table in front of stale rows
+
+# ---- clean_state of many regions: one launch per CLEAN_BOXES_MAX non-empty regions -----------------------------------------------------
+# (number of operations, {position: how it is skipped}): "empty" = hi < lo in one direction, "zero" = ntimes 0
+CLEAN_FAB = dict(valid=(3, 2, 4), ng=2)
+CLEAN_CASES = {
+    # 70 cleaning operations and 11 skipped ones among them: at positions 0, 31, 32, 33 and 69, either side of the 32nd and of the 64th
+    # cleaning operation (positions 36 and 72: the last entries of the first and the second table), and at the end
+    "seventy": (81, {0: "empty", 31: "zero", 32: "empty", 33: "zero", 35: "empty", 37: "zero", 38: "empty", 69: "zero", 71: "zero",
+                     73: "empty", 80: "zero"}),
+    "thirty_two": (35, {0: "empty", 5: "zero", 34: "zero"}),      # one full table; an unskipped ntimes 0 would open a second
+    "thirty_three": (37, {0: "zero", 17: "empty", 33: "zero", 35: "empty"}),   # positions 34 and 36: the 32nd and 33rd cleaning operation
+}
+
+# ---- halo groups: the regions of a FAB in chunks of CASTRO_AMD_MAX_REGIONS ---------------------------------------------------------------
+HALO_DOMAIN = ((0, 0, 0), (15, 15, 15))
+HALO_NG = 4
+HALO_BOXES = [((0, 0, 0), (7, 15, 15))] + [((8, j, k), (15, j + 3, k + 3)) for k in (0, 4, 8, 12) for j in (0, 4, 8, 12)]
+HALO_PERIODIC = {"x": (True, False, False), "xz": (True, False, True), "xyz": (True, True, True)}
+HALO_FAB0_MESSAGES = {"x": 32, "xz": 50, "xyz": 80}            # sends = receives of FAB 0
+HALO_FAB0_CHUNKS = {"x": [32], "xz": [32, 18], "xyz": [32, 32, 16]}
+
+# ---- pack_regions_fab / unpack_regions_fab at the cap ---------------------------------------------------------------------------------
+REGIONS_FAB = dict(lo=(-5, -3, -7), ext=(13, 11, 9), ncomp=8)
+REGIONS_CUTS = ((0, 3, 6, 10, 13), (0, 2, 5, 8, 11), (0, 4, 9))  # 4 x 4 x 2 cells, one region inside each
+REGIONS_EMPTY = (0, 15, 31)
+
+# ---- k_estdt / k_clean_state_reduce: 2048 workgroups of 256 zones a trip ---------------------------------------------------------------
+REDUCE_BOX = dict(lo=(3, -2, 5), ext=(128, 64, 130), ng=4)
+REDUCE_SLABS = ((0, 64), (64, 128), (128, 130))                   # k-planes of the three trips, relative to lo
+# (k-plane, j, i) relative to lo of the zone that decides the CFL estimate and of the one with the smallest raw density
+REDUCE_PLACEMENTS = {
+    "last_trip": dict(cfl=(129, 17, 41), rho=(100, 50, 7), below_small_dens=False),
+    "control": dict(cfl=(3, 17, 41), rho=(3, 50, 7), below_small_dens=False),
+    "edges": dict(cfl=(64, 0, 0), rho=(129, 63, 127), below_small_dens=True),
+}
+
+
+def scan_trips(n, block, trip):
+    """k_tracer_dest / k_tracer_scan: (blocks of `block` particles, trips of `trip` blocks, blocks of the last trip)"""
+    blocks = ceil_div(n, block)
+    trips = ceil_div(blocks, trip)
+    return blocks, trips, blocks - (trips - 1) * trip
+
+
+def clean_kinds(case):
+    """per position "clean", "empty" or "zero" """
+    total, skipped = CLEAN_CASES[case]
+    return [skipped.get(p, "clean") for p in range(total)]
+
+
+def clean_tables(kinds, cap):
+    """launch_clean_state_boxes: the positions of the cleaning operations of every launch"""
+    out, done = [], 0
+    while done < len(kinds):
+        table = []
+        while done < len(kinds) and len(table) < cap:
+            if kinds[done] == "clean":
+                table.append(done)
+            done += 1
+        if table:
+            out.append(table)
+    return out
+
+
+def chunk_sizes(count, cap):
+    """group_chunks: the chunks of `count` regions of one FAB"""
+    out = [cap] * (count // cap)
+    return out + ([count % cap] if count % cap else [])
+
+
+def regions():
+    """32 disjoint regions (lo, hi) of REGIONS_FAB, one inside every cell of REGIONS_CUTS: whole cells, cells trimmed on one side,
+    and slabs one zone thick in x, y or z"""
+    lo0 = REGIONS_FAB["lo"]
+    cx, cy, cz = REGIONS_CUTS
+    out = []
+    for c in range(2):
+        for b in range(4):
+            for a in range(4):
+                r = len(out)
+                lo = [lo0[0] + cx[a], lo0[1] + cy[b], lo0[2] + cz[c]]
+                hi = [lo0[0] + cx[a + 1] - 1, lo0[1] + cy[b + 1] - 1, lo0[2] + cz[c + 1] - 1]
+                if r % 4 == 1:
+                    lo[r % 3] += 1                              # trimmed
+                elif r % 4 == 2:
+                    hi[r % 3] = lo[r % 3]                       # one zone thick
+                elif r % 4 == 3:
+                    lo[(r + 1) % 3] = hi[(r + 1) % 3]
+                out.append((tuple(lo), tuple(hi)))
+    return out
+
+
+def region_offsets(boxes, ncomp, empty=()):
+    """offsets (in doubles) of the slices: handed out in the order r * 13 mod 32, not in region order, with a gap of 1 .. 5 doubles
+    in front of every slice (an empty region takes a slice of no doubles) and a tail longer than any slice behind the last: a
+    slice written at the offset of another region still ends inside the buffer.  (offsets, doubles of the buffer)"""
+    n = len(boxes)
+    tail = 1 + max(ncomp * zones(tuple(b[1][d] - b[0][d] + 1 for d in range(3))) for b in boxes)
+    off, at = [0] * n, 0
+    for q in range(n):
+        r = (q * 13) % n if n == 32 else q
+        at += 1 + r % 5
+        off[r] = at
+        if r not in empty:
+            at += ncomp * zones(tuple(boxes[r][1][d] - boxes[r][0][d] + 1 for d in range(3)))
+    return off, at + tail
+
+
+def reduce_trips(ext, wg, max_wg):
+    """launch_estdt / launch_clean_state_reduce: (zones a trip, trips, the k-plane each trip starts on or None)"""
+    per = wg * max_wg
+    n = zones(ext)
+    plane = ext[0] * ext[1]
+    starts = [t * per for t in range(ceil_div(n, per))]
+    return per, len(starts), [s // plane if s % plane == 0 else None for s in starts]

@@ -1391,6 +1391,30 @@ def test_rccl_process_group_of_one_rank(tmp_path, halo, monkeypatch):
     assert np.array_equal(got["dts"], np.array(dts)) and np.array_equal(got["S"], c.S_new().cpu().numpy())
 
 
+def _ghosts_from_the_level(boxes, host, ng, periodic, n=16):
+    """the expectation of a same-level ghost exchange on the domain [0, n)^3: for every box (want, take) -- its FAB `host[b]` with
+    the ghost zones `take` that lie in a box of the level, or in a periodic image of one, replaced by that box's valid data
+    (a numpy gather through the periodic wrap); every other zone keeps its value"""
+    ncomp = host[0].shape[0]
+    G = np.full((ncomp, n, n, n), np.nan)
+    for (lo, hi), a in zip(boxes, host):
+        G[:, lo[2]:hi[2] + 1, lo[1]:hi[1] + 1, lo[0]:hi[0] + 1] = a[:, ng:-ng, ng:-ng, ng:-ng]
+    out = []
+    for (lo, hi), a in zip(boxes, host):
+        want = a.copy()
+        idx = [np.arange(lo[x] - ng, hi[x] + ng + 1) for x in range(3)]
+        ok = [np.ones_like(idx[x], dtype=bool) if periodic[x] else ((idx[x] >= 0) & (idx[x] <= n - 1)) for x in range(3)]
+        wrapped = [idx[x] % n for x in range(3)]
+        src = G[:, wrapped[2][:, None, None], wrapped[1][None, :, None], wrapped[0][None, None, :]]
+        inside = ok[2][:, None, None] & ok[1][None, :, None] & ok[0][None, None, :]
+        valid = np.zeros(want.shape[1:], dtype=bool)
+        valid[ng:-ng, ng:-ng, ng:-ng] = True
+        take = inside & ~valid & ~np.isnan(src[0])
+        want[:, take] = src[:, take]
+        out.append((want, take))
+    return out
+
+
 @pytest.mark.parametrize("self_send", [0, 1])
 def test_many_boxes_per_rank_fill_boundary_group(hip, self_send, monkeypatch):
     """castro_amd_halo_group / castro_amd_fill_boundary_group (round 6: the C++ twin of the many-box plan of castro_amd/amr.py):
@@ -1416,21 +1440,7 @@ def test_many_boxes_per_rank_fill_boundary_group(hip, self_send, monkeypatch):
     dev = [_to_dev(hip, a) for a in host]
     hip.fill_boundary_group(group, dev, gboxes)
     torch.cuda.synchronize()
-    # expectation: the level's valid data on the domain, ghost zones read from it through the periodic wrap
-    G = np.full((ncomp, 16, 16, 16), np.nan)
-    for (lo, hi), a in zip(boxes, host):
-        G[:, lo[2]:hi[2] + 1, lo[1]:hi[1] + 1, lo[0]:hi[0] + 1] = a[:, ng:-ng, ng:-ng, ng:-ng]
-    for (glo, ghi), (lo, hi), a, d in zip(gboxes, boxes, host, dev):
-        want = a.copy()
-        idx = [np.arange(glo[x], ghi[x] + 1) for x in range(3)]
-        ok = [np.ones_like(idx[x], dtype=bool) if periodic[x] else ((idx[x] >= 0) & (idx[x] <= 15)) for x in range(3)]
-        wrapped = [idx[x] % 16 for x in range(3)]
-        src = G[:, wrapped[2][:, None, None], wrapped[1][None, :, None], wrapped[0][None, None, :]]
-        inside = ok[2][:, None, None] & ok[1][None, :, None] & ok[0][None, None, :]
-        valid = np.zeros(want.shape[1:], dtype=bool)
-        valid[ng:-ng, ng:-ng, ng:-ng] = True
-        take = inside & ~valid & ~np.isnan(src[0])
-        want[:, take] = src[:, take]
+    for (want, take), d in zip(_ghosts_from_the_level(boxes, host, ng, periodic), dev):
         assert np.array_equal(d.cpu().numpy(), want)
         assert take.sum() > 0
     # with the physical-boundary fill (outflow in y): the zones beyond the y faces copy the first / last in-domain row

@@ -111,9 +111,9 @@ def _equal(P, Q, what):
 @pytest.mark.parametrize("nranks", [2, 3, 8, CAP])
 @pytest.mark.parametrize("n", NS)
 def test_count_and_pack_bits(hydro, n, nranks):
-    """N at the wave edge, the block edge and over four blocks (the scan over blocks); 2, 3, 8 ranks and the cap; all stay, all
-    leave to one rank, every destination inside one wave, destinations alternating lane by lane, a third invalid, grids and
-    levels outside the table"""
+    """N at the wave edge, the block edge and over four blocks (one trip of the scan over blocks, which takes 256 blocks a trip; two
+    and three trips are tests/test_chunk_caps_gpu.py); 2, 3, 8 ranks and the cap; all stay, all leave to one rank, every
+    destination inside one wave, destinations alternating lane by lane, a third invalid, grids and levels outside the table"""
     owners = _owners(nranks)
     for q, kind in enumerate(("stay", "one", "wave", "alternate", "invalid", "outside")):
         me = (q + nranks - 1) % nranks
