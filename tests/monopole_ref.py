@@ -42,16 +42,18 @@ def _axes(lo, shape, geom, mono, half):
 def radial_mass(boxes, geom, mono):
     """Gravity::compute_radial_mass.  boxes: [(rho (nz, ny, nx) of the valid zones, lo, mask (nz, ny, nx) uint8 or None)].
     Returns dict(mass=fsum per bin, count=int64 per bin, vol=count * vol_frac, A=fsum of |terms| per bin, dropped=sub-zones
-    beyond the last bin or of zones whose centre lies beyond it)."""
+    beyond the last bin or of zones whose centre lies beyond it, seq / vol_seq=the mass and the volume as the reference's single
+    thread adds them: one accumulator per bin, the boxes in their order, the loop nest (k, j, i, kk, jj, ii) within a box --
+    vol_seq adds vol_frac once per sub-zone and differs from count * vol_frac where a partial sum is inexact)."""
     n1d, f = mono.n1d, mono.drdxfac
     dr = geom.dx[0] / float(f)
     drinv = 1.0 / dr
     fac = float(f)
     frac = [geom.dx[d] / fac for d in range(3)]
     vf = vol_frac(geom, mono)
-    idx_all, t_all = [], []
+    idx_all, t_all, ord_all = [], [], []
     dropped = 0
-    for rho, lo, mask in boxes:
+    for nbox, (rho, lo, mask) in enumerate(boxes):
         rho = np.asarray(rho, dtype=np.float64)
         shape = rho.shape
         xc, yc, zc = _axes(lo, shape, geom, mono, 0.5)
@@ -64,6 +66,7 @@ def radial_mass(boxes, geom, mono):
         dropped += int((keep & (index0 > n1d - 1)).sum()) * f ** 3
         keep &= index0 <= n1d - 1
         term = vf * rho
+        zone = (np.arange(rho.size, dtype=np.int64).reshape(shape) + nbox * (1 << 32)) * f ** 3
         for kk in range(f):
             zz = lo_k + (float(kk) + 0.5) * frac[2]
             zzsq = zz * zz
@@ -79,6 +82,7 @@ def radial_mass(boxes, geom, mono):
                     dropped += int((keep & ~ok).sum())
                     idx_all.append(index[ok])
                     t_all.append(np.broadcast_to(term, index.shape)[ok])
+                    ord_all.append(zone[ok] + (kk * f + jj) * f + ii)
     idx = np.concatenate(idx_all) if idx_all else np.zeros(0, dtype=np.int64)
     t = np.concatenate(t_all) if t_all else np.zeros(0)
     count = np.bincount(idx, minlength=n1d).astype(np.int64)
@@ -91,7 +95,13 @@ def radial_mass(boxes, geom, mono):
         if seg.size:
             mass[b] = math.fsum(seg.tolist())
             A[b] = math.fsum(np.abs(seg).tolist())
-    return dict(mass=mass, count=count, vol=count.astype(np.float64) * vf, A=A, dropped=dropped)
+    seq, vol_seq = np.zeros(n1d), np.zeros(n1d)
+    if idx.size:
+        nest = np.argsort(np.concatenate(ord_all), kind="stable")
+        for b, v in zip(idx[nest].tolist(), t[nest].tolist()):
+            seq[b] += v
+            vol_seq[b] += vf
+    return dict(mass=mass, count=count, vol=count.astype(np.float64) * vf, A=A, dropped=dropped, seq=seq, vol_seq=vol_seq)
 
 
 def mass_bounds(ref):
